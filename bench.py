@@ -4,8 +4,9 @@
 A "step" is ONE self-play episode: `games` concurrent 15x15 games per GPU, two agents (trees) per game, `sims` PUCT
 simulations per move in rounds of K with one batched net forward per round, random-init net (seed 0), played until every
 game has ended (src/trainer.rs:95-205).  Every step runs on its own RNG stream (one reset = one trainer iteration).
-`value` = completed games / second over the timed steps, whole job (all ranks).  Warm-up steps are episodes cut after
---warmup-plies plies (untimed: they warm clocks, code objects and allocations; the timed steps are whole episodes).
+`value` = completed games / second over the timed steps, whole job (all ranks).  Warm-up steps are untimed steps
+like the timed ones, whole episodes (they warm clocks, code objects and allocations); each costs what a timed step does,
+so (warmup + steps) x ms_per_step is the time spent in steps.  --warmup-plies N cuts them after N plies instead.
 
 Default workload = BASELINE.json configs[1]: 4096 concurrent 15x15 games, 800 sims/move, K = 16.
 Multi-GPU (configs[3]): one process per GPU, games sharded by global id (game_offset = rank * games), no collective on the
@@ -13,9 +14,14 @@ hot path; --gather adds the RCCL all-gather-v of (s, pi, z) replay tuples at epi
 --gpus N` starts its N ranks by itself (torch.distributed.run as a child process, before the parent touches the GPU);
 started under torchrun it uses the environment it finds.
 
-Output: rank 0 prints the result line as soon as the timed region ends (flush), and -- if the extra legs ran -- the same
-line again enriched with `cpu_baseline`, `precision`, `replay_postprocess`, `train_phase`.  The LAST line is the complete
-one; the first one exists so that a run killed at its time limit still leaves a measured line.
+Output: a plain run sets up, warms up, times the steps and prints ONE result line with the headline figures (games/s,
+ms_per_step, the counters of the timed region); it times no kernel category and runs no extra leg.  --full adds the
+rest: per-category HIP-event timing inside the timed steps, the rooflines, clock samples and the extra legs after the
+timed region.  A --full run prints the line as soon as the timed region ends (flush), and -- if the extra legs ran -- the
+same line again enriched with `cpu_baseline`, `precision`, `replay_postprocess`, `train_phase`.  The LAST line is the
+complete one; the first one exists so that a run killed at its time limit still leaves a measured line.
+--dump-outputs DIR writes what the last timed step computed (every game's result, the replay tuples of a fixed sample of
+games) as float32 .npy files, right after the timed region: same arguments, same inputs, so two builds compare file by file.
 """
 import argparse
 import json
@@ -130,11 +136,14 @@ def compact_line(full):
     return line
 
 
-def emit(full, final):
-    """print the driver's line (flush) and leave the verbose record beside it"""
+def emit(full, final, record=True):
+    """print the driver's line (flush) and, with `record`, leave the verbose record beside it"""
     line = compact_line(full)
-    if not final:  # the early safety line: a measured line exists from here on whatever happens to the extra legs; it carries no null placeholders
+    if not final:  # the early safety line (and a plain run's only line): what was measured, no null placeholders
         line = {k: v for k, v in line.items() if v is not None or k == "vs_baseline"}
+    print(json.dumps(line), flush=True)
+    if not record:
+        return
     path = os.environ.get("OMOK_BENCH_FULL") or os.path.join(ROOT, "gpurun_out", "bench_full.json")
     try:
         os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -142,7 +151,6 @@ def emit(full, final):
             json.dump(full, f, default=lambda o: float(o) if hasattr(o, "__float__") else str(o))
     except OSError:
         pass
-    print(json.dumps(line), flush=True)
 
 
 
@@ -151,7 +159,7 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=0)
-    ap.add_argument("--warmup-plies", type=int, default=4, help="plies of a warm-up step (0 = whole episodes)")
+    ap.add_argument("--warmup-plies", type=int, default=0, help="plies of a warm-up step (0 = whole episodes, like a timed step)")
     ap.add_argument("--board", type=int, default=15)
     ap.add_argument("--games", type=int, default=4096, help="concurrent games per GPU")
     ap.add_argument("--sims", type=int, default=800)
@@ -175,6 +183,9 @@ def parse(argv=None):
                     help="wall-clock budget of the whole process: the extra legs only run while there is room")
     ap.add_argument("--window-plies", type=int, default=20, help="extra leg: time the first N plies of one more episode (SURVEY 8d's fixed-length window; 0 = skip)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: kernel-category timing in the timed steps (--profile-every), "
+                    "rooflines, clock samples, the extra legs and the verbose record; the leg options above apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last one computed as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -576,6 +587,26 @@ def precision_check(args, rows, device):
     return out
 
 
+DUMP_GAMES = 64  # replay tuples of this many games (all 4096 of configs[1] would be ~0.44 GB as float32)
+
+
+def dump_outputs(path, sp):
+    """What the episode just played hands its caller (the trainer), as float32 arrays under `path`: every game's result and
+    length, and the replay tuples (board, side to move, pi, z) of DUMP_GAMES games drawn with a fixed seed; replay_game
+    names the game of each tuple.  Rank 0's games on multi-GPU runs."""
+    import numpy as np
+    _, status, plies = sp.game_info()
+    games = np.sort(np.random.default_rng(0).choice(len(status), size=min(DUMP_GAMES, len(status)), replace=False))
+    recs = [sp.replay(int(g)) for g in games]
+    arrays = {"game_status": status, "game_plies": plies,
+              "replay_game": np.concatenate([np.full(len(r[0]), g) for g, r in zip(games, recs)]),
+              "replay_board": np.concatenate([r[0] for r in recs]), "replay_turn": np.concatenate([r[1] for r in recs]),
+              "replay_pi": np.concatenate([r[2] for r in recs]), "replay_z": np.concatenate([r[3] for r in recs])}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 # ------------------------------------------------------------------------------------------------------------------
 def main():
     args = parse()
@@ -588,7 +619,7 @@ def main():
     if world != args.gpus:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: using the launcher's world size", file=sys.stderr)
 
-    sampler = start_clock_sampler() if rank == 0 else None  # (a child process: started before anything here initialises the GPU)
+    sampler = start_clock_sampler() if rank == 0 and args.full else None  # (a child process: started before anything here initialises the GPU)
 
     import numpy as np
     import torch
@@ -620,7 +651,8 @@ def main():
                     seed=args.seed, game_offset=oa.dist.game_offset(rank, games))
     eng.load_random_weights(0)
     sp = oa.SelfPlay(eng)
-    eng.set_profiling(max(1, args.profile_every))
+    if args.full:
+        eng.set_profiling(max(1, args.profile_every))
 
     def barrier():
         if use_cuda:
@@ -679,14 +711,45 @@ def main():
             dist.destroy_process_group()
         return
 
+    complete = args.max_plies == 0
+    mean_plies = ply_games / max(finished, 1.0) if complete else float(plies.mean())
+    games_per_s = finished / dt if complete else (ply_games / max(mean_plies, 1.0)) / dt
+    fc0_short = {0: "fp6", 1: "f16", 2: "mixed f16/fp6"}.get(int(st.get("fc0_format", 0)), "f32")
+    out = {
+        "metric": "self-play games/sec (15x15, 800 sims/move); MCTS nodes/sec",
+        "value": games_per_s, "unit": "games/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / max(args.steps, 1), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": f"f16x3 split MFMA, fp32 acc; fc0 corrections {fc0_short}" if args.net_mode != "f32" else "f32",
+        "data": "synthetic (empty boards, random-init net seed 0)",
+        "config": {"workload": f"{games} concurrent {n}x{n} games per GPU, {args.sims} sims/move, K={k}, two trees per game"
+                               + ("" if complete else f", first {args.max_plies} plies only (games/s extrapolated)"),
+                   "games_per_gpu": games, "board": n, "sims_per_move": args.sims, "batch_k": k,
+                   "warmup_step": f"episode cut after {args.warmup_plies} plies" if args.warmup_plies else "whole episode",
+                   "parallelism": f"games sharded x{world}, no hot-path collective" + (f", {'RCCL' if backend == 'nccl' else backend} all-gather-v of replay tuples per episode" if args.gather else "")},
+        "mcts_sims_per_s": sims / dt, "nn_evals_per_s": evals / dt, "plies_per_s": ply_games / dt,
+        "mean_plies_per_game": mean_plies, "games_finished": finished,
+        "rank0_timed_region_ms": 1e3 * dt,
+    }
+    if args.gather:
+        out["replay_gather"] = {"records_per_episode": gathered["records"] / max(args.steps, 1), "bytes_per_episode": gathered["bytes"] / max(args.steps, 1),
+                                "seconds_per_episode": gathered["seconds"] / max(args.steps, 1), "inside_timed_region": True,
+                                "method": "8 x int64 counts all-gather, then exact-size grouped send/recv (all-gather-v)", "backend": "RCCL" if backend == "nccl" else backend,
+                                "last_counts": gathered.get("last_counts"), "last_ids": gathered.get("last_ids")}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sp)
+    if not args.full:
+        out["seconds_since_process_start"] = elapsed()
+        emit(out, final=False, record=False)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     hw = n * n
     flop_eval = 2.0 * (3 * 128 * hw + 3 * hw * (128 * 32 + 9 * 32 + 32 * 32 + 32 * 128) + 128 * hw * 512 + 512 * 512 + 512 + 512 * hw)
     flop_fc0 = 2.0 * 128 * hw * 512
     flop_tail = 2.0 * (512 * 512 + 512 + 512 * hw)
     flop_trunk = flop_eval - flop_fc0 - flop_tail
-    complete = args.max_plies == 0
-    mean_plies = ply_games / max(finished, 1.0) if complete else float(plies.mean())
-    games_per_s = finished / dt if complete else (ply_games / max(mean_plies, 1.0)) / dt
     rows = st["fc0_rows"]                       # net rows evaluated on rank 0 in the timed region
     launches = max(st["fc0_launches"], 1.0)     # one trunk + one fc0 launch per forward
     k_ms = {"k_trunk": st["ms_trunk"], "k_fc0_mx": st["ms_fc0"], "tail (fc1, heads, softmax)": st["ms_tail"],
@@ -813,15 +876,10 @@ def main():
                 "child's difference row, i.e. ~0.28x (N = 15) / ~0.65x (N = 9) of the algorithmic work is EXECUTED: `achieved` counts useful work and can exceed "
                 "what a dense kernel could reach")
     fc0_fmt = {0: "block-scaled fp6 (e2m3)", 1: "f16", 2: "mixed: f16 on full operand rows, block-scaled fp6 on the difference rows of sibling rounds"}.get(int(st.get("fc0_format", 0)), "f32")
-    fc0_short = {0: "fp6", 1: "f16", 2: "mixed f16/fp6"}.get(int(st.get("fc0_format", 0)), "f32")
     net_s = (st["ms_trunk"] + st["ms_fc0"] + st["ms_tail"]) * 1e-3
     tree_s = st["ms_tree"] * 1e-3
     tree_traffic = pmc.get("tree_hbm_bytes_per_sim")
-    out = {
-        "metric": "self-play games/sec (15x15, 800 sims/move); MCTS nodes/sec",
-        "value": games_per_s, "unit": "games/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * dt / max(args.steps, 1), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": f"f16x3 split MFMA, fp32 acc; fc0 corrections {fc0_short}" if args.net_mode != "f32" else "f32",
+    out.update({
         "dtype_long": (f"f16 (split hi+lo MFMA operands: f16 main term + two correction terms, fp32 accumulate; fc0's correction terms in {fc0_fmt}, "
                        + ("chosen by omok_net_commit's probe)" if args.net_mode == "f16x3" else "forced by --net-mode)")) if args.net_mode != "f32" else "f32",
         "fc0_format": {"in_use": fc0_fmt, "in_use_short": fc0_short, "probe_rows": st.get("probe_rows"), "probe_limit": st.get("probe_limit"),
@@ -843,14 +901,6 @@ def main():
         "children_kernel_launches": {"k_sib_children2": st.get("children2_launches"), "k_sib_children": st.get("children1_launches"),
                                      "note": "sibling rounds of the timed region by the kernel that evaluated the runs' children: k_sib_children2 on the difference path "
                                              "(rounds of >= 2048 rows at N = 15 in the mixed operand format, >= 3072 in the fp6 / f16 formats, >= 1024 at N = 9), k_sib_children on the copy path (smaller rounds)"},
-        "data": "synthetic (empty boards, random-init net seed 0)",
-        "config": {"workload": f"{games} concurrent {n}x{n} games per GPU, {args.sims} sims/move, K={k}, two trees per game"
-                               + ("" if complete else f", first {args.max_plies} plies only (games/s extrapolated)"),
-                   "games_per_gpu": games, "board": n, "sims_per_move": args.sims, "batch_k": k,
-                   "warmup_step": f"episode cut after {args.warmup_plies} plies" if args.warmup_plies else "whole episode",
-                   "parallelism": f"games sharded x{world}, no hot-path collective" + (f", {'RCCL' if backend == 'nccl' else backend} all-gather-v of replay tuples per episode" if args.gather else "")},
-        "mcts_sims_per_s": sims / dt, "nn_evals_per_s": evals / dt, "plies_per_s": ply_games / dt,
-        "mean_plies_per_game": mean_plies, "games_finished": finished,
         "roofline": mfma_roofline(dominant, flop_trunk if dominant == "k_trunk" else flop_fc0, note_trunk if dominant == "k_trunk" else note_fc0),
         "roofline_trunk": mfma_roofline("k_trunk", flop_trunk, note_trunk),
         "roofline_fc0": mfma_roofline("k_fc0_mx", flop_fc0, note_fc0),
@@ -873,13 +923,12 @@ def main():
         "rank0_kernel_ms": {kk: st[kk] for kk in ("ms_round", "ms_tree", "ms_trunk", "ms_fc0", "ms_tail", "ms_ply")},
         "rank0_kernel_ms_method": f"HIP events on the engine's stream around every kernel category of 1 search round in {max(1, args.profile_every)} "
                                   "(ply-level work: always), sampled sums scaled by rounds seen / rounds timed",
-        "rank0_timed_region_ms": 1e3 * dt,
         "game_length_percentiles": {str(q): float(np.percentile(plies, q)) for q in (0, 10, 25, 50, 75, 90, 99, 100)},
         "arena": {"max_nodes": max_nodes, "max_tables": max_tables, "peak_nodes": st["peak_nodes"], "peak_tables": st["peak_tables"]},
         "cpu_baseline": None,
         "clocks": clocks,
         "seconds_since_process_start": elapsed(),
-    }
+    })
     if clocks and clocks["sclk_mhz_busy_median"] > 0:
         # `peak` is quoted at the boost clock (2400 MHz); the well-filled rounds run at the package power limit, below it: the same fraction against the peak at the clock they got
         scale = BOOST_SCLK_MHZ / clocks["sclk_mhz_busy_median"]
@@ -889,11 +938,6 @@ def main():
             if out[key].get("frac_executed") is not None:
                 out[key]["frac_executed_at_sustained_clock"] = out[key]["frac_executed"] * scale
         clocks["boost_sclk_mhz"] = BOOST_SCLK_MHZ
-    if args.gather:
-        out["replay_gather"] = {"records_per_episode": gathered["records"] / max(args.steps, 1), "bytes_per_episode": gathered["bytes"] / max(args.steps, 1),
-                                "seconds_per_episode": gathered["seconds"] / max(args.steps, 1), "inside_timed_region": True,
-                                "method": "8 x int64 counts all-gather, then exact-size grouped send/recv (all-gather-v)", "backend": "RCCL" if backend == "nccl" else backend,
-                                "last_counts": gathered.get("last_counts"), "last_ids": gathered.get("last_ids")}
     emit(out, final=False)  # the measured line exists from here on, whatever happens to the extra legs
 
     # ---- extra legs, outside the timed region, only while the wall-clock budget has room ----------------------------

@@ -58,6 +58,19 @@ class SelfPlay:
         g = self.eng.games
         return np.zeros(g, np.uint8), np.full(g, 2, np.uint8), np.full(g, 10, np.int32)
 
+    def replay(self, game):
+        """10 plies per game (game_info), synthetic tuples keyed by the global game id and the episode"""
+        hw, gid = self.eng.hw, self.eng.game_offset + game
+        boards = np.zeros((10, hw), np.uint8)
+        for i in range(1, 10):
+            boards[i] = boards[i - 1]
+            boards[i, (gid + 7 * i) % hw] = 1 + (i - 1) % 2
+        pi = np.full((10, hw), 1.0 / hw, np.float32)
+        pi[:, gid % hw] += 0.5 * self.eng.episodes
+        z = np.zeros(10, np.float32)
+        z[-1] = 1.0
+        return boards, np.arange(10, dtype=np.uint8) % 2, pi, z
+
     def replay_record_bytes(self):
         return (self.eng.hw + 1 + 3) // 4 * 4 + 4 * self.eng.hw + 4
 

@@ -21,7 +21,7 @@ def _run(args, tmp_path, extra_env=None):
 
 
 def test_bench_self_launches_two_ranks_and_gathers_exact_counts(tmp_path):
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--games", "6", "--gather", "--cpu-seconds", "0"], tmp_path)
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--games", "6", "--gather", "--cpu-seconds", "0", "--full"], tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
     assert lines, r.stdout + r.stderr[-2000:]
@@ -68,7 +68,7 @@ def test_result_line_is_short_and_complete(tmp_path):
     and carries the contract's keys, `roofline` and `cpu_baseline` (here: the mock engine + the real CPU leg, bounded to a few seconds); the verbose record goes
     to the sidecar file."""
     full = tmp_path / "full.json"
-    r = _run(["--steps", "1", "--warmup", "0", "--games", "4", "--cpu-seconds", "14"], tmp_path, {"OMOK_BENCH_FULL": str(full)})
+    r = _run(["--steps", "1", "--warmup", "0", "--games", "4", "--cpu-seconds", "14", "--full"], tmp_path, {"OMOK_BENCH_FULL": str(full)})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 2 and all(len(x) < 8000 for x in lines)
@@ -86,6 +86,44 @@ def test_result_line_is_short_and_complete(tmp_path):
     rec = json.load(open(full))  # the verbose record of the same run
     assert rec["value"] == first["value"] or abs(rec["value"] - first["value"]) <= 1e-4 * abs(rec["value"])
     assert "legs" in rec["cpu_baseline"] and "mm_calibration_tflops_by_threads" in rec["cpu_baseline"]
+
+
+def test_plain_run_prints_one_headline_line(tmp_path):
+    """Without --full: one line with the headline figures, no kernel-category timing, no extra leg, no verbose record; --steps sets the timed steps."""
+    full = tmp_path / "full.json"
+    r = _run(["--steps", "3", "--warmup", "1", "--games", "4"], tmp_path, {"OMOK_BENCH_FULL": str(full)})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["unit"] == "games/s" and out["higher_is_better"] is True and out["value"] > 0
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["games_finished"] == 3 * 4  # the mock finishes every game of every timed step
+    assert out["config"]["warmup_step"] == "whole episode"  # a warm-up step costs what a timed step does: (warmup + steps) x ms_per_step is the time in steps
+    assert abs(3 * out["ms_per_step"] - out["rank0_timed_region_ms"]) <= 1e-3 * out["rank0_timed_region_ms"]
+    assert not any(k.startswith(("roofline", "rank0_kernel_ms", "precision", "value_")) for k in out)
+    assert "cpu_baseline" not in out and "clocks" not in out and not full.exists()
+
+
+def test_dump_outputs_are_float_arrays_equal_from_run_to_run(tmp_path):
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = _run(["--steps", "2", "--games", "70", "--dump-outputs", str(d)], tmp_path)
+        assert r.returncode == 0, r.stderr[-2000:]
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {"game_status.npy", "game_plies.npy", "replay_game.npy", "replay_board.npy", "replay_turn.npy", "replay_pi.npy", "replay_z.npy"} == set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    games = np.load(dirs[0] / "replay_game.npy")
+    assert len(np.unique(games)) == 64 and len(games) == 64 * 10  # a fixed sample of the 70 games, all 10 tuples of each
+    assert np.load(dirs[0] / "replay_pi.npy").shape == (640, 225) and np.load(dirs[0] / "game_status.npy").shape == (70,)
 
 
 def test_compact_line_of_a_real_verbose_record():

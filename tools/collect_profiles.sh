@@ -6,7 +6,7 @@
 # 3. rocprofv3 --pmc passes over the SAME self-play workload (first 2 plies: 100 rounds of 65536 rows, tree kernels included),
 #    one counter group per pass, --kernel-trace only (no other trace domain)  -> pmc_selfplay_c2_first2plies.txt, pmc_bytes.json
 out=${1:-gpurun_out/r02}; mkdir -p $out; R=$PWD
-echo "[1] bench"; python3 bench.py --steps 1 --warmup 1 > $out/bench_c2_full_episode.json 2> $out/bench.err || exit 1
+echo "[1] bench"; python3 bench.py --full --steps 1 --warmup 1 > $out/bench_c2_full_episode.json 2> $out/bench.err || exit 1
 tail -c 300 $out/bench_c2_full_episode.json; echo
 cd /tmp; export TMPDIR=/tmp
 echo "[2] kernel stats"
