@@ -116,12 +116,17 @@ pub mod ffi {
         pub fn omok_net_commit(e: *mut OmokEngine) -> c_int;
         pub fn omok_net_load_file(e: *mut OmokEngine, path: *const c_char) -> c_int;
         pub fn omok_net_save_file(e: *mut OmokEngine, path: *const c_char) -> c_int;
+        pub fn omok_net2_load(e: *mut OmokEngine, index: c_int, data: *const f32, count: i64) -> c_int;
+        pub fn omok_net2_commit(e: *mut OmokEngine) -> c_int;
+        pub fn omok_net2_load_file(e: *mut OmokEngine, path: *const c_char) -> c_int;
+        pub fn omok_net2_info(e: *mut OmokEngine, fc0_format: *mut i32, probe_outside: *mut i32, evals: *mut f64) -> c_int;
         pub fn omok_evaluate_pv(e: *mut OmokEngine, input: *const f32, batch: i32, p: *mut f32, v: *mut f32) -> c_int;
         pub fn omok_evaluate_logits(e: *mut OmokEngine, input: *const f32, batch: i32, logits: *mut f32, vpre: *mut f32) -> c_int;
         pub fn omok_env_play(e: *mut OmokEngine, moves: *const i32, batch: i32, len: i32, status_out: *mut i32, boards_out: *mut u8, turns_out: *mut u8, legal_out: *mut u16) -> c_int;
         pub fn omok_encode_nn_input(e: *mut OmokEngine, boards: *const u8, turns: *const u8, batch: i32, mode: i32, out: *mut f32) -> c_int;
         pub fn omok_env_place_stone(e: *mut OmokEngine, boards: *mut u8, turns: *mut u8, legal: *mut u16, actions: *const i32, batch: i32, status_out: *mut i32) -> c_int;
         pub fn omok_selfplay_reset(e: *mut OmokEngine) -> c_int;
+        pub fn omok_match_reset(e: *mut OmokEngine, split: i32) -> c_int;
         pub fn omok_set_episode(e: *mut OmokEngine, episode: u64) -> c_int;
         pub fn omok_execute(e: *mut OmokEngine, count: i32, batch_size: i32, epsilon: f32, alpha: f32) -> c_int;
         pub fn omok_execute_shared(e: *mut OmokEngine, count: i32, batch_size: i32, epsilon: f32, alpha: f32, waves: i32) -> c_int;

@@ -95,6 +95,20 @@ int omok_net_load_file(omok_engine* e, const char* path);
 /* ModelIO::save (model_io.rs:59-90): writes the same format from the tensors currently loaded (canonical names
  * conv_w, conv_b, residual_{i}_..., fc0_w, ...; the reference stores TF-uniquified names and never reads them back). */
 int omok_net_save_file(omok_engine* e, const char* path);
+/* ---- second net slot: the model of the second agent of benchmark/src/main.rs:14-108 (each Agent of benchmark/src/agent.rs holds its own
+ *      AgentModel).  Same tensors, same life cycle and the same commit-time fc0 format probe (net_mode of the engine) as net 1 above; the
+ *      slot's device buffers are allocated on its first load.  Only match episodes (omok_match_reset) evaluate it: every other entry point
+ *      uses net 1.  The omok_debug_* switches act on net 1 only (net 2 keeps their defaults), and every OMOK_STAT_* figure that describes a
+ *      net -- fc0 format and probe, children-kernel launches, the work counters -- describes net 1 (in a match: net 1's share of the rows);
+ *      net 2's commit outcome and the rows each net evaluated are in omok_net2_info. */
+int omok_net2_load(omok_engine* e, int index, const float* data, int64_t count);
+int omok_net2_commit(omok_engine* e);
+/* ModelIO::load (model_io.rs:92-120) into net 2, as omok_net_load_file; commits net 2 on success */
+int omok_net2_load_file(omok_engine* e, const char* path);
+/* Net 2's commit outcome (OMOK_STAT_FC0_FORMAT / OMOK_STAT_PROBE_OUTSIDE keep describing net 1): *fc0_format = -1 (fp32 kernels), 0 fp6,
+ * 1 f16, 2 mixed; *probe_outside as OMOK_STAT_PROBE_OUTSIDE.  evals [2] (may be NULL): rows evaluated by net 1 / net 2 in match episodes
+ * since omok_reset_stats (search rounds and mirror evaluations).  Each pointer may be NULL.  OMOK_ERR_STATE before omok_net2_commit. */
+int omok_net2_info(omok_engine* e, int32_t* fc0_format, int32_t* probe_outside, double* evals);
 /* AgentModel::evaluate_pv (agent_model.rs:116-134): in [B][N][N][3] f32 (encoder.rs layout),
  * p [B][N*N] softmax probabilities, v [B] tanh.  evaluate_p (:105-114) = same with v NULL. */
 int omok_evaluate_pv(omok_engine* e, const float* in, int32_t batch, float* p, float* v);
@@ -126,6 +140,19 @@ int omok_env_place_stone(omok_engine* e, uint8_t* boards, uint8_t* turns, uint16
  * (src/trainer.rs:74-93, fresh thread_rng draws): it takes RNG stream `episode` and advances the counter; the first reset
  * after omok_create is episode 0. */
 int omok_selfplay_reset(omok_engine* e);
+/* Match episode: net 1 against net 2 (benchmark/src/main.rs:14-108).  Agent::new of every agent with its OWN net (agent.rs:16-35): in games
+ * [0, split) net 1 plays Black (tree side 0) and net 2 White (side 1); in games [split, G) the colours are reversed (main.rs plays half of
+ * its games each way).  0 <= split <= G.  RNG streams, the episode counter and the replay buffer as omok_selfplay_reset.  Until the next
+ * omok_selfplay_reset every evaluation uses the net of the tree it serves: the search requests of omok_execute / omok_selfplay_run /
+ * omok_round_* that of the side-to-move tree (Agent::search with its own model, main.rs:71-78,91-98), the ensure_action_exists rows of
+ * omok_advance / omok_selfplay_run / omok_mirror_* that of the OPPONENT's tree (main.rs:79-82,99-102); the step-wise calls keep their row
+ * order (game order).  A whole match is omok_selfplay_run (threshold = 0: sample_action(Best) every move, as main.rs:77,97); per-game
+ * results from omok_game_info.  With the same weights in both slots a match reproduces omok_selfplay_reset + the same calls bit for bit
+ * (board_size 9, OMOK_NET_F16X3_ROWS, OMOK_NET_F32; in the default net mode at board_size 15 each net's sibling rounds group fewer rows:
+ * ~5e-5 of path-dependent rounding, see OMOK_NET_F16X3_ROWS).  omok_play_actions, omok_execute_shared(_recorded) and
+ * omok_selfplay_run_slots return OMOK_ERR_STATE in a match episode.  OMOK_ERR_STATE without a committed net 2, OMOK_ERR_INVALID for a
+ * split outside [0, G]. */
+int omok_match_reset(omok_engine* e, int32_t split);
 /* index of the RNG stream the NEXT omok_selfplay_reset uses (resuming a training run at iteration i: omok_set_episode(e, i)) */
 int omok_set_episode(omok_engine* e, uint64_t episode);
 /* ParallelMCTSExecutor::execute (alpha-zero/src/parallel_mcts_executor.rs:26-35) on the

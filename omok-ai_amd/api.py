@@ -7,6 +7,8 @@ Names follow the reference so parity tests read like its own code:
   SelfPlay.execute                 ParallelMCTSExecutor::execute, alpha-zero/src/parallel_mcts_executor.rs:26-35
   SelfPlay.sample_actions/advance  Agent::{sample_action, play_action, ensure_action_exists}, agent.rs:83-232
   SelfPlay.run                     Trainer::train self-play phase, src/trainer.rs:95-205
+  Engine.load_weights2 / load2     the second agent's AgentModel of benchmark/src/main.rs:14-108
+  SelfPlay.match_reset             benchmark/src/main.rs: net 1 against net 2, half of the games per colour
 All compute happens in the HIP library; nothing here has a CPU path.
 """
 import ctypes as C
@@ -73,6 +75,27 @@ class Engine:
 
     def load_random_weights(self, seed=0):
         self.load_weights(W.init_random(self.n, seed))
+
+    # ---- second net slot (match episodes) ---------------------------------------------------
+    def load_weights2(self, tensors):
+        """net 2 from 31 tensors (same order as load_weights), committed with its own fc0 format probe"""
+        assert len(tensors) == B.lib().omok_net_num_tensors()
+        for i, t in enumerate(tensors):
+            t = np.ascontiguousarray(t, dtype=np.float32).ravel()
+            self._chk(B.lib().omok_net2_load(self.h, i, B.fptr(t), t.size))
+        self._chk(B.lib().omok_net2_commit(self.h))
+
+    def load2(self, path):
+        """net 2 from a ModelIO weights file (omok_net2_load_file)"""
+        self._chk(B.lib().omok_net2_load_file(self.h, os.fsencode(path)))
+
+    def net2_info(self):
+        """net 2's commit outcome and the rows each net evaluated in match episodes since reset_stats:
+        {"fc0_format": "fp6" | "f16" | "mixed" | "f32", "probe_outside": int, "evals": (net 1, net 2)}"""
+        fmt, outside = C.c_int32(), C.c_int32()
+        ev = (C.c_double * 2)()
+        self._chk(B.lib().omok_net2_info(self.h, C.byref(fmt), C.byref(outside), ev))
+        return {"fc0_format": B.FC0_FORMATS[fmt.value], "probe_outside": outside.value, "evals": (ev[0], ev[1])}
 
     def evaluate_pv(self, inputs):
         x = np.ascontiguousarray(inputs, dtype=np.float32).reshape(-1, 3 * self.hw)
@@ -196,6 +219,11 @@ class SelfPlay:
 
     def reset(self):
         self._chk(B.lib().omok_selfplay_reset(self.h))
+
+    def match_reset(self, split):
+        """Match episode (omok_match_reset): in games [0, split) net 1 plays Black and net 2 White, in [split, G) the reverse; every
+        evaluation uses the net of the tree it serves until the next reset().  A whole match is run(..., threshold=0)."""
+        self._chk(B.lib().omok_match_reset(self.h, int(split)))
 
     def set_episode(self, episode):
         """index of the RNG stream the NEXT reset uses (each reset = one trainer iteration advances it by itself)"""

@@ -26,7 +26,7 @@ STAT_NAMES = ["sims", "evals", "ply_games", "finished", "ms_tree", "ms_trunk", "
 # every symbol include/omok_mi355x.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "omok_create", "omok_destroy", "omok_last_error", "omok_net_num_tensors", "omok_net_tensor_size", "omok_net_load",
-    "omok_net_commit", "omok_net_load_file", "omok_net_save_file", "omok_evaluate_pv", "omok_evaluate_logits", "omok_env_play", "omok_env_place_stone", "omok_encode_nn_input", "omok_selfplay_reset", "omok_set_episode", "omok_execute", "omok_execute_shared", "omok_execute_shared_recorded",
+    "omok_net_commit", "omok_net_load_file", "omok_net_save_file", "omok_net2_load", "omok_net2_commit", "omok_net2_load_file", "omok_net2_info", "omok_match_reset", "omok_evaluate_pv", "omok_evaluate_logits", "omok_env_play", "omok_env_place_stone", "omok_encode_nn_input", "omok_selfplay_reset", "omok_set_episode", "omok_execute", "omok_execute_shared", "omok_execute_shared_recorded",
     "omok_compute_policy", "omok_play_actions", "omok_set_actions", "omok_root_children",
     "omok_sample_actions", "omok_advance", "omok_selfplay_run", "omok_selfplay_run_slots", "omok_round_generate", "omok_round_inputs",
     "omok_round_eval", "omok_round_outputs", "omok_round_logits", "omok_round_inject", "omok_round_scatter", "omok_mirror_generate",
@@ -78,6 +78,11 @@ def lib():
     L.omok_net_commit.argtypes = [H]
     L.omok_net_load_file.argtypes = [H, C.c_char_p]
     L.omok_net_save_file.argtypes = [H, C.c_char_p]
+    L.omok_net2_load.argtypes = [H, C.c_int, fp, C.c_int64]
+    L.omok_net2_commit.argtypes = [H]
+    L.omok_net2_load_file.argtypes = [H, C.c_char_p]
+    L.omok_net2_info.argtypes = [H, ip, ip, C.POINTER(C.c_double)]
+    L.omok_match_reset.argtypes = [H, C.c_int32]
     L.omok_evaluate_pv.argtypes = [H, fp, C.c_int32, fp, fp]
     L.omok_evaluate_logits.argtypes = [H, fp, C.c_int32, fp, fp]
     L.omok_env_play.argtypes = [H, ip, C.c_int32, C.c_int32, ip, u8p, u8p, C.POINTER(C.c_uint16)]

@@ -158,6 +158,15 @@ void launch_replay_augment(int n, const Store& S, const long long* offsets_dev, 
                            uint8_t* dst_dev, long long cap_records, hipStream_t st);
 size_t advance_lds_bytes(int cap_nodes, int cap_tables);
 
+// match episodes (omok_match_reset; tree side * G + g is evaluated by net side ^ (g >= split)): the dense list of trees of `tree_side` in S.req_ref,
+// S.d_count[0] rows -> block 0 (games < split) stays there, cnt[0] rows; block 1 is copied to ref2 / aux2, cnt[1] rows; evals[net] += the rows of each net
+void launch_match_split(const Store& S, int tree_side, int split, uint32_t* ref2, uint32_t* aux2, int32_t* cnt, unsigned long long* evals, int max_rows,
+                        hipStream_t st);
+// block 1's outputs (v2 and / or p2 [rows][rowp], NULL: skipped) behind block 0's in v1 / p1: one array in list order
+void launch_match_join(const int32_t* cnt, const float* v2, float* v1, const float* p2, float* p1, int rowp, int max_rows, hipStream_t st);
+// the root policy of the trees net 2 owns (after launch_reset with net 1's)
+void launch_match_roots(int n, const Store& S, const float* root_policy2, int split, hipStream_t st);
+
 // ---- net_kernels.hip --------------------------------------------------------------------------
 struct NetBuffers; // defined in net.h
 } // namespace omok

@@ -97,6 +97,16 @@ struct omok_engine {
     uint8_t* d_has = nullptr;           // [G]
     long long* d_aug_offsets = nullptr; // [games + 1] first augmented-replay record of every game
     uint8_t* d_aug_scratch = nullptr;   // one game's 6 * HW records (omok_replay_augmented_game)
+    // second net slot and match episodes (omok_net2_*, omok_match_reset)
+    Net* net2 = nullptr;                // allocated on its first load
+    bool match = false;                 // the current episode is a match: tree side * G + g is evaluated by net side ^ (g >= split) (0 = net, 1 = net2)
+    int split = 0;
+    int match_cnt[2] = {0, 0};          // rows of the two blocks of the pending step-wise round / mirror batch (launch_match_split)
+    uint32_t* d_mref = nullptr;         // [max_b] the second block's request list
+    uint32_t* d_maux = nullptr;
+    int32_t* d_mcnt = nullptr;          // [0] rows of the first block (games < split), [1] of the second
+    unsigned long long* d_mevals = nullptr; // [2] rows evaluated by net 1 / net 2 in match episodes
+    float* d_root_policy2 = nullptr;
     // host-side stats
     double sims = 0, evals = 0, ply_games = 0, finished = 0;
     uint32_t peak_nodes = 0, peak_tables = 0;
@@ -185,9 +195,26 @@ extern "C" void omok_destroy(omok_engine* e) {
     if (e->st) hipStreamSynchronize(e->st);
     e->prof.destroy();
     net_free(e->net);
+    if (e->net2) { net_free(*e->net2); delete e->net2; }
     for (void* p : e->allocs) hipFree(p);
     if (e->st) hipStreamDestroy(e->st);
     delete e;
+}
+
+// a Net of this engine's board size, net mode and batch capacity (before net_alloc)
+static void configure_net(omok_engine* e, Net& net, int max_b) {
+    const omok_config* cfg = &e->cfg;
+    net.device = cfg->device;
+    net.n = e->n;
+    net.hw = e->hw;
+    net.rowp = e->rowp;
+    net.mode = cfg->net_mode == OMOK_NET_F32 ? OMOK_NET_F32 : OMOK_NET_F16X3;
+    net.siblings = cfg->net_mode != OMOK_NET_F16X3_ROWS;
+    net.fc0_policy = cfg->net_mode == OMOK_NET_F16X3_FP6 ? FC0_FP6 : cfg->net_mode == OMOK_NET_F16X3_F16 ? FC0_F16
+                   : cfg->net_mode == OMOK_NET_F16X3_MIXED ? FC0_MIXED : FC0_AUTO;
+    net.max_b = max_b;
+    net.games = cfg->games;
+    for (int i = 0; i < NET_TENSORS; ++i) net.wsize[i] = net_tensor_size(e->n, i);
 }
 
 extern "C" int omok_create(const omok_config* cfg, omok_engine** out) {
@@ -286,17 +313,7 @@ extern "C" int omok_create(const omok_config* cfg, omok_engine** out) {
         omok_destroy(e);
         return OMOK_ERR_HIP;
     }
-    e->net.device = cfg->device;
-    e->net.n = e->n;
-    e->net.hw = e->hw;
-    e->net.rowp = e->rowp;
-    e->net.mode = cfg->net_mode == OMOK_NET_F32 ? OMOK_NET_F32 : OMOK_NET_F16X3;
-    e->net.siblings = cfg->net_mode != OMOK_NET_F16X3_ROWS;
-    e->net.fc0_policy = cfg->net_mode == OMOK_NET_F16X3_FP6 ? FC0_FP6 : cfg->net_mode == OMOK_NET_F16X3_F16 ? FC0_F16
-                      : cfg->net_mode == OMOK_NET_F16X3_MIXED ? FC0_MIXED : FC0_AUTO;
-    e->net.max_b = (int)max_b;
-    e->net.games = cfg->games;
-    for (int i = 0; i < NET_TENSORS; ++i) e->net.wsize[i] = net_tensor_size(e->n, i);
+    configure_net(e, e->net, (int)max_b);
     if (net_alloc(e->net) == 0) {
         g_create_error = "net buffer allocation failed (hipMalloc)";
         omok_destroy(e);
@@ -315,28 +332,76 @@ extern "C" int omok_create(const omok_config* cfg, omok_engine** out) {
 extern "C" int omok_net_num_tensors(void) { return NET_TENSORS; }
 extern "C" int64_t omok_net_tensor_size(const omok_engine* e, int index) { return e ? net_tensor_size(e->n, index) : -1; }
 
-extern "C" int omok_net_load(omok_engine* e, int index, const float* data, int64_t count) {
+static int sync_and_check(omok_engine* e, const char* what);
+
+// net slot 1 = e->net, slot 2 = *e->net2 (allocated on its first load, with the buffers of the match episodes: engines that never load it pay nothing)
+static int net2_alloc(omok_engine* e) {
+    if (e->net2) return 0;
+    // the match buffers first: e->net2 is set only once everything a match needs exists (a failed attempt leaves the slot empty, the next load retries;
+    // buffers an earlier attempt did allocate are kept)
+    const size_t mb = (size_t)e->net.max_b;
+    if (!e->d_mref && dalloc(e, &e->d_mref, mb)) return OMOK_ERR_HIP;
+    if (!e->d_maux && dalloc(e, &e->d_maux, mb)) return OMOK_ERR_HIP;
+    if (!e->d_mcnt && dalloc(e, &e->d_mcnt, 4)) return OMOK_ERR_HIP;
+    if (!e->d_mevals && dalloc(e, &e->d_mevals, 2)) return OMOK_ERR_HIP;
+    if (!e->d_root_policy2 && dalloc(e, &e->d_root_policy2, (size_t)e->rowp)) return OMOK_ERR_HIP;
+    HIPCHK(e, hipMemset(e->d_mcnt, 0, 16));
+    HIPCHK(e, hipMemset(e->d_mevals, 0, 16));
+    Net* n2 = new Net();
+    configure_net(e, *n2, e->net.max_b);
+    if (net_alloc(*n2) == 0) { delete n2; return fail(e, OMOK_ERR_HIP, "net 2 buffer allocation failed (hipMalloc)"); } // (net_alloc frees what it got)
+    e->net2 = n2;
+    return 0;
+}
+
+static int net_load_slot(omok_engine* e, int slot, int index, const float* data, int64_t count) {
     if (!e || !data) return OMOK_ERR_INVALID;
     if (index < 0 || index >= NET_TENSORS) return fail(e, OMOK_ERR_INVALID, "tensor index %d out of range", index);
     if (count != e->net.wsize[index]) return fail(e, OMOK_ERR_INVALID, "tensor %d: expected %lld values, got %lld", index, (long long)e->net.wsize[index], (long long)count);
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipMemcpyAsync(e->net.w[index], data, sizeof(float) * (size_t)count, hipMemcpyHostToDevice, e->st));
+    if (slot == 2 && net2_alloc(e)) return OMOK_ERR_HIP;
+    Net& net = slot == 2 ? *e->net2 : e->net;
+    HIPCHK(e, hipMemcpyAsync(net.w[index], data, sizeof(float) * (size_t)count, hipMemcpyHostToDevice, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
-    e->net.loaded[index] = true;
-    e->net.committed = false;
+    net.loaded[index] = true;
+    net.committed = false;
     return OMOK_OK;
 }
 
-extern "C" int omok_net_commit(omok_engine* e) {
+static int net_commit_slot(omok_engine* e, int slot) {
     if (!e) return OMOK_ERR_INVALID;
+    if (slot == 2 && !e->net2) return fail(e, OMOK_ERR_STATE, "net 2: no tensor was ever loaded");
+    Net& net = slot == 2 ? *e->net2 : e->net;
     for (int i = 0; i < NET_TENSORS; ++i)
-        if (!e->net.loaded[i]) return fail(e, OMOK_ERR_STATE, "tensor %d was never loaded", i);
+        if (!net.loaded[i]) return fail(e, OMOK_ERR_STATE, "tensor %d was never loaded", i);
     HIPCHK(e, hipSetDevice(e->cfg.device));
     if (e->round_reqs >= 0 || e->mirror_reqs >= 0) return fail(e, OMOK_ERR_STATE, "omok_net_commit while a round / mirror batch is pending");
-    if (net_commit(e->net, e->S, e->st) != 0) return fail(e, OMOK_ERR_HIP, "weight packing / format probe failed");
-    net_invalidate_sibling_cache(e->net); // (new weights: cached base evaluations are void)
+    if (net_commit(net, e->S, e->st) != 0) return fail(e, OMOK_ERR_HIP, "weight packing / format probe failed");
+    net_invalidate_sibling_cache(net); // (new weights: cached base evaluations are void)
     HIPCHK(e, hipStreamSynchronize(e->st));
-    e->net.committed = true;
+    net.committed = true;
+    return OMOK_OK;
+}
+
+extern "C" int omok_net_load(omok_engine* e, int index, const float* data, int64_t count) { return net_load_slot(e, 1, index, data, count); }
+extern "C" int omok_net_commit(omok_engine* e) { return net_commit_slot(e, 1); }
+extern "C" int omok_net2_load(omok_engine* e, int index, const float* data, int64_t count) { return net_load_slot(e, 2, index, data, count); }
+extern "C" int omok_net2_commit(omok_engine* e) { return net_commit_slot(e, 2); }
+
+extern "C" int omok_net2_info(omok_engine* e, int32_t* fc0_format, int32_t* probe_outside, double* evals) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (!e->net2 || !e->net2->committed) return fail(e, OMOK_ERR_STATE, "net 2 not loaded/committed (omok_net2_load x31 + omok_net2_commit)");
+    ENTER(e);
+    const Net& n2 = *e->net2;
+    if (fc0_format) *fc0_format = n2.mode == OMOK_NET_F32 ? -1 : (n2.diff_fp6 ? FC0_MIXED : n2.fc0_fmt);
+    if (probe_outside) *probe_outside = n2.probe_outside;
+    if (evals) {
+        unsigned long long ev[2] = {0, 0};
+        if (sync_and_check(e, "net2_info")) return OMOK_ERR_HIP;
+        HIPCHK(e, hipMemcpy(ev, e->d_mevals, sizeof(ev), hipMemcpyDeviceToHost));
+        evals[0] = (double)ev[0];
+        evals[1] = (double)ev[1];
+    }
     return OMOK_OK;
 }
 
@@ -367,7 +432,7 @@ static bool wr_u64(FILE* f, uint64_t v) {
     return fwrite(b, 1, 8, f) == 8;
 }
 
-extern "C" int omok_net_load_file(omok_engine* e, const char* path) {
+static int net_load_file_slot(omok_engine* e, int slot, const char* path) {
     if (!e || !path) return OMOK_ERR_INVALID;
     FILE* f = fopen(path, "rb");
     if (!f) return fail(e, OMOK_ERR_INVALID, "cannot open weights file %s", path);
@@ -396,10 +461,12 @@ extern "C" int omok_net_load_file(omok_engine* e, const char* path) {
         if (fread(params[i].data(), sizeof(float), (size_t)len, f) != (size_t)len) { rc = fail(e, OMOK_ERR_INVALID, "weights file %s: truncated inside parameter %d", path, i); break; }
     }
     fclose(f);
-    for (int i = 0; rc == OMOK_OK && i < NET_TENSORS; ++i) rc = omok_net_load(e, i, params[i].data(), (int64_t)params[i].size());
+    for (int i = 0; rc == OMOK_OK && i < NET_TENSORS; ++i) rc = net_load_slot(e, slot, i, params[i].data(), (int64_t)params[i].size());
     if (rc != OMOK_OK) return rc;
-    return omok_net_commit(e);
+    return net_commit_slot(e, slot);
 }
+extern "C" int omok_net_load_file(omok_engine* e, const char* path) { return net_load_file_slot(e, 1, path); }
+extern "C" int omok_net2_load_file(omok_engine* e, const char* path) { return net_load_file_slot(e, 2, path); }
 
 extern "C" int omok_net_save_file(omok_engine* e, const char* path) {
     if (!e || !path) return OMOK_ERR_INVALID;
@@ -429,6 +496,50 @@ extern "C" int omok_net_save_file(omok_engine* e, const char* path) {
 
 static int need_net(omok_engine* e) {
     if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    if (e->match && !e->net2->committed) return fail(e, OMOK_ERR_STATE, "match episode: net 2 was reloaded and not committed (omok_net2_commit)");
+    return 0;
+}
+
+// ---- match episodes: routing --------------------------------------------------------------------
+// net index 0 = e->net (net 1), 1 = *e->net2.  A dense list of the trees of `tree_side` falls into block 0 (games < split: net tree_side) and
+// block 1 (games >= split: the other net), see launch_match_split.
+static Net& net_at(omok_engine* e, int idx) { return idx == 0 ? e->net : *e->net2; }
+static void invalidate_nets(omok_engine* e) { // the trees changed outside the search rounds: both nets' cached base evaluations are void
+    net_invalidate_sibling_cache(e->net);
+    if (e->net2) net_invalidate_sibling_cache(*e->net2);
+}
+static bool block_live(const omok_engine* e, int b) { return b == 0 ? e->split > 0 : e->split < e->cfg.games; } // (false: the block has no game)
+static Store block_view(const omok_engine* e, int b) { // the block's rows as a dense list of its own
+    Store V = e->S;
+    if (b == 0) V.d_count = e->d_mcnt;
+    else { V.req_ref = e->d_mref; V.req_aux = e->d_maux; V.d_count = e->d_mcnt + 1; }
+    return V;
+}
+// one forward of block b's rows by its net (search rounds: sibling_side = the trees' side; its k_group takes the block's games only)
+static void match_forward(omok_engine* e, int b, int tree_side, int max_count, int sibling_side, bool skip_softmax) {
+    Net& X = net_at(e, tree_side ^ b);
+    X.grp_lo = b ? e->split : 0;
+    X.grp_hi = b ? e->cfg.games : e->split;
+    X.grp_sub = b ? e->d_mcnt : nullptr;
+    net_forward_requests(X, block_view(e, b), max_count, e->st, &e->prof, sibling_side, skip_softmax);
+    X.grp_hi = -1;
+    X.grp_sub = nullptr;
+}
+static void match_split(omok_engine* e, int tree_side, int max_rows) {
+    launch_match_split(e->S, tree_side, e->split, e->d_mref, e->d_maux, e->d_mcnt, e->d_mevals, max_rows, e->st);
+}
+// block 1's v (and p) behind block 0's, in the first block's net: one array in list order for k_scatter / k_round / k_advance
+static void match_join(omok_engine* e, int tree_side, bool p, int max_rows) {
+    if (!block_live(e, 1)) return;
+    Net &A = net_at(e, tree_side), &B = net_at(e, tree_side ^ 1);
+    launch_match_join(e->d_mcnt, B.v, A.v, p ? B.p : nullptr, p ? A.p : nullptr, e->rowp, max_rows, e->st);
+}
+static int match_counts(omok_engine* e) { // the pending batch's block sizes -> host
+    HIPCHK(e, hipMemcpyAsync(e->match_cnt, e->d_mcnt, sizeof(e->match_cnt), hipMemcpyDeviceToHost, e->st));
+    return sync_and_check(e, "match counts") ? OMOK_ERR_HIP : 0;
+}
+static int no_match(omok_engine* e, const char* what) {
+    if (e->match) return fail(e, OMOK_ERR_STATE, "%s is not available in a match episode (omok_match_reset): start self-play with omok_selfplay_reset", what);
     return 0;
 }
 
@@ -557,30 +668,54 @@ static int tree_error(omok_engine* e, uint32_t bits) {
     return 0;
 }
 
-extern "C" int omok_selfplay_reset(omok_engine* e) {
-    if (!e) return OMOK_ERR_INVALID;
-    if (need_net(e)) return OMOK_ERR_STATE;
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    // Agent::new: evaluate_p on the empty board in Player mode (agent.rs:19-20); the result is the
-    // same for every tree of a fixed net, so it is computed once.
+// Agent::new: evaluate_p on the empty board in Player mode (agent.rs:19-20); the result is the same for every tree of a fixed net, so it is
+// computed once per net
+static int enqueue_root_policy(omok_engine* e, Net& net, float* dst) {
     std::vector<float> in(3 * (size_t)e->hw, 0.0f);
     for (int i = 2 * e->hw; i < 3 * e->hw; ++i) in[i] = 1.0f; // Black to move (encoder.rs:34-37)
     const int one = 1;
-    HIPCHK(e, hipMemcpyAsync(e->net.in_f32, in.data(), sizeof(float) * in.size(), hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, hipMemcpyAsync(net.in_f32, in.data(), sizeof(float) * in.size(), hipMemcpyHostToDevice, e->st));
     HIPCHK(e, hipMemcpyAsync(e->S.d_count, &one, sizeof(int32_t), hipMemcpyHostToDevice, e->st));
-    net_forward_inputs(e->net, e->S, 1, e->st, &e->prof);
-    k_copy_root_policy<<<1, 256, 0, e->st>>>(e->net.p, e->d_root_policy, e->hw, e->rowp);
-    launch_reset(e->n, e->S, e->d_root_policy, e->st);
-    net_invalidate_sibling_cache(e->net);
-    if (sync_and_check(e, "selfplay_reset")) return OMOK_ERR_HIP;
+    net_forward_inputs(net, e->S, 1, e->st, &e->prof);
+    k_copy_root_policy<<<1, 256, 0, e->st>>>(net.p, dst, e->hw, e->rowp);
+    HIPCHK(e, hipStreamSynchronize(e->st)); // (the host input buffer goes out of scope)
     e->evals += 1;
+    return 0;
+}
+
+static int reset_episode(omok_engine* e, bool match, int split) {
+    if (enqueue_root_policy(e, e->net, e->d_root_policy)) return OMOK_ERR_HIP;
+    if (match && enqueue_root_policy(e, *e->net2, e->d_root_policy2)) return OMOK_ERR_HIP;
+    launch_reset(e->n, e->S, e->d_root_policy, e->st);
+    if (match) launch_match_roots(e->n, e->S, e->d_root_policy2, split, e->st);
+    invalidate_nets(e);
+    if (sync_and_check(e, match ? "match_reset" : "selfplay_reset")) return OMOK_ERR_HIP;
     e->key = e->cfg.seed + e->episode * 0x9E3779B97F4A7C15ULL; // a fresh RNG stream per episode (the reference draws thread_rng anew, trainer.rs:71-93)
     e->episode += 1;
     e->ply = 0;
     e->reset_done = true;
     e->sampled = false;
     e->round_reqs = e->mirror_reqs = -1;
+    e->match = match;
+    e->split = match ? split : 0;
     return OMOK_OK;
+}
+
+extern "C" int omok_selfplay_reset(omok_engine* e) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    return reset_episode(e, false, 0);
+}
+
+// benchmark/src/main.rs:14-108: net 1 against net 2, Agent::new of each agent with its own model (agent.rs:16-35)
+extern "C" int omok_match_reset(omok_engine* e, int32_t split) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    if (!e->net2 || !e->net2->committed) return fail(e, OMOK_ERR_STATE, "net 2 not loaded/committed (omok_net2_load x31 + omok_net2_commit)");
+    if (split < 0 || split > e->cfg.games) return fail(e, OMOK_ERR_INVALID, "split %d outside [0, games = %d]", split, e->cfg.games);
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    return reset_episode(e, true, split);
 }
 
 static int need_reset(omok_engine* e) {
@@ -590,15 +725,51 @@ static int need_reset(omok_engine* e) {
 
 // defer_backups (run loops): this round's backups are not launched here; pending_backups: the previous round's run at the head of this round's
 // kernel.  The caller launches the last round's backups itself (launch_backups).
+// A round of a match episode: the one request list in two blocks, one forward per net on its own block, the policies scattered block by block,
+// then v of the second block joined behind the first's (in the first block's net, which the backups read).
+static void enqueue_match_round(omok_engine* e, int side, int K, bool eval_and_scatter, int alive, bool defer_backups) {
+    const int max_req = std::min(alive * K, e->net.max_b);
+    launch_scan(e->n, e->S, side, K, e->st, e->d_evals);
+    match_split(e, side, max_req);
+    e->prof.end(e->st);
+    if (!eval_and_scatter) return;
+    for (int b = 0; b < 2; ++b) {
+        if (!block_live(e, b)) continue;
+        Net& X = net_at(e, side ^ b);
+        const Store V = block_view(e, b);
+        const bool fused = net_logits_cover_batch(X, alive * K);
+        match_forward(e, b, side, alive * K, side, fused);
+        e->prof.begin(PC_TREE_OTHER, e->st);
+        if (fused) {
+            int lrow = 0;
+            const float* lg = net_logits(X, &lrow);
+            launch_softmax_scatter(e->n, V, side, lg, lrow, X.v, X.vpre, alive * K, e->st, false);
+        } else launch_scatter(e->n, V, side, X.p, X.v, alive * K, e->st, false);
+        e->prof.end(e->st);
+    }
+    e->prof.begin(PC_TREE_OTHER, e->st);
+    match_join(e, side, false, max_req);
+    if (!defer_backups) launch_backups(e->n, e->S, side, net_at(e, side).v, e->st);
+    e->prof.end(e->st);
+}
+
+// the net whose v holds the backups' values of a round on `side` (match episodes: the first block's, after match_join)
+static Net& backup_net(omok_engine* e, int side) { return e->match ? net_at(e, side) : e->net; }
+
 static void enqueue_round(omok_engine* e, int round, int K, float eps, float alpha, bool eval_and_scatter, int alive, bool defer_backups = false,
                           bool pending_backups = false) {
     const int side = e->ply & 1;
-    RoundArgs a{side, round, K, e->ply, eps, alpha, e->key, e->cfg.game_offset, pending_backups ? e->net.v : nullptr};
+    RoundArgs a{side, round, K, e->ply, eps, alpha, e->key, e->cfg.game_offset, pending_backups ? backup_net(e, side).v : nullptr};
     e->prof.round_begin();
     e->prof.begin(PC_ROUND, e->st);
     launch_round(e->n, e->S, a, e->st);
     e->prof.end(e->st);
     e->prof.begin(PC_TREE_OTHER, e->st);
+    if (e->match) {
+        enqueue_match_round(e, side, K, eval_and_scatter, alive, defer_backups);
+        e->prof.round_end();
+        return;
+    }
     // run-loop rounds whose forward groups the requests by parent: k_scan zeroes the grouping counters, k_group writes the dense request list
     // (two launches less per round); the step-wise API keeps the separate kernels (its callers read the request list before the forward)
     int max_req = alive * K;
@@ -633,7 +804,7 @@ static int enqueue_execute(omok_engine* e, int count, int K, float eps, float al
     }
     if (round > 0) { // the last round's backups
         e->prof.begin(PC_TREE_OTHER, e->st);
-        launch_backups(e->n, e->S, e->ply & 1, e->net.v, e->st);
+        launch_backups(e->n, e->S, e->ply & 1, backup_net(e, e->ply & 1).v, e->st);
         e->prof.end(e->st);
     }
     return round;
@@ -666,6 +837,7 @@ extern "C" int omok_execute_shared(omok_engine* e, int32_t count, int32_t batch_
     if (!e) return OMOK_ERR_INVALID;
     if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
     if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
+    if (no_match(e, "omok_execute_shared")) return OMOK_ERR_STATE;
     if (e->cfg.games != 1) return fail(e, OMOK_ERR_INVALID, "omok_execute_shared searches ONE tree: create the engine with games = 1 (got %d)", e->cfg.games);
     if (waves < 1 || waves > MAX_TREE_WAVES || waves * batch_size > e->net.max_b) // (cfg.max_tree_waves sizes the net batch: it binds through max_b)
         return fail(e, OMOK_ERR_INVALID, "waves must be in [1, %d] and waves * batch_size <= %d (the net batch, sized by max(games, max_tree_waves = %d) * max_batch_k)",
@@ -705,6 +877,7 @@ extern "C" int omok_execute_shared_recorded(omok_engine* e, int32_t count, int32
     if (!e || !sim_order || !backup_order || !group_counts || !p || !v || !n_groups || !n_requests) return OMOK_ERR_INVALID;
     if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
     if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
+    if (no_match(e, "omok_execute_shared_recorded")) return OMOK_ERR_STATE;
     if (e->cfg.games != 1) return fail(e, OMOK_ERR_INVALID, "omok_execute_shared_recorded searches ONE tree: create the engine with games = 1 (got %d)", e->cfg.games);
     if (waves < 1 || waves > MAX_TREE_WAVES || waves * batch_size > e->net.max_b) // (cfg.max_tree_waves sizes the net batch: it binds through max_b)
         return fail(e, OMOK_ERR_INVALID, "waves must be in [1, %d] and waves * batch_size <= %d (the net batch, sized by max(games, max_tree_waves = %d) * max_batch_k)",
@@ -784,11 +957,20 @@ static void enqueue_mirror_and_advance(omok_engine* e, int alive) {
     e->prof.begin(PC_PLY, e->st);
     launch_mirror_scan(e->n, e->S, side, e->st);
     k_add_evals<<<1, 64, 0, e->st>>>(e->S.d_count, e->d_evals);
+    if (e->match) match_split(e, 1 - side, alive); // ensure_action_exists on the opponent's tree: the opponent's net (benchmark/src/main.rs:79-82,99-102)
     e->prof.end(e->st);
-    net_forward_requests(e->net, e->S, alive, e->st, &e->prof);
-    e->prof.begin(PC_PLY, e->st);
-    launch_advance(e->n, e->S, side, e->net.p, e->st);
-    net_invalidate_sibling_cache(e->net);
+    if (e->match) {
+        for (int b = 0; b < 2; ++b)
+            if (block_live(e, b)) match_forward(e, b, 1 - side, alive, -1, false);
+        e->prof.begin(PC_PLY, e->st);
+        match_join(e, 1 - side, true, alive);
+        launch_advance(e->n, e->S, side, net_at(e, 1 - side).p, e->st);
+    } else {
+        net_forward_requests(e->net, e->S, alive, e->st, &e->prof);
+        e->prof.begin(PC_PLY, e->st);
+        launch_advance(e->n, e->S, side, e->net.p, e->st);
+    }
+    invalidate_nets(e);
     e->prof.end(e->st);
 }
 
@@ -853,6 +1035,7 @@ extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int3
     const int G = e->cfg.games;
     if (total_games < G) return fail(e, OMOK_ERR_INVALID, "total_games (%d) must be >= the engine's game slots (%d)", total_games, G);
     if (!records_dev || cap_records < 1) return fail(e, OMOK_ERR_INVALID, "records buffer required (omok_replay_record_bytes per record)");
+    if (no_match(e, "omok_selfplay_run_slots")) return OMOK_ERR_STATE;
     if (e->ply != 0) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots starts from a fresh omok_selfplay_reset (ply %d)", e->ply);
     ENTER(e);
     uint8_t* d_mask = nullptr;
@@ -882,7 +1065,7 @@ extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int3
         e->prof.begin(PC_PLY, e->st);
         launch_harvest(e->n, e->S, d_mask, d_slot_off, d_out, d_meta, (uint8_t*)records_dev, cap_records, e->st);
         if ((e->ply & 1) == 0) launch_refill(e->n, e->S, e->d_root_policy, d_next, total_games, d_new, e->st);
-        net_invalidate_sibling_cache(e->net);
+        invalidate_nets(e);
         e->prof.end(e->st);
         uint32_t after = 0;
         if (read_status(e, &bits, &after)) { cleanup(); return OMOK_ERR_HIP; }
@@ -894,7 +1077,7 @@ extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int3
             if (next >= total_games) break;
             e->ply += 1;
             launch_refill(e->n, e->S, e->d_root_policy, d_next, total_games, d_new, e->st);
-            net_invalidate_sibling_cache(e->net);
+            invalidate_nets(e);
             if (read_status(e, &bits, &alive)) { cleanup(); return OMOK_ERR_HIP; }
         }
     }
@@ -966,6 +1149,7 @@ extern "C" int omok_set_actions(omok_engine* e, const int32_t* actions) {
 extern "C" int omok_play_actions(omok_engine* e, const int32_t* actions) {
     if (!e || !actions) return OMOK_ERR_INVALID;
     if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
+    if (no_match(e, "omok_play_actions")) return OMOK_ERR_STATE;
     ENTER(e);
     const int rc = stage_actions(e, actions);
     if (rc != OMOK_OK) return rc;
@@ -1047,6 +1231,7 @@ extern "C" int omok_round_generate(omok_engine* e, int32_t round, int32_t batch_
     HIPCHK(e, hipMemcpyAsync(&cnt, e->S.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, e->st));
     uint32_t bits = 0, alive = 0;
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
+    if (e->match && match_counts(e)) return OMOK_ERR_HIP;
     e->sims += (double)batch_size * alive;
     e->round_reqs = cnt;
     e->round_cap = (int)alive * batch_size;
@@ -1061,24 +1246,36 @@ static int requests_to_inputs(omok_engine* e, int cnt, float* inputs) {
     return sync_and_check(e, "request inputs") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
-static int outputs_to_host(omok_engine* e, int cnt, float* p, float* v) {
+static int outputs_to_host(omok_engine* e, Net& net, int cnt, float* p, float* v) {
     if (cnt <= 0) return OMOK_OK;
-    float* d_pack = e->net.in_f32;
+    float* d_pack = net.in_f32;
     const size_t tot = (size_t)cnt * e->hw;
-    k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(e->net.p, d_pack, e->hw, e->rowp, cnt);
+    k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(net.p, d_pack, e->hw, e->rowp, cnt);
     HIPCHK(e, hipMemcpyAsync(p, d_pack, sizeof(float) * tot, hipMemcpyDeviceToHost, e->st));
-    if (v) HIPCHK(e, hipMemcpyAsync(v, e->net.v, sizeof(float) * cnt, hipMemcpyDeviceToHost, e->st));
+    if (v) HIPCHK(e, hipMemcpyAsync(v, net.v, sizeof(float) * cnt, hipMemcpyDeviceToHost, e->st));
     return sync_and_check(e, "outputs") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
-static int inject_outputs(omok_engine* e, int cnt, const float* p, const float* v) {
+static int inject_outputs(omok_engine* e, Net& net, int cnt, const float* p, const float* v) {
     if (cnt <= 0) return OMOK_OK;
-    float* d_pack = e->net.in_f32;
+    float* d_pack = net.in_f32;
     HIPCHK(e, hipMemcpyAsync(d_pack, p, sizeof(float) * (size_t)cnt * e->hw, hipMemcpyHostToDevice, e->st));
     const size_t tot = (size_t)cnt * e->rowp;
-    k_unpack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(d_pack, e->net.p, e->hw, e->rowp, cnt);
-    if (v) HIPCHK(e, hipMemcpyAsync(e->net.v, v, sizeof(float) * cnt, hipMemcpyHostToDevice, e->st));
+    k_unpack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(d_pack, net.p, e->hw, e->rowp, cnt);
+    if (v) HIPCHK(e, hipMemcpyAsync(net.v, v, sizeof(float) * cnt, hipMemcpyHostToDevice, e->st));
     return sync_and_check(e, "inject") ? OMOK_ERR_HIP : OMOK_OK;
+}
+
+// the step-wise rows of a match episode, block by block (the list's row order): block b's rows are in its net's buffers
+static int match_outputs_to_host(omok_engine* e, int tree_side, float* p, float* v) {
+    for (int b = 0, off = 0; b < 2; off += e->match_cnt[b], ++b)
+        if (outputs_to_host(e, net_at(e, tree_side ^ b), e->match_cnt[b], p + (size_t)off * e->hw, v ? v + off : nullptr)) return OMOK_ERR_HIP;
+    return OMOK_OK;
+}
+static int match_inject(omok_engine* e, int tree_side, const float* p, const float* v) {
+    for (int b = 0, off = 0; b < 2; off += e->match_cnt[b], ++b)
+        if (inject_outputs(e, net_at(e, tree_side ^ b), e->match_cnt[b], p + (size_t)off * e->hw, v ? v + off : nullptr)) return OMOK_ERR_HIP;
+    return OMOK_OK;
 }
 
 extern "C" int omok_round_inputs(omok_engine* e, float* inputs) {
@@ -1092,14 +1289,18 @@ extern "C" int omok_round_eval(omok_engine* e) {
     if (need_net(e)) return OMOK_ERR_STATE;
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
     if (e->round_reqs == 0) return OMOK_OK;
-    net_forward_requests(e->net, e->S, e->round_cap, e->st, &e->prof, e->ply & 1);
+    if (e->match) {
+        for (int b = 0; b < 2; ++b)
+            if (e->match_cnt[b] > 0) match_forward(e, b, e->ply & 1, e->round_cap, e->ply & 1, false);
+    } else net_forward_requests(e->net, e->S, e->round_cap, e->st, &e->prof, e->ply & 1);
     return sync_and_check(e, "round_eval") ? OMOK_ERR_HIP : OMOK_OK;
 }
 extern "C" int omok_round_outputs(omok_engine* e, float* p, float* v) {
     if (!e || !p) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
-    return outputs_to_host(e, e->round_reqs, p, v);
+    if (e->match) return match_outputs_to_host(e, e->ply & 1, p, v);
+    return outputs_to_host(e, e->net, e->round_reqs, p, v);
 }
 // the pre-softmax policy logits and the pre-tanh value of the pending round's evaluation (precision evidence for the path the search rounds take)
 extern "C" int omok_round_logits(omok_engine* e, float* logits, float* vpre) {
@@ -1107,29 +1308,45 @@ extern "C" int omok_round_logits(omok_engine* e, float* logits, float* vpre) {
     ENTER(e);
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
     if (e->round_reqs == 0) return OMOK_OK;
-    if (e->net.mode != OMOK_NET_F32 && !net_logits_cover_batch(e->net, e->round_reqs))
-        return fail(e, OMOK_ERR_STATE, "omok_round_logits: the round was evaluated in chunks (OMOK_NET_CHUNK): its logits are not kept");
-    if (e->net.mode == OMOK_NET_F32 && e->round_reqs > e->net.chunk)
-        return fail(e, OMOK_ERR_STATE, "omok_round_logits: OMOK_NET_F32 keeps the logits of its last chunk of %d rows only", e->net.chunk);
-    int stride = 0;
-    const float* lg = net_logits(e->net, &stride);
-    float* d_pack = e->net.in_f32;
-    const size_t tot = (size_t)e->round_reqs * e->hw;
-    k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(lg, d_pack, e->hw, stride, e->round_reqs);
-    HIPCHK(e, hipMemcpyAsync(logits, d_pack, sizeof(float) * tot, hipMemcpyDeviceToHost, e->st));
-    if (vpre) HIPCHK(e, hipMemcpyAsync(vpre, e->net.vpre, sizeof(float) * e->round_reqs, hipMemcpyDeviceToHost, e->st));
-    return sync_and_check(e, "round_logits") ? OMOK_ERR_HIP : OMOK_OK;
+    const int blocks = e->match ? 2 : 1;
+    for (int b = 0, off = 0; b < blocks; off += e->match_cnt[b], ++b) { // (match episodes: block by block, each from its own net)
+        Net& net = e->match ? net_at(e, (e->ply & 1) ^ b) : e->net;
+        const int rows = e->match ? e->match_cnt[b] : e->round_reqs;
+        if (rows == 0) continue;
+        if (net.mode != OMOK_NET_F32 && !net_logits_cover_batch(net, rows))
+            return fail(e, OMOK_ERR_STATE, "omok_round_logits: the round was evaluated in chunks (OMOK_NET_CHUNK): its logits are not kept");
+        if (net.mode == OMOK_NET_F32 && rows > net.chunk)
+            return fail(e, OMOK_ERR_STATE, "omok_round_logits: OMOK_NET_F32 keeps the logits of its last chunk of %d rows only", net.chunk);
+        int stride = 0;
+        const float* lg = net_logits(net, &stride);
+        float* d_pack = net.in_f32;
+        const size_t tot = (size_t)rows * e->hw;
+        k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(lg, d_pack, e->hw, stride, rows);
+        HIPCHK(e, hipMemcpyAsync(logits + (size_t)off * e->hw, d_pack, sizeof(float) * tot, hipMemcpyDeviceToHost, e->st));
+        if (vpre) HIPCHK(e, hipMemcpyAsync(vpre + off, net.vpre, sizeof(float) * rows, hipMemcpyDeviceToHost, e->st));
+        if (sync_and_check(e, "round_logits")) return OMOK_ERR_HIP;
+    }
+    return OMOK_OK;
 }
 extern "C" int omok_round_inject(omok_engine* e, const float* p, const float* v) {
     if (!e || !p || !v) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
-    return inject_outputs(e, e->round_reqs, p, v);
+    if (e->match) return match_inject(e, e->ply & 1, p, v);
+    return inject_outputs(e, e->net, e->round_reqs, p, v);
 }
 extern "C" int omok_round_scatter(omok_engine* e) {
     ENTER(e);
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
-    if (e->round_reqs > 0) launch_scatter(e->n, e->S, e->ply & 1, e->net.p, e->net.v, e->round_reqs, e->st);
+    const int side = e->ply & 1;
+    if (e->round_reqs > 0 && e->match) {
+        for (int b = 0; b < 2; ++b) {
+            Net& X = net_at(e, side ^ b);
+            if (e->match_cnt[b] > 0) launch_scatter(e->n, block_view(e, b), side, X.p, X.v, e->match_cnt[b], e->st, false);
+        }
+        match_join(e, side, false, e->round_reqs);
+        launch_backups(e->n, e->S, side, net_at(e, side).v, e->st);
+    } else if (e->round_reqs > 0) launch_scatter(e->n, e->S, side, e->net.p, e->net.v, e->round_reqs, e->st);
     e->round_reqs = -1;
     return sync_and_check(e, "round_scatter") ? OMOK_ERR_HIP : OMOK_OK;
 }
@@ -1140,9 +1357,11 @@ extern "C" int omok_mirror_generate(omok_engine* e, int32_t* n_requests) {
     if (!e->sampled) return fail(e, OMOK_ERR_STATE, "omok_sample_actions must precede the mirror step");
     launch_mirror_scan(e->n, e->S, e->ply & 1, e->st);
     k_add_evals<<<1, 64, 0, e->st>>>(e->S.d_count, e->d_evals);
+    if (e->match) match_split(e, 1 - (e->ply & 1), e->cfg.games);
     int32_t cnt = 0;
     HIPCHK(e, hipMemcpyAsync(&cnt, e->S.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, e->st));
     if (sync_and_check(e, "mirror_generate")) return OMOK_ERR_HIP;
+    if (e->match && match_counts(e)) return OMOK_ERR_HIP;
     e->mirror_reqs = cnt;
     if (n_requests) *n_requests = cnt;
     return OMOK_OK;
@@ -1157,28 +1376,36 @@ extern "C" int omok_mirror_eval(omok_engine* e) {
     ENTER(e);
     if (need_net(e)) return OMOK_ERR_STATE;
     if (e->mirror_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated mirror batch");
-    if (e->mirror_reqs > 0) net_forward_requests(e->net, e->S, e->mirror_reqs, e->st, &e->prof);
+    if (e->mirror_reqs > 0 && e->match) {
+        for (int b = 0; b < 2; ++b)
+            if (e->match_cnt[b] > 0) match_forward(e, b, 1 - (e->ply & 1), e->match_cnt[b], -1, false);
+    } else if (e->mirror_reqs > 0) net_forward_requests(e->net, e->S, e->mirror_reqs, e->st, &e->prof);
     return sync_and_check(e, "mirror_eval") ? OMOK_ERR_HIP : OMOK_OK;
 }
 extern "C" int omok_mirror_outputs(omok_engine* e, float* p) {
     if (!e || !p) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->mirror_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated mirror batch");
-    return outputs_to_host(e, e->mirror_reqs, p, nullptr);
+    if (e->match) return match_outputs_to_host(e, 1 - (e->ply & 1), p, nullptr);
+    return outputs_to_host(e, e->net, e->mirror_reqs, p, nullptr);
 }
 extern "C" int omok_mirror_inject(omok_engine* e, const float* p) {
     if (!e || !p) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->mirror_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated mirror batch");
-    return inject_outputs(e, e->mirror_reqs, p, nullptr);
+    if (e->match) return match_inject(e, 1 - (e->ply & 1), p, nullptr);
+    return inject_outputs(e, e->net, e->mirror_reqs, p, nullptr);
 }
 extern "C" int omok_mirror_apply(omok_engine* e) {
     ENTER(e);
     if (e->mirror_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated mirror batch");
     uint32_t bits = 0, before = 0, after = 0;
     if (read_status(e, &bits, &before)) return OMOK_ERR_HIP;
-    launch_advance(e->n, e->S, e->ply & 1, e->net.p, e->st);
-    net_invalidate_sibling_cache(e->net);
+    if (e->match) {
+        match_join(e, 1 - (e->ply & 1), true, e->cfg.games);
+        launch_advance(e->n, e->S, e->ply & 1, net_at(e, 1 - (e->ply & 1)).p, e->st);
+    } else launch_advance(e->n, e->S, e->ply & 1, e->net.p, e->st);
+    invalidate_nets(e);
     if (read_status(e, &bits, &after)) return OMOK_ERR_HIP;
     e->ply_games += before;
     e->finished += (double)before - (double)after;
@@ -1456,6 +1683,7 @@ extern "C" int omok_reset_stats(omok_engine* e) {
     hipMemset(e->d_evals, 0, 16);
     hipMemset(e->S.d_bytes, 0, 16);
     if (e->net.d_work) hipMemset(e->net.d_work, 0, sizeof(unsigned long long) * NET_WORK_COUNT);
+    if (e->d_mevals) hipMemset(e->d_mevals, 0, 16);
     return OMOK_OK;
 }
 

@@ -109,6 +109,10 @@ struct Net {
     float probe[24] = {};     // commit-time probe: [0] plain rows, [1] |dp| fp6, [2] |dv| fp6, [3] |dp| f16, [4] |dv| f16, [5] max |logit| (fp32), [6] 1 = measured,
                               // [7] |dlogit| fp6, [8] |dlogit| f16 (plain rows); [9] rows of the synthetic sibling round checked, [10..18] its |dp|, |dv|, |dlogit| in fp6 / mixed / f16
     size_t bytes = 0;         // device bytes held
+    // match episodes (omok_match_reset): a search round's forward of this net covers the trees of games [grp_lo, grp_hi) of the side only (k_group), and their
+    // request rows are the engine's dense list minus grp_sub[0] (the rows of the games in front, NULL: none); grp_hi < 0: every game (self-play)
+    int grp_lo = 0, grp_hi = -1;
+    const int32_t* grp_sub = nullptr;
 };
 
 // sizes

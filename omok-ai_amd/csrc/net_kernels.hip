@@ -865,26 +865,30 @@ __device__ inline void sib_window(int n, int action, int& wy0, int& wx0) { // th
 // result does not depend on its slot).
 // One wave per tree, GROUP_TREES trees per workgroup: the workgroup counts in LDS and claims its ranges of the global lists with one
 // atomic per counter (per-row atomics on 3 + 81 addresses serialised in L2: 0.24 ms per round).
+// MATCH (match episodes, Net::grp_*): the games [g_lo, g_hi) only, request rows relative to row_sub[0] (the forward's own list; NULL: 0).
 constexpr int GROUP_TREES = 16;
+template <bool MATCH>
 __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, uint2* __restrict__ groups, int32_t* __restrict__ singles,
                                                              uint4* __restrict__ sib_rows, int32_t* __restrict__ cnt, uint32_t* __restrict__ sib_slot,
                                                              int32_t* __restrict__ tags, uint2* __restrict__ comp, int bn, int do_fill,
-                                                             unsigned long long* __restrict__ work) {
+                                                             unsigned long long* __restrict__ work, int g_lo, int g_hi, const int32_t* __restrict__ row_sub) {
     // Difference path (sib_slot != NULL): base slots.  The FIRST run of a tree uses one of the game's SIB_WAYS slots (SIB_WAYS g + way), whose content is
     // reused while a tag names the run's parent (a leaf is its tree's expansion target for ~14 rounds); further runs of the tree in the same
     // round (rare) take a slot behind the games' and are always evaluated.  comp[] lists the (first request row, slot) pairs to evaluate.
     constexpr int NP0 = 225, LC = 3 + NP0 + 2; // runs, singles, rows in runs | children per net pixel of their stone (P0) | full evaluations, uncacheable runs
     __shared__ int l_cnt[LC], l_base[LC];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int g = blockIdx.x * GROUP_TREES + (tid >> 6);
+    const int g = (MATCH ? g_lo : 0) + blockIdx.x * GROUP_TREES + (tid >> 6);
+    const int g_end = MATCH ? g_hi : S.games;
     if (tid < LC) l_cnt[tid] = 0;
     __syncthreads();
     int n = 0;
     TreeState ts{};
-    const int t = side * S.games + (g < S.games ? g : 0);
-    if (g < S.games && S.gs[g].alive) {
+    const int t = side * S.games + (g < g_end ? g : 0);
+    if (g < g_end && S.gs[g].alive) {
         ts = S.ts[t];
         n = (int)ts.n_req;
+        if (MATCH && row_sub) ts.req_base -= (uint32_t)row_sub[0];
     }
     int parent = -1 - lane; // distinct for the lanes beyond the list
     uint32_t tn = 0, ta = 0;
@@ -4445,8 +4449,15 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
         hipMemsetAsync(net.d_tags, 0xFF, sizeof(int32_t) * (size_t)net.games * SIB_WAYS, st);
         net.sib_cache_valid = true;
     }
-    k_group<<<(S.games + GROUP_TREES - 1) / GROUP_TREES, 64 * GROUP_TREES, 0, st>>>(S, side, (uint2*)net.d_groups, net.d_singles, (uint4*)net.d_sib_rows, net.d_gcnt,
-                                                                                     delta ? net.d_sib_slot : nullptr, net.d_tags, (uint2*)net.d_comp, net.n, do_fill, net.d_work);
+    if (net.grp_hi >= 0) { // match episode: this net's games only
+        const int ng = net.grp_hi - net.grp_lo;
+        k_group<true><<<ng > 0 ? (ng + GROUP_TREES - 1) / GROUP_TREES : 1, 64 * GROUP_TREES, 0, st>>>(S, side, (uint2*)net.d_groups, net.d_singles, (uint4*)net.d_sib_rows,
+                                                                    net.d_gcnt, delta ? net.d_sib_slot : nullptr, net.d_tags, (uint2*)net.d_comp, net.n, do_fill,
+                                                                    net.d_work, net.grp_lo, net.grp_hi, net.grp_sub);
+    } else
+        k_group<false><<<(S.games + GROUP_TREES - 1) / GROUP_TREES, 64 * GROUP_TREES, 0, st>>>(S, side, (uint2*)net.d_groups, net.d_singles, (uint4*)net.d_sib_rows, net.d_gcnt,
+                                                                                     delta ? net.d_sib_slot : nullptr, net.d_tags, (uint2*)net.d_comp, net.n, do_fill, net.d_work,
+                                                                                     0, 0, nullptr);
     if (!delta) {
         // (the copy path keeps the runs' h grids in sib_h[run index]: the slots the difference path caches bases in -- cached bases are void)
         net.sib_cache_valid = false;

@@ -2447,6 +2447,68 @@ __global__ __launch_bounds__(64) void k_replay_augment(Store S, const long long*
 }
 
 // ---------------------------------------------------------------------------------------------
+// match episodes (omok_match_reset): net 1 against net 2
+// ---------------------------------------------------------------------------------------------
+// Tree side * G + g is evaluated by net side ^ (g >= split).  A dense request list (k_scan + k_fill, k_mirror_scan) is in game order, so it
+// falls into two BLOCKS: games [0, split), evaluated by net tree_side, then games [split, G), evaluated by the other net.  k_match_split
+// finds the first row of the second block, copies that block to the second list and writes both counts; each net's forward then reads its
+// own block as a dense list of its own.  k_match_join puts the second net's outputs behind the first's, so that the backups (k_scatter and
+// the head of k_round) and the re-rooting (k_advance) read one array in list order, as they do in self-play.
+__global__ __launch_bounds__(256) void k_match_split(const uint32_t* __restrict__ ref, const uint32_t* __restrict__ aux, const int32_t* __restrict__ d_total,
+                                                     int tree_side, int games, int split, uint32_t* __restrict__ ref2, uint32_t* __restrict__ aux2,
+                                                     int32_t* __restrict__ cnt, unsigned long long* __restrict__ evals) {
+    __shared__ int s_first;
+    const int total = d_total[0];
+    if (threadIdx.x == 0) { // binary search: the first row whose game is >= split
+        int lo = 0, hi = total;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((int)(ref[mid] >> 16) - tree_side * games < split) lo = mid + 1;
+            else hi = mid;
+        }
+        s_first = lo;
+        if (blockIdx.x == 0) {
+            cnt[0] = lo;
+            cnt[1] = total - lo;
+            evals[tree_side] += (unsigned long long)lo; // rows per net (omok_net2_info)
+            evals[tree_side ^ 1] += (unsigned long long)(total - lo);
+        }
+    }
+    __syncthreads();
+    const int first = s_first;
+    for (int d = first + (int)(blockIdx.x * blockDim.x + threadIdx.x); d < total; d += (int)(gridDim.x * blockDim.x)) {
+        ref2[d - first] = ref[d];
+        aux2[d - first] = aux[d];
+    }
+}
+
+// rows [0, cnt[1]) of the second block's outputs -> rows [cnt[0], cnt[0] + cnt[1]) of the first's (v and / or p, NULL: not joined)
+__global__ __launch_bounds__(256) void k_match_join(const int32_t* __restrict__ cnt, const float* __restrict__ v2, float* __restrict__ v1,
+                                                    const float* __restrict__ p2, float* __restrict__ p1, int rowp) {
+    const size_t first = (size_t)cnt[0], m = (size_t)cnt[1];
+    const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+    if (v1)
+        for (size_t i = i0; i < m; i += step) v1[first + i] = v2[i];
+    if (p1)
+        for (size_t i = i0; i < m * (size_t)rowp; i += step) p1[first * rowp + i] = p2[i];
+}
+
+// Agent::new with the agent's own net (agent.rs:16-35): the root policy row of every tree net 2 owns (k_reset wrote net 1's into all)
+template <int N>
+__global__ __launch_bounds__(64) void k_match_roots(Store S, const float* __restrict__ root_policy2, int split) {
+    using G = Geo<N>;
+    const int t = blockIdx.x;
+    const int side = t >= S.games ? 1 : 0, g = t - side * S.games;
+    if ((side ^ (g >= split ? 1 : 0)) != 1) return;
+    const Tree<N> T(S, t);
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + LANE;
+        T.pol[a] = a < G::HW ? root_policy2[a] : 0.0f;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 #define DISPATCH_N(n, CALL9, CALL15) \
@@ -2554,6 +2616,19 @@ void launch_harvest(int n, const Store& S, uint8_t* mask, long long* slot_off, l
                     hipStream_t st) {
     DISPATCH_N(n, (k_harvest_scan<9><<<1, 1024, 0, st>>>(S, mask, slot_off, out_count, meta)), (k_harvest_scan<15><<<1, 1024, 0, st>>>(S, mask, slot_off, out_count, meta)));
     DISPATCH_N(n, (k_replay_pack<9><<<S.games, 64, 0, st>>>(S, slot_off, dst, cap, mask)), (k_replay_pack<15><<<S.games, 64, 0, st>>>(S, slot_off, dst, cap, mask)));
+}
+void launch_match_split(const Store& S, int tree_side, int split, uint32_t* ref2, uint32_t* aux2, int32_t* cnt, unsigned long long* evals, int max_rows,
+                        hipStream_t st) {
+    const int grid = std::max(1, std::min(256, (max_rows + 255) / 256));
+    k_match_split<<<grid, 256, 0, st>>>(S.req_ref, S.req_aux, S.d_count, tree_side, S.games, split, ref2, aux2, cnt, evals);
+}
+void launch_match_join(const int32_t* cnt, const float* v2, float* v1, const float* p2, float* p1, int rowp, int max_rows, hipStream_t st) {
+    const size_t work = (size_t)max_rows * (p1 ? (size_t)rowp : 1);
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>(1024, (work + 255) / 256));
+    k_match_join<<<grid, 256, 0, st>>>(cnt, v2, v1, p2, p1, rowp);
+}
+void launch_match_roots(int n, const Store& S, const float* root_policy2, int split, hipStream_t st) {
+    DISPATCH_N(n, (k_match_roots<9><<<2 * S.games, 64, 0, st>>>(S, root_policy2, split)), (k_match_roots<15><<<2 * S.games, 64, 0, st>>>(S, root_policy2, split)));
 }
 void launch_refill(int n, const Store& S, const float* rp, int32_t* next_gid, int total_games, int32_t* new_gid, hipStream_t st) {
     k_refill_assign<<<1, 1024, 0, st>>>(S, next_gid, total_games, new_gid);
