@@ -282,8 +282,7 @@ int omok_debug_operand_rows(omok_engine* e, int32_t first_row, int32_t rows, voi
 int omok_debug_set_base_cache(omok_engine* e, int32_t enabled);
 /* Debugging aid / A-B switch: which kernel evaluates the children of a sibling run on the difference path: 2 = k_sib_children2 (default: one wave
  * per child, windows that grow with the blocks), 1 = k_sib_children (a wave pair per child, the 7x7 window through every block; always used on the copy path).
- * Outputs agree within 2e-4 (tests); cached base positions are dropped (the kernels read different base-slot layouts).  The environment variable
- * OMOK_SIB_V2=0 at omok_create selects 1 as the engine's default.  In the MIXED operand format (the usual outcome of omok_net_commit's probe) only k_sib_children2 writes
+ * Outputs agree within 2e-4 (tests); cached base positions are dropped (the kernels read different base-slot layouts).  In the MIXED operand format (the usual outcome of omok_net_commit's probe) only k_sib_children2 writes
  * the fp6 difference rows: which = 1 then returns OMOK_ERR_STATE instead of silently changing nothing (use OMOK_NET_F16X3_FP6 / _F16 engines for an A-B run). */
 int omok_debug_set_children_kernel(omok_engine* e, int32_t which);
 /* Debugging aid: enabled = 0 makes the fc0 window tiles of sibling rounds walk the whole 7x7 window of their bin instead of the rectangle of window pixels their rows can

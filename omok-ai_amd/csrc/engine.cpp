@@ -1313,8 +1313,6 @@ extern "C" int omok_round_logits(omok_engine* e, float* logits, float* vpre) {
         Net& net = e->match ? net_at(e, (e->ply & 1) ^ b) : e->net;
         const int rows = e->match ? e->match_cnt[b] : e->round_reqs;
         if (rows == 0) continue;
-        if (net.mode != OMOK_NET_F32 && !net_logits_cover_batch(net, rows))
-            return fail(e, OMOK_ERR_STATE, "omok_round_logits: the round was evaluated in chunks (OMOK_NET_CHUNK): its logits are not kept");
         if (net.mode == OMOK_NET_F32 && rows > net.chunk)
             return fail(e, OMOK_ERR_STATE, "omok_round_logits: OMOK_NET_F32 keeps the logits of its last chunk of %d rows only", net.chunk);
         int stride = 0;

@@ -75,19 +75,10 @@ __device__ inline void split8(const float* v, half8& hi, half8& lo) {
     hi = H.h;
     lo = L.h;
 }
-// LeakyRelu on a pair: one packed multiply + two v_max.  The multiply is written as the instruction: left to the compiler, `(f32x2){a, b} * 0.2f` came out as two
-// v_mul_f32 in 114 of k_sib_children2's 216 pairs (tools/isa_hist.py).  Same rounding either way.
-#ifndef LRELU_PK_ASM
-#define LRELU_PK_ASM 0 // (round 6 A-B, profiles/r06_ab_children_diet.txt: -115 VALU per child, no change in time: off)
-#endif
+// LeakyRelu on a pair: a multiply + two v_max.  The multiply is left to the compiler: `(f32x2){a, b} * 0.2f` comes out as two v_mul_f32 in 114 of
+// k_sib_children2's 216 pairs (tools/isa_hist.py); forcing v_pk_mul_f32 saved 115 VALU per child and no time (profiles/r06_ab_children_diet.txt).
 __device__ inline f32x2 lrelu2(float a, float b) {
-#if LRELU_PK_ASM
-    const f32x2 x = {a, b}, c = {0.2f, 0.2f};
-    f32x2 y;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(y) : "v"(x), "s"(c));
-#else
     const f32x2 y = (f32x2){a, b} * 0.2f;
-#endif
     f32x2 r;
     asm("v_max_f32 %0, %1, %2" : "=v"(r[0]) : "v"(a), "v"(y[0]));
     asm("v_max_f32 %0, %1, %2" : "=v"(r[1]) : "v"(b), "v"(y[1]));
@@ -236,10 +227,7 @@ constexpr int OPX_BLK_U4 = 512;
 constexpr int fmt_blk_u4(bool f16lo) { return f16lo ? OPX_BLK_U4 : OP_BLK_U4; }
 // MX6 block scales: 2^(floor(log2(amax * 32/31)) - 2).  With the plain floor(log2 amax) a block whose largest magnitude lies in [7.75, 8) x scale rounds up
 // past e2m3's largest code (7.5) and saturates: up to 6 % error on the block's largest element in ~6 % of the blocks -- the outliers a max-error probe sees.
-#ifndef MX6_AMAX_ADJ_ON
-#define MX6_AMAX_ADJ_ON 1
-#endif
-constexpr float MX6_AMAX_ADJ = MX6_AMAX_ADJ_ON ? 32.0f / 31.0f : 1.0f;
+constexpr float MX6_AMAX_ADJ = 32.0f / 31.0f;
 constexpr bool MX6 = true;   // fc0 correction terms on fp6 (e2m3) operands with per-lane E8M0 block scales (false: fp8, global scales)
 constexpr bool LO_SCALE_FROM_BOUND = false; // true: -16 VALU per block in the trunk epilogue (trunk -2 %), N = 9 max|dv| 3.6e-4 -> 5.9e-4
 constexpr int MX_SA = 2;        // fp8 copies of the fc0 operand are x * 2^MX_SA (|x| <= 112 representable; clamped beyond)
@@ -276,11 +264,8 @@ struct TrunkGeo {
     static constexpr int WG_THREADS = SPW * THREADS;
 };
 
-#ifndef TRUNK_PRIO
-#define TRUNK_PRIO 0
-#endif
-template <int N, bool FROM_F32, int ABL = 0> // ABL: timing-only ablations (1 = no depthwise exchange, 2 = no operand epilogue, 4 = no conv_in, 8 = epilogue without the global stores);
-                                             // 16 = BASE mode of the sibling path (not an ablation): see k_group / k_sib_children below
+template <int N, bool FROM_F32, bool BASE = false, bool DELTA = false, bool F16LO = false> // BASE: the base pass of the sibling path (see k_group / k_sib_children below), DELTA: the
+                                                                                           // difference path, F16LO: operand rows in the FC0_F16 format (f16 residuals)
 __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_t* __restrict__ req_ref, const uint32_t* __restrict__ req_aux,
                                                                     const uint64_t* __restrict__ board, const NodeHdr* __restrict__ hdr,
                                                                     const int32_t* __restrict__ d_count, int cap_nodes, const float* __restrict__ in_f32,
@@ -298,8 +283,6 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
     // (copy path) or, DELTA (difference path), to the compact row i (fc0 of this round's evaluated positions) AND to base slot groups[i].y of
     // a_base (what the children read, this round and while the slot's tag stays: the h grids go to hscr[slot] likewise); with DELTA the rows
     // of a row list go to compact rows d_out_base[0] + i (behind the runs').
-    constexpr bool BASE = (ABL & 16) != 0, DELTA = (ABL & 32) != 0;
-    constexpr bool F16LO = (ABL & 64) != 0; // operand rows in the FC0_F16 format (f16 residuals)
     constexpr int BLK_U4 = fmt_blk_u4(F16LO);
     using TG = TrunkGeo<N>;
     constexpr int HW = TG::HW, NW = Geo<N>::NW;
@@ -313,7 +296,6 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
     const float* lside = (const float*)(smem + TR_WBYTES + TG::SPW * TG::GRID_BYTES);
     const int h = lane >> 5;
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1"); // fp8 / f16 conversions saturate (MODE.FP16_OVFL)
-    if (TRUNK_PRIO && ((tid >> 6) & 4)) __builtin_amdgcn_s_setprio(TRUNK_PRIO); // the two waves of a SIMD (w, w+4) run the same phases: let one lead
     // ---- one-time: weights, side table, zero halo grid ----
     for (int i = tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
     for (int i = tid; i < TR_SIDE_FLOATS; i += blockDim.x) ((float*)lside)[i] = side[i];
@@ -480,21 +462,14 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
             bl = bh; // (unused: the inputs are exact in f16)
         }
         f32x16 x[4];
-        if (ABL & 4) {
 #pragma unroll
-            for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < 4; ++m) {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) x[m][i] = (FROM_F32 ? in.f[0] : (float)in.turn) + 0.01f * (float)(i + 16 * m);
-        } else {
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) x[m][i] = 0.0f;
-                x[m] = MFMA16(cwh[m], bh, x[m]);
-                x[m] = MFMA16(cwl[m], bh, x[m]);
-                if (FROM_F32) x[m] = MFMA16(cwh[m], bl, x[m]); // (board inputs are 0 / 1 and the bias 1: exact in f16, bl = 0)
-                LRELU16(x[m]);
-            }
+            for (int i = 0; i < 16; ++i) x[m][i] = 0.0f;
+            x[m] = MFMA16(cwh[m], bh, x[m]);
+            x[m] = MFMA16(cwl[m], bh, x[m]);
+            if (FROM_F32) x[m] = MFMA16(cwh[m], bl, x[m]); // (board inputs are 0 / 1 and the bias 1: exact in f16, bl = 0)
+            LRELU16(x[m]);
         }
         // ---- 3 bottleneck residual blocks ----
 #pragma unroll 1
@@ -531,10 +506,6 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
                 MFMA3(ah, al, bh, bl, acc);
             }
             float d[16];
-            if (ABL & 1) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) d[i] = lrelu(acc[i]);
-            } else {
             // (no barrier here: a pixel's grid row is written below and was last read -- as depthwise output of the
             //  previous block, or as staging row of the previous sample's operand stores -- by this same lane; the other
             //  waves' window reads of it ended before B3 and their write-backs before B4 of the previous block)
@@ -606,7 +577,6 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
                 for (int i = 0; i < 4; ++i) d[4 * g + i] = dv[i];
                 if (to_sib2) sb2[sib2_grid(HW, blk, 1, px, g, h)] = __builtin_bit_cast(uint4, dv);
             }
-            }
             // L1: pointwise 32 -> 32 + bias + lrelu
             f32x16 accg;
 #pragma unroll
@@ -657,150 +627,139 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
         //      8 full lines per instruction.  Three passes of 128 B per pixel: f16 part of q = 0, of q = 1, both fp8 parts.
         //      (Lanes past the last pixel skip the LDS write; the read-back side then stores the clamped pixel's data into
         //      the pad slots of the row: no branch around the global stores, so the compiler counts them exactly.)
-        if (!(ABL & 2)) {
-            // BASE: the row is stored into EVERY child row of the run (the rows fc0 reads must exist; k_sib_children then overwrites
-            // each child's 7x7 window): `row` = the first child's row, the others follow at the row stride
-            uint32_t orow = (uint32_t)b;
-            const bool sgl = single(bi);
-            if (BASE) orow = DELTA ? (uint32_t)(active ? bi : 0) : (active ? (sgl ? (uint32_t)row_list[bi - n_base] : groups[bi].x) : 0u);
-            else if (DELTA && row_list) orow = (uint32_t)(d_out_base[0] + (active ? bi : 0));
-            uint4* row = a_out + (size_t)orow * row_u4;
-            uint4* row2 = (BASE && DELTA && !sgl) ? a_base + (size_t)(active ? groups[bi].y : 0u) * row_u4 : nullptr; // the base slot
-            const int copies = (BASE && !DELTA) ? (active ? (sgl ? 1 : (int)groups[bi].y) : 0) : 1;
-            uint4* stage_w = (uint4*)(grid + gi * GRID_STRIDE);          // this lane's pixel row (8 slots of 16 B)
-            if constexpr (F16LO) {
-                // FC0_F16: four passes of 128 B per pixel through the same staging rows -- per channel half q the f16 hi pieces, then the
-                // f16 residual pieces (split8: 1.5 VALU per value, no block maxima, no fp6 packing)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    half8 hi8[4], lo8[4];
-#pragma unroll
-                    for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-                        for (int sx = 0; sx < 2; ++sx) {
-                            float v[8];
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) v[j] = x[2 * q + mm][8 * sx + j];
-                            split8(v, hi8[mm * 2 + sx], lo8[mm * 2 + sx]);
-                        }
-#pragma unroll
-                    for (int part = 0; part < 2; ++part) {
-                        if (valid) {
-#pragma unroll
-                            for (int p4 = 0; p4 < 4; ++p4) stage_w[p4 * 2 + h] = __builtin_bit_cast(uint4, part ? lo8[p4] : hi8[p4]);
-                        }
-                        WAVE_LDS_FENCE();
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const uint4 v = *(const uint4*)(grid + st_gi[i] * GRID_STRIDE + 4 * (lane & 7));
-                            if (i == 3) WAVE_LDS_FENCE();
-                            if (!(ABL & 8)) {
-                                if (st_ok[i] && active) {
-                                    uint4* dst = &row[(size_t)(tile * 2 + q) * BLK_U4 + part * OP_LO_U4 + (8 * i + (lane >> 3)) * 8 + (lane & 7)];
-                                    if (BASE && !DELTA) for (int c = 0; c < copies; ++c) nt_store(v, dst + (size_t)c * row_u4);
-                                    else if (DELTA) { *dst = v; if (BASE && row2) row2[dst - row] = v; }
-                                    else nt_store(v, dst);
-                                }
-                            }
-                            else if (v.x == 0x12345678u && v.y == 0x9abcdef0u) row[lane] = v;
-                        }
-                    }
-                }
-            } else {
-            const float sc_lo_inv = __uint_as_float((uint32_t)(127 - MX_SA - 11) << 23); // fp8 = (x - hi) / 2^-(SA+11)
-            uint32_t p8l[2][8];
-            u32x6 lo6[2];        // MX6: fp6 residuals of the lane's 32 values per channel half q, natural slot order 16*mm + reg
-            uint32_t esc[2];     // MX6: E8M0 bytes of the two block scales (hi copy | residual << 8)
+        // BASE: the row is stored into EVERY child row of the run (the rows fc0 reads must exist; k_sib_children then overwrites
+        // each child's 7x7 window): `row` = the first child's row, the others follow at the row stride
+        uint32_t orow = (uint32_t)b;
+        const bool sgl = single(bi);
+        if (BASE) orow = DELTA ? (uint32_t)(active ? bi : 0) : (active ? (sgl ? (uint32_t)row_list[bi - n_base] : groups[bi].x) : 0u);
+        else if (DELTA && row_list) orow = (uint32_t)(d_out_base[0] + (active ? bi : 0));
+        uint4* row = a_out + (size_t)orow * row_u4;
+        uint4* row2 = (BASE && DELTA && !sgl) ? a_base + (size_t)(active ? groups[bi].y : 0u) * row_u4 : nullptr; // the base slot
+        const int copies = (BASE && !DELTA) ? (active ? (sgl ? 1 : (int)groups[bi].y) : 0) : 1;
+        uint4* stage_w = (uint4*)(grid + gi * GRID_STRIDE);          // this lane's pixel row (8 slots of 16 B)
+        if constexpr (F16LO) {
+            // FC0_F16: four passes of 128 B per pixel through the same staging rows -- per channel half q the f16 hi pieces, then the
+            // f16 residual pieces (split8: 1.5 VALU per value, no block maxima, no fp6 packing)
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                float res[32], amax_v = 0.0f, amax_l = 0.0f;
+                half8 hi8[4], lo8[4];
 #pragma unroll
                 for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
                     for (int sx = 0; sx < 2; ++sx) {
-                        union { uint32_t u[4]; uint4 v; } H;
+                        float v[8];
 #pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            const float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
-                            // round-to-nearest hi; residual by one mixed-precision fma per value; scaled saturating
-                            // (MODE.FP16_OVFL) packed fp8 convert: 2 VALU per value
-                            const uint32_t ph = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v0, v1}, half2v));
-                            H.u[jj] = ph;
-                            float l0, l1;
-                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(ph), "v"(v0));
-                            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(ph), "v"(v1));
-                            const int slot = 16 * mm + 8 * sx + 2 * jj; // byte slot of v0
-                            const int w = slot >> 2;
-                            if (MX6) {
-                                res[slot] = l0; res[slot + 1] = l1;
-                                // (from asm: fmaxf() drags a canonicalising v_max per operand along under IEEE mode)
-                                asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_v) : "v"(v0), "v"(v1));
-                                if (!LO_SCALE_FROM_BOUND) asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_l) : "v"(l0), "v"(l1));
-                            } else if ((slot & 3) == 0)
-                                p8l[q][w] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(short2v{0, 0}, l0, l1, sc_lo_inv, false));
-                            else
-                                p8l[q][w] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(__builtin_bit_cast(short2v, p8l[q][w]), l0, l1, sc_lo_inv, true));
-                        }
-                        if (valid) stage_w[(mm * 2 + sx) * 2 + h] = H.v;
+                        for (int j = 0; j < 8; ++j) v[j] = x[2 * q + mm][8 * sx + j];
+                        split8(v, hi8[mm * 2 + sx], lo8[mm * 2 + sx]);
                     }
-                WAVE_LDS_FENCE();
-                if (MX6) { // block scales 2^(floor(log2 max) - 2) (e2m3 emax = 2) and the packed fp6 residuals
-                    // (option: residual scale from the bound |x - f16(x)| <= 2^(floor(log2 |x|) - 11) instead of a second block maximum)
-                    int eh = (int)((__float_as_uint(amax_v * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2, el = LO_SCALE_FROM_BOUND ? eh - 11 : (int)((__float_as_uint(amax_l * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2;
-                    eh = eh < 1 ? 1 : eh;
-                    el = el < 1 ? 1 : el;
-                    esc[q] = (uint32_t)eh | ((uint32_t)el << 8);
-                    f32x16v ev, od; // v_cvt_scalef32_2xpk16_fp6_f32 interleaves its two sources: field 2i = ev[i], 2i+1 = od[i]
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) { ev[i] = res[2 * i]; od[i] = res[2 * i + 1]; }
-                    lo6[q] = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, __uint_as_float((uint32_t)el << 23));
-                }
-                // read back: lanes 8i'..8i'+7 hold the 8 pieces of pixel 8i + i' of the tile
+                for (int part = 0; part < 2; ++part) {
+                    if (valid) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const uint4 v = *(const uint4*)(grid + st_gi[i] * GRID_STRIDE + 4 * (lane & 7));
-                    if (!(ABL & 8)) {
+                        for (int p4 = 0; p4 < 4; ++p4) stage_w[p4 * 2 + h] = __builtin_bit_cast(uint4, part ? lo8[p4] : hi8[p4]);
+                    }
+                    WAVE_LDS_FENCE();
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const uint4 v = *(const uint4*)(grid + st_gi[i] * GRID_STRIDE + 4 * (lane & 7));
+                        if (i == 3) WAVE_LDS_FENCE();
                         if (st_ok[i] && active) {
-                            uint4* dst = &row[(size_t)(tile * 2 + q) * OP_BLK_U4 + (8 * i + (lane >> 3)) * 8 + (lane & 7)];
+                            uint4* dst = &row[(size_t)(tile * 2 + q) * BLK_U4 + part * OP_LO_U4 + (8 * i + (lane >> 3)) * 8 + (lane & 7)];
                             if (BASE && !DELTA) for (int c = 0; c < copies; ++c) nt_store(v, dst + (size_t)c * row_u4);
-                            else if (DELTA) { *dst = v; if (BASE && row2) row2[dst - row] = v; } // (read again right away: by fc0; by the children of the run)
+                            else if (DELTA) { *dst = v; if (BASE && row2) row2[dst - row] = v; }
                             else nt_store(v, dst);
                         }
                     }
-                    else if (v.x == 0x12345678u && v.y == 0x9abcdef0u) row[lane] = v; // timing only: keep the staging alive
                 }
-                WAVE_LDS_FENCE();
             }
-            if (valid) {
+        } else {
+        const float sc_lo_inv = __uint_as_float((uint32_t)(127 - MX_SA - 11) << 23); // fp8 = (x - hi) / 2^-(SA+11)
+        uint32_t p8l[2][8];
+        u32x6 lo6[2];        // MX6: fp6 residuals of the lane's 32 values per channel half q, natural slot order 16*mm + reg
+        uint32_t esc[2];     // MX6: E8M0 bytes of the two block scales (hi copy | residual << 8)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    if (MX6) { // 64 B per (pixel, q): [h0 dwords 0..3][h1 dwords 0..3][h0 dwords 4,5 | h1 dwords 4,5][scale bytes h0, h1 | pad]
-                        stage_w[q * 4 + h] = make_uint4(lo6[q][0], lo6[q][1], lo6[q][2], lo6[q][3]);
-                        ((uint2*)(stage_w + q * 4 + 2))[h] = make_uint2(lo6[q][4], lo6[q][5]);
-                        ((uint16_t*)(stage_w + q * 4 + 3))[h] = (uint16_t)esc[q];
-                    } else {
-                        stage_w[q * 4 + h * 2 + 0] = make_uint4(p8l[q][0], p8l[q][1], p8l[q][2], p8l[q][3]);
-                        stage_w[q * 4 + h * 2 + 1] = make_uint4(p8l[q][4], p8l[q][5], p8l[q][6], p8l[q][7]);
+        for (int q = 0; q < 2; ++q) {
+            float res[32], amax_v = 0.0f, amax_l = 0.0f;
+#pragma unroll
+            for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+                for (int sx = 0; sx < 2; ++sx) {
+                    union { uint32_t u[4]; uint4 v; } H;
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        const float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
+                        // round-to-nearest hi; residual by one mixed-precision fma per value; scaled saturating
+                        // (MODE.FP16_OVFL) packed fp8 convert: 2 VALU per value
+                        const uint32_t ph = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v0, v1}, half2v));
+                        H.u[jj] = ph;
+                        float l0, l1;
+                        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(ph), "v"(v0));
+                        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(ph), "v"(v1));
+                        const int slot = 16 * mm + 8 * sx + 2 * jj; // byte slot of v0
+                        const int w = slot >> 2;
+                        if (MX6) {
+                            res[slot] = l0; res[slot + 1] = l1;
+                            // (from asm: fmaxf() drags a canonicalising v_max per operand along under IEEE mode)
+                            asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_v) : "v"(v0), "v"(v1));
+                            if (!LO_SCALE_FROM_BOUND) asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_l) : "v"(l0), "v"(l1));
+                        } else if ((slot & 3) == 0)
+                            p8l[q][w] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(short2v{0, 0}, l0, l1, sc_lo_inv, false));
+                        else
+                            p8l[q][w] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(__builtin_bit_cast(short2v, p8l[q][w]), l0, l1, sc_lo_inv, true));
                     }
+                    if (valid) stage_w[(mm * 2 + sx) * 2 + h] = H.v;
                 }
-            }
             WAVE_LDS_FENCE();
+            if (MX6) { // block scales 2^(floor(log2 max) - 2) (e2m3 emax = 2) and the packed fp6 residuals
+                // (option: residual scale from the bound |x - f16(x)| <= 2^(floor(log2 |x|) - 11) instead of a second block maximum)
+                int eh = (int)((__float_as_uint(amax_v * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2, el = LO_SCALE_FROM_BOUND ? eh - 11 : (int)((__float_as_uint(amax_l * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2;
+                eh = eh < 1 ? 1 : eh;
+                el = el < 1 ? 1 : el;
+                esc[q] = (uint32_t)eh | ((uint32_t)el << 8);
+                f32x16v ev, od; // v_cvt_scalef32_2xpk16_fp6_f32 interleaves its two sources: field 2i = ev[i], 2i+1 = od[i]
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { ev[i] = res[2 * i]; od[i] = res[2 * i + 1]; }
+                lo6[q] = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, __uint_as_float((uint32_t)el << 23));
+            }
+            // read back: lanes 8i'..8i'+7 hold the 8 pieces of pixel 8i + i' of the tile
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const uint4 v = *(const uint4*)(grid + st_gi[i] * GRID_STRIDE + 4 * (lane & 7));
-                const int q = (lane >> 2) & 1;
-                if (!(ABL & 8)) {
-                    if (st_ok[i] && active) {
-                        uint4* dst = &row[(size_t)(tile * 2 + q) * OP_BLK_U4 + OP_LO_U4 + (8 * i + (lane >> 3)) * 4 + (lane & 3)];
-                        if (BASE && !DELTA) for (int c = 0; c < copies; ++c) nt_store(v, dst + (size_t)c * row_u4);
-                        else if (DELTA) { *dst = v; if (BASE && row2) row2[dst - row] = v; }
-                        else nt_store(v, dst);
-                    }
+                if (st_ok[i] && active) {
+                    uint4* dst = &row[(size_t)(tile * 2 + q) * OP_BLK_U4 + (8 * i + (lane >> 3)) * 8 + (lane & 7)];
+                    if (BASE && !DELTA) for (int c = 0; c < copies; ++c) nt_store(v, dst + (size_t)c * row_u4);
+                    else if (DELTA) { *dst = v; if (BASE && row2) row2[dst - row] = v; } // (read again right away: by fc0; by the children of the run)
+                    else nt_store(v, dst);
                 }
-                else if (v.x == 0x12345678u && v.y == 0x9abcdef0u) row[lane] = v;
             }
-            } // (fp6 format)
+            WAVE_LDS_FENCE();
         }
+        if (valid) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                if (MX6) { // 64 B per (pixel, q): [h0 dwords 0..3][h1 dwords 0..3][h0 dwords 4,5 | h1 dwords 4,5][scale bytes h0, h1 | pad]
+                    stage_w[q * 4 + h] = make_uint4(lo6[q][0], lo6[q][1], lo6[q][2], lo6[q][3]);
+                    ((uint2*)(stage_w + q * 4 + 2))[h] = make_uint2(lo6[q][4], lo6[q][5]);
+                    ((uint16_t*)(stage_w + q * 4 + 3))[h] = (uint16_t)esc[q];
+                } else {
+                    stage_w[q * 4 + h * 2 + 0] = make_uint4(p8l[q][0], p8l[q][1], p8l[q][2], p8l[q][3]);
+                    stage_w[q * 4 + h * 2 + 1] = make_uint4(p8l[q][4], p8l[q][5], p8l[q][6], p8l[q][7]);
+                }
+            }
+        }
+        WAVE_LDS_FENCE();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint4 v = *(const uint4*)(grid + st_gi[i] * GRID_STRIDE + 4 * (lane & 7));
+            const int q = (lane >> 2) & 1;
+            if (st_ok[i] && active) {
+                uint4* dst = &row[(size_t)(tile * 2 + q) * OP_BLK_U4 + OP_LO_U4 + (8 * i + (lane >> 3)) * 4 + (lane & 3)];
+                if (BASE && !DELTA) for (int c = 0; c < copies; ++c) nt_store(v, dst + (size_t)c * row_u4);
+                else if (DELTA) { *dst = v; if (BASE && row2) row2[dst - row] = v; }
+                else nt_store(v, dst);
+            }
+        }
+        } // (fp6 format)
     }
 }
 
@@ -963,10 +922,7 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
     // pulls ~28 KB per child through L2 instead of ~35 (the stone's pixel lies in rows 0..9, columns 0..14: the column separates more).  Which wave evaluates a
     // row changes nothing in the row.
     int pos_in_run = lane - rs;
-#ifndef GROUP_SORT
-#define GROUP_SORT 1 // (A-B builds: 0 = request order, same results)
-#endif
-    if (sib_slot && GROUP_SORT) {
+    if (sib_slot) {
         const int pc = (2 * (int)(ta >> 8) + 1) / 3;
         const int key = in_run ? (((pc % 15) * 16 + pc / 15) << 6) | lane : 0x7FFFFFFF;
         int rank_in_run = 0;
@@ -1271,26 +1227,17 @@ __global__ __launch_bounds__(256) void k_facc_reduce(const float* __restrict__ p
 // DELTA (difference path): a_out holds the FULL rows (one per run, written by k_trunk<BASE | DELTA>); the child's window entries are
 // stored as DIFFERENCES to the base's entries (dequantised: f16 hi + fp6 residual * 2^scale, exactly what fc0 will multiply), in the
 // same entry format, into the child's slot row of d_rows: fc0(child) = fc0(base row) + W[window] * difference row.
-template <bool DELTA, bool TPROF = false, bool F16LO = false, int N = 15> // TPROF (OMOK_SIB_PROF=1, timing only): shader-clock cycles per phase, summed over wave 0's passes, into tprof[]
-                                                                // F16LO: operand / difference rows in the FC0_F16 format (f16 residuals)
+template <bool DELTA, bool F16LO = false, int N = 15> // F16LO: operand / difference rows in the FC0_F16 format (f16 residuals)
 __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict__ board, const uint4* __restrict__ wt, const float* __restrict__ side,
                                                       uint4* __restrict__ a_out, size_t row_u4, const uint4* __restrict__ sib_rows,
                                                       const int32_t* __restrict__ d_cnt, const float* __restrict__ hscr,
                                                       const uint32_t* __restrict__ sib_slot, const int32_t* __restrict__ bin_start,
                                                       uint4* __restrict__ d_rows, uint2* __restrict__ slot_desc,
-                                                      unsigned long long* __restrict__ tprof) {
+                                                      unsigned long long* __restrict__ /* (k_sib_children2's profile buffer: the two kernels share a launch signature) */) {
     constexpr int BLK_U4 = fmt_blk_u4(F16LO);
     constexpr int DROW_U4 = F16LO ? SIBX_DROW_U4 : SIB_DROW_U4;
     constexpr int SIB_HB_FLOATS = sib_hb_floats(N);
     constexpr int SWW = 4; // depthwise strips of the 7-wide window: 4 | 3 pixels
-    unsigned long long tp_acc[12] = {}, tp_last = 0;
-    auto TP = [&](int phase) { // (phase = what ended here)
-        if (TPROF) {
-            const unsigned long long now = __builtin_readcyclecounter();
-            tp_acc[phase] += now - tp_last;
-            tp_last = now;
-        }
-    };
     using TG = TrunkGeo<N>;
     constexpr int HW = TG::HW, NW = Geo<N>::NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1671,7 +1618,6 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
         const float* dwt = lside + blk * TR_SIDE_PER_BLOCK;
         f32x16 acc;
         L0_tile(x, blk, acc);
-        TP(1);
         if (c_valid) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -1684,7 +1630,6 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
 #pragma unroll
         for (int u = 0; u < 2; ++u) *(uint4*)(cgrid + ring_off[u]) = ring[u]; // halo ring <- the base's h of this block (zero outside the board)
         lds_barrier(); // B2
-        TP(2);
         if (fetch_next_ring) ring_fetch(hb, blk + 1, wy0, wx0, ring);
         // depthwise over the 7x7 window: (row, strip of 4 | 3 pixels, 4-channel group) = 112 items for the pair's 128 threads
         f32x4 dout[SWW];
@@ -1714,7 +1659,6 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
                 dout[p] = o;
             }
         }
-        TP(3);
         bar_wait(); // B3, second half: the grid can be overwritten in place
         if (ptid < 7 * 2 * 8) {
 #pragma unroll
@@ -1728,7 +1672,6 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
 #pragma unroll
             for (int i = 0; i < 4; ++i) d[4 * g + i] = dv[i];
         }
-        TP(4);
     };
     // A workgroup takes a CONTIGUOUS range of the rows (a run's children are adjacent: the 16 children of a run are four consecutive
     // passes of one workgroup, so the base's h grids and operand row come from HBM once and from this XCD's L2 afterwards; dealt
@@ -1739,7 +1682,6 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
     window_of(ent_c, wy0, wx0);
     ring_fetch(hscr + (size_t)ent_c.y * 3 * SIB_HB_FLOATS, 0, wy0, wx0, ring);
     for (int e0 = e_begin; e0 < e_end; e0 += pass_stride) { // one child per pass and pair; uniform over the pair
-        if (TPROF) tp_last = __builtin_readcyclecounter();
         const bool act = e0 < e_end;
         const uint4 ent = ent_c;
         const int crow = (int)ent.x;
@@ -1761,18 +1703,15 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
         input_bits(cw, turn, q, bits);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         conv_in_tile(x, bits[0], bits[1], bits[2]);
-        TP(0);
         float d[16];
 #pragma unroll 1
         for (int blk = 0; blk < 2; ++blk) {
             block_front(blk, d, true);
             L1L2_tile(x, blk, d);
-            TP(5);
         }
         block_front(2, d, false);
         if (DELTA) base_fetch(a_out + (size_t)ent.y * row_u4, q);
         L1L2_tile(x, 2, d);
-        TP(5);
         { // the window's 49 pixel entries: over the copied base row, or (DELTA) as differences into the slot's row
             int rd_gi[4], rd_px[4];
             bool rd_ok[4];
@@ -1791,7 +1730,6 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
                 else base_subtract(x);
                 if (act && wt2 == 0 && lane == 0) slot_desc[slot] = make_uint2((uint32_t)crow, ent.y);
             }
-            TP(6);
             // the next pass's first halo ring before this pass's stores queue up behind it
             window_of(ent_n, wy0, wx0);
             ring_fetch(hscr + (size_t)ent_n.y * 3 * SIB_HB_FLOATS, 0, wy0, wx0, ring);
@@ -1803,16 +1741,8 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
         slot_c = slot_n;
         slot_n = slot_nn;
         word_c = word_n;
-        TP(7);
         // (no barrier here: the staging rows a wave read back are its own pixels' rows, the board words its own copy; the mate's next
         //  accesses to this wave's rows are window reads behind B2 of the next pass)
-    }
-    if (TPROF && lane == 0 && (wv == 0 || wv == 5))
-        for (int i = 0; i < 9; ++i) atomicAdd(&tprof[(wv ? 16 : 0) + i], tp_acc[i]);
-    if (TPROF && lane == 0 && (wv & 1) == 0) { // per pair: cycles in the loop (all phases)
-        unsigned long long t = 0;
-        for (int i = 0; i < 9; ++i) t += tp_acc[i];
-        atomicAdd(&tprof[28 + (wv >> 1)], t);
     }
 }
 
@@ -1829,43 +1759,12 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
 // pixel-major in the piece order of the accumulators (sib2_grid, sib2_x2).  Results are within rounding of k_sib_children's (a different summation order in the
 // depthwise) and need not be bit-identical -- on the rows the tests compare they are, every layer boundary re-quantising to ~22 bits -- so the difference path
 // is tolerance-checked; the copy path (rows bit-identical to a full evaluation by construction) keeps k_sib_children.
-#ifndef SIB2_EXP
-#define SIB2_EXP 0 // A-B builds (tools/build_variant.sh): 1 = every child reads base slot 0 (timing only), 3 = a workgroup barrier per pass, 6 = per 4 passes, 4 = plain stores, 7 = no stores (timing only), 8 = contiguous shares per wave (round 3), 9 / 10 = no conv_in / block 0 (timing only), 17 = every wave's cycles per launch -> stderr (diagnostic, results unchanged)
-#endif
-#if SIB2_EXP != 0 && !defined(OMOK_EXPERIMENT)
-#error "SIB2_EXP builds are timing experiments, most with wrong results: build them with -DOMOK_EXPERIMENT (tools/build_variant.sh does), never as the product"
-#endif
-#if SIB2_EXP == 4
-#define ROW_STORE(V, P) (*(P) = (V))
-#elif SIB2_EXP == 12 // (timing only: everything of the store phase -- staging, read-back, addresses -- except the store instructions themselves)
-#define ROW_STORE(V, P) do { const uint4 v_ = (V); const uint4* p_ = (P); asm volatile("" ::"v"(v_.x), "v"(v_.y), "v"(v_.z), "v"(v_.w), "v"(p_)); } while (0)
-#elif SIB2_EXP == 13 // (timing only: every store goes to the first row of the wave's workgroup: the instructions without their HBM traffic)
-#define ROW_STORE(V, P) nt_store((V), d_rows + ((size_t)blockIdx.x * 2048 + (size_t)((P) - d_rows) % 2048))
-#else
-#define ROW_STORE(V, P) nt_store((V), (P))
-#endif
 constexpr int V2_TW = 5, V2_TPX = V2_TW * V2_TW;          // tile window side, pixels
 constexpr int V2_RING = SIB_WPX - V2_TPX;                 // 24
 constexpr int V2_ZERO_CELL = 32, V2_WORD_CELL = 33;       // cells 0..31: tile grid / staging rows
 constexpr int V2_CELLS = 34;
 constexpr int V2_WAVE_FLOATS = V2_CELLS * GRID_STRIDE;
-// Round 6: the last layer's bias (b2, 128 channels per block) is added by ONE more MFMA per m-tile instead of 64 vector adds + 16 LDS reads per call: A = the bias as three f16 pieces
-// (hi, lo, lo of lo: 33 bits) in k = 0..2 of a 512-B fragment (only the k = 0..7 half of a fragment is stored: B is zero in k = 8..15, so both lane halves read the same 32 lanes),
-// B = 1.0 in k = 0..2.  216 MFMAs per child instead of 200, 128 vector adds fewer per L1L2 call pair (tools/isa_hist.py); the matrix pipes are the idle unit of this kernel.
-#ifndef V2_BIAS_MFMA
-#define V2_BIAS_MFMA 0 // (round 6 A-B: measured, no gain: off)
-#endif
-#ifndef V2_DYNAMIC
-#define V2_DYNAMIC 1 // a workgroup's children handed out from an LDS counter (0: every wave takes every eighth entry)
-#endif
-#if V2_DYNAMIC && SIB2_EXP == 8
-#error "SIB2_EXP=8 (contiguous shares per wave) needs -DV2_DYNAMIC=0"
-#endif
-#ifndef V2_FAR_BY_STORE
-#define V2_FAR_BY_STORE 0 // (round 6 A-B: no gain: off) the exact zeros of far pixels: staged pieces overwritten under a branch instead of selected value by value (44 selects per store_rows call)
-#endif
-constexpr int V2_BIAS_BYTES = V2_BIAS_MFMA ? 3 * 4 * 512 : 0;
-constexpr int V2_LDS = TR_WBYTES + TR_SIDE_FLOATS * 4 + 8 * V2_WAVE_FLOATS * 4 + V2_BIAS_BYTES;
+constexpr int V2_LDS = TR_WBYTES + TR_SIDE_FLOATS * 4 + 8 * V2_WAVE_FLOATS * 4;
 static_assert(V2_LDS <= 160 * 1024, "k_sib_children2 LDS");
 #define OL() ({ int lq_ = lane; asm volatile("" : "+v"(lq_)); lq_; })
 #define TILE_A(LQ) (((LQ) & 31) < V2_TPX ? ((LQ) & 31) : V2_TPX - 1)
@@ -1901,16 +1800,6 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     for (int i = tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
     for (int i = tid; i < TR_SIDE_FLOATS; i += blockDim.x) ((float*)lside)[i] = side[i];
     for (int i = tid; i < 8 * V2_WAVE_FLOATS; i += blockDim.x) ((float*)(smem + TR_WBYTES + TR_SIDE_FLOATS * 4))[i] = 0.0f;
-    const half8* lbias = (const half8*)(smem + TR_WBYTES + TR_SIDE_FLOATS * 4 + 8 * V2_WAVE_FLOATS * 4); // [blk][m][row 32]: b2 as f16 pieces in k = 0..2
-    if (V2_BIAS_MFMA)
-        for (int i = tid; i < 3 * 4 * 32; i += blockDim.x) {
-            const float b = side[(i >> 7) * TR_SIDE_PER_BLOCK + 11 * NM + (i & 127)];
-            const _Float16 p0 = (_Float16)b;
-            const float r1 = b - (float)p0;
-            const _Float16 p1 = (_Float16)r1, p2 = (_Float16)(r1 - (float)p1);
-            ((half8*)lbias)[i] = (half8){p0, p1, p2, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f};
-        }
-#if V2_DYNAMIC
     // Round 6: the children of a workgroup are handed out from a counter in LDS instead of every wave taking every eighth entry.  The second wave of a SIMD (waves 4..7)
     // runs ~15 % slower than the first (issue arbitration favours the older wave: profiles/r05_children_store_order.txt, item 7), so with equal shares waves 0..3 end early
     // and the others finish alone; handed out on demand, all eight end together.  A child's arithmetic does not depend on the wave that takes it: same bits.
@@ -1920,17 +1809,9 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         const int wb0 = (int)blockIdx.x * per0 < nsib0 ? (int)blockIdx.x * per0 : nsib0;
         s_next_entry = wb0 + 16; // (entries wb0 .. wb0 + 15: the waves' first two passes)
     }
-#endif
     __syncthreads(); // (the only workgroup barrier: from here on a wave touches read-only LDS and its own cells)
     for (int i = 0; i < (wv >> 2); ++i) __builtin_amdgcn_s_sleep(120); // the two waves of a SIMD (w, w + 4) start about half a pass apart
-#ifdef V2_PRIO // (round 6 A-B: static issue priority for one wave of each SIMD's pair -- 1: the younger waves 4..7, 2: the older waves 0..3)
-    if ((V2_PRIO == 1) == (wv >= 4)) __builtin_amdgcn_s_setprio(1);
-#endif
-#if SIB2_EXP == 17 // (diagnostic, results unchanged: every wave's cycles from here to its end -> tprof[workgroup * 8 + wave], summed over the launches)
-    const unsigned long long wt0 = __builtin_readcyclecounter();
-#endif
     const int nsib = d_cnt[2];
-    const bool st_on = SIB2_EXP != 7 || nsib < 0; // (timing experiment 7: no difference-row stores; a run-time condition, so that nothing is dead code)
     const half8* convW = (const half8*)(wt + TR_WBYTES / 16);
     half8 cwh[4], cwl[4]; // conv_in fragments: fetched again at the end of every pass (see k_sib_children)
     auto load_conv_w = [&]() {
@@ -1992,21 +1873,13 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         half8 gh[2], gl[2];
         split8(gv, gh[0], gl[0]);
         split8(gv + 8, gh[1], gl[1]);
-        union { uint32_t u[4]; half8 v; } one3; // B of the bias MFMA: 1.0 in k = 0..2 (lanes of half h = 0), zero elsewhere
-        one3.u[0] = h == 0 ? 0x3C003C00u : 0u;
-        one3.u[1] = h == 0 ? 0x00003C00u : 0u;
-        one3.u[2] = 0u;
-        one3.u[3] = 0u;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            if (V2_BIAS_MFMA) x[m] = MFMA16(lbias[(blk * 4 + m) * 32 + (lane & 31)], one3.v, x[m]);
-            else {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 bv = *(const f32x4*)(b2 + 32 * m + 8 * g + 4 * h);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) x[m][4 * g + i] += bv[i];
-            }
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -2076,7 +1949,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                     for (int i = 0; i < 4; ++i) {
                         const uint4 v = *(const uint4*)(wgrid + rd_gi[i] * GRID_STRIDE + 4 * (lane & 7));
                         if (i == 3) WAVE_LDS_FENCE();
-                        if (rd_ok[i] && st_on) ROW_STORE(v, &row[part * SIB_DLO_U4 + (q * SIB_WPX + rd_px[i]) * 8 + (lane & 7)]);
+                        if (rd_ok[i]) nt_store(v, &row[part * SIB_DLO_U4 + (q * SIB_WPX + rd_px[i]) * 8 + (lane & 7)]);
                     }
                 }
             }
@@ -2105,12 +1978,8 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                         asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_v) : "v"(v0), "v"(v1));
                         asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_l) : "v"(l0), "v"(l1));
                     }
-                    if (lane_valid) stage_w[(mm * 2 + sx) * 2 + h] = V2_FAR_BY_STORE ? H.v : (far ? make_uint4(0u, 0u, 0u, 0u) : H.v);
+                    if (lane_valid) stage_w[(mm * 2 + sx) * 2 + h] = far ? make_uint4(0u, 0u, 0u, 0u) : H.v;
                 }
-            if (V2_FAR_BY_STORE && lane_valid && far) { // a far lane's pieces are overwritten with zeros (a branch most passes of interior children skip) instead of 32 selects per call
-#pragma unroll
-                for (int p4 = 0; p4 < 4; ++p4) stage_w[p4 * 2 + h] = make_uint4(0u, 0u, 0u, 0u);
-            }
             WAVE_LDS_FENCE();
             int eh = (int)((__float_as_uint(amax_v * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2, el = (int)((__float_as_uint(amax_l * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2;
             eh = eh < 1 ? 1 : eh;
@@ -2120,11 +1989,11 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
 #pragma unroll
             for (int i = 0; i < 16; ++i) { ev[i] = res[2 * i]; od[i] = res[2 * i + 1]; }
             lo6[q] = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, __uint_as_float((uint32_t)el << 23));
-            if (!V2_FAR_BY_STORE && far) lo6[q] = (u32x6){0u, 0u, 0u, 0u, 0u, 0u};
+            if (far) lo6[q] = (u32x6){0u, 0u, 0u, 0u, 0u, 0u};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const uint4 v = *(const uint4*)(wgrid + rd_gi[i] * GRID_STRIDE + 4 * (lane & 7));
-                if (rd_ok[i] && st_on) ROW_STORE(v, &row[(q * SIB_WPX + rd_px[i]) * 8 + (lane & 7)]);
+                if (rd_ok[i]) nt_store(v, &row[(q * SIB_WPX + rd_px[i]) * 8 + (lane & 7)]);
             }
             WAVE_LDS_FENCE();
         }
@@ -2135,20 +2004,13 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 ((uint2*)(stage_w + q * 4 + 2))[h] = make_uint2(lo6[q][4], lo6[q][5]);
                 ((uint16_t*)(stage_w + q * 4 + 3))[h] = (uint16_t)esc[q];
             }
-            if (V2_FAR_BY_STORE && far) { // zero codes (the scale bytes stay: any scale times zero)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    stage_w[q * 4 + h] = make_uint4(0u, 0u, 0u, 0u);
-                    ((uint2*)(stage_w + q * 4 + 2))[h] = make_uint2(0u, 0u);
-                }
-            }
         }
         WAVE_LDS_FENCE();
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint4 v = *(const uint4*)(wgrid + rd_gi[i] * GRID_STRIDE + 4 * (lane & 7));
             const int q = (lane >> 2) & 1;
-            if (rd_ok[i] && st_on) ROW_STORE(v, &row[SIB_DLO_U4 + (q * SIB_WPX + rd_px[i]) * 4 + (lane & 3)]);
+            if (rd_ok[i]) nt_store(v, &row[SIB_DLO_U4 + (q * SIB_WPX + rd_px[i]) * 4 + (lane & 3)]);
         }
         WAVE_LDS_FENCE();
     };
@@ -2156,15 +2018,12 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     uint4 bs_hi[2][4], bs_lo[2];
     uint2 bs_lt[2];
     uint32_t bs_sc[2];
-    auto base_fetch = [&](const uint4* frow, int px, int (&cpx4)[4]) {
+    auto base_fetch = [&](const uint4* frow, int px) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * BLK_U4;
 #pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) {
-                if (SIB2_EXP == 14) bs_hi[q][p4] = (frow + (size_t)((cpx4[p4] >> 5) * 2 + q) * BLK_U4)[(cpx4[p4] & 31) * 8 + (lane & 7)]; // (timing only: whole lines per load)
-                else bs_hi[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
-            }
+            for (int p4 = 0; p4 < 4; ++p4) bs_hi[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
             if (F16LO) continue;
             const uint4* lp = bp + OP_LO_U4 + (px & 31) * 4;
             bs_lo[q] = lp[h];
@@ -2189,16 +2048,13 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 }
             }
     };
-    auto base_sub_f16lo = [&](f32x16 (&x)[4], const uint4* frow, int px, int (&cpx4)[4]) {
+    auto base_sub_f16lo = [&](f32x16 (&x)[4], const uint4* frow, int px) {
         uint4 lo[2][4];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * BLK_U4 + OP_LO_U4;
 #pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) {
-                if (SIB2_EXP == 14) lo[q][p4] = (frow + (size_t)((cpx4[p4] >> 5) * 2 + q) * BLK_U4 + OP_LO_U4)[(cpx4[p4] & 31) * 8 + (lane & 7)];
-                else lo[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
-            }
+            for (int p4 = 0; p4 < 4; ++p4) lo[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
         }
 #pragma unroll
         for (int q = 0; q < 2; ++q) sub_pieces(x, q, bs_hi[q]);
@@ -2239,15 +2095,10 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     const int wg_begin = (int)blockIdx.x * per_wg < nsib ? (int)blockIdx.x * per_wg : nsib, wg_end = wg_begin + per_wg < nsib ? wg_begin + per_wg : nsib;
     // (equal shares: the in-kernel counters show waves 4..7 18 % slower per child than the four launched first, but shares of 134 .. 146 / 1024 for waves 0..3
     //  measured the same as 128: A-B builds, 144.7 - 148.8 ms of trunk kernels per three plies with no order in them)
-#if SIB2_EXP != 8
     // the 8 waves take consecutive entries: a run's ~15 siblings are in flight together on ONE CU, and what one wave pulled into this XCD's L2 the others find there
     // (FETCH_SIZE per launch -30 % against contiguous shares per wave, same time: profiles/r04_children_traffic_experiments.txt)
     constexpr int ESTR = 8;
     const int e_begin = wg_begin + wv, e_end = wg_end;
-#else
-    constexpr int ESTR = 1;
-    const int e_begin = wg_begin + (int)(((long long)(wg_end - wg_begin) * wv) >> 3), e_end = wg_begin + (int)(((long long)(wg_end - wg_begin) * (wv + 1)) >> 3);
-#endif
     auto entry_of = [&](int e0) { return e0 < e_end ? e0 : (e_begin < e_end ? e_begin : 0); };
     auto fetch_word = [&](const uint4& ent) {
         uint64_t word = 0ULL;
@@ -2257,17 +2108,9 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     uint4 ent_c = sib_rows[entry_of(e_begin)], ent_n = sib_rows[entry_of(e_begin + ESTR)];
     uint32_t slot_c = sib_slot[entry_of(e_begin)], slot_n = sib_slot[entry_of(e_begin + ESTR)];
     uint64_t word_c = fetch_word(ent_c);
-#if V2_DYNAMIC
     int e_nn_keep = 0;
     int e_next = e_begin + ESTR; // entry of the next pass (its descriptor is in ent_n); the one after that comes from the counter
     for (int e0 = e_begin; e0 < e_end; e0 = e_next, e_next = e_nn_keep) {
-#else
-    for (int e0 = e_begin; e0 < e_end; e0 += ESTR) {
-#endif
-#if SIB2_EXP == 3 || SIB2_EXP == 6
-        // (experiment: the waves of the workgroup stay on the same entries by a barrier per pass / per 4 passes; a wave that has left the loop has ended and no longer counts)
-        if (SIB2_EXP == 3 || (((e0 - e_begin) >> 3) & 3) == 0) __builtin_amdgcn_s_barrier();
-#endif
         if (TPROF) tp_last = __builtin_readcyclecounter();
         // lane "constants" (tile pixel (ty, tx) of the 5x5 window, ring index, depthwise strip item) are derived again in every phase from an opaque
         // copy of the lane index (OL): hoisted out of the loop or to the top of the pass, they and the addresses built on them were spilled to scratch
@@ -2305,60 +2148,23 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             ring_at(RING_B(OL()), wyB, wxB);
             bpxB = (wy0 + wyB) * N + wx0 + wxB;
         }
-        // SIB2_EXP == 14 (timing only, wrong data): every base load covers WHOLE 128-B lines -- lanes 8 p' .. 8 p' + 7 read the eight pieces of pixel 8 i + p' (instruction i of
-        // a group of four) instead of each lane reading one piece of its own pixel: the same bytes and lines per group, each line touched by ONE instruction
-        int cpxA[4] = {0, 0, 0, 0}, cpxB[4] = {0, 0, 0, 0};
-        if (SIB2_EXP == 14) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                int t = 8 * i + (lane >> 3);
-                asm volatile("" : "+v"(t));
-                const int ta = t < V2_TPX ? t : V2_TPX - 1;
-                cpxA[i] = (vy0 + ta / V2_TW) * N + vx0 + ta % V2_TW;
-                int wy, wx;
-                ring_at(t < V2_RING ? t : V2_RING - 1, wy, wx);
-                cpxB[i] = (wy0 + wy) * N + wx0 + wx;
-            }
-        }
-#define GIDX(BLK, KIND, RING, G) (SIB2_EXP == 14 ? ((size_t)((BLK) * 2 + (KIND)) * HW + ((RING) ? cpxB[G] : cpxA[G])) * 8 + (lane & 7) : sib2_grid(HW, BLK, KIND, (RING) ? bpxB : bpxA, G, h))
-
         const int slot = bin_start[slot_c >> 24] + (int)(slot_c & 0xFFFFFFu);
         uint4* crow_p = d_rows + (size_t)slot * DROW_U4;
-        const uint4* sb = sib2 + (size_t)(SIB2_EXP == 1 ? 0u : ent.y) * SLOT_U4; // (timing experiment 1: every child reads base slot 0 -- all hits)
-        const uint4* frow = a_out + (size_t)(SIB2_EXP == 1 ? 0u : ent.y) * row_u4;
+        const uint4* sb = sib2 + (size_t)ent.y * SLOT_U4;
+        const uint4* frow = a_out + (size_t)ent.y * row_u4;
         uint64_t* cw = (uint64_t*)(wgrid + V2_WORD_CELL * GRID_STRIDE);
         if (lane < 2 * NW) cw[lane] = word_c;
         const uint64_t word_n = fetch_word(ent_n);
-#if V2_DYNAMIC
         int e_nn = 0;
         if (lane == 0) e_nn = atomicAdd(&s_next_entry, 1);
         e_nn = __builtin_amdgcn_readfirstlane(e_nn);
         e_nn_keep = e_nn;
-#else
-        const int e_nn = e0 + 2 * ESTR;
-#endif
         const uint4 ent_nn = sib_rows[entry_of(e_nn)];
         const uint32_t slot_nn = sib_slot[entry_of(e_nn)];
         WAVE_LDS_FENCE();
         uint32_t bits[3];
         input_bits(cw, turn, bpxA, bits);
-        if (SIB2_EXP != 9 && SIB2_EXP != 10) conv_in_tile(x, bits[0], bits[1], bits[2]);
-        if (SIB2_EXP == 9) { // (timing experiment: no conv_in, no block 0 -- what a kernel that starts from the base's residual stream in front of block 1 would save)
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) x[m][i] = (float)(bits[0] + m + i);
-        }
-        if (SIB2_EXP == 10) { // (... and with the tile's residual stream loaded instead: 25 pixels x 512 B)
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 v = __builtin_bit_cast(f32x4, sb[sib2_x2(HW, bpxA, m, g, h)]);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) x[m][4 * g + i] = v[i] + (float)bits[0];
-                }
-        }
+        conv_in_tile(x, bits[0], bits[1], bits[2]);
         TP(0);
         // h_child - h_base of the tile -> the wave's cells; `hb` / `db`: the base's h and d pieces of this lane's pixel
         auto grid_write = [&](const f32x16& acc, const uint4 (&hb)[4]) {
@@ -2423,7 +2229,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             }
             WAVE_LDS_FENCE();
         };
-        if (SIB2_EXP != 9 && SIB2_EXP != 10) { // ---- block 0: h differs from the base's in ONE pixel (P0): its difference goes to one cell, and every tile pixel next to P0 adds one tap of it ----
+        { // ---- block 0: h differs from the base's in ONE pixel (P0): its difference goes to one cell, and every tile pixel next to P0 adds one tap of it ----
             int blk0 = 0;
             asm volatile("" : "+s"(blk0));
             const int tP = (py - vy0) * V2_TW + (pxx - vx0); // P0's pixel index in the tile (wave-uniform)
@@ -2434,7 +2240,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             for (int g = 0; g < 4; ++g) {
                 hb[g] = make_uint4(0u, 0u, 0u, 0u);
                 if (at_p0) hb[g] = sb[sib2_grid(HW, 0, 0, bpxA, g, h)];
-                db[g] = sb[GIDX(0, 1, false, g)];
+                db[g] = sb[sib2_grid(HW, 0, 1, bpxA, g, h)];
             }
             f32x16 acc;
             L0_tile(x, blk0, acc);
@@ -2473,8 +2279,8 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             uint4 hb[4], db[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                hb[g] = sb[GIDX(1, 0, false, g)];
-                db[g] = sb[GIDX(1, 1, false, g)];
+                hb[g] = sb[sib2_grid(HW, 1, 0, bpxA, g, h)];
+                db[g] = sb[sib2_grid(HW, 1, 1, bpxA, g, h)];
             }
             f32x16 acc;
             L0_tile(x, blk1, acc);
@@ -2493,9 +2299,9 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             uint4 hb[4], db[4], dbB[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                hb[g] = sb[GIDX(2, 0, false, g)];
-                dbB[g] = sb[GIDX(2, 1, true, g)];
-                db[g] = sb[GIDX(2, 1, false, g)];
+                hb[g] = sb[sib2_grid(HW, 2, 0, bpxA, g, h)];
+                dbB[g] = sb[sib2_grid(HW, 2, 1, bpxB, g, h)];
+                db[g] = sb[sib2_grid(HW, 2, 1, bpxA, g, h)];
             }
             f32x16 acc;
             L0_tile(x, blk2, acc);
@@ -2540,7 +2346,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             strip_dw(dwt, db);
         }
         TP(4);
-        base_fetch(frow, bpxA, cpxA);
+        base_fetch(frow, bpxA);
         L1L2_tile(x, blk2, d);
         TP(5);
         {
@@ -2554,7 +2360,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 rd_px[i] = (oy + tc / V2_TW) * SIB_WIN + ox + tc % V2_TW;
                 rd_ok[i] = t < V2_TPX;
             }
-            if constexpr (F16LO) base_sub_f16lo(x, frow, bpxA, cpxA);
+            if constexpr (F16LO) base_sub_f16lo(x, frow, bpxA);
             else base_subtract(x);
             if (lane == 0) slot_desc[slot] = make_uint2((uint32_t)crow, ent.y);
             TP(6);
@@ -2563,7 +2369,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 int bq = bpxA;
                 asm volatile("" : "+v"(bq));
                 const int yA = bq / N, xA = bq - yA * N;
-                farA = (yA - py > 3 || py - yA > 3 || xA - pxx > 3 || pxx - xA > 3) && SIB2_EXP != 15; // (timing experiment 15: no exact zeros -- only valid with the rectangles off)
+                farA = (yA - py > 3 || py - yA > 3 || xA - pxx > 3 || pxx - xA > 3);
             }
             store_rows(x, crow_p, (OL() & 31) < V2_TPX, rd_px, rd_ok, farA);
             TP(7);
@@ -2573,17 +2379,11 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                size_t xi = sib2_x2(HW, bpxB, m, g, h);
-                if (SIB2_EXP == 14) { // (two pixels x 512 B per instruction; the ring's 24 pixels take 12 of the 16, the last four repeat)
-                    int t = 2 * (4 * m + g) + (lane >> 5);
-                    t = t < V2_RING ? t : V2_RING - 1;
-                    xi = (size_t)48 * HW + (size_t)cpxB[(t >> 3) & 3] * 32 + (lane & 31); // (pixel 8 i + p' of the table; the pixel within the group is that of lane t & 7 -- close enough for timing)
-                }
-                const f32x4 v = __builtin_bit_cast(f32x4, sb[xi]);
+                const f32x4 v = __builtin_bit_cast(f32x4, sb[sib2_x2(HW, bpxB, m, g, h)]);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) x[m][4 * g + i] = v[i];
             }
-        base_fetch(frow, bpxB, cpxB);
+        base_fetch(frow, bpxB);
 #pragma unroll
         for (int i = 0; i < 16; ++i) d[i] = dBk[i];
         TP(8);
@@ -2601,7 +2401,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 rd_px[i] = wy * SIB_WIN + wx;
                 rd_ok[i] = t < V2_RING;
             }
-            if constexpr (F16LO) base_sub_f16lo(x, frow, bpxB, cpxB);
+            if constexpr (F16LO) base_sub_f16lo(x, frow, bpxB);
             else base_subtract(x);
             TP(10);
             bool farB;
@@ -2609,7 +2409,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 int bq = bpxB;
                 asm volatile("" : "+v"(bq));
                 const int yB = bq / N, xB = bq - yB * N;
-                farB = (yB - py > 3 || py - yB > 3 || xB - pxx > 3 || pxx - xB > 3) && SIB2_EXP != 15;
+                farB = (yB - py > 3 || py - yB > 3 || xB - pxx > 3 || pxx - xB > 3);
             }
             store_rows(x, crow_p, (OL() & 31) < V2_RING, rd_px, rd_ok, farB);
         }
@@ -2623,16 +2423,11 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     }
     if (TPROF && lane == 0 && (wv == 0 || wv == 5))
         for (int i = 0; i < 12; ++i) atomicAdd(&tprof[(wv ? 16 : 0) + i], tp_acc[i]);
-#if SIB2_EXP == 17
-    if (lane == 0 && tprof) atomicAdd(&tprof[blockIdx.x * 8 + wv], __builtin_readcyclecounter() - wt0);
-#endif
 }
 
 #undef OL
-#undef ROW_STORE
 #undef TILE_A
 #undef RING_B
-#undef GIDX
 // ===============================================================================================
 // OMOK_NET_F16X3: fc0 with block-scaled fp6 (or fp8) correction terms
 // ===============================================================================================
@@ -2699,7 +2494,6 @@ __device__ inline void f16x8_to_fp8(const half8& v, float inv_mul, uint32_t& d0,
 // super-step are read from LDS once and stay in registers for its 4 stages; a weight fragment is read from LDS by
 // exactly one wave.  LDS traffic per stage drops from 144 KiB (8-wave form) to ~48 KiB and the matrix pipe is fed
 // by one wave with 4 independent accumulator chains.
-constexpr int NET_CHUNK_DEFAULT = 0; // rows per forward launch (0 = unchunked); OMOK_NET_CHUNK overrides
 constexpr bool A_NT = true;     // the sample-operand stream is read once: non-temporal, so it does not displace the weight stream in L2
 // MX6 helpers: fp6 (e2m3) copy of 32 f16 values (4 consecutive 8-element pieces, natural slot order) = x / 2^(E - 127)
 __device__ inline v8i f16x32_to_fp6(const half8& p0, const half8& p1, const half8& p2, const half8& p3, uint32_t e8m0) {
@@ -2732,7 +2526,7 @@ constexpr bool STAGGER = false; // (skewing the waves by s_nops after the barrie
 // 49 window pixels x 2 channel halves), the weight stages of super-step (w, q) are those of the window pixel's board pixel, and the
 // epilogue adds the fp32 fc0 row of the slot's FULL row (facc: the run's base position; slot_desc = (request row, full row)).  Tiles
 // of the single rows (bin SIB_BINS) have no super-steps at all.
-template <int EPI, int DBG = 0, bool WIN = false> // DBG: timing-only ablations (1 = no weight DMA, 2 = no sample DMA, 4 = no fp8 derivation, 8 = no vmcnt waits)
+template <int EPI, bool WIN = false>
 __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, const uint4* __restrict__ act, int ksup,
                                                 size_t act_row_u4, int full_tiles, int last_cnt, MxScales sc,
                                                 const float* __restrict__ bias, uint4* __restrict__ out_split, size_t out_row_u4,
@@ -2854,7 +2648,7 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     asm volatile("" : "+s"(w_dma_off));
     asm volatile("" : "+v"(w_rd_off));
     auto issue_w1 = [&](int uabs, int g, int slot, int k) { // fragment k of this wave's 6, stage g of absolute super-step uabs
-        if (!(DBG & 1)) dma16s(wsrc + ((size_t)uabs * 4 + g) * MXS_U4 + k * 64, w_voff, ring(slot) + w_dma_off + k * 64);
+        dma16s(wsrc + ((size_t)uabs * 4 + g) * MXS_U4 + k * 64, w_voff, ring(slot) + w_dma_off + k * 64);
     };
     // Sample operands of a super-step: per sample 128 B of f16 pieces (2j+h) and 64 B of fp8 residual pieces (2h+e)
     // (two regions of the row's dense (tile, q) block).  The DMA reads them with ADJACENT LANES ON ADJACENT 16-B PIECES of one sample (8
@@ -2882,9 +2676,9 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
         const int blk = uo >> 5, pl = uo & 31; // f16 part: 8 uint4 per pixel; fp8 part: 4 per pixel behind the 32 x 8
         if (WIN) {
             const int e = (uo & 1) * SIB_WPX + (uo >> 1); // difference row: [q][w] f16 parts, then [q][w] residual parts
-            if (!(DBG & 2)) dma16s<A_NT>(abase + (k < 4 ? e * 8 : SIB_DLO_U4 + e * 4), a_voff[k], ldsA + buf * MXS_U4 + dst);
+            dma16s<A_NT>(abase + (k < 4 ? e * 8 : SIB_DLO_U4 + e * 4), a_voff[k], ldsA + buf * MXS_U4 + dst);
         } else
-        if (!(DBG & 2)) dma16s<A_NT>(abase + blk * OP_BLK_U4 + (k < 4 ? pl * 8 : OP_LO_U4 + pl * 4), a_voff[k], ldsA + buf * MXS_U4 + dst);
+        dma16s<A_NT>(abase + blk * OP_BLK_U4 + (k < 4 ? pl * 8 : OP_LO_U4 + pl * 4), a_voff[k], ldsA + buf * MXS_U4 + dst);
     };
     // LDS read offsets (uint4 units) of this lane's pieces inside sample tile 0; tile c adds 256 / 128
     const int sl = lane & 31;
@@ -2979,7 +2773,7 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
             uint32_t w8[8]; // fp8 copy of ah[0..3]: dword 2j, 2j+1
             if (g == 3) { // every wave's share of A(ul+1) must have landed before anyone reads it: its last pieces were
                           // issued at the head of stage g = 1, with 6 + 6 weight pieces behind them
-                if (!(DBG & 8)) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+                asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 // the barrier releases the four waves in the same cycle and they would then reach every DMA gap together
@@ -3008,24 +2802,24 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
                 for (int c = 0; c < 4; ++c) {
                     acc[g][c] = MFMA16(ah[j], bh[c][j], acc[g][c]);
                     if (MX6) { // one packed convert per 32 values: the weight block in the first gap, sample tile c in gap (1, c) of g = 0
-                        if (j == 0 && c == 0) w6h = (DBG & 4) ? w8l : f16x32_to_fp6(ah[0], ah[1], ah[2], ah[3], wsc & 0xFFu);
-                        if (g == 0 && j == 1) a8h[c] = (DBG & 4) ? a8l[c] : f16x32_to_fp6(bh[c][0], bh[c][1], bh[c][2], bh[c][3], (sc_hi >> (8 * c)) & 0xFFu);
+                        if (j == 0 && c == 0) w6h = f16x32_to_fp6(ah[0], ah[1], ah[2], ah[3], wsc & 0xFFu);
+                        if (g == 0 && j == 1) a8h[c] = f16x32_to_fp6(bh[c][0], bh[c][1], bh[c][2], bh[c][3], (sc_hi >> (8 * c)) & 0xFFu);
                     } else {
-                    if (!(DBG & 4)) { // weight pair c of piece j -> one half of dword 2j + (c >> 1)
+                    { // weight pair c of piece j -> one half of dword 2j + (c >> 1)
                         const uint4 aq = __builtin_bit_cast(uint4, ah[j]);
                         const uint32_t src = c == 0 ? aq.x : c == 1 ? aq.y : c == 2 ? aq.z : aq.w;
                         w8[2 * j + (c >> 1)] = (c & 1) ? cvt_fp8_hi(w8[2 * j + (c >> 1)], src, w_inv) : cvt_fp8_lo(src, w_inv);
-                    } else if (!(c & 1)) w8[2 * j + (c >> 1)] = (uint32_t)w8l[j] + c;
+                    }
                     if (g == 0) { // fp8 copy of this super-step's piece (c, j)
                         uint32_t d0, d1;
-                        if (DBG & 4) { d0 = (uint32_t)w8l[2] + c; d1 = (uint32_t)w8l[7] + j; } else f16x8_to_fp8(bh[c][j], a_inv, d0, d1);
+                        f16x8_to_fp8(bh[c][j], a_inv, d0, d1);
                         a8h[c][2 * j] = (int)d0; a8h[c][2 * j + 1] = (int)d1;
                     }
                     }
                     if (g == 3) bh[c][j] = *(const half8*)(LAn + c * 256 + a_rd_hi[j]); // next super-step's piece
                     if (j == 3) { // stage q+1's weights (issued during stage q-3): everything but the pieces of stages q-2, q-1
                                   // (8 each, 6 for a g = 2 stage) and the first 4 of this stage has landed
-                        if (c == 0 && !(DBG & 8)) {
+                        if (c == 0) {
                             if (g == 0 || g == 3) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
                             else asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
                         }
@@ -3426,13 +3220,7 @@ __global__ __launch_bounds__(256) void k_fc0_x3(const uint4* __restrict__ wp, co
 // Wp : [ksteps][MT][hi|lo][lane][8] f16 (1 KiB fragments), Act: rows of [ksteps][hi h0|hi h1|lo h0|lo h1]
 // 8 waves: wm = wave>>1 owns MT/4 m-tiles, ws = wave&1 owns 2 of the 4 sample tiles.
 
-#ifndef GEMM_T_TERM_MAJOR
-#define GEMM_T_TERM_MAJOR 1 // the k-step's MFMAs term by term over all the wave's accumulators (0: accumulator by accumulator, three dependent MFMAs in a row)
-#endif
-#ifndef GEMM_T_DB
-#define GEMM_T_DB 0 // (round 6 A-B: 1 = fragments of k-step t + 1 read into a second register set during the MFMAs of k-step t: fc1 + heads 28.5 ms per 150 rounds against 26.8: slower, off)
-#endif
-template <int MT, int EPI, int TAG, int NST, int PRIO>
+template <int MT, int EPI, int TAG, int NST>
 __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, const uint4* __restrict__ act, int ksteps,
                                                 size_t act_row_u4, int k_full, int last_cnt, int lo_off,
                                                 const float* __restrict__ bias, uint4* __restrict__ out_split,
@@ -3500,74 +3288,6 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][c][r] = 0.0f;
 
-#if GEMM_T_DB
-    // Round 6: the fragments of k-step t + 1 are read from LDS into a second register set while the MFMAs of k-step t run, and the LDS-DMA of k-step t + 3 goes out behind
-    // the same barrier (its slot's readers -- k-step t -- have all passed their lgkmcnt wait in front of that barrier): nothing waits on the LDS or on L2 between a barrier and the
-    // k-step's 6 MTW MFMAs.  Before (one register set, read after the barrier): fc1 35 % of the matrix peak, the heads 34 %.  Same MFMAs in the same order: same bits.
-    static_assert(NST == 3, "the double-buffered loop is written for a 3-slot ring");
-    struct Frags { half8 bh[2], bl[2], ah[MTW], al[MTW]; };
-    auto lds_read = [&](Frags& f, int sl) {
-        const half8* L = (const half8*)(lds + sl * STAGE_U4);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            f.bh[c] = L[(WFR + (2 * ws + c) * 2 + 0) * 64 + lane];
-            f.bl[c] = L[(WFR + (2 * ws + c) * 2 + 1) * 64 + lane];
-        }
-#pragma unroll
-        for (int i = 0; i < MTW; ++i) {
-            f.ah[i] = L[((wm * MTW + i) * 2 + 0) * 64 + lane];
-            f.al[i] = L[((wm * MTW + i) * 2 + 1) * 64 + lane];
-        }
-    };
-    const int pre = ksteps < 3 ? ksteps : 3;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-        if (p < pre) issue(p);
-    // k-step 0's share has landed (later ones stay in flight), every wave's share is visible, its fragments go to the first register set
-    if (pre == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPW) : "memory");
-    else if (pre == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    Frags fa, fb;
-    lds_read(fa, 0);
-    auto kstep = [&](const Frags& cur, Frags& nxt, int t, int sl) { // sl = t % 3
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // `cur` (read a whole k-step ago) is complete; behind the barrier below slot sl is free
-        const bool more = t + 1 < ksteps;
-        if (more) { // this wave's share of k-step t + 1 has landed (k-step t + 2's may still be in flight)
-            if (t + 2 < ksteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (more) lds_read(nxt, sl == 2 ? 0 : sl + 1);
-        const bool stage = t + 3 < ksteps;
-        if (stage) issue_begin();
-        if (PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < MTW; ++i) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) MFMA3(cur.ah[i], cur.al[i], cur.bh[c], cur.bl[c], acc[i][c]);
-            if (stage) {
-#pragma unroll
-                for (int q = i; q < LPW; q += MTW) issue_one(q, sl);
-            }
-        }
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
-        if (stage) kt += 1;
-    };
-    {
-        int sl = 0;
-        for (int t = 0; t < ksteps; t += 2) {
-            kstep(fa, fb, t, sl);
-            sl = sl == 2 ? 0 : sl + 1;
-            if (t + 1 < ksteps) {
-                kstep(fb, fa, t + 1, sl);
-                sl = sl == 2 ? 0 : sl + 1;
-            }
-        }
-    }
-#else
 #pragma unroll
     for (int p = 0; p < NST - 1; ++p)
         if (p < ksteps) issue(p);
@@ -3596,8 +3316,6 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
             ah[i] = L[((wm * MTW + i) * 2 + 0) * 64 + lane];
             al[i] = L[((wm * MTW + i) * 2 + 1) * 64 + lane];
         }
-        if (PRIO) __builtin_amdgcn_s_setprio(1);
-#if GEMM_T_TERM_MAJOR
         // term-major: the 2 MTW accumulators of the wave take the hi x hi products, then all take lo x hi, then hi x lo -- consecutive MFMAs are independent (a dependent one
         // is 2 MTW instructions away instead of 2) and every accumulator still sums its three terms in the same order: same bits
 #pragma unroll
@@ -3611,24 +3329,10 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
                     for (int q = i; q < LPW; q += MTW) issue_one(q, nslot);
                 }
             }
-#else
-#pragma unroll
-        for (int i = 0; i < MTW; ++i) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) MFMA3(ah[i], al[i], bh[c], bl[c], acc[i][c]);
-            if (stage) {
-#pragma unroll
-                for (int q = i; q < LPW; q += MTW) issue_one(q, nslot);
-            }
-        }
-#endif
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
         if (stage) kt += 1;
         slot = slot + 1 == NST ? 0 : slot + 1;
         nslot = nslot + 1 == NST ? 0 : nslot + 1;
     }
-
-#endif
 
     // ---- epilogue ----
 #pragma unroll
@@ -3694,9 +3398,6 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
 // Measured (profiles/r06_ab_gemm_w.txt, three interleaved A-B pairs of the first three plies of configs[1]): tail group 25.8 -> 26.1 ms per 150 rounds and every OTHER
 // group 1.2 - 1.4 % slower beside it (the package is at its power limit: a kernel that keeps its pipes busier between barriers lowers the clock for its neighbours and
 // gains nothing itself).  Built, bit-identical (tests/test_gpu_tail_gemm.py), default OFF: OMOK_GEMM_W=1 selects it.
-#ifndef GEMM_W
-#define GEMM_W 1 // (0: not even selectable)
-#endif
 constexpr int GW_DA = 3, GW_NB = 3;
 constexpr int gemm_w_lds(int mt) { return (8 * GW_DA * (mt / 8) * 2 + GW_NB * 16) * 1024; }
 template <int MT, int EPI>
@@ -4011,7 +3712,6 @@ size_t net_alloc(Net& net) {
     };
     bool ok = true;
     for (int i = 0; i < NET_TENSORS && ok; ++i) ok = A((void**)&net.w[i], sizeof(float) * (size_t)net.wsize[i]);
-    ok = ok && A((void**)&net.d_chunk, sizeof(int32_t) * 64 * 4);
     ok = ok && A((void**)&net.p, sizeof(float) * mb * rp);
     ok = ok && A((void**)&net.v, sizeof(float) * mb);
     ok = ok && A((void**)&net.vpre, sizeof(float) * mb);
@@ -4028,7 +3728,7 @@ size_t net_alloc(Net& net) {
         ok = ok && A((void**)&net.s1, sizeof(float) * c * NF);
     } else {
         const size_t ks0 = hw * 8;
-        const size_t row_pad = getenv("OMOK_ROWPAD_U4") ? atoi(getenv("OMOK_ROWPAD_U4")) : 80;
+        const size_t row_pad = 80;
         net.row_u4_fmt[FC0_FP6] = (size_t)((hw + 31) / 32) * 2 * OP_BLK_U4 + row_pad;
         net.row_u4_fmt[FC0_F16] = (size_t)((hw + 31) / 32) * 2 * OPX_BLK_U4 + row_pad;
         net.row_u4 = net.row_u4_fmt[net.fc0_fmt];
@@ -4048,19 +3748,9 @@ size_t net_alloc(Net& net) {
             ok = ok && A((void**)&net.d_gcnt, sizeof(int32_t) * SIB_CNT_INTS);
             ok = ok && A((void**)&net.d_work, sizeof(unsigned long long) * NET_WORK_COUNT);
             if (ok) hipMemset(net.d_work, 0, sizeof(unsigned long long) * NET_WORK_COUNT);
-            {
-                const char* e = getenv("OMOK_SIDE_STREAM"); // (A-B runs: 0 = everything on the engine's stream)
-                const bool want = SIDE_STREAM_DEFAULT ? !(e && atoi(e) == 0) : (e && atoi(e) != 0);
-                if (ok && want && hipStreamCreateWithFlags(&net.side, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&net.ev_base, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&net.ev_full, hipEventDisableTiming) == hipSuccess)
-                    net.side_on = true;
-            }
             ok = ok && A((void**)&net.d_sib_rows, sizeof(uint4) * mb);
             net.base_slots = (size_t)SIB_WAYS * net.games + mb / SIB_MIN + 1; // SIB_WAYS slots per game + the other runs a round can hold
-            { // V2 children (default; OMOK_SIB_V2=0 or omok_debug_set_children_kernel(1): k_sib_children on the difference path too): a base slot holds 1280 B per pixel instead of 3 h grids
-                const char* e = getenv("OMOK_SIB_V2");
-                net.sib_v2 = !(e && atoi(e) == 0);
-            }
+            // V2 children (Net::sib_v2, the default; omok_debug_set_children_kernel(1): k_sib_children on the difference path too): a base slot holds 1280 B per pixel instead of 3 h grids
             ok = ok && A((void**)&net.sib_h, net.base_slots * std::max<size_t>(sizeof(float) * 3 * (size_t)sib_hb_floats(net.n), sib2_slot_u4(net.n) * 16)); // (either kernel's slots: omok_debug_set_children_kernel)
             // difference path: slots (bins padded to whole tiles), their difference rows
             net.d_slots = mb + (size_t)(SIB_BINS + 1) * GT_BS;
@@ -4091,10 +3781,6 @@ size_t net_alloc(Net& net) {
 }
 
 void net_free(Net& net) {
-    if (net.side) { hipStreamSynchronize(net.side); hipStreamDestroy(net.side); net.side = nullptr; }
-    if (net.ev_base) { hipEventDestroy(net.ev_base); net.ev_base = nullptr; }
-    if (net.ev_full) { hipEventDestroy(net.ev_full); net.ev_full = nullptr; }
-    net.side_on = false;
     if (net.s0_x3 || net.s0_f32) { // (a split-precision engine that has taken the fp32 fallback holds two buffers behind s0)
         net.s0 = nullptr;
         if (net.s0_x3) hipFree(net.s0_x3);
@@ -4103,7 +3789,7 @@ void net_free(Net& net) {
     }
     void** ptrs[] = {(void**)&net.p, (void**)&net.v, (void**)&net.vpre, (void**)&net.in_f32, (void**)&net.sx, (void**)&net.sh, (void**)&net.sd,
                      (void**)&net.sg, (void**)&net.s0, (void**)&net.s1, &net.wt_trunk, (void**)&net.wt_first, &net.wt_fc0,
-                     &net.wt_fc0x, &net.wt_fc1, &net.wt_heads, &net.a_fc0, &net.h0, (void**)&net.part, (void**)&net.d_chunk, (void**)&net.d_groups,
+                     &net.wt_fc0x, &net.wt_fc1, &net.wt_heads, &net.a_fc0, &net.h0, (void**)&net.part, (void**)&net.d_groups,
                      (void**)&net.d_singles, (void**)&net.d_gcnt, (void**)&net.d_work, (void**)&net.sib_h, (void**)&net.d_sib_rows, (void**)&net.d_sib_slot,
                      (void**)&net.d_bin_start, (void**)&net.d_tile_info, &net.d_slot_desc, &net.d_rows, (void**)&net.part_w, &net.a_base, (void**)&net.facc, (void**)&net.d_tags, &net.d_comp};
     for (void** p : ptrs) { if (*p) hipFree(*p); *p = nullptr; }
@@ -4325,12 +4011,12 @@ static int net_pack(Net& net, hipStream_t st) {
     return 0;
 }
 
-template <int N, bool FROM_F32, int ABL = 0>
+template <int N, bool FROM_F32, bool BASE = false, bool DELTA = false, bool F16LO = false>
 static void launch_trunk(Net& net, const Store& S, int max_count, hipStream_t st, const int32_t* row_list = nullptr, const int32_t* d_nrows = nullptr,
                          const int32_t* d_out_base = nullptr, const int32_t* d_nrows2 = nullptr, bool v2 = false) {
     using TG = TrunkGeo<N>;
     static bool attr_done[64] = {}; // per device: the attribute belongs to the device's copy of the code object
-    auto kern = k_trunk<N, FROM_F32, ABL>;
+    auto kern = k_trunk<N, FROM_F32, BASE, DELTA, F16LO>;
     if (!attr_done[net.device & 63]) {
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, TG::LDS_BYTES);
         attr_done[net.device & 63] = true;
@@ -4339,35 +4025,32 @@ static void launch_trunk(Net& net, const Store& S, int max_count, hipStream_t st
     const int grid = wgs < 256 ? wgs : 256;
     kern<<<grid, TG::WG_THREADS, TG::LDS_BYTES, st>>>(S.req_ref, S.req_aux, S.board, S.hdr, S.d_count, S.stride_nodes, net.in_f32, (const uint4*)net.wt_trunk, net.wt_first,
                                                        (uint4*)net.a_fc0, net.row_u4, max_count, row_list, d_nrows,
-                                                       (ABL & 48) == 48 ? (const uint2*)net.d_comp : (const uint2*)net.d_groups, net.sib_h, d_out_base, (uint4*)net.a_base,
+                                                       (BASE && DELTA) ? (const uint2*)net.d_comp : (const uint2*)net.d_groups, net.sib_h, d_out_base, (uint4*)net.a_base,
                                                        d_nrows2, v2 ? (uint4*)net.sib_h : nullptr);
 }
 
-// the same in the engine's current operand format (ABL bit 64 = FC0_F16 rows)
-template <int N, bool FROM_F32, int ABL = 0>
+// the same in the engine's current operand format (F16LO = FC0_F16 rows)
+template <int N, bool FROM_F32, bool BASE = false, bool DELTA = false>
 static void launch_trunk_fmt(Net& net, const Store& S, int max_count, hipStream_t st, const int32_t* row_list = nullptr, const int32_t* d_nrows = nullptr,
                              const int32_t* d_out_base = nullptr, const int32_t* d_nrows2 = nullptr, bool v2 = false) {
-    if (net.fc0_fmt == FC0_F16) launch_trunk<N, FROM_F32, ABL | 64>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2);
-    else launch_trunk<N, FROM_F32, ABL>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2);
+    if (net.fc0_fmt == FC0_F16) launch_trunk<N, FROM_F32, BASE, DELTA, true>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2);
+    else launch_trunk<N, FROM_F32, BASE, DELTA, false>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2);
 }
 
-// ring depth of the full-round fc1 / heads launches and a raised wave priority around their MFMA blocks (A-B knobs: same arithmetic, same bits)
+// ring depth of the full-round fc1 / heads launches (A-B knobs: same arithmetic, same bits)
 #ifndef FC1_NST
 #define FC1_NST 3
 #endif
 #ifndef HEADS_NST
 #define HEADS_NST 3
 #endif
-#ifndef TAIL_PRIO
-#define TAIL_PRIO 0
-#endif
-template <int MT, int EPI, int TAG, int NST = 3, int PRIO = 0>
+template <int MT, int EPI, int TAG, int NST = 3>
 static void launch_gemm(const void* wp, const void* act, int ksteps, size_t act_row_u4, int k_full, int last_cnt, int lo_off,
                         const float* bias, void* out_split, size_t out_row_u4, float* out_logits, const Store& S, int max_count,
                         hipStream_t st, int device, int nsplit = 1) {
     constexpr int LDS = (MT * 2 + 8) * 1024 * NST;
     static bool attr_done[64] = {};
-    auto kern = k_gemm_t<MT, EPI, TAG, NST, PRIO>;
+    auto kern = k_gemm_t<MT, EPI, TAG, NST>;
     if (!attr_done[device & 63]) {
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         attr_done[device & 63] = true;
@@ -4395,10 +4078,9 @@ static void launch_gemm_w(const void* wp, const void* act, int ksteps, size_t ac
 // K splits of the difference path's fc0 launches (chosen on the device, k_bin_prefix): the full rows up to 30 ways as far as the
 // partial slab holds ways x (the launch's row capacity); window tiles of the split set up to 14 ways (7 super-steps each)
 constexpr int SIB_MAX_WWAYS = 14;
-static int sib_max_fways(const Net&, int) { // (capped on the device by the slab: part_rows / (tiles of full rows x 128), and by CUs / tiles)
-    static const int env = getenv("OMOK_SIB_FWAYS") ? atoi(getenv("OMOK_SIB_FWAYS")) : 0; // (A-B runs)
-    return env > 0 ? env : 64; // (30 until round 4; per full round in the mixed format: k_fc0_x3 on the full rows 73.7 -> 64.5 us, k_facc_reduce 9.6 -> 13.2 us)
-}
+// (capped on the device by the slab: part_rows / (tiles of full rows x 128), and by CUs / tiles; 30 until round 4; per full round in the mixed format: k_fc0_x3 on the
+//  full rows 73.7 -> 64.5 us, k_facc_reduce 9.6 -> 13.2 us)
+constexpr int SIB_MAX_FWAYS = 64;
 __global__ void k_zero_ints(int32_t* __restrict__ p, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
 }
@@ -4406,11 +4088,11 @@ __global__ void k_zero_ints(int32_t* __restrict__ p, int n) {
 // delta = true: difference path (full rows for the runs' bases and the single rows, difference rows for the children; fc0 = launch_fc0_delta).
 typedef void (*sib_kernel_t)(const uint64_t*, const uint4*, const float*, uint4*, size_t, const uint4*, const int32_t*, const float*, const uint32_t*, const int32_t*,
                              uint4*, uint2*, unsigned long long*);
-static sib_kernel_t sib_kernel(bool delta, bool x16, int n) { // k_sib_children<DELTA, false, F16LO, N>
-    if (n == 9) return delta ? (x16 ? k_sib_children<true, false, true, 9> : k_sib_children<true, false, false, 9>)
-                             : (x16 ? k_sib_children<false, false, true, 9> : k_sib_children<false, false, false, 9>);
-    return delta ? (x16 ? k_sib_children<true, false, true, 15> : k_sib_children<true, false, false, 15>)
-                 : (x16 ? k_sib_children<false, false, true, 15> : k_sib_children<false, false, false, 15>);
+static sib_kernel_t sib_kernel(bool delta, bool x16, int n) { // k_sib_children<DELTA, F16LO, N>
+    if (n == 9) return delta ? (x16 ? k_sib_children<true, true, 9> : k_sib_children<true, false, 9>)
+                             : (x16 ? k_sib_children<false, true, 9> : k_sib_children<false, false, 9>);
+    return delta ? (x16 ? k_sib_children<true, true, 15> : k_sib_children<true, false, 15>)
+                 : (x16 ? k_sib_children<false, true, 15> : k_sib_children<false, false, 15>);
 }
 typedef void (*sib2_kernel_t)(const uint64_t*, const uint4*, const float*, uint4*, size_t, const uint4*, const int32_t*, const uint4*, const uint32_t*, const int32_t*,
                               uint4*, uint2*, unsigned long long*);
@@ -4418,16 +4100,6 @@ static sib2_kernel_t sib2_kernel(bool x16, int n, bool mixed = false) { // k_sib
     if (mixed) return n == 9 ? k_sib_children2<true, 9, false, false> : k_sib_children2<true, 15, false, false>;
     if (n == 9) return x16 ? k_sib_children2<true, 9> : k_sib_children2<false, 9>;
     return x16 ? k_sib_children2<true, 15> : k_sib_children2<false, 15>;
-}
-// A-B builds only (tools/power_by_kernel.sh): OMOK_REPEAT_<WHICH>=n launches one (idempotent) kernel n times in a row, so that a sampled clock / power reading is that kernel's own
-static int repeat_env(const char* name) {
-#ifdef OMOK_EXPERIMENT
-    const char* v = getenv(name);
-    const int n = v ? atoi(v) : 1;
-    return n > 0 ? n : 1;
-#else
-    return 1;
-#endif
 }
 static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_count, hipStream_t st, bool delta) {
     constexpr int LDS = TR_WBYTES + 4 * SIB_CGRID_BYTES + TR_SIDE_FLOATS * 4;
@@ -4462,22 +4134,20 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
         // (the copy path keeps the runs' h grids in sib_h[run index]: the slots the difference path caches bases in -- cached bases are void)
         net.sib_cache_valid = false;
         // base positions of the runs, then the rows outside runs
-        if (net.n == 9) launch_trunk_fmt<9, false, 16>(net, S, max_count, st, net.d_singles, net.d_gcnt, nullptr, net.d_gcnt + 1);
-        else launch_trunk_fmt<15, false, 16>(net, S, max_count, st, net.d_singles, net.d_gcnt, nullptr, net.d_gcnt + 1);
+        if (net.n == 9) launch_trunk_fmt<9, false, true>(net, S, max_count, st, net.d_singles, net.d_gcnt, nullptr, net.d_gcnt + 1);
+        else launch_trunk_fmt<15, false, true>(net, S, max_count, st, net.d_singles, net.d_gcnt, nullptr, net.d_gcnt + 1);
         net.children_launches[1] += 1.0;
         sib_kernel(false, x16, net.n)<<<256, 512, LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_fc0, net.row_u4,
                                                              (const uint4*)net.d_sib_rows, net.d_gcnt, net.sib_h, nullptr, nullptr, nullptr, nullptr, nullptr);
         return;
     }
-    static const int tprof_mode = getenv("OMOK_SIB_PROF") ? atoi(getenv("OMOK_SIB_PROF")) : 0; // timing experiments only (N = 15, fp6 format): 1 = k_sib_children, 2 = k_sib_children2
-    const bool tprof = tprof_mode == 1;
+    static const int tprof_mode = getenv("OMOK_SIB_PROF") ? atoi(getenv("OMOK_SIB_PROF")) : 0; // timing experiments only (N = 15, fp6 format): 2 = k_sib_children2's phase profile
     const bool mixed = x16 && net.diff_fp6; // FC0_MIXED: full rows f16, difference rows fp6 (k_sib_children2 only)
-    const bool v2 = (net.sib_v2 && !tprof) || mixed;
+    const bool v2 = net.sib_v2 || mixed;
     // per-tile rectangles of window pixels (k_bin_prefix): only k_sib_children2 writes the exact zeros outside a child's own region that make a row's sum independent of its tile
-    static const bool rects_env = !(getenv("OMOK_SIB_RECTS") && atoi(getenv("OMOK_SIB_RECTS")) == 0); // (A-B runs)
-    const bool rects = v2 && rects_env && net.win_rects;
+    const bool rects = v2 && net.win_rects;
     k_bin_prefix<<<1, BP_THREADS, 0, st>>>(net.d_gcnt, net.d_bin_start, net.d_tile_info, (uint2*)net.d_slot_desc, net.d_singles, net.n_cu,
-                                    sib_max_fways(net, max_count), SIB_MAX_WWAYS, (int)std::min<size_t>(net.part_w_rows * 7, (size_t)1 << 30), (int)net.base_slots,
+                                    SIB_MAX_FWAYS, SIB_MAX_WWAYS, (int)std::min<size_t>(net.part_w_rows * 7, (size_t)1 << 30), (int)net.base_slots,
                                     (int)std::min<size_t>(net.part_rows, (size_t)1 << 30), 2 * net.hw, net.n, rects ? 1 : 0, (int)(net.d_slots / GT_BS), net.d_work);
     static const bool stats = getenv("OMOK_SIB_STATS") && atoi(getenv("OMOK_SIB_STATS")); // diagnostics only: synchronises every round
     if (stats) {
@@ -4503,9 +4173,8 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
         }
     }
     // runs without a cached base -> compact rows [0, misses) + their base slots; then the single rows -> compact rows [misses, misses + singles)
-    if (net.n == 9) launch_trunk_fmt<9, false, 48>(net, S, max_count, st, net.d_singles, net.d_gcnt + 96, nullptr, net.d_gcnt + 1, v2);
-    else launch_trunk_fmt<15, false, 48>(net, S, max_count, st, net.d_singles, net.d_gcnt + 96, nullptr, net.d_gcnt + 1, v2);
-    if (net.side_on) hipEventRecord(net.ev_base, st); // (the full rows' fc0 may start from here: launch_fc0_delta)
+    if (net.n == 9) launch_trunk_fmt<9, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + 96, nullptr, net.d_gcnt + 1, v2);
+    else launch_trunk_fmt<15, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + 96, nullptr, net.d_gcnt + 1, v2);
     if (v2 && tprof_mode == 2 && !x16 && net.n == 15) {
         static unsigned long long* d_tp = nullptr;
         static unsigned long long acc[32] = {};
@@ -4531,65 +4200,8 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
     }
     net.children_launches[v2 ? 0 : 1] += 1.0;
     if (v2) {
-        static const int rep = repeat_env("OMOK_REPEAT_CHILDREN");
-        unsigned long long* wave_times = nullptr;
-#if SIB2_EXP == 17
-        static unsigned long long* d_wt = nullptr;
-        static int wt_launches = 0;
-        if (!d_wt) { hipMalloc(&d_wt, 2048 * 8); hipMemset(d_wt, 0, 2048 * 8); }
-        wave_times = d_wt;
-#endif
-        for (int r = 0; r < rep; ++r)
         sib2_kernel(x16, net.n, mixed)<<<256, 512, V2_LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4, (const uint4*)net.d_sib_rows,
-                                                          net.d_gcnt, (const uint4*)net.sib_h, net.d_sib_slot, net.d_bin_start, (uint4*)net.d_rows, (uint2*)net.d_slot_desc, wave_times);
-#if SIB2_EXP == 17
-        if (++wt_launches % 150 == 0) {
-            static unsigned long long h[2048];
-            hipStreamSynchronize(st);
-            hipMemcpy(h, d_wt, sizeof(h), hipMemcpyDeviceToHost);
-            hipMemset(d_wt, 0, sizeof(h));
-            double sum = 0, mx = 0, mn = 1e30, wgmax = 0, wgsum = 0, xcd[8] = {}, early = 0, late = 0;
-            for (int b = 0; b < 256; ++b) {
-                double wm = 0;
-                for (int w = 0; w < 8; ++w) {
-                    const double v = (double)h[b * 8 + w] / 150.0;
-                    sum += v; mx = v > mx ? v : mx; mn = v < mn ? v : mn; wm = v > wm ? v : wm;
-                    (w < 4 ? early : late) += v;
-                }
-                wgsum += wm; wgmax = wm > wgmax ? wm : wgmax;
-                xcd[b & 7] += wm;
-            }
-            fprintf(stderr, "[sib2 wave times] cycles per launch: wave mean %.0f min %.0f max %.0f | slowest wave of a workgroup: mean %.0f max %.0f (max / mean %.3f) | waves 0-3 mean %.0f, 4-7 mean %.0f | per XCD:",
-                    sum / 2048, mn, mx, wgsum / 256, wgmax, wgmax / (wgsum / 256), early / 1024, late / 1024);
-            for (int x = 0; x < 8; ++x) fprintf(stderr, " %.0f", xcd[x] / 32);
-            fprintf(stderr, "\n");
-        }
-#endif
-        return;
-    }
-    if (tprof && !x16 && net.n == 15) {
-        static unsigned long long* d_tp = nullptr;
-        static unsigned long long acc[32] = {};
-        static int launches = 0;
-        if (!d_tp) { hipMalloc(&d_tp, 256); hipMemset(d_tp, 0, 256); hipFuncSetAttribute((const void*)k_sib_children<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); }
-        k_sib_children<true, true><<<256, 512, LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4,
-                                                           (const uint4*)net.d_sib_rows, net.d_gcnt, net.sib_h, net.d_sib_slot, net.d_bin_start,
-                                                           (uint4*)net.d_rows, (uint2*)net.d_slot_desc, d_tp);
-        if (++launches % 100 == 0) {
-            hipStreamSynchronize(st);
-            hipMemcpy(acc, d_tp, 256, hipMemcpyDeviceToHost);
-            static const char* names[9] = {"inputs+conv_in", "L0", "grid write + B2", "ring fetch + depthwise", "B3 + write + B4 + read d", "L1L2 (+ base fetch)",
-                                           "base subtract", "stores (+ next ring fetch)", "end barrier"};
-            for (int w = 0; w < 2; ++w) {
-                double tot = 0;
-                for (int i = 0; i < 9; ++i) tot += (double)acc[16 * w + i];
-                fprintf(stderr, "[sib prof] wave %d, %d launches x 256 workgroups: ", w ? 5 : 0, launches);
-                for (int i = 0; i < 9; ++i) fprintf(stderr, "%s %.1f%%  ", names[i], 100.0 * (double)acc[16 * w + i] / tot);
-                fprintf(stderr, " | %.0f cycles per workgroup and launch\n", tot / 256.0 / launches);
-            }
-            fprintf(stderr, "[sib prof] cycles in the loop per pair, workgroup and launch: %.0f %.0f %.0f %.0f\n", (double)acc[28] / 256.0 / launches,
-                    (double)acc[29] / 256.0 / launches, (double)acc[30] / 256.0 / launches, (double)acc[31] / 256.0 / launches);
-        }
+                                                          net.d_gcnt, (const uint4*)net.sib_h, net.d_sib_slot, net.d_bin_start, (uint4*)net.d_rows, (uint2*)net.d_slot_desc, nullptr);
         return;
     }
     sib_kernel(true, x16, net.n)<<<256, 512, LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4,
@@ -4606,20 +4218,11 @@ static void launch_fc0_delta(Net& net, int max_count, const MxScales& sc, const 
     const int n_cu = net.n_cu;
     // the live count of full rows is only known on the device: k_bin_prefix chose the K split and the partial slab's row stride (d_gcnt[98], [99])
     const int fgrid = ((tiles_max > n_cu ? tiles_max : n_cu) + 7) / 8 * 8; // (tiles x ways <= CUs by construction unless there are more tiles than CUs: then 1 way; whole eighths: xcd_item)
-    // the full rows' fc0 + its reduction: behind the base trunk on the side stream (Net::side), joined in front of the window tiles
-    hipStream_t fs = net.side_on ? net.side : st;
-    if (net.side_on) hipStreamWaitEvent(net.side, net.ev_base, 0);
-    auto join_side = [&]() {
-        if (!net.side_on) return;
-        hipEventRecord(net.ev_full, net.side);
-        hipStreamWaitEvent(st, net.ev_full, 0);
-    };
     if (net.fc0_fmt == FC0_F16) { // the same four launches on f16 residuals (k_fc0_x3)
         const int lc = (hw % 32) ? (hw % 32) : 1;
-        k_fc0_x3<EPI_PARTIAL, false><<<dim3(fgrid, 1), 256, 0, fs>>>((const uint4*)net.wt_fc0x, (const uint4*)net.a_fc0, nsup, net.row_u4, hw / 32, lc, bias_fc0, nullptr,
+        k_fc0_x3<EPI_PARTIAL, false><<<dim3(fgrid, 1), 256, 0, st>>>((const uint4*)net.wt_fc0x, (const uint4*)net.a_fc0, nsup, net.row_u4, hw / 32, lc, bias_fc0, nullptr,
                                                                      cap_rows, net.part, net.d_gcnt + 3, max_count, net.d_gcnt + 98, nullptr, nullptr, net.n);
-        k_facc_reduce<<<512, 256, 0, fs>>>(net.part, cap_rows, net.d_gcnt + 3, net.d_gcnt + 98, net.facc, (const uint2*)net.d_comp, net.d_gcnt + 96, (int)net.base_slots);
-        join_side();
+        k_facc_reduce<<<512, 256, 0, st>>>(net.part, cap_rows, net.d_gcnt + 3, net.d_gcnt + 98, net.facc, (const uint2*)net.d_comp, net.d_gcnt + 96, (int)net.base_slots);
     }
     if (net.fc0_fmt == FC0_F16 && !net.diff_fp6) {
         const int lc = (hw % 32) ? (hw % 32) : 1;
@@ -4634,21 +4237,18 @@ static void launch_fc0_delta(Net& net, int max_count, const MxScales& sc, const 
         return;
     }
     if (net.fc0_fmt != FC0_F16) { // (FC0_MIXED: the full rows went through k_fc0_x3 above; the window tiles below run on fp6 difference rows)
-    k_fc0_mx<EPI_PARTIAL><<<dim3(fgrid, 1), 256, 0, fs>>>((const uint4*)net.wt_fc0, (const uint4*)net.a_fc0, nsup, net.row_u4, hw / 32,
+    k_fc0_mx<EPI_PARTIAL><<<dim3(fgrid, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.a_fc0, nsup, net.row_u4, hw / 32,
                                                                (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, nullptr, cap_rows, net.part, net.d_gcnt + 3,
                                                                max_count, net.d_gcnt + 98, nullptr, nullptr, net.n);
-    k_facc_reduce<<<512, 256, 0, fs>>>(net.part, cap_rows, net.d_gcnt + 3, net.d_gcnt + 98, net.facc, (const uint2*)net.d_comp, net.d_gcnt + 96, (int)net.base_slots);
-    join_side();
+    k_facc_reduce<<<512, 256, 0, st>>>(net.part, cap_rows, net.d_gcnt + 3, net.d_gcnt + 98, net.facc, (const uint2*)net.d_comp, net.d_gcnt + 96, (int)net.base_slots);
     }
     // window tiles: whole rounds of workgroups at full K, the tiles of the last partial round split over K (k_bin_prefix)
     const int wtiles_max = (tiles_max + SIB_BINS + 1 + 7) / 8 * 8 + 8; // (the XCD-aware tile mapping rounds an eighth of the tiles up)
-    static const int rep_win = repeat_env("OMOK_REPEAT_WIN");
-    for (int r = 0; r < rep_win; ++r)
-    k_fc0_mx<EPI_SPLIT, 0, true><<<dim3((wtiles_max + 255) / 256 * 256, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.d_rows, 0, (size_t)SIB_DROW_U4, hw / 32,
+    k_fc0_mx<EPI_SPLIT, true><<<dim3((wtiles_max + 255) / 256 * 256, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.d_rows, 0, (size_t)SIB_DROW_U4, hw / 32,
                                                                        (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, h0, 128, nullptr, net.d_gcnt, max_count,
                                                                        net.d_tile_info, (const uint2*)net.d_slot_desc, net.facc, net.n);
     const int stiles = wtiles_max < n_cu + 8 ? wtiles_max : n_cu + 8;
-    k_fc0_mx<EPI_PARTIAL, 0, true><<<dim3(n_cu + 8, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.d_rows, 0, (size_t)SIB_DROW_U4, hw / 32,
+    k_fc0_mx<EPI_PARTIAL, true><<<dim3(n_cu + 8, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.d_rows, 0, (size_t)SIB_DROW_U4, hw / 32,
                                                                      (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, nullptr, net.part_w_rows, net.part_w, net.d_gcnt,
                                                                      max_count, net.d_tile_info, (const uint2*)net.d_slot_desc, nullptr, net.n);
     k_win_finish<<<(unsigned)(((size_t)stiles * GT_BS * 64 + 255) / 256), 256, 0, st>>>(net.part_w, net.part_w_rows, net.d_gcnt, net.d_tile_info,
@@ -4658,10 +4258,6 @@ static void launch_fc0_delta(Net& net, int max_count, const MxScales& sc, const 
 static int sib_env() { // OMOK_TRUNK_SIB: 0: every row through k_trunk, 1: copy path, 2: difference path
     static const int use_sib = getenv("OMOK_TRUNK_SIB") ? atoi(getenv("OMOK_TRUNK_SIB")) : 2;
     return use_sib;
-}
-static int chunk_env() {
-    static const int chunk_max = getenv("OMOK_NET_CHUNK") ? atoi(getenv("OMOK_NET_CHUNK")) : NET_CHUNK_DEFAULT;
-    return chunk_max;
 }
 // THE decision whether a forward of request rows groups them by parent (launch_trunk_siblings): forward_f16x3 takes it from here, and so does the engine's
 // prediction of it (net_round_takes_sibling_path), on which it hands the request-list fill and the zeroing of d_gcnt to that path
@@ -4675,9 +4271,8 @@ static int sib_delta_min_rows(const Net& net) {
     return net.diff_fp6 ? 2048 : 3072;
 }
 static bool sibling_path(const Net& net, bool from_f32, int sib_side) { return !from_f32 && sib_side >= 0 && sib_env() && net.siblings && net.d_groups; }
-bool net_round_takes_sibling_path(const Net& net, int max_count) { // (forward_chunked: a chunked forward passes no sibling side)
+bool net_round_takes_sibling_path(const Net& net, int max_count) {
     if (net.mode == OMOK_NET_F32 || max_count <= 0) return false;
-    if (chunk_env() > 0 && max_count > chunk_env()) return false;
     return sibling_path(net, false, 0);
 }
 // The engine skipped k_fill / the zeroing of d_gcnt for this round (Net::fill_in_group, Net::gcnt_zeroed) because it expected the sibling path: a forward that
@@ -4708,17 +4303,7 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     if (sib) launch_trunk_siblings(net, S, sib_side, max_count, st, delta);
     else if (net.n == 9) { if (from_f32) launch_trunk_fmt<9, true>(net, S, max_count, st); else launch_trunk_fmt<9, false>(net, S, max_count, st); }
     else {
-#ifdef OMOK_EXPERIMENT // (timing-only ablations with WRONG results: compiled into A-B builds only, tools/build_variant.sh)
-        static const int abl = getenv("OMOK_ABL_TRUNK") ? atoi(getenv("OMOK_ABL_TRUNK")) : 0;
-#else
-        constexpr int abl = 0;
-#endif
-        if (from_f32 && abl == 1) launch_trunk<15, true, 1>(net, S, max_count, st);
-        else if (from_f32 && abl == 2) launch_trunk<15, true, 2>(net, S, max_count, st);
-        else if (from_f32 && abl == 3) launch_trunk<15, true, 3>(net, S, max_count, st);
-        else if (from_f32 && abl == 7) launch_trunk<15, true, 7>(net, S, max_count, st);
-        else if (from_f32 && abl == 8) launch_trunk<15, true, 8>(net, S, max_count, st);
-        else if (from_f32) launch_trunk_fmt<15, true>(net, S, max_count, st);
+        if (from_f32) launch_trunk_fmt<15, true>(net, S, max_count, st);
         else launch_trunk_fmt<15, false>(net, S, max_count, st);
     }
     if (prof) { prof->end(st); prof->begin(PC_FC0, st); }
@@ -4748,11 +4333,10 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
                 n_cu = (hipGetDeviceProperties(&prop, net.device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
             }
             double best = 1e30;
-            static const int dmax_env = getenv("OMOK_FC0_DMAX") ? atoi(getenv("OMOK_FC0_DMAX")) : 0; // (A-B runs)
             // Up to 64 ways (round 4; 16 before): a thin round's few tiles then spread over all CUs -- per three plies at 16 / 32 / 64 live games: fp6 42.7 / 44.0 / 45.6 ->
             // 38.0 / 39.3 / 42.3 ms, mixed (f16 rows) 48.0 / 49.1 / 51.5 -> 40.1 / 41.7 / 47.8 ms.  (Round 2 had measured 30 ways slower than 15 at 8 tiles; with the items
             // dealt per XCD -- xcd_item -- it is the other way round.)
-            const int dmax = dmax_env > 0 ? dmax_env : 64;
+            constexpr int dmax = 64;
             for (int d = 1; d <= dmax; ++d) { // (uneven splits: ceil(nsup / d) super-steps per split, the last one shorter but never empty)
                 const int per = (nsup + d - 1) / d;
                 if ((d - 1) * per >= nsup) continue;
@@ -4777,16 +4361,9 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
             }
         } else
         if (nsplit == 1) {
-#ifdef OMOK_EXPERIMENT // (timing-only ablations with WRONG results: A-B builds only)
-            static const int dbg = getenv("OMOK_DBG_FC0") ? atoi(getenv("OMOK_DBG_FC0")) : 0;
-#else
-            constexpr int dbg = 0;
-#endif
-            auto kern = dbg == 1 ? k_fc0_mx<EPI_SPLIT, 1> : dbg == 2 ? k_fc0_mx<EPI_SPLIT, 2> : dbg == 3 ? k_fc0_mx<EPI_SPLIT, 3>
-                      : dbg == 4 ? k_fc0_mx<EPI_SPLIT, 4> : dbg == 7 ? k_fc0_mx<EPI_SPLIT, 7> : dbg == 8 ? k_fc0_mx<EPI_SPLIT, 8> : k_fc0_mx<EPI_SPLIT, 0>;
-            kern<<<dim3(tiles128, 1), 256, LDS, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.a_fc0, nsup, net.row_u4,
-                                                      hw / 32, (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, h0, 128, nullptr,
-                                                      S.d_count, max_count, nullptr, nullptr, nullptr, net.n);
+            k_fc0_mx<EPI_SPLIT><<<dim3(tiles128, 1), 256, LDS, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.a_fc0, nsup, net.row_u4,
+                                                                     hw / 32, (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, h0, 128, nullptr,
+                                                                     S.d_count, max_count, nullptr, nullptr, nullptr, net.n);
         } else {
             const size_t cap_rows = (size_t)tiles128 * GT_BS;
             k_fc0_mx<EPI_PARTIAL><<<dim3((tiles128 * nsplit + 7) / 8 * 8, 1), 256, LDS, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.a_fc0,
@@ -4808,20 +4385,15 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     const size_t cap_t = (size_t)tiles_t * GT_BS;
     const size_t fin_threads = (size_t)max_count * 64;
     if (tsplit == 1) {
-        static const int rep_fc1 = repeat_env("OMOK_REPEAT_FC1"), rep_heads = repeat_env("OMOK_REPEAT_HEADS");
         // whole-K launches: k_gemm_t; OMOK_GEMM_W=1 selects k_gemm_w (wave-private weight rings, one barrier per two k-steps; same bits, measured no faster: see the
         // kernel) for A-B runs and the test that compares the two kernels' outputs bit for bit; the N = 9 heads (4 m-tiles: less than one per wave) stay on k_gemm_t
         const char* gw_env = getenv("OMOK_GEMM_W");
-        const bool gw = GEMM_W && gw_env && gw_env[0] == '1';
-        for (int r = 0; r < rep_fc1; ++r) {
-            if (gw) launch_gemm_w<16, EPI_SPLIT>(net.wt_fc1, h0, 32, 128, bias_fc1, h1, 128, nullptr, S, max_count, st, net.device);
-            else launch_gemm<16, EPI_SPLIT, 1, FC1_NST, TAIL_PRIO>(net.wt_fc1, h0, 32, 128, 32, 1, 2, bias_fc1, h1, 128, nullptr, S, max_count, st, net.device);
-        }
-        for (int r = 0; r < rep_heads; ++r) {
-            if (MT == 8 && gw) launch_gemm_w<8, EPI_LOGITS>(net.wt_heads, h1, 32, 128, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
-            else if (MT == 8) launch_gemm<8, EPI_LOGITS, 2, HEADS_NST, TAIL_PRIO>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
-            else launch_gemm<4, EPI_LOGITS, 2>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
-        }
+        const bool gw = gw_env && gw_env[0] == '1';
+        if (gw) launch_gemm_w<16, EPI_SPLIT>(net.wt_fc1, h0, 32, 128, bias_fc1, h1, 128, nullptr, S, max_count, st, net.device);
+        else launch_gemm<16, EPI_SPLIT, 1, FC1_NST>(net.wt_fc1, h0, 32, 128, 32, 1, 2, bias_fc1, h1, 128, nullptr, S, max_count, st, net.device);
+        if (MT == 8 && gw) launch_gemm_w<8, EPI_LOGITS>(net.wt_heads, h1, 32, 128, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
+        else if (MT == 8) launch_gemm<8, EPI_LOGITS, 2, HEADS_NST>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
+        else launch_gemm<4, EPI_LOGITS, 2>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
     } else {
         launch_gemm<16, EPI_PARTIAL, 1>(net.wt_fc1, h0, 32 / tsplit, 128, 32, 1, 2, bias_fc1, nullptr, cap_t, net.part, S, max_count, st, net.device, tsplit);
         k_splitk_finish<<<(unsigned)((fin_threads + 255) / 256), 256, 0, st>>>(net.part, tsplit, cap_t, bias_fc1, h1, 128, S.d_count, max_count);
@@ -4833,48 +4405,6 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     const int sg = max_count < 32768 ? max_count : 32768; // one wave per row up to 32 waves per SIMD: the row loop is a chain of dependent loads
     if (!skip_softmax) k_softmax<<<sg, 64, 0, st>>>(net.s0, MT * 32, hw, net.rowp, net.p, net.v, net.vpre, S.d_count, max_count);
     if (prof) prof->end(st);
-}
-
-// Optional (OMOK_NET_CHUNK, default off): a forward over more rows than the chunk size runs as consecutive launches over
-// row chunks (same kernels, offset request / output pointers, chunk-local scratch rows).  Isolated launches of 16-32 K
-// rows take 10 % less time per row than one launch of 64 K rows (tools/bench_net.py: trunk 4.24 vs 4.71 ms, fc0 3.15 vs
-// 3.54 ms per 65536 rows), but that is the idle gap between timed launches, not the size: back to back inside a
-// self-play episode the chunked rounds are 2-4 % SLOWER (first 8 plies of C2: 3.06 / 2.94 s unchunked, 3.13 / 3.11 s
-// at 16384, 3.10 s at 32768), so it stays off.
-__global__ void k_chunk_counts(const int32_t* __restrict__ d_count, int max_count, int chunk, int n_chunks, int32_t* __restrict__ out) {
-    const int i = threadIdx.x;
-    if (i >= n_chunks) return;
-    int c = d_count[0];
-    if (c > max_count) c = max_count;
-    const int v = c - i * chunk;
-    out[i * 4] = v < 0 ? 0 : (v > chunk ? chunk : v);
-}
-
-static void forward_chunked(Net& net, const Store& S, int max_count, bool from_f32, hipStream_t st, Prof* prof, int sib_side = -1, bool skip_softmax = false) {
-    const int chunk_max = chunk_env();
-    if (chunk_max <= 0 || max_count <= chunk_max) {
-        forward_f16x3(net, S, max_count, from_f32, st, prof, sib_side, skip_softmax);
-        return;
-    }
-    int n_chunks = (max_count + chunk_max - 1) / chunk_max;
-    if (n_chunks > 64) n_chunks = 64;
-    const int chunk = ((max_count + n_chunks - 1) / n_chunks + GT_BS - 1) / GT_BS * GT_BS; // balanced, whole tiles
-    k_chunk_counts<<<1, 64, 0, st>>>(S.d_count, max_count, chunk, n_chunks, net.d_chunk);
-    for (int c = 0; c < n_chunks; ++c) {
-        const int base = c * chunk;
-        const int mc = max_count - base < chunk ? max_count - base : chunk;
-        if (mc <= 0) break;
-        Net v = net; // a view: same scratch buffers, outputs of this chunk's rows
-        Store S2 = S;
-        S2.req_ref += base;
-        S2.req_aux += base;
-        S2.d_count = net.d_chunk + 4 * c;
-        v.p += (size_t)base * net.rowp;
-        v.v += base;
-        v.vpre += base;
-        v.in_f32 += (size_t)base * 3 * net.hw;
-        forward_f16x3(v, S2, mc, from_f32, st, prof);
-    }
 }
 
 // ===============================================================================================
@@ -5132,10 +4662,7 @@ static int net_probe(Net& net, const Store& S, hipStream_t st) {
     return 0;
 }
 
-bool net_logits_cover_batch(const Net& net, int max_count) {
-    const int chunk_max = chunk_env();
-    return net.mode != OMOK_NET_F32 && max_count <= net.max_b && (chunk_max <= 0 || max_count <= chunk_max);
-}
+bool net_logits_cover_batch(const Net& net, int max_count) { return net.mode != OMOK_NET_F32 && max_count <= net.max_b; }
 
 void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t st, Prof* prof, int sibling_side, bool skip_softmax) {
     if (max_count <= 0) return;
@@ -5145,14 +4672,14 @@ void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t s
         launch_encode_requests(net.n, S, net.in_f32, max_count, st);
         forward_f32(net, S, max_count, st, prof);
     } else {
-        forward_chunked(net, S, max_count, false, st, prof, sibling_side, skip_softmax);
+        forward_f16x3(net, S, max_count, false, st, prof, sibling_side, skip_softmax);
     }
 }
 
 void net_forward_inputs(Net& net, const Store& S, int count, hipStream_t st, Prof* prof) {
     if (count <= 0) return;
     if (net.mode == OMOK_NET_F32) forward_f32(net, S, count, st, prof);
-    else forward_chunked(net, S, count, true, st, prof);
+    else forward_f16x3(net, S, count, true, st, prof);
 }
 
 } // namespace omok

@@ -135,9 +135,6 @@ __device__ float gamma_draw(float alpha_f, uint64_t seed, uint32_t cell, uint32_
 // ---------------------------------------------------------------------------------------------
 // wave helpers
 // ---------------------------------------------------------------------------------------------
-#ifndef WAVE_MAX_DPP
-#define WAVE_MAX_DPP 1 // (A-B builds: 0 = the butterfly of 64-bit shuffles, 12 ds_bpermute in a dependent chain; same result)
-#endif
 // unsigned maximum over the 64 lanes by data-parallel-primitive moves (no LDS crossbar): inclusive max-scan inside each row of 16 lanes (row_shr 1, 2, 4, 8; lanes without
 // a source keep the identity 0), lane 15 of rows 0 / 2 into rows 1 / 3 (row_bcast15), lane 31 into rows 2 and 3 (row_bcast31): lane 63 holds the wave's maximum.
 __device__ inline uint32_t wave_max_u32_dpp(uint32_t x) {
@@ -154,20 +151,11 @@ __device__ inline uint32_t wave_max_u32_dpp(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 __device__ inline unsigned long long wave_max_u64(unsigned long long v) {
-#if WAVE_MAX_DPP
     // lexicographic: the maximum of the high words, then the maximum of the low words among the lanes that hold it (a lane with v = 0 never wins against a candidate)
     const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
     const uint32_t H = wave_max_u32_dpp(hi);
     const uint32_t L = wave_max_u32_dpp(hi == H ? lo : 0u);
     return ((unsigned long long)H << 32) | (unsigned long long)L;
-#else
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long x = __shfl_xor(v, o, 64);
-        v = x > v ? x : v;
-    }
-    return v;
-#endif
 }
 __device__ inline uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll
@@ -236,9 +224,6 @@ __device__ unsigned int g_klaunch;
 #define KP(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); kp[i] += now_ - kp_last; kp_last = now_; } while (0)
 #else
 #define KP(i) do { } while (0)
-#endif
-#ifndef PARALLEL_PICKS
-#define PARALLEL_PICKS 1 // (A-B builds: 0 = run_sims picks its cells and checks its children one at a time, as in round 4; same results)
 #endif
 template <int N>
 struct Tree {
@@ -820,7 +805,6 @@ __device__ void run_sims(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>
         uint32_t my_x = 0u;
         if (lane < m) my_x = philox(A.seed, first_sim + (uint32_t)(done + lane), (uint32_t)A.ply, tree_global, RNG_EXPAND).x;
         int my_action = 0, my_status = ST_IN_PROGRESS;
-#if PARALLEL_PICKS
         {
             // Simulation i draws r_i = floor(x_i (total - i) / 2^32) and takes the r_i-th of the cells the earlier ones left.  In RANK space (rank = position among the leaf's
             // untried cells as they are now): with the ranks taken so far sorted, s_0 < s_1 < ..., the r-th remaining rank is r + #{j : s_j - j <= r}.  The sorted list lives across
@@ -852,33 +836,9 @@ __device__ void run_sims(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>
                 for (int j = 0; j < G::IT; ++j) cand[j] &= ~((a >> 6) == j ? (1ULL << (a & 63)) : 0ULL);
             }
         }
-#else
-        {
-            int tot = total;
-            for (int i = 0; i < m; ++i) {
-                const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)my_x, i);
-                int r = (int)__umulhi(x, (uint32_t)tot);
-                int action = 0;
-                bool found = false;
-#pragma unroll
-                for (int j = 0; j < G::IT; ++j) {
-                    const int c = __popcll(cand[j]);
-                    if (!found) {
-                        if (r < c) { action = j * 64 + nth_set_bit(cand[j], r); found = true; }
-                        else r -= c;
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < G::IT; ++j) cand[j] &= ~((action >> 6) == j ? (1ULL << (action & 63)) : 0ULL);
-                if (lane == i) my_action = action;
-                tot -= 1;
-            }
-        }
-#endif
         KP(5); // picks
         // ---- place the stones (pme.rs:128-135): win check per child, up to the first terminal one ----
         int n_commit = m, term_status = ST_IN_PROGRESS;
-#if PARALLEL_PICKS
         {
             // lane 4 c + p checks direction pair p of child c (16 children at a time); a child is a win if any of its four pairs makes exactly five, a draw if it took the
             // leaf's last cell; the first terminal child ends the batch (the loop this replaces checked one child at a time with 40 lanes: ~1300 cycles each)
@@ -904,19 +864,6 @@ __device__ void run_sims(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>
                 if (lane == first) my_status = term_status;
             }
         }
-#else
-        for (int i = 0; i < m; ++i) {
-            const int a = __builtin_amdgcn_readlane(my_action, i);
-            uint64_t mine[NW];
-#pragma unroll
-            for (int w = 0; w < NW; ++w) mine[w] = h.turn == 0 ? bb[w] : bb[NW + w];
-            set_bit<NW>(mine, a);
-            const int five = exactly_five<N>(mine, a);
-            const int st = five ? (h.turn == 0 ? ST_BLACK_WIN : ST_WHITE_WIN) : (h.legal == 1 ? ST_DRAW : ST_IN_PROGRESS);
-            if (lane == i) my_status = st;
-            if (st != ST_IN_PROGRESS) { n_commit = i + 1; term_status = st; break; }
-        }
-#endif
         KP(6); // win checks
         // ---- expand (node.rs:61-81), n_commit children in one pass ----
         int tab = h.table;
@@ -984,9 +931,6 @@ __device__ void run_sims(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>
     }
 }
 
-#ifndef SCATTER_SEGMENTS
-#define SCATTER_SEGMENTS 1 // (A-B builds: 0 = rounds with several request parents back up one request at a time, as in round 4; same results)
-#endif
 #ifndef KROUND_BATCH
 #define KROUND_BATCH 1 // 0: one simulation at a time (run_sim; A-B builds and the reference point of the batched form)
 #endif
@@ -1009,13 +953,7 @@ __global__ __launch_bounds__(64, KROUND_WPS) void k_round(Store S, RoundArgs A) 
     unsigned long long& kp_last = R.kp_last;
     kp_last = __builtin_readcyclecounter();
 #endif
-#ifndef KROUND_EXP
-#define KROUND_EXP 0 // timing-only A-B builds: 1 = no deferred backups, 2 = no simulations
-#endif
-#if KROUND_EXP != 0 && !defined(OMOK_EXPERIMENT)
-#error "KROUND_EXP builds are timing experiments with wrong results: build them with -DOMOK_EXPERIMENT, never as the product"
-#endif
-    if (KROUND_EXP != 1 && A.scatter_v && ts.n_req > 0) { // the previous round's backups, deferred into this kernel (run loop)
+    if (A.scatter_v && ts.n_req > 0) { // the previous round's backups, deferred into this kernel (run loop)
         scatter_tree<N>(S, T, ts, R, A.scatter_v);
         R.dirty = true;
     }
@@ -1027,8 +965,7 @@ __global__ __launch_bounds__(64, KROUND_WPS) void k_round(Store S, RoundArgs A) 
     if (A.round == 0) apply_noise<N>(T, A, tree_global, s_row);
     KP(1); // noise
     LeafCache<N> C;
-    if (KROUND_EXP == 2) { /* timing only */ }
-    else if (KROUND_BATCH) run_sims<N>(S, T, R, C, A, (uint32_t)(A.round * A.K), A.K, tree_global);
+    if (KROUND_BATCH) run_sims<N>(S, T, R, C, A, (uint32_t)(A.round * A.K), A.K, tree_global);
     else for (int i = 0; i < A.K; ++i) run_sim<N>(S, T, R, C, A, (uint32_t)(A.round * A.K + i), tree_global);
     if (LANE == 0) {
         TreeState o = ts;
@@ -1536,16 +1473,6 @@ __device__ inline void scatter_tree(const Store& S, const Tree<N>& T, const Tree
     }
     const int prev_par = __shfl_up(par, 1, 64);
     unsigned long long rem = __ballot(lane < nreq && (lane == 0 || par != prev_par)); // segment starts
-#if SCATTER_SEGMENTS == 0
-    if (__popcll(rem) > 1) { // (A-B builds: the round-4 form -- a second parent sends every backup of the round through the walk)
-        for (uint32_t r = 0; r < ts.n_req; ++r) {
-            backup<N>(T, R, T.req[r], -V[(size_t)ts.req_base + r]);
-            __syncthreads();
-            R.bytes += 8ull * G::HW + 4;
-        }
-        return;
-    }
-#endif
     while (rem) {
         const int s0 = __ffsll((long long)rem) - 1;
         rem &= rem - 1ULL;

@@ -1,5 +1,5 @@
 """Kernel-level timing of the net forward through the C ABI (evaluate_pv), HIP-event times.
-usage: python tools/bench_net.py [batch] [reps]   (env OMOK_DBG_TRUNK = ablation bits, timing only)"""
+usage: python tools/bench_net.py [batch] [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -18,4 +18,4 @@ eng.reset_stats()
 for _ in range(reps):
     eng.evaluate_pv(x)
 st = eng.stats()
-print(f"B={B} dbg={os.environ.get('OMOK_DBG_TRUNK','0')}: trunk {st['ms_trunk']/reps:.3f} ms  fc0 {st['ms_fc0']/reps:.3f} ms  tail {st['ms_tail']/reps:.3f} ms")
+print(f"B={B}: trunk {st['ms_trunk']/reps:.3f} ms  fc0 {st['ms_fc0']/reps:.3f} ms  tail {st['ms_tail']/reps:.3f} ms")

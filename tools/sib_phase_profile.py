@@ -1,5 +1,6 @@
-"""Phase profile of the children kernels of the difference path (OMOK_SIB_PROF=1: k_sib_children, 2: k_sib_children2): plays the first plies of
-configs[1] and lets the library print its in-kernel cycle counters to stderr.  usage: OMOK_SIB_PROF=2 python tools/sib_phase_profile.py [plies]"""
+"""Phase profile of k_sib_children2, the children kernel of the difference path (OMOK_SIB_PROF=2): plays the first plies of
+configs[1] and lets the library print its in-kernel cycle counters to stderr (k_sib_children's profiler was removed with its one profile kept:
+profiles/r03_sib_children_phase_profile.txt, docs/experiments/r08_retired_switches.diff).  usage: OMOK_SIB_PROF=2 python tools/sib_phase_profile.py [plies]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import omok_ai_amd as oa
