@@ -54,6 +54,7 @@ pub const OMOK_NET_F16X3_FP6: i32 = 3;
 pub const OMOK_NET_F16X3_F16: i32 = 4;
 pub const OMOK_NET_F16X3_MIXED: i32 = 5;
 pub const OMOK_MAX_ARENA: i32 = 16384;
+pub const OMOK_PLAN_INTS: i32 = 16;
 pub const OMOK_STAT_SIMS: i32 = 0;
 pub const OMOK_STAT_EVALS: i32 = 1;
 pub const OMOK_STAT_PLY_GAMES: i32 = 2;
@@ -167,6 +168,7 @@ pub mod ffi {
         pub fn omok_debug_set_base_cache(e: *mut OmokEngine, enabled: i32) -> c_int;
         pub fn omok_debug_set_children_kernel(e: *mut OmokEngine, which: i32) -> c_int;
         pub fn omok_debug_set_window_rects(e: *mut OmokEngine, enabled: i32) -> c_int;
+        pub fn omok_debug_last_plan(e: *mut OmokEngine, out: *mut i32, cap: i32) -> c_int;
         pub fn omok_get_stats(e: *mut OmokEngine, stats: *mut f64) -> c_int;
         pub fn omok_reset_stats(e: *mut OmokEngine) -> c_int;
         pub fn omok_set_profiling(e: *mut OmokEngine, enabled: i32) -> c_int;

@@ -289,6 +289,16 @@ int omok_debug_set_children_kernel(omok_engine* e, int32_t which);
  * differ in (a child differs from its base only within its stone's pixel +- 3 clipped to the board; outside that region its difference row holds exact zeros).
  * Results must not change by a bit (tests): skipped pixels contribute exact zeros. */
 int omok_debug_set_window_rects(omok_engine* e, int32_t enabled);
+/* Debugging aid of the launch-shape tests: what the LAST net forward of the engine (net 1) decided.  Writes min(cap, OMOK_PLAN_INTS) ints and returns that number:
+ *   [0] path: 0 = plain rows (omok_evaluate_pv, mirror and root evaluations), 1 = sibling round on the copy path, 2 = on the difference path,
+ *       3 = fp32 kernels, -1 = no forward yet;  [1] the host's bound on the rows (live games x K in a search round);
+ *   [2] K split of the dense fc0 (1..64; 0 on paths 2 / 3);  [3] K split of the fc1 / heads GEMMs (1, 2, 4, 8; 0 on path 3);
+ *   sibling rounds: [4] runs, [5] rows outside runs, [6] rows inside runs;  difference path, as chosen on the device: [7] runs whose base was evaluated in
+ *   full, [8] fc0 window tiles, [9] first tile of the K-split set (== [8]: none), [10] its ways, [11] K split of the full-row fc0;
+ *   [12] fc0 operand format as OMOK_STAT_FC0_FORMAT, [13] compute units the planners count with, [14] fc0 super-steps (2 N N), [15] 0.
+ * Synchronises the engine's stream; changes no result.  The sibling-round counters are valid until the next omok_round_generate / omok_execute. */
+#define OMOK_PLAN_INTS 16
+int omok_debug_last_plan(omok_engine* e, int32_t* out, int32_t cap);
 
 #define OMOK_STAT_SIMS 0        /* simulations run (incl. terminal hits / no-action sims) */
 #define OMOK_STAT_EVALS 1       /* net evaluations (search requests + mirror evals + root) */

@@ -171,6 +171,15 @@ class Engine:
         """2: k_sib_children2 (default), 1: k_sib_children on the difference path of sibling rounds (A-B / tests)."""
         self._chk(B.lib().omok_debug_set_children_kernel(self.h, int(which)))
 
+    def last_plan(self):
+        """what the last net forward decided (omok_debug_last_plan): dict of B.PLAN_NAMES, "path" as a name of B.PLAN_PATHS"""
+        out = np.zeros(len(B.PLAN_NAMES), dtype=np.int32)
+        n = self._chk(B.lib().omok_debug_last_plan(self.h, B.iptr(out), out.size))
+        assert n == out.size
+        d = dict(zip(B.PLAN_NAMES, (int(x) for x in out)))
+        d["path"] = B.PLAN_PATHS[d["path"]]
+        return d
+
     def set_profiling(self, on=True):
         """True / 1: time every launch; N > 1: time one search round in N (stats are scaled); False: off."""
         self._chk(B.lib().omok_set_profiling(self.h, int(on)))

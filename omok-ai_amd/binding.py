@@ -14,6 +14,10 @@ OK = 0
 NET_F16X3, NET_F32, NET_F16X3_ROWS, NET_F16X3_FP6, NET_F16X3_F16, NET_F16X3_MIXED = 0, 1, 2, 3, 4, 5
 FC0_FORMATS = {-1: "f32", 0: "fp6", 1: "f16", 2: "mixed"}
 MODE_PLAYER, MODE_OPPONENT = 0, 1
+# omok_debug_last_plan: names of its ints; PLAN_PATHS: values of "path"
+PLAN_NAMES = ["path", "rows", "nsplit", "tsplit", "runs", "singles", "run_rows", "full_runs", "tiles", "t_split", "ways", "fways",
+              "fc0_format", "n_cu", "nsup", "reserved"]
+PLAN_PATHS = {-1: "none", 0: "plain", 1: "copy", 2: "difference", 3: "f32"}
 STAT_NAMES = ["sims", "evals", "ply_games", "finished", "ms_tree", "ms_trunk", "ms_fc0", "ms_tail", "ms_ply",
               "fc0_launches", "fc0_rows", "tree_bytes", "round_launches", "ms_round", "peak_nodes", "peak_tables",
               "fc0_format", "probe_rows", "probe_dp_fp6", "probe_dv_fp6", "probe_dp_f16", "probe_dv_f16", "probe_limit", "probe_logit_max",
@@ -32,7 +36,7 @@ SYMBOLS = [
     "omok_round_eval", "omok_round_outputs", "omok_round_logits", "omok_round_inject", "omok_round_scatter", "omok_mirror_generate",
     "omok_mirror_inputs", "omok_mirror_eval", "omok_mirror_outputs", "omok_mirror_inject", "omok_mirror_apply",
     "omok_alive_count", "omok_current_ply", "omok_game_info", "omok_tree_dump", "omok_tree_root", "omok_replay_game",
-    "omok_operand_row_bytes", "omok_debug_operand_rows", "omok_debug_set_base_cache", "omok_debug_set_children_kernel", "omok_debug_set_window_rects",
+    "omok_operand_row_bytes", "omok_debug_operand_rows", "omok_debug_set_base_cache", "omok_debug_set_children_kernel", "omok_debug_set_window_rects", "omok_debug_last_plan",
     "omok_replay_pack_dev", "omok_replay_record_bytes", "omok_replay_augment_dev", "omok_replay_augmented_game", "omok_get_stats", "omok_reset_stats", "omok_set_profiling",
 ]
 
@@ -95,6 +99,7 @@ def lib():
     L.omok_debug_set_base_cache.argtypes = [H, C.c_int32]
     L.omok_debug_set_children_kernel.argtypes = [H, C.c_int32]
     L.omok_debug_set_window_rects.argtypes = [H, C.c_int32]
+    L.omok_debug_last_plan.argtypes = [H, ip, C.c_int32]
     L.omok_set_episode.argtypes = [H, C.c_uint64]
     L.omok_env_place_stone.argtypes = [H, u8p, u8p, C.POINTER(C.c_uint16), ip, C.c_int32, ip]
     L.omok_compute_policy.argtypes = [H, fp, u8p]

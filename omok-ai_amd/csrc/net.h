@@ -105,6 +105,9 @@ struct Net {
     // request rows are the engine's dense list minus grp_sub[0] (the rows of the games in front, NULL: none); grp_hi < 0: every game (self-play)
     int grp_lo = 0, grp_hi = -1;
     const int32_t* grp_sub = nullptr;
+    // what the LAST forward decided on the host (omok_debug_last_plan; the device-side choices of k_bin_prefix stay in d_gcnt): path 0 plain rows, 1 copy path,
+    // 2 difference path, 3 fp32 kernels (-1: no forward yet), its row bound, the dense fc0's K split (0: difference path / fp32) and the tail GEMMs' K split
+    int plan_path = -1, plan_rows = 0, plan_nsplit = 0, plan_tsplit = 0;
 };
 
 // sizes

@@ -4316,6 +4316,9 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     // fc0.  Small batches (late plies of an episode) cannot fill 256 CUs with 128-sample tiles: split K over
     // blockIdx.y into fp32 partials and finish (sum in split order + bias + LeakyReLU + hi|lo) in a second kernel.
     const MxScales sc{127 - net.mx_sw, 127 - (net.mx_sw + 11), 127 - MX_SA, 127 - (MX_SA + 11), ldexpf(1.0f, net.mx_sw), ldexpf(1.0f, MX_SA)};
+    net.plan_path = sib ? (delta ? 2 : 1) : 0;
+    net.plan_rows = max_count;
+    net.plan_nsplit = 0;
     if (delta) launch_fc0_delta(net, max_count, sc, bias_fc0, h0, st);
     else {
         const int nsup = hw * 2;
@@ -4346,6 +4349,7 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
                 if (cost < best - 1e-9) { best = cost; nsplit = d; }
             }
         }
+        net.plan_nsplit = nsplit;
         constexpr int LDS = 0; // static LDS objects: (2 + MXS_SLOTS) x 24 KiB
         if (net.fc0_fmt == FC0_F16) {
             const int lc = (hw % 32) ? (hw % 32) : 1;
@@ -4382,6 +4386,7 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     const int tiles_t = (max_count + GT_BS - 1) / GT_BS;
     int tsplit = 1;
     while (tsplit < 8 && tiles_t * tsplit * 2 <= net.n_cu_all && (size_t)(tsplit * 2) * (size_t)(tiles_t * GT_BS) <= net.part_rows) tsplit *= 2;
+    net.plan_tsplit = tsplit;
     const size_t cap_t = (size_t)tiles_t * GT_BS;
     const size_t fin_threads = (size_t)max_count * 64;
     if (tsplit == 1) {
@@ -4671,6 +4676,7 @@ void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t s
         recover_handed_over_fill(net, S, st, "fp32 kernels");
         launch_encode_requests(net.n, S, net.in_f32, max_count, st);
         forward_f32(net, S, max_count, st, prof);
+        net.plan_path = 3; net.plan_rows = max_count; net.plan_nsplit = net.plan_tsplit = 0;
     } else {
         forward_f16x3(net, S, max_count, false, st, prof, sibling_side, skip_softmax);
     }
@@ -4678,8 +4684,10 @@ void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t s
 
 void net_forward_inputs(Net& net, const Store& S, int count, hipStream_t st, Prof* prof) {
     if (count <= 0) return;
-    if (net.mode == OMOK_NET_F32) forward_f32(net, S, count, st, prof);
-    else forward_f16x3(net, S, count, true, st, prof);
+    if (net.mode == OMOK_NET_F32) {
+        forward_f32(net, S, count, st, prof);
+        net.plan_path = 3; net.plan_rows = count; net.plan_nsplit = net.plan_tsplit = 0;
+    } else forward_f16x3(net, S, count, true, st, prof);
 }
 
 } // namespace omok
