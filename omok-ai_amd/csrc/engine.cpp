@@ -1629,14 +1629,17 @@ extern "C" int omok_debug_last_plan(omok_engine* e, int32_t* out, int32_t cap) {
     int32_t plan[OMOK_PLAN_INTS] = {};
     plan[0] = net.plan_path; plan[1] = net.plan_rows; plan[2] = net.plan_nsplit; plan[3] = net.plan_tsplit;
     plan[12] = net.mode == OMOK_NET_F32 ? -1 : net.diff_fp6 ? FC0_MIXED : net.fc0_fmt;
-    plan[13] = net.n_cu_all;
+    plan[13] = net.n_cu;
     plan[14] = 2 * net.hw;
     if (sync_and_check(e, "debug_last_plan")) return OMOK_ERR_HIP;
     if ((net.plan_path == 1 || net.plan_path == 2) && net.d_gcnt) {
-        int32_t c[100];
+        int32_t c[NET_GCNT_HEAD_INTS];
         HIPCHK(e, hipMemcpy(c, net.d_gcnt, sizeof(c), hipMemcpyDeviceToHost));
-        plan[4] = c[0]; plan[5] = c[1]; plan[6] = c[2];
-        if (net.plan_path == 2) { plan[7] = c[96]; plan[8] = c[4]; plan[9] = c[5]; plan[10] = c[6]; plan[11] = c[98]; }
+        plan[4] = c[NET_GCNT_RUNS]; plan[5] = c[NET_GCNT_SINGLES]; plan[6] = c[NET_GCNT_ROWS_IN_RUNS];
+        if (net.plan_path == 2) {
+            plan[7] = c[NET_GCNT_FULL_EVALS]; plan[8] = c[NET_GCNT_WIN_TILES]; plan[9] = c[NET_GCNT_SPLIT_TILE0]; plan[10] = c[NET_GCNT_WIN_WAYS];
+            plan[11] = c[NET_GCNT_FULL_WAYS];
+        }
     }
     const int n = cap < OMOK_PLAN_INTS ? cap : OMOK_PLAN_INTS;
     for (int i = 0; i < n; ++i) out[i] = plan[i];

@@ -57,8 +57,7 @@ struct Net {
     void* d_groups = nullptr;
     int32_t* d_singles = nullptr;
     void* d_sib_rows = nullptr; // (request row, run) of the rows inside runs
-    int32_t* d_gcnt = nullptr;  // [0] runs, [1] rows outside runs, [2] rows inside runs, [3] full rows (runs + singles), [4] fc0 window tiles,
-                                // [8 + b] children whose window is bin b (SIB_CNT_INTS in all)
+    int32_t* d_gcnt = nullptr;  // the sibling round's counters: [NET_GCNT_INTS], indexed by the NET_GCNT_* enum below
     unsigned long long* d_work = nullptr; // [NET_WORK_COUNT] executed-work counters summed over the rounds since omok_reset_stats (k_group, k_bin_prefix add; only omok_get_stats reads)
     float* sib_h = nullptr;     // [run][3 blocks][225][32] the base passes' depthwise inputs
     // difference path: a child's fc0 input = its run's base row + a 7x7-window difference row
@@ -86,8 +85,7 @@ struct Net {
     bool sib_cache_valid = false;    // false: the trees changed outside the search rounds (reset, advance, refill): tags are cleared first
     float* part_w = nullptr;         // fp32 partials of the K-split window tiles: [7][part_w_rows][512]
     size_t part_w_rows = 0;
-    int n_cu = 256;                  // compute units of the device
-    int n_cu_all = 256;              // the same, set for every board size (n_cu above only with the sibling buffers)
+    int n_cu = 256;                  // compute units of the device (net_alloc; the fp32 mode plans no launch by it and keeps the default)
     int mx_sw = 0;            // fc0 weights: fp8 copies are w * 2^mx_sw (hi) and (w - f16(w)) * 2^(mx_sw + 11) (lo)
     // fc0 operand format: the correction terms hi*lo + lo*hi of fc0 run either on block-scaled fp6 operands (FC0_FP6: 4
     // significant bits, products good to ~2^-15) or on f16 operands (FC0_F16: three f16 MFMAs per product, ~2^-22).  net_commit packs the
@@ -142,6 +140,24 @@ bool net_logits_cover_batch(const Net& net, int max_count);
 // true if net_forward_requests(net, S, max_count, ..., sibling_side >= 0) will group the requests by parent (k_group): the caller may then hand
 // the zeroing of net.d_gcnt and the request-list fill to it (Net::gcnt_zeroed, Net::fill_in_group)
 bool net_round_takes_sibling_path(const Net& net, int max_count);
+// Net::d_gcnt: what k_group counts, what k_bin_prefix derives from it on the device, and what the fc0 kernels of the difference path, k_win_finish, k_facc_reduce and
+// the host (omok_debug_last_plan, OMOK_SIB_STATS) read
+enum {
+    NET_GCNT_RUNS = 0,          // runs of sibling requests (k_group)
+    NET_GCNT_SINGLES = 1,       // rows outside runs
+    NET_GCNT_ROWS_IN_RUNS = 2,  // rows inside runs
+    NET_GCNT_FULL_ROWS = 3,     // difference path (k_bin_prefix, as everything up to NET_GCNT_BINS): rows evaluated in full = NET_GCNT_FULL_EVALS + NET_GCNT_SINGLES
+    NET_GCNT_WIN_TILES = 4,     // fc0 window tiles
+    NET_GCNT_SPLIT_TILE0 = 5,   // first tile of the K-split set (the tiles below it run the whole K)
+    NET_GCNT_WIN_WAYS = 6,      // K splits of the tiles of that set
+    NET_GCNT_TILE_ORDER = 7,    // offset inside Net::d_tile_info of the whole-K launch's tile order
+    NET_GCNT_BINS = 8,          // [+ b] children whose window is bin b (diagnostics; 81 bins, padded to 88 ints)
+    NET_GCNT_FULL_EVALS = 96,   // runs whose base is evaluated in full (base-cache misses + uncacheable runs; k_group)
+    NET_GCNT_UNCACHEABLE = 97,  // ... of them: runs that have no base slot of their game (k_group)
+    NET_GCNT_FULL_WAYS = 98,    // K splits of the full-row fc0 (k_bin_prefix)
+    NET_GCNT_FULL_STRIDE = 99,  // ... and the row stride of its partial slab (the kernels read the pair through one pointer: FULL_STRIDE follows FULL_WAYS)
+    NET_GCNT_HEAD_INTS = 100    // ints in front of the padding and the per-pixel counts
+};
 constexpr int NET_GCNT_P0 = 8 + 81 + 7 + 16;   // Net::d_gcnt[NET_GCNT_P0 + pixel]: children whose stone lands in net pixel `pixel` (their rows take consecutive slots inside the window bin)
 constexpr int NET_GCNT_INTS = NET_GCNT_P0 + 225; // ints of Net::d_gcnt
 // Net::d_work: [DIFF + 0..2] runs, single rows, rows in runs of the rounds on the difference path, [COPY + 0..2] the same on the copy path, [DIFF_FULL] runs of the difference

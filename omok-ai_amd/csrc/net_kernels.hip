@@ -803,8 +803,7 @@ constexpr int sib_hb_floats(int n) { return n * n * NM; } // one base h grid in 
 constexpr int SIB_PAIR_CUT1 = 289, SIB_PAIR_CUT2 = 578, SIB_PAIR_CUT3 = 801; // shares of a workgroup's children per wave pair, cumulative / 1024 (k_sib_children)
 // difference path: window bins (window origin (wy0, wx0) in 0..8 each), the single rows as bin SIB_BINS, counters, difference rows
 constexpr int SIB_ORG = 15 - SIB_WIN + 1, SIB_BINS = SIB_ORG * SIB_ORG; // 9, 81: bin = wy0 * 9 + wx0 for EVERY board size (N = 9: origins 0..2, 9 bins in use)
-constexpr int SIB_CNT_INTS = NET_GCNT_INTS;                                // d_gcnt: 8 counters, bin counts (96 ints), [96] full evaluations of runs (base-cache
-                                                                          // misses + uncacheable runs), [97] uncacheable runs
+constexpr int SIB_CNT_INTS = NET_GCNT_INTS;                                // ints of d_gcnt (net.h: the NET_GCNT_* enum)
 constexpr int SIB_WPX = SIB_WIN * SIB_WIN;                                // 49 window pixels = 98 fc0 super-steps
 constexpr int SIB_DROW_U4 = SIB_WPX * 2 * 12;                             // 1176 uint4 = 18816 B: [q][w] 128-B f16 parts, [q][w] 64-B residual parts
 constexpr int SIB_DLO_U4 = SIB_WPX * 2 * 8;                               // 784: first residual part
@@ -818,7 +817,7 @@ __device__ inline void sib_window(int n, int action, int& wy0, int& wx0) { // th
     wx0 = wx0 < 0 ? 0 : (wx0 > n - SIB_WIN ? n - SIB_WIN : wx0);
 }
 
-// cnt[0] runs, cnt[1] rows outside runs, cnt[2] rows inside runs.  sib_rows[i] = descriptor of a row inside a run: (request row, run
+// cnt = Net::d_gcnt (NET_GCNT_*): runs, rows outside runs, rows inside runs.  sib_rows[i] = descriptor of a row inside a run: (request row, run
 // index, node record index t * stride_nodes + node, turn | action << 8); a run's rows are adjacent.
 // sib_slot[i] (difference path, else NULL) = net pixel of the child's stone (P0) << 24 | rank of the row among that pixel's rows (any order: a row's
 // result does not depend on its slot).
@@ -834,7 +833,8 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
     // Difference path (sib_slot != NULL): base slots.  The FIRST run of a tree uses one of the game's SIB_WAYS slots (SIB_WAYS g + way), whose content is
     // reused while a tag names the run's parent (a leaf is its tree's expansion target for ~14 rounds); further runs of the tree in the same
     // round (rare) take a slot behind the games' and are always evaluated.  comp[] lists the (first request row, slot) pairs to evaluate.
-    constexpr int NP0 = 225, LC = 3 + NP0 + 2; // runs, singles, rows in runs | children per net pixel of their stone (P0) | full evaluations, uncacheable runs
+    constexpr int NP0 = 225, L_P0 = 3, L_FULL = L_P0 + NP0, L_UNC = L_FULL + 1, LC = L_UNC + 1; // [NET_GCNT_RUNS, _SINGLES, _ROWS_IN_RUNS] as in d_gcnt | [L_P0 +] children per net pixel of their stone (P0) | full evaluations, uncacheable runs
+    static_assert(NET_GCNT_ROWS_IN_RUNS + 1 == L_P0 && NET_GCNT_UNCACHEABLE == NET_GCNT_FULL_EVALS + 1, "k_group's local counters mirror d_gcnt");
     __shared__ int l_cnt[LC], l_base[LC];
     const int tid = threadIdx.x, lane = tid & 63;
     const int g = (MATCH ? g_lo : 0) + blockIdx.x * GROUP_TREES + (tid >> 6);
@@ -876,8 +876,8 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
     int bslot = -1, mi = -1, ex = -1; // base slot (>= 0: decided), index in the evaluation list (-1: cache hit), index among the uncacheable runs
     const unsigned long long qual = __ballot(start && len >= SIB_MIN);
     if (start && len >= SIB_MIN) {
-        gslot = atomicAdd(&l_cnt[0], 1);
-        rbase = atomicAdd(&l_cnt[2], len);
+        gslot = atomicAdd(&l_cnt[NET_GCNT_RUNS], 1);
+        rbase = atomicAdd(&l_cnt[NET_GCNT_ROWS_IN_RUNS], len);
         if (sib_slot) {
             if (lane == __ffsll((long long)qual) - 1) {
                 // SIB_WAYS slots per game, most recently used first; a tag = leaf node | slot << 16, -1 = empty (one slot hits 77 % of the
@@ -898,7 +898,7 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
                         way = __ffs((int)~used) - 1;
                     }
                     hit = SIB_WAYS - 1;
-                    mi = atomicAdd(&l_cnt[3 + NP0], 1);
+                    mi = atomicAdd(&l_cnt[L_FULL], 1);
                 }
                 if (hit > 0 || mi >= 0) { // move to the front
 #pragma unroll
@@ -910,8 +910,8 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
                 }
                 bslot = SIB_WAYS * g + way;
             } else {
-                ex = atomicAdd(&l_cnt[3 + NP0 + 1], 1);
-                mi = atomicAdd(&l_cnt[3 + NP0], 1);
+                ex = atomicAdd(&l_cnt[L_UNC], 1);
+                mi = atomicAdd(&l_cnt[L_FULL], 1);
             }
         }
     }
@@ -937,29 +937,29 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
             // slots are handed out per net PIXEL of the child's stone (P0), not per window bin: a bin's rows are then ordered by P0, and an fc0 window tile
             // only has to walk the window pixels its own rows can differ in (k_bin_prefix: the tile's rectangle)
             bin = (2 * (int)(ta >> 8) + 1) / 3;
-            rank = atomicAdd(&l_cnt[3 + bin], 1);
+            rank = atomicAdd(&l_cnt[L_P0 + bin], 1);
         }
-    } else if (lane < n) sidx = atomicAdd(&l_cnt[1], 1);
+    } else if (lane < n) sidx = atomicAdd(&l_cnt[NET_GCNT_SINGLES], 1);
     __syncthreads();
-    if (tid < LC && l_cnt[tid] > 0 && (tid < 3 || sib_slot))
-        l_base[tid] = atomicAdd(&cnt[tid < 3 ? tid : (tid < 3 + NP0 ? NET_GCNT_P0 + (tid - 3) : 96 + (tid - 3 - NP0))], l_cnt[tid]);
+    if (tid < LC && l_cnt[tid] > 0 && (tid < L_P0 || sib_slot))
+        l_base[tid] = atomicAdd(&cnt[tid < L_P0 ? tid : (tid < L_FULL ? NET_GCNT_P0 + (tid - L_P0) : NET_GCNT_FULL_EVALS + (tid - L_FULL))], l_cnt[tid]);
     // executed-work counters of the stats (Net::d_work: never read by a kernel): runs, single rows, rows in runs per path; the runs evaluated in full
-    if (tid < 3 && l_cnt[tid] > 0) atomicAdd(&work[(sib_slot ? NET_WORK_DIFF : NET_WORK_COPY) + tid], (unsigned long long)l_cnt[tid]);
-    if (tid == 3 + NP0 && sib_slot && l_cnt[tid] > 0) atomicAdd(&work[NET_WORK_DIFF_FULL], (unsigned long long)l_cnt[tid]);
+    if (tid < L_P0 && l_cnt[tid] > 0) atomicAdd(&work[(sib_slot ? NET_WORK_DIFF : NET_WORK_COPY) + tid], (unsigned long long)l_cnt[tid]);
+    if (tid == L_FULL && sib_slot && l_cnt[tid] > 0) atomicAdd(&work[NET_WORK_DIFF_FULL], (unsigned long long)l_cnt[tid]);
     __syncthreads();
     if (start && len >= SIB_MIN) {
-        groups[l_base[0] + gslot] = make_uint2(ts.req_base + (uint32_t)lane, (uint32_t)len);
+        groups[l_base[NET_GCNT_RUNS] + gslot] = make_uint2(ts.req_base + (uint32_t)lane, (uint32_t)len);
         if (sib_slot) {
-            if (ex >= 0) bslot = SIB_WAYS * S.games + l_base[3 + NP0 + 1] + ex;
-            if (mi >= 0) comp[l_base[3 + NP0] + mi] = make_uint2(ts.req_base + (uint32_t)lane, (uint32_t)bslot);
+            if (ex >= 0) bslot = SIB_WAYS * S.games + l_base[L_UNC] + ex;
+            if (mi >= 0) comp[l_base[L_FULL] + mi] = make_uint2(ts.req_base + (uint32_t)lane, (uint32_t)bslot);
         }
     }
     bslot = __shfl(bslot, rs, 64);
     if (in_run) {
-        const int ri = l_base[2] + rbase + pos_in_run;
-        sib_rows[ri] = make_uint4(ts.req_base + (uint32_t)lane, sib_slot ? (uint32_t)bslot : (uint32_t)(l_base[0] + gslot), tn, ta);
-        if (sib_slot) sib_slot[ri] = ((uint32_t)bin << 24) | (uint32_t)(l_base[3 + bin] + rank);
-    } else if (lane < n) singles[l_base[1] + sidx] = (int32_t)(ts.req_base + (uint32_t)lane);
+        const int ri = l_base[NET_GCNT_ROWS_IN_RUNS] + rbase + pos_in_run;
+        sib_rows[ri] = make_uint4(ts.req_base + (uint32_t)lane, sib_slot ? (uint32_t)bslot : (uint32_t)(l_base[NET_GCNT_RUNS] + gslot), tn, ta);
+        if (sib_slot) sib_slot[ri] = ((uint32_t)bin << 24) | (uint32_t)(l_base[L_P0 + bin] + rank);
+    } else if (lane < n) singles[l_base[NET_GCNT_SINGLES] + sidx] = (int32_t)(ts.req_base + (uint32_t)lane);
 }
 
 // Difference path: slots.  Every bin's rows get consecutive slots, bins padded to whole 128-sample fc0 tiles (a tile's super-steps are
@@ -969,8 +969,8 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
 // XCD's chunk of a round = consecutive tiles = a few bins' weight slices through one L2), so round 1 holds the full-price tiles and a CU's second tile is a cheap
 // one: the 18 % of window pixels the rectangles skip then shorten the launch (in the old corner-first order with an eighth of the tiles per XCD, the XCDs of the interior
 // bins ran two full-price tiles per CU and nothing was gained).  T tiles take ceil(T / CUs) rounds of workgroups: the tiles of the last, partial round are instead
-// split over K (cnt[6] ways, fp32 partials + k_win_finish), so that the round costs 1 / cnt[6] of a full one.  The split set is made of
-// WHOLE bins from the end of the layout (tiles >= cnt[5]): a row's bin -- unlike its slot -- is a function of the position alone, so
+// split over K (NET_GCNT_WIN_WAYS ways, fp32 partials + k_win_finish), so that the round costs 1 / ways of a full one.  The split set is made of
+// WHOLE bins from the end of the layout (tiles >= NET_GCNT_SPLIT_TILE0): a row's bin -- unlike its slot -- is a function of the position alone, so
 // the summation order of a row never depends on the order in which k_group's atomics handed out the slots.
 __device__ inline int sib_bin_at(int pos, int bn) { // layout position -> bin: interior bins, edge bins, corner bins, a tail of interior bins, the single rows
     if (pos >= SIB_BINS) return SIB_BINS;
@@ -999,6 +999,9 @@ __device__ inline void sib_p0_range(int bn, int o, int& lo, int& hi) { // net-pi
     lo = o == 0 ? 0 : o + SIB_WIN / 2;
     hi = o == bn - SIB_WIN ? bn - 1 : o + SIB_WIN / 2;
 }
+__host__ __device__ inline void tile_rect(int ti, int& y0, int& y1, int& x0, int& x1) { // the rectangle of window pixels in a tile_info word (k_bin_prefix packs it)
+    y0 = (ti >> 16) & 7; y1 = (ti >> 19) & 7; x0 = (ti >> 22) & 7; x1 = (ti >> 25) & 7;
+}
 constexpr int BP_THREADS = 256, BP_MAXT = 2048; // k_bin_prefix: threads, tiles of the whole-K launch it can order by cost (more: layout order)
 __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__ cnt, int32_t* __restrict__ bin_start, int32_t* __restrict__ tile_info,
                                                            uint2* __restrict__ slot_desc, const int32_t* __restrict__ singles, int n_cu, int max_fways,
@@ -1021,7 +1024,7 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
         }
         for (int y = ylo; y <= yhi; ++y)
             for (int x = xlo; x <= xhi; ++x) { p0o[y * bn + x] = c; c += p0c[y * bn + x]; } // (offset of the P0's rows inside the bin: row-major P0 order)
-    } else if (tid == SIB_BINS) c = cnt[1];
+    } else if (tid == SIB_BINS) c = cnt[NET_GCNT_SINGLES];
     if (tid <= SIB_BINS) { bcnt[tid] = c; binc[tid] = (c + GT_BS - 1) / GT_BS; order[tid] = sib_bin_at(tid, bn); } // (tiles per bin and the layout order in parallel:
     __syncthreads();                                                                                                     //  the serial part below only adds)
     if (tid < 64) { // wave 0: exclusive scan of the bins' tile counts in layout order (82 positions = two passes of 64 lanes), then the split point
@@ -1059,8 +1062,8 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
         if (ntiles > t_split && ways > part_w_rows / ((ntiles - t_split) * GT_BS)) ways = part_w_rows / ((ntiles - t_split) * GT_BS); // (partials slab)
         while (ways > 1 && (ways - 1) * ((2 * SIB_WPX + ways - 1) / ways) >= 2 * SIB_WPX) --ways; // (no empty split of the 98 super-steps)
         if (ways < 2) { ways = 1; t_split = ntiles; }
-        cnt[3] = cnt[96] + cnt[1]; // positions evaluated in full this round: runs without a cached base, then the single rows
-        const int ftiles = (cnt[3] + GT_BS - 1) / GT_BS;          // fc0 of the full rows: K split so that one round of workgroups covers it;
+        cnt[NET_GCNT_FULL_ROWS] = cnt[NET_GCNT_FULL_EVALS] + cnt[NET_GCNT_SINGLES]; // positions evaluated in full this round: runs without a cached base, then the single rows
+        const int ftiles = (cnt[NET_GCNT_FULL_ROWS] + GT_BS - 1) / GT_BS; // fc0 of the full rows: K split so that one round of workgroups covers it;
         int fways = ftiles > 0 ? n_cu / ftiles : 1;              // partials [split][row < ftiles * 128]: as many ways as the slab holds
         const int fcap = (ftiles > 0 ? ftiles : 1) * GT_BS;
         if (fways > part_f_rows / fcap) fways = part_f_rows / fcap;
@@ -1068,11 +1071,11 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
         // no empty split: with ceil(nsup / ways) super-steps each, the last of `ways` splits must still start inside K (N = 9: 162 super-steps
         // in 30 ways of 6 would leave splits 27..29 empty -- their workgroups would stream weights from beyond the matrix)
         while (fways > 1 && (fways - 1) * ((nsup_full + fways - 1) / fways) >= nsup_full) --fways;
-        cnt[98] = fways;
-        cnt[99] = fcap;
-        cnt[4] = ntiles;
-        cnt[5] = t_split;
-        cnt[6] = ways;
+        cnt[NET_GCNT_FULL_WAYS] = fways;
+        cnt[NET_GCNT_FULL_STRIDE] = fcap;
+        cnt[NET_GCNT_WIN_TILES] = ntiles;
+        cnt[NET_GCNT_SPLIT_TILE0] = t_split;
+        cnt[NET_GCNT_WIN_WAYS] = ways;
         s_split = t_split;
         s_ntiles = ntiles;
       }
@@ -1080,7 +1083,7 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
     __syncthreads();
     constexpr int FULL_RECT = (0 << 16) | ((SIB_WIN - 1) << 19) | (0 << 22) | ((SIB_WIN - 1) << 25);
     if (tid < SIB_BINS) {
-        cnt[8 + tid] = c; // (the bin's total: diagnostics)
+        cnt[NET_GCNT_BINS + tid] = c; // (the bin's total: diagnostics)
         const int off = tile0[tid] * GT_BS;
         for (int y = ylo; y <= yhi; ++y)
             for (int x = xlo; x <= xhi; ++x) bin_start[y * bn + x] = off + p0o[y * bn + x]; // first slot of the P0's rows
@@ -1124,7 +1127,7 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
     if (tid == 0) {
         atomicAdd(&work[NET_WORK_WIN_PIXELS], (unsigned long long)s_area);
         atomicAdd(&work[NET_WORK_WIN_TILES], (unsigned long long)(ntiles - binc[SIB_BINS]));
-        atomicAdd(&work[NET_WORK_FULL_TILES], (unsigned long long)((cnt[3] + GT_BS - 1) / GT_BS));
+        atomicAdd(&work[NET_WORK_FULL_TILES], (unsigned long long)((cnt[NET_GCNT_FULL_ROWS] + GT_BS - 1) / GT_BS));
     }
     // Order of the whole-K launch (tiles below t_split).  With rectangles a tile costs 16 .. 49 window pixels, and a launch of two rounds of workgroups takes as long as
     // its slowest CU's two tiles: in layout order the CUs of the interior bins ran two full-price tiles and the 18 % of skipped work bought nothing.  The tiles are
@@ -1135,7 +1138,7 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
         int* tile_order = tile_info + tile_cap;
         __syncthreads();
         const int n = t_split <= BP_MAXT ? t_split : 0;
-        if (tid == 0) cnt[7] = tile_cap;
+        if (tid == 0) cnt[NET_GCNT_TILE_ORDER] = tile_cap;
         if (tid < 64) {
             // first position of every cost bucket, dearest first: lane a keeps bucket a's running start in a register
             const int hv = hist[63 - tid];
@@ -1164,7 +1167,7 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
         }
         for (int T = n + tid; T < t_split; T += blockDim.x) tile_order[T] = T; // (n = 0: more tiles than the table holds)
     }
-    const int nsing = cnt[1], s0 = tile0[SIB_BINS] * GT_BS;
+    const int nsing = cnt[NET_GCNT_SINGLES], s0 = tile0[SIB_BINS] * GT_BS;
     for (int i = tid; i < nsing; i += blockDim.x) slot_desc[s0 + i] = make_uint2((uint32_t)singles[i], (uint32_t)(facc_single_base + i)); // (fp32 fc0 row index)
 }
 
@@ -1173,7 +1176,7 @@ __global__ __launch_bounds__(256) void k_win_finish(const float* __restrict__ pa
                                                     const int32_t* __restrict__ tile_info, const uint2* __restrict__ slot_desc,
                                                     const float* __restrict__ facc, const float* __restrict__ bias, uint4* __restrict__ out_split,
                                                     size_t out_row_u4) {
-    const int nt = cnt[4], t0 = cnt[5], ways = cnt[6];
+    const int nt = cnt[NET_GCNT_WIN_TILES], t0 = cnt[NET_GCNT_SPLIT_TILE0], ways = cnt[NET_GCNT_WIN_WAYS];
     if (ways < 2) return;
     cap_rows = (size_t)(nt - t0) * GT_BS; // the split set's slots, densely
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; // (local slot, mt 16, s 2, h 2)
@@ -1210,7 +1213,7 @@ __global__ __launch_bounds__(256) void k_facc_reduce(const float* __restrict__ p
                                                      float* __restrict__ facc, const uint2* __restrict__ comp, const int32_t* __restrict__ d_nmiss, int facc_single_base) {
     const size_t total = (size_t)d_nrows[0] * (NF / 4);
     const int nsplit = d_nsplit[0], nmiss = d_nmiss[0];
-    cap_rows = (size_t)d_nsplit[1];
+    cap_rows = (size_t)d_nsplit[NET_GCNT_FULL_STRIDE - NET_GCNT_FULL_WAYS]; // (d_nsplit = d_gcnt + NET_GCNT_FULL_WAYS)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         f32x4 a = *(const f32x4*)(part + i * 4);
         for (int sp = 1; sp < nsplit; ++sp) {
@@ -1273,7 +1276,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
     };
     auto lds_barrier = [&]() { bar_post(); bar_wait(); };
     for (int i = 0; i < (wv >> 1); ++i) __builtin_amdgcn_s_sleep(118); // (64 clocks per unit: a quarter of a ~30 k-cycle pass per pair index)
-    const int nsib = d_cnt[2];
+    const int nsib = d_cnt[NET_GCNT_ROWS_IN_RUNS];
     const half8* convW = (const half8*)(wt + TR_WBYTES / 16);
     // conv_in fragments: 32 registers that are only needed at the top of a pass.  They are fetched again at the END of every pass (from
     // L2, under the stores) instead of living through the blocks, where they pushed lane-constant addresses into scratch whose
@@ -1805,13 +1808,13 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     // and the others finish alone; handed out on demand, all eight end together.  A child's arithmetic does not depend on the wave that takes it: same bits.
     __shared__ int s_next_entry;
     if (tid == 0) {
-        const int nsib0 = d_cnt[2], per0 = (nsib0 + (int)gridDim.x - 1) / (int)gridDim.x;
+        const int nsib0 = d_cnt[NET_GCNT_ROWS_IN_RUNS], per0 = (nsib0 + (int)gridDim.x - 1) / (int)gridDim.x;
         const int wb0 = (int)blockIdx.x * per0 < nsib0 ? (int)blockIdx.x * per0 : nsib0;
         s_next_entry = wb0 + 16; // (entries wb0 .. wb0 + 15: the waves' first two passes)
     }
     __syncthreads(); // (the only workgroup barrier: from here on a wave touches read-only LDS and its own cells)
     for (int i = 0; i < (wv >> 2); ++i) __builtin_amdgcn_s_sleep(120); // the two waves of a SIMD (w, w + 4) start about half a pass apart
-    const int nsib = d_cnt[2];
+    const int nsib = d_cnt[NET_GCNT_ROWS_IN_RUNS];
     const half8* convW = (const half8*)(wt + TR_WBYTES / 16);
     half8 cwh[4], cwl[4]; // conv_in fragments: fetched again at the end of every pass (see k_sib_children)
     auto load_conv_w = [&]() {
@@ -2521,8 +2524,160 @@ __device__ inline bool xcd_item(int total, int& item) {
     return j < per_xcd && item < total;
 }
 constexpr bool STAGGER = false; // (skewing the waves by s_nops after the barrier: 3.52 -> 3.88 ms, the delay costs more than it saves)
+// ---- fc0: which tile and which part of K a workgroup owns, and what it does with its accumulators (k_fc0_mx and k_fc0_x3 share both) ----
+struct Fc0Tile {
+    int b0, count;                 // first sample (WIN: slot) of the tile; samples at or beyond `count` are not stored
+    int ubeg, ksup;                // first super-step and number of super-steps of this workgroup's part of K
+    int split_y, part_row0;        // EPI_PARTIAL: K split index; WIN: first slot of the K-split set (partials are indexed by the slot inside it)
+    size_t out_row_u4;             // EPI_SPLIT: output row stride; EPI_PARTIAL: rows of the partial slab per split
+    int win_oy, win_ox;            // WIN: origin of the bin's 7x7 window on the board
+    int wr_y0, wr_x0, wr_w, wr_n, wr_inv; // WIN: the tile's rectangle of window pixels (k_bin_prefix): origin, width, super-steps (2 per pixel), 65536 / width + 1
+    // WIN: super-step j of the tile's rectangle -> super-step u = 2 w + q of the 7x7 window (steps past the end -- prefetches -- re-read the last)
+    __device__ __forceinline__ int win_u(int j) const {
+        j = j < wr_n ? j : wr_n - 1;
+        j = j < 0 ? 0 : j;
+        const int wl = j >> 1, ry = (wl * wr_inv) >> 16, rx = wl - ry * wr_w;
+        return 2 * ((wr_y0 + ry) * SIB_WIN + wr_x0 + rx) + (j & 1);
+    }
+};
+// The arguments are the kernels' (ksup: the host's super-steps per workgroup, out_row_u4: its row stride).  false: the workgroup has no work.
+template <int EPI, bool WIN>
+__device__ __forceinline__ bool fc0_map_tile(Fc0Tile& t, int ksup, size_t out_row_u4, int full_tiles, int last_cnt, const int32_t* __restrict__ d_count,
+                                             int max_count, const int32_t* __restrict__ tile_info) {
+    t.b0 = blockIdx.x * GT_BS;
+    t.ubeg = 0; t.part_row0 = 0; t.split_y = (int)blockIdx.y;
+    t.win_oy = 0; t.win_ox = 0;
+    t.wr_y0 = 0; t.wr_x0 = 0; t.wr_w = SIB_WIN; t.wr_n = 2 * SIB_WPX; t.wr_inv = 65536 / SIB_WIN + 1;
+    if (WIN) { // d_count = Net::d_gcnt.  EPI_SPLIT: the tiles below the K-split set, whole K; EPI_PARTIAL: the tiles from NET_GCNT_SPLIT_TILE0 on, K split NET_GCNT_WIN_WAYS ways
+        // Workgroups go to the 8 XCDs round-robin and every XCD has its own L2: XCD x takes a contiguous eighth of the tiles (tiles are
+        // ordered by bin = by weight slice), so the workgroups that share an L2 stream the same 9 MB of weights in step instead of
+        // every L2 streaming every slice (dealt round-robin, 46 % of the weight reads missed L2: 2.5 GB per launch, HBM-bound).
+        const int nt = d_count[NET_GCNT_WIN_TILES], t_split = d_count[NET_GCNT_SPLIT_TILE0];
+        const int n_here = EPI == EPI_PARTIAL ? nt - t_split : t_split;
+        int tile, ways = 1;
+        if (EPI == EPI_PARTIAL) { // 1-D grid over (tile of the split set, split): tiles x ways <= CUs (a 2-D grid of mostly idle, LDS-heavy workgroups
+                                  // costs more to dispatch than the work takes); XCD x takes consecutive tiles, each with all its splits
+            ways = d_count[NET_GCNT_WIN_WAYS];
+            int item;
+            if (n_here <= 0 || !xcd_item(n_here * ways, item)) return false;
+            t.split_y = item % ways;
+            tile = t_split + item / ways;
+            t.part_row0 = t_split * GT_BS;
+            out_row_u4 = (size_t)n_here * GT_BS; // partials: [split][slot inside the split set]
+        } else { // position p of the cost-sorted order (k_bin_prefix), dealt in rounds of 8 x 32 workgroups: XCD x = blockIdx & 7 takes chunk x of an even round and chunk
+                 // 7 - x of an odd one (the XCD with the dearest tiles of round 1 gets the cheapest of round 2)
+            const int per_x = (int)gridDim.x >> 3, cu_x = per_x < 32 ? per_x : 32, j = (int)blockIdx.x >> 3, r = j / cu_x; // (32 CUs per XCD)
+            const int xc = (int)blockIdx.x & 7, p = r * (8 * cu_x) + ((r & 1) ? 7 - xc : xc) * cu_x + j % cu_x;
+            if (p >= n_here) return false;
+            tile = tile_info[d_count[NET_GCNT_TILE_ORDER] + p];
+        }
+        t.b0 = tile * GT_BS;
+        const int ti = tile_info[tile], bin = ti & 0xFF;
+        t.count = t.b0 + ((ti >> 8) & 0xFF);
+        // the tile's rectangle of window pixels (k_bin_prefix): rows wr_y0 .. y1, columns wr_x0 .. x1 of the 7x7 window; super-step j of the tile = pixel j / 2 of the rectangle in
+        // row-major order, channel half j & 1
+        int wr_y1, wr_x1;
+        tile_rect(ti, t.wr_y0, wr_y1, t.wr_x0, wr_x1);
+        t.wr_w = wr_x1 - t.wr_x0 + 1;
+        t.wr_n = 2 * (wr_y1 - t.wr_y0 + 1) * t.wr_w;
+        t.wr_inv = 65536 / t.wr_w + 1; // (j / 2) / wr_w = ((j / 2) * wr_inv) >> 16 for j / 2 < 49
+        const int nsup = bin < SIB_BINS ? t.wr_n : 0, per = (nsup + ways - 1) / ways;
+        t.ubeg = t.split_y * per;
+        ksup = nsup - t.ubeg < per ? nsup - t.ubeg : per;
+        t.win_oy = bin < SIB_BINS ? bin / SIB_ORG : 0; // (the single rows' bin has no window: its tiles run no super-step, and their prologue's prefetches
+        t.win_ox = bin < SIB_BINS ? bin % SIB_ORG : 0; //  must stay inside the matrix)
+    } else {
+        const int nsup = full_tiles * 64 + 2 * last_cnt;
+        t.count = d_count[0];
+        if (t.count > max_count) t.count = max_count;
+        if (EPI == EPI_PARTIAL && tile_info) { // full rows of the difference path (d_count = d_gcnt + NET_GCNT_FULL_ROWS, tile_info = d_gcnt + NET_GCNT_FULL_WAYS): the number
+            // of K splits and the partial slab's row stride were chosen on the device (k_bin_prefix); uneven split.
+            // 1-D grid over (split, tile) items dealt by xcd_item -- a (tiles_max x ways_max) grid of which a few dozen workgroups have work
+            // costs more to dispatch (~65-100 workgroups per us) than the work takes
+            const int ways = tile_info[0], per = (nsup + ways - 1) / ways;
+            const int tiles = (t.count + GT_BS - 1) / GT_BS;
+            int item;
+            if (tiles == 0 || !xcd_item(tiles * ways, item)) return false;
+            t.split_y = item / tiles;
+            t.b0 = (item % tiles) * GT_BS;
+            out_row_u4 = (size_t)tile_info[NET_GCNT_FULL_STRIDE - NET_GCNT_FULL_WAYS];
+            t.ubeg = t.split_y * per;
+            ksup = nsup - t.ubeg < per ? nsup - t.ubeg : per;
+        } else {
+            if (EPI == EPI_PARTIAL) { // K split chosen on the host: 1-D grid over (split, tile) items, `ksup` super-steps per split, out_row_u4 = tiles x 128 rows of partials per split
+                const int tiles = (int)(out_row_u4 / GT_BS), ways = (nsup + ksup - 1) / ksup;
+                int item;
+                if (!xcd_item(tiles * ways, item)) return false;
+                t.split_y = item / tiles;
+                t.b0 = (item % tiles) * GT_BS;
+                t.ubeg = t.split_y * ksup; // (uneven split: the last split takes what is left; the host never makes it empty)
+                ksup = nsup - t.ubeg < ksup ? nsup - t.ubeg : ksup;
+            }
+            if (t.b0 >= t.count) return false;
+        }
+        // an empty split (never chosen on purpose) contributes zeros and must not stream from beyond the matrix
+        if (EPI == EPI_PARTIAL && t.ubeg >= nsup) { t.ubeg = nsup - 1; ksup = 0; }
+    }
+    t.ksup = ksup < 0 ? 0 : ksup; // (a split that starts behind the end of K)
+    t.out_row_u4 = out_row_u4;
+    return true;
+}
+// accumulator g of a wave = m-tile 4g + wave of the tile's 128 samples.  EPI_PARTIAL: fp32 partials into the slab; EPI_SPLIT: bias, LeakyReLU, hi|lo operand row
+// (WIN: of the slot's request row, with the fp32 fc0 row of the slot's full row added first: slot_desc = (request row, full row))
+template <int EPI, bool WIN>
+__device__ __forceinline__ void fc0_epilogue(const f32x16 (&acc)[4][4], const Fc0Tile& t, int wave, int lane, const float* __restrict__ bias,
+                                             uint4* __restrict__ out_split, float* __restrict__ out_part, const uint2* __restrict__ slot_desc,
+                                             const float* __restrict__ facc) {
+    const int h = lane >> 5;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        int sample = t.b0 + 32 * c + (lane & 31);
+        if (sample >= t.count) continue;
+        const float* fa = nullptr;
+        if (WIN && EPI == EPI_PARTIAL) sample -= t.part_row0; // partials are indexed by the slot inside the split set
+        if (WIN && EPI != EPI_PARTIAL) { // slot -> (request row, full row)
+            const uint2 dsc = slot_desc[sample];
+            sample = (int)dsc.x;
+            fa = facc + (size_t)dsc.y * NF;
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int mt = 4 * g + wave;
+            if (EPI == EPI_PARTIAL) {
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    f32x4 o;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) o[q] = acc[g][c][4 * q4 + q];
+                    *(f32x4*)(out_part + ((size_t)t.split_y * t.out_row_u4 + sample) * NF + 32 * mt + 8 * q4 + 4 * h) = o;
+                }
+            } else {
+                float y[16];
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const f32x4 bv = *(const f32x4*)(bias + 32 * mt + 8 * q4 + 4 * h);
+                    f32x4 fv = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if (WIN) fv = *(const f32x4*)(fa + 32 * mt + 8 * q4 + 4 * h);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) y[4 * q4 + q] = WIN ? (acc[g][c][4 * q4 + q] + fv[q]) + bv[q] : acc[g][c][4 * q4 + q] + bv[q];
+                }
+#pragma unroll
+                for (int sx = 0; sx < 2; ++sx) {
+                    float v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = lrelu(y[8 * sx + j]);
+                    half8 hi, lo;
+                    split8(v, hi, lo);
+                    uint4* row = out_split + (size_t)sample * t.out_row_u4 + (size_t)(2 * mt + sx) * 4;
+                    row[h] = *(const uint4*)&hi;
+                    row[2 + h] = *(const uint4*)&lo;
+                }
+            }
+        }
+    }
+}
 // WIN (difference path of the sibling rounds, N = 15): workgroup = one tile of 128 SLOTS whose rows share a 7x7 window (tile_info: bin |
-// live slots << 8; d_count = the path's counters, [4] = tiles).  `act` holds the slots' difference rows (SIB_DROW_U4: 98 super-steps =
+// live slots << 8; d_count = the path's counters, Net::d_gcnt).  `act` holds the slots' difference rows (SIB_DROW_U4: 98 super-steps =
 // 49 window pixels x 2 channel halves), the weight stages of super-step (w, q) are those of the window pixel's board pixel, and the
 // epilogue adds the fp32 fc0 row of the slot's FULL row (facc: the run's base position; slot_desc = (request row, full row)).  Tiles
 // of the single rows (bin SIB_BINS) have no super-steps at all.
@@ -2539,93 +2694,16 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     __shared__ uint4 ldsA[2 * MXS_U4];        // [2]{ f16 [128 samples][8 pieces] | fp8 [128 samples][4 pieces] }
     __shared__ uint4 ldsW0[MXS_U4], ldsW1[MXS_U4], ldsW2[MXS_U4], ldsW3[MXS_U4]; // [4 i][6 frag][64] each
     auto ring = [&](int slot) -> uint4* { return slot == 0 ? ldsW0 : slot == 1 ? ldsW1 : slot == 2 ? ldsW2 : ldsW3; };
-    int b0 = blockIdx.x * GT_BS;
-    int count, win_oy = 0, win_ox = 0, ubeg = 0, part_row0 = 0, split_y = (int)blockIdx.y;
-    int wr_y0 = 0, wr_x0 = 0, wr_w = SIB_WIN, wr_n = 2 * SIB_WPX, wr_inv = 65536 / SIB_WIN + 1;
-    auto win_u = [&](int j) { // WIN: super-step j of the tile's rectangle -> super-step u = 2 w + q of the 7x7 window (steps past the end -- prefetches -- re-read the last)
-        j = j < wr_n ? j : wr_n - 1;
-        j = j < 0 ? 0 : j;
-        const int wl = j >> 1, ry = (wl * wr_inv) >> 16, rx = wl - ry * wr_w;
-        return 2 * ((wr_y0 + ry) * SIB_WIN + wr_x0 + rx) + (j & 1);
-    };
-    if (WIN) { // EPI_SPLIT: the tiles below the K-split set, whole K; EPI_PARTIAL: tile d_count[5] + blockIdx.x, K split d_count[6] ways over blockIdx.y
-        // Workgroups go to the 8 XCDs round-robin and every XCD has its own L2: XCD x takes a contiguous eighth of the tiles (tiles are
-        // ordered by bin = by weight slice), so the workgroups that share an L2 stream the same 9 MB of weights in step instead of
-        // every L2 streaming every slice (dealt round-robin, 46 % of the weight reads missed L2: 2.5 GB per launch, HBM-bound).
-        const int nt = d_count[4], t_split = d_count[5];
-        const int n_here = EPI == EPI_PARTIAL ? nt - t_split : t_split, eighth = (n_here + 7) >> 3;
-        int tile, ways = 1;
-        if (EPI == EPI_PARTIAL) { // 1-D grid over (tile of the split set, split): tiles x ways <= CUs (a 2-D grid of mostly idle, LDS-heavy workgroups
-                                  // costs more to dispatch than the work takes)
-            ways = d_count[6];
-            const int total = n_here * ways, per_xcd = (total + 7) >> 3;                    // XCD x takes consecutive tiles, each with all its splits
-            const int item = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-            if (n_here <= 0 || ((int)blockIdx.x >> 3) >= per_xcd || item >= total) return;
-            split_y = item % ways;
-            tile = t_split + item / ways;
-            part_row0 = t_split * GT_BS;
-            out_row_u4 = (size_t)n_here * GT_BS; // partials: [split][slot inside the split set]
-        } else { // position p of the cost-sorted order (k_bin_prefix), dealt in rounds of 8 x 32 workgroups: XCD x = blockIdx & 7 takes chunk x of an even round and chunk
-                 // 7 - x of an odd one (the XCD with the dearest tiles of round 1 gets the cheapest of round 2)
-            (void)eighth;
-            const int per_x = (int)gridDim.x >> 3, cu_x = per_x < 32 ? per_x : 32, j = (int)blockIdx.x >> 3, r = j / cu_x; // (32 CUs per XCD)
-            const int xc = (int)blockIdx.x & 7, p = r * (8 * cu_x) + ((r & 1) ? 7 - xc : xc) * cu_x + j % cu_x;
-            if (p >= n_here) return;
-            tile = tile_info[d_count[7] + p];
-        }
-        b0 = tile * GT_BS;
-        const int ti = tile_info[tile], bin = ti & 0xFF;
-        count = b0 + ((ti >> 8) & 0xFF);
-        // the tile's rectangle of window pixels (k_bin_prefix): rows wr_y0 .. y1, columns wr_x0 .. x1 of the 7x7 window; super-step j of the tile = pixel j / 2 of the rectangle in
-        // row-major order, channel half j & 1
-        wr_y0 = (ti >> 16) & 7; wr_x0 = (ti >> 22) & 7; wr_w = ((ti >> 25) & 7) - wr_x0 + 1;
-        wr_n = 2 * (((ti >> 19) & 7) - wr_y0 + 1) * wr_w;
-        wr_inv = 65536 / wr_w + 1; // (j / 2) / wr_w = ((j / 2) * wr_inv) >> 16 for j / 2 < 49
-        const int nsup = bin < SIB_BINS ? wr_n : 0, per = (nsup + ways - 1) / ways;
-        ubeg = split_y * per;
-        ksup = nsup - ubeg < per ? nsup - ubeg : per;
-        if (ksup < 0) ksup = 0;
-        win_oy = bin < SIB_BINS ? bin / SIB_ORG : 0; // (the single rows' bin has no window: its tiles run no super-step, and their prologue's prefetches
-        win_ox = bin < SIB_BINS ? bin % SIB_ORG : 0; //  must stay inside the matrix)
-    } else {
-        count = d_count[0];
-        if (count > max_count) count = max_count;
-        if (EPI == EPI_PARTIAL && tile_info) { // the number of K splits and the partial slab's row capacity were chosen on the device (tile_info[0], [1]); uneven split.
-            // 1-D grid over (split, tile) items dealt by xcd_item -- a (tiles_max x ways_max) grid of which a few dozen workgroups have work
-            // costs more to dispatch (~65-100 workgroups per us) than the work takes
-            const int ways = tile_info[0], nsup = full_tiles * 64 + 2 * last_cnt, per = (nsup + ways - 1) / ways;
-            const int tiles = (count + GT_BS - 1) / GT_BS;
-            int item;
-            if (tiles == 0 || !xcd_item(tiles * ways, item)) return;
-            split_y = item / tiles;
-            b0 = (item % tiles) * GT_BS;
-            out_row_u4 = (size_t)tile_info[1];
-            ubeg = split_y * per;
-            ksup = nsup - ubeg < per ? nsup - ubeg : per;
-        } else {
-            if (EPI == EPI_PARTIAL) { // K split chosen on the host: 1-D grid over (split, tile) items, `ksup` super-steps per split, out_row_u4 = tiles x 128 rows of partials per split
-                const int nsup = full_tiles * 64 + 2 * last_cnt, tiles = (int)(out_row_u4 / GT_BS), ways = (nsup + ksup - 1) / ksup;
-                int item;
-                if (!xcd_item(tiles * ways, item)) return;
-                split_y = item / tiles;
-                b0 = (item % tiles) * GT_BS;
-                ubeg = split_y * ksup; // (uneven split: the last split takes what is left; the host never makes it empty)
-                ksup = nsup - ubeg < ksup ? nsup - ubeg : ksup;
-            }
-            if (b0 >= count) return;
-        }
-        if (EPI == EPI_PARTIAL) { // an empty split (never chosen on purpose) contributes zeros and must not stream from beyond the matrix
-            const int nsup = full_tiles * 64 + 2 * last_cnt;
-            if (ubeg >= nsup) { ubeg = nsup - 1; ksup = 0; }
-            if (ksup < 0) ksup = 0;
-        }
-    }
+    Fc0Tile t;
+    if (!fc0_map_tile<EPI, WIN>(t, ksup, out_row_u4, full_tiles, last_cnt, d_count, max_count, tile_info)) return;
+    const int b0 = t.b0, ubeg = t.ubeg, win_oy = t.win_oy, win_ox = t.win_ox;
+    ksup = t.ksup;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6); // 0..3 = m-tile inside a group
     const int h = lane >> 5;
 
     auto uoff = [&](int u) { // (block, pixel) of super-step u inside a sample row, packed as block * 32 + pixel
-        if (WIN) return win_u(u); // difference rows: super-step u = 2 w + q of the window
+        if (WIN) return t.win_u(u); // difference rows: super-step u = 2 w + q of the window
         const int full = full_tiles * 64;
         int tile, q, pl;
         if (u < full) { tile = u >> 6; q = (u >> 5) & 1; pl = u & 31; }
@@ -2635,7 +2713,7 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     // absolute super-step (= weight stage group) of this workgroup's local super-step ul
     auto ustep = [&](int ul) {
         if (!WIN) return ubeg + ul;
-        const int u = win_u(ubeg + ul);
+        const int u = t.win_u(ubeg + ul);
         const int w = u >> 1, qq = u & 1, wy = w / SIB_WIN, wx = w - wy * SIB_WIN;
         const int px = (win_oy + wy) * bn + win_ox + wx;
         return px < full_tiles * 32 ? (px >> 5) * 64 + qq * 32 + (px & 31) : full_tiles * 64 + qq * last_cnt + (px - full_tiles * 32);
@@ -2863,53 +2941,7 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 0");
 
-    // ---- epilogue (accumulator g = m-tile 4g + wave) ----
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        int sample = b0 + 32 * c + (lane & 31);
-        if (sample >= count) continue;
-        const float* fa = nullptr;
-        if (WIN && EPI == EPI_PARTIAL) sample -= part_row0; // partials are indexed by the slot inside the split set
-        if (WIN && EPI != EPI_PARTIAL) { // slot -> (request row, full row)
-            const uint2 dsc = slot_desc[sample];
-            sample = (int)dsc.x;
-            fa = facc + (size_t)dsc.y * NF;
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int mt = 4 * g + wave;
-            if (EPI == EPI_PARTIAL) {
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    f32x4 o;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o[q] = acc[g][c][4 * q4 + q];
-                    *(f32x4*)(out_part + ((size_t)split_y * out_row_u4 + sample) * NF + 32 * mt + 8 * q4 + 4 * h) = o;
-                }
-            } else {
-                float y[16];
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const f32x4 bv = *(const f32x4*)(bias + 32 * mt + 8 * q4 + 4 * h);
-                    f32x4 fv = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (WIN) fv = *(const f32x4*)(fa + 32 * mt + 8 * q4 + 4 * h);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) y[4 * q4 + q] = WIN ? (acc[g][c][4 * q4 + q] + fv[q]) + bv[q] : acc[g][c][4 * q4 + q] + bv[q];
-                }
-#pragma unroll
-                for (int sx = 0; sx < 2; ++sx) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = lrelu(y[8 * sx + j]);
-                    half8 hi, lo;
-                    split8(v, hi, lo);
-                    uint4* row = out_split + (size_t)sample * out_row_u4 + (size_t)(2 * mt + sx) * 4;
-                    row[h] = *(const uint4*)&hi;
-                    row[2 + h] = *(const uint4*)&lo;
-                }
-            }
-        }
-    }
+    fc0_epilogue<EPI, WIN>(acc, t, wave, lane, bias, out_split, out_part, slot_desc, facc);
 }
 
 // ===============================================================================================
@@ -2934,82 +2966,11 @@ __global__ __launch_bounds__(256) void k_fc0_x3(const uint4* __restrict__ wp, co
     __shared__ uint4 ldsA[2 * X3_U4];         // [2]{ hi [128 samples][4 pieces] | lo [128 samples][4 pieces] }
     __shared__ uint4 ldsW0[X3_U4], ldsW1[X3_U4], ldsW2[X3_U4], ldsW3[X3_U4]; // one object per ring slot (see k_fc0_mx)
     auto ring = [&](int slot) -> uint4* { return slot == 0 ? ldsW0 : slot == 1 ? ldsW1 : slot == 2 ? ldsW2 : ldsW3; };
-    // ---- which tile, which part of K: exactly k_fc0_mx's mapping ----
-    int b0 = blockIdx.x * GT_BS;
-    int count, win_oy = 0, win_ox = 0, ubeg = 0, part_row0 = 0, split_y = (int)blockIdx.y;
-    int wr_y0 = 0, wr_x0 = 0, wr_w = SIB_WIN, wr_n = 2 * SIB_WPX, wr_inv = 65536 / SIB_WIN + 1;
-    auto win_u = [&](int j) { // WIN: super-step j of the tile's rectangle -> super-step u = 2 w + q of the 7x7 window (steps past the end -- prefetches -- re-read the last)
-        j = j < wr_n ? j : wr_n - 1;
-        j = j < 0 ? 0 : j;
-        const int wl = j >> 1, ry = (wl * wr_inv) >> 16, rx = wl - ry * wr_w;
-        return 2 * ((wr_y0 + ry) * SIB_WIN + wr_x0 + rx) + (j & 1);
-    };
-    if (WIN) {
-        const int nt = d_count[4], t_split = d_count[5];
-        const int n_here = EPI == EPI_PARTIAL ? nt - t_split : t_split, eighth = (n_here + 7) >> 3;
-        int tile, ways = 1;
-        if (EPI == EPI_PARTIAL) {
-            ways = d_count[6];
-            const int total = n_here * ways, per_xcd = (total + 7) >> 3;
-            const int item = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-            if (n_here <= 0 || ((int)blockIdx.x >> 3) >= per_xcd || item >= total) return;
-            split_y = item % ways;
-            tile = t_split + item / ways;
-            part_row0 = t_split * GT_BS;
-            out_row_u4 = (size_t)n_here * GT_BS;
-        } else { // position p of the cost-sorted order (k_bin_prefix), dealt in rounds of 8 x 32 workgroups: XCD x = blockIdx & 7 takes chunk x of an even round and chunk
-                 // 7 - x of an odd one (the XCD with the dearest tiles of round 1 gets the cheapest of round 2)
-            (void)eighth;
-            const int per_x = (int)gridDim.x >> 3, cu_x = per_x < 32 ? per_x : 32, j = (int)blockIdx.x >> 3, r = j / cu_x; // (32 CUs per XCD)
-            const int xc = (int)blockIdx.x & 7, p = r * (8 * cu_x) + ((r & 1) ? 7 - xc : xc) * cu_x + j % cu_x;
-            if (p >= n_here) return;
-            tile = tile_info[d_count[7] + p];
-        }
-        b0 = tile * GT_BS;
-        const int ti = tile_info[tile], bin = ti & 0xFF;
-        count = b0 + ((ti >> 8) & 0xFF);
-        // the tile's rectangle of window pixels (k_bin_prefix): rows wr_y0 .. y1, columns wr_x0 .. x1 of the 7x7 window; super-step j of the tile = pixel j / 2 of the rectangle in
-        // row-major order, channel half j & 1
-        wr_y0 = (ti >> 16) & 7; wr_x0 = (ti >> 22) & 7; wr_w = ((ti >> 25) & 7) - wr_x0 + 1;
-        wr_n = 2 * (((ti >> 19) & 7) - wr_y0 + 1) * wr_w;
-        wr_inv = 65536 / wr_w + 1; // (j / 2) / wr_w = ((j / 2) * wr_inv) >> 16 for j / 2 < 49
-        const int nsup = bin < SIB_BINS ? wr_n : 0, per = (nsup + ways - 1) / ways;
-        ubeg = split_y * per;
-        ksup = nsup - ubeg < per ? nsup - ubeg : per;
-        if (ksup < 0) ksup = 0;
-        win_oy = bin < SIB_BINS ? bin / SIB_ORG : 0; // (the single rows' bin has no window: its tiles run no super-step, and their prologue's prefetches
-        win_ox = bin < SIB_BINS ? bin % SIB_ORG : 0; //  must stay inside the matrix)
-    } else {
-        count = d_count[0];
-        if (count > max_count) count = max_count;
-        if (EPI == EPI_PARTIAL && tile_info) {
-            const int ways = tile_info[0], nsup = full_tiles * 64 + 2 * last_cnt, per = (nsup + ways - 1) / ways;
-            const int tiles = (count + GT_BS - 1) / GT_BS;
-            int item;
-            if (tiles == 0 || !xcd_item(tiles * ways, item)) return;
-            split_y = item / tiles;
-            b0 = (item % tiles) * GT_BS;
-            out_row_u4 = (size_t)tile_info[1];
-            ubeg = split_y * per;
-            ksup = nsup - ubeg < per ? nsup - ubeg : per;
-        } else {
-            if (EPI == EPI_PARTIAL) { // K split chosen on the host: 1-D grid over (split, tile) items, `ksup` super-steps per split, out_row_u4 = tiles x 128 rows of partials per split
-                const int nsup = full_tiles * 64 + 2 * last_cnt, tiles = (int)(out_row_u4 / GT_BS), ways = (nsup + ksup - 1) / ksup;
-                int item;
-                if (!xcd_item(tiles * ways, item)) return;
-                split_y = item / tiles;
-                b0 = (item % tiles) * GT_BS;
-                ubeg = split_y * ksup; // (uneven split: the last split takes what is left; the host never makes it empty)
-                ksup = nsup - ubeg < ksup ? nsup - ubeg : ksup;
-            }
-            if (b0 >= count) return;
-        }
-        if (EPI == EPI_PARTIAL) { // an empty split contributes zeros and must not stream from beyond the matrix
-            const int nsup = full_tiles * 64 + 2 * last_cnt;
-            if (ubeg >= nsup) { ubeg = nsup - 1; ksup = 0; }
-        }
-        if (ksup < 0) ksup = 0;
-    }
+    // (which tile, which part of K: fc0_map_tile)
+    Fc0Tile t;
+    if (!fc0_map_tile<EPI, WIN>(t, ksup, out_row_u4, full_tiles, last_cnt, d_count, max_count, tile_info)) return;
+    const int b0 = t.b0, ubeg = t.ubeg, win_oy = t.win_oy, win_ox = t.win_ox;
+    ksup = t.ksup;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5;
@@ -3023,7 +2984,7 @@ __global__ __launch_bounds__(256) void k_fc0_x3(const uint4* __restrict__ wp, co
         vl = vl < 0 ? 0 : vl;
         const int u = ubeg + (vl >> 1), mm = vl & 1;
         if (WIN) {
-            const int uc = win_u(u);
+            const int uc = t.win_u(u);
             return ((uc & 1) * SIB_WPX + (uc >> 1)) * 8 + 4 * mm; // difference row: [q][w] parts, super-step u = 2 w + q
         }
         const int full = full_tiles * 64;
@@ -3039,7 +3000,7 @@ __global__ __launch_bounds__(256) void k_fc0_x3(const uint4* __restrict__ wp, co
         int us;
         if (!WIN) us = ubeg + ul;
         else {
-            const int u = win_u(ubeg + ul);
+            const int u = t.win_u(ubeg + ul);
             const int w = u >> 1, qq = u & 1, wy = w / SIB_WIN, wx = w - wy * SIB_WIN;
             const int px = (win_oy + wy) * bn + win_ox + wx;
             us = px < full_tiles * 32 ? (px >> 5) * 64 + qq * 32 + (px & 31) : full_tiles * 64 + qq * last_cnt + (px - full_tiles * 32);
@@ -3165,53 +3126,7 @@ __global__ __launch_bounds__(256) void k_fc0_x3(const uint4* __restrict__ wp, co
 #undef GAP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    // ---- epilogue (accumulator g = m-tile 4g + wave): k_fc0_mx's ----
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        int sample = b0 + 32 * c + (lane & 31);
-        if (sample >= count) continue;
-        const float* fa = nullptr;
-        if (WIN && EPI == EPI_PARTIAL) sample -= part_row0;
-        if (WIN && EPI != EPI_PARTIAL) {
-            const uint2 dsc = slot_desc[sample];
-            sample = (int)dsc.x;
-            fa = facc + (size_t)dsc.y * NF;
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int mt = 4 * g + wave;
-            if (EPI == EPI_PARTIAL) {
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    f32x4 o;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o[q] = acc[g][c][4 * q4 + q];
-                    *(f32x4*)(out_part + ((size_t)split_y * out_row_u4 + sample) * NF + 32 * mt + 8 * q4 + 4 * h) = o;
-                }
-            } else {
-                float y[16];
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const f32x4 bv = *(const f32x4*)(bias + 32 * mt + 8 * q4 + 4 * h);
-                    f32x4 fv = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (WIN) fv = *(const f32x4*)(fa + 32 * mt + 8 * q4 + 4 * h);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) y[4 * q4 + q] = WIN ? (acc[g][c][4 * q4 + q] + fv[q]) + bv[q] : acc[g][c][4 * q4 + q] + bv[q];
-                }
-#pragma unroll
-                for (int sx = 0; sx < 2; ++sx) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = lrelu(y[8 * sx + j]);
-                    half8 hi, lo;
-                    split8(v, hi, lo);
-                    uint4* row = out_split + (size_t)sample * out_row_u4 + (size_t)(2 * mt + sx) * 4;
-                    row[h] = *(const uint4*)&hi;
-                    row[2 + h] = *(const uint4*)&lo;
-                }
-            }
-        }
-    }
+    fc0_epilogue<EPI, WIN>(acc, t, wave, lane, bias, out_split, out_part, slot_desc, facc);
 }
 
 // ===============================================================================================
@@ -3764,15 +3679,11 @@ size_t net_alloc(Net& net) {
             ok = ok && A((void**)&net.d_tags, sizeof(int32_t) * (size_t)SIB_WAYS * (size_t)(net.games > 0 ? net.games : 1));
             ok = ok && A(&net.d_comp, sizeof(uint2) * (mb / SIB_MIN + 1));
             hipDeviceProp_t prop;
-            net.n_cu = (hipGetDeviceProperties(&prop, net.device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+            net.n_cu = (hipGetDeviceProperties(&prop, net.device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256; // (the one query: every planner reads net.n_cu)
             net.part_w_rows = std::min<size_t>((size_t)net.n_cu * GT_BS, net.d_slots); // K-split window tiles: at most one round of workgroups, 7 ways
             ok = ok && A((void**)&net.part_w, sizeof(float) * net.part_w_rows * 7 * NF);
         }
         net.part_rows = mb * 8 > 32768 ? mb * 8 : 32768;                                // split-K partials: rows x split ways (2 KiB each)
-        {
-            hipDeviceProp_t prop;
-            net.n_cu_all = (hipGetDeviceProperties(&prop, net.device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        }
         ok = ok && A((void**)&net.part, sizeof(float) * net.part_rows * NF);
     }
     if (!ok) { net_free(net); return 0; }
@@ -4134,8 +4045,8 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
         // (the copy path keeps the runs' h grids in sib_h[run index]: the slots the difference path caches bases in -- cached bases are void)
         net.sib_cache_valid = false;
         // base positions of the runs, then the rows outside runs
-        if (net.n == 9) launch_trunk_fmt<9, false, true>(net, S, max_count, st, net.d_singles, net.d_gcnt, nullptr, net.d_gcnt + 1);
-        else launch_trunk_fmt<15, false, true>(net, S, max_count, st, net.d_singles, net.d_gcnt, nullptr, net.d_gcnt + 1);
+        if (net.n == 9) launch_trunk_fmt<9, false, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + NET_GCNT_RUNS, nullptr, net.d_gcnt + NET_GCNT_SINGLES);
+        else launch_trunk_fmt<15, false, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + NET_GCNT_RUNS, nullptr, net.d_gcnt + NET_GCNT_SINGLES);
         net.children_launches[1] += 1.0;
         sib_kernel(false, x16, net.n)<<<256, 512, LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_fc0, net.row_u4,
                                                              (const uint4*)net.d_sib_rows, net.d_gcnt, net.sib_h, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -4151,30 +4062,34 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
                                     (int)std::min<size_t>(net.part_rows, (size_t)1 << 30), 2 * net.hw, net.n, rects ? 1 : 0, (int)(net.d_slots / GT_BS), net.d_work);
     static const bool stats = getenv("OMOK_SIB_STATS") && atoi(getenv("OMOK_SIB_STATS")); // diagnostics only: synchronises every round
     if (stats) {
+        // per round: runs, runs evaluated in full (base-cache misses + uncacheable runs), singles, rows in runs, window tiles, first tile of the split set, its ways, full-row K split
+        static const int shown[8] = {NET_GCNT_RUNS, NET_GCNT_FULL_EVALS, NET_GCNT_SINGLES, NET_GCNT_ROWS_IN_RUNS, NET_GCNT_WIN_TILES, NET_GCNT_SPLIT_TILE0, NET_GCNT_WIN_WAYS, NET_GCNT_FULL_WAYS};
         static long long acc[8] = {}, launches = 0;
-        int32_t c[8], c2[4];
+        int32_t c[NET_GCNT_HEAD_INTS];
         hipStreamSynchronize(st);
         hipMemcpy(c, net.d_gcnt, sizeof(c), hipMemcpyDeviceToHost);
-        hipMemcpy(c2, net.d_gcnt + 96, sizeof(c2), hipMemcpyDeviceToHost);
-        c[3] = c2[0]; // (runs evaluated in full: base-cache misses + uncacheable runs)
-        c[7] = c2[2]; // (K split of the full-row fc0)
-        for (int i = 0; i < 8; ++i) acc[i] += c[i];
+        for (int i = 0; i < 8; ++i) acc[i] += c[shown[i]];
         if ((launches + 1) % 50 == 0) { // this round's window tiles: the work their rectangles leave
-            std::vector<int32_t> ti((size_t)(c[4] > 0 ? c[4] : 1));
+            const int nt = c[NET_GCNT_WIN_TILES], whole = c[NET_GCNT_SPLIT_TILE0];
+            std::vector<int32_t> ti((size_t)(nt > 0 ? nt : 1));
             hipMemcpy(ti.data(), net.d_tile_info, sizeof(int32_t) * ti.size(), hipMemcpyDeviceToHost);
             long long tot = 0;
-            for (int t = 0; t < c[5] && t < c[4]; ++t) tot += (((ti[t] >> 19) & 7) - ((ti[t] >> 16) & 7) + 1) * (((ti[t] >> 25) & 7) - ((ti[t] >> 22) & 7) + 1);
-            fprintf(stderr, "[sib stats] whole-K window tiles: %d, rectangle pixels %lld = %.3f of full 7x7 windows\n", c[5], tot, (double)tot / (49.0 * (c[5] > 0 ? c[5] : 1)));
+            for (int t = 0; t < whole && t < nt; ++t) {
+                int y0, y1, x0, x1;
+                tile_rect(ti[t], y0, y1, x0, x1);
+                tot += (y1 - y0 + 1) * (x1 - x0 + 1);
+            }
+            fprintf(stderr, "[sib stats] whole-K window tiles: %d, rectangle pixels %lld = %.3f of full 7x7 windows\n", whole, tot, (double)tot / (49.0 * (whole > 0 ? whole : 1)));
         }
         if (++launches % 50 == 0) {
             fprintf(stderr, "[sib stats] rounds %lld: per round runs %.0f (evaluated in full %.0f) singles %.0f rows-in-runs %.0f (run length %.2f) window tiles %.1f (split set from %.1f, %.1f ways) full-row K split %.1f\n",
-                    launches, acc[0] / 50.0, acc[3] / 50.0, acc[1] / 50.0, acc[2] / 50.0, acc[0] ? (double)acc[2] / acc[0] : 0.0, acc[4] / 50.0, acc[5] / 50.0, acc[6] / 50.0, acc[7] / 50.0);
+                    launches, acc[0] / 50.0, acc[1] / 50.0, acc[2] / 50.0, acc[3] / 50.0, acc[0] ? (double)acc[3] / acc[0] : 0.0, acc[4] / 50.0, acc[5] / 50.0, acc[6] / 50.0, acc[7] / 50.0);
             for (int i = 0; i < 8; ++i) acc[i] = 0;
         }
     }
     // runs without a cached base -> compact rows [0, misses) + their base slots; then the single rows -> compact rows [misses, misses + singles)
-    if (net.n == 9) launch_trunk_fmt<9, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + 96, nullptr, net.d_gcnt + 1, v2);
-    else launch_trunk_fmt<15, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + 96, nullptr, net.d_gcnt + 1, v2);
+    if (net.n == 9) launch_trunk_fmt<9, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + NET_GCNT_FULL_EVALS, nullptr, net.d_gcnt + NET_GCNT_SINGLES, v2);
+    else launch_trunk_fmt<15, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + NET_GCNT_FULL_EVALS, nullptr, net.d_gcnt + NET_GCNT_SINGLES, v2);
     if (v2 && tprof_mode == 2 && !x16 && net.n == 15) {
         static unsigned long long* d_tp = nullptr;
         static unsigned long long acc[32] = {};
@@ -4209,50 +4124,45 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
                                                         (uint4*)net.d_rows, (uint2*)net.d_slot_desc, nullptr);
 }
 
-// fc0 of a sibling round on the difference path: fp32 fc0 rows of the full rows (split-K over blockIdx.y: there are ~16x fewer full rows
+// One fc0 launch: kernel <EPI, WIN> on operands of format `fmt` -- FC0_FP6: k_fc0_mx on net.wt_fc0 with its block scales, FC0_F16: k_fc0_x3 on net.wt_fc0x.  `grid` workgroups;
+// the other arguments are the kernels' own, the same for both.
+static MxScales fc0_scales(const Net& net) { return MxScales{127 - net.mx_sw, 127 - (net.mx_sw + 11), 127 - MX_SA, 127 - (MX_SA + 11), ldexpf(1.0f, net.mx_sw), ldexpf(1.0f, MX_SA)}; }
+template <int EPI, bool WIN>
+static void launch_fc0(const Net& net, int fmt, int grid, hipStream_t st, const void* act, int ksup, size_t act_row_u4, const float* bias, uint4* out_split, size_t out_row_u4,
+                       float* out_part, const int32_t* d_count, int max_count, const int32_t* tile_info = nullptr, const void* slot_desc = nullptr, const float* facc = nullptr) {
+    const int full_tiles = net.hw / 32, last_cnt = (net.hw % 32) ? (net.hw % 32) : 1;
+    if (fmt == FC0_F16)
+        k_fc0_x3<EPI, WIN><<<dim3(grid, 1), 256, 0, st>>>((const uint4*)net.wt_fc0x, (const uint4*)act, ksup, act_row_u4, full_tiles, last_cnt, bias, out_split, out_row_u4, out_part,
+                                                          d_count, max_count, tile_info, (const uint2*)slot_desc, facc, net.n);
+    else
+        k_fc0_mx<EPI, WIN><<<dim3(grid, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)act, ksup, act_row_u4, full_tiles, last_cnt, fc0_scales(net), bias, out_split,
+                                                          out_row_u4, out_part, d_count, max_count, tile_info, (const uint2*)slot_desc, facc, net.n);
+}
+
+// fc0 of a sibling round on the difference path: fp32 fc0 rows of the full rows (split-K: there are ~16x fewer full rows
 // than requests), then one window tile per 128 slots: 98 of the 450 super-steps, + the slot's full row, bias, LeakyReLU, hi|lo.
-static void launch_fc0_delta(Net& net, int max_count, const MxScales& sc, const float* bias_fc0, uint4* h0, hipStream_t st) {
-    const int hw = net.hw, nsup = hw * 2;
+static void launch_fc0_delta(Net& net, int max_count, const float* bias_fc0, uint4* h0, hipStream_t st) {
+    const int nsup = net.hw * 2, n_cu = net.n_cu;
     const int tiles_max = (max_count + GT_BS - 1) / GT_BS;
     const size_t cap_rows = (size_t)tiles_max * GT_BS;
-    const int n_cu = net.n_cu;
-    // the live count of full rows is only known on the device: k_bin_prefix chose the K split and the partial slab's row stride (d_gcnt[98], [99])
+    const int32_t* cnt = net.d_gcnt;
+    // full rows, in the format of full operand rows.  Their live count is only known on the device: k_bin_prefix chose the K split and the partial slab's row stride
+    // (NET_GCNT_FULL_WAYS, NET_GCNT_FULL_STRIDE)
     const int fgrid = ((tiles_max > n_cu ? tiles_max : n_cu) + 7) / 8 * 8; // (tiles x ways <= CUs by construction unless there are more tiles than CUs: then 1 way; whole eighths: xcd_item)
-    if (net.fc0_fmt == FC0_F16) { // the same four launches on f16 residuals (k_fc0_x3)
-        const int lc = (hw % 32) ? (hw % 32) : 1;
-        k_fc0_x3<EPI_PARTIAL, false><<<dim3(fgrid, 1), 256, 0, st>>>((const uint4*)net.wt_fc0x, (const uint4*)net.a_fc0, nsup, net.row_u4, hw / 32, lc, bias_fc0, nullptr,
-                                                                     cap_rows, net.part, net.d_gcnt + 3, max_count, net.d_gcnt + 98, nullptr, nullptr, net.n);
-        k_facc_reduce<<<512, 256, 0, st>>>(net.part, cap_rows, net.d_gcnt + 3, net.d_gcnt + 98, net.facc, (const uint2*)net.d_comp, net.d_gcnt + 96, (int)net.base_slots);
-    }
-    if (net.fc0_fmt == FC0_F16 && !net.diff_fp6) {
-        const int lc = (hw % 32) ? (hw % 32) : 1;
-        const int wtiles_max = (tiles_max + SIB_BINS + 1 + 7) / 8 * 8 + 8;
-        k_fc0_x3<EPI_SPLIT, true><<<dim3((wtiles_max + 255) / 256 * 256, 1), 256, 0, st>>>((const uint4*)net.wt_fc0x, (const uint4*)net.d_rows, 0, (size_t)SIBX_DROW_U4, hw / 32, lc, bias_fc0, h0, 128,
-                                                                       nullptr, net.d_gcnt, max_count, net.d_tile_info, (const uint2*)net.d_slot_desc, net.facc, net.n);
-        const int stiles = wtiles_max < n_cu + 8 ? wtiles_max : n_cu + 8;
-        k_fc0_x3<EPI_PARTIAL, true><<<dim3(n_cu + 8, 1), 256, 0, st>>>((const uint4*)net.wt_fc0x, (const uint4*)net.d_rows, 0, (size_t)SIBX_DROW_U4, hw / 32, lc, bias_fc0, nullptr,
-                                                                       net.part_w_rows, net.part_w, net.d_gcnt, max_count, net.d_tile_info, (const uint2*)net.d_slot_desc, nullptr, net.n);
-        k_win_finish<<<(unsigned)(((size_t)stiles * GT_BS * 64 + 255) / 256), 256, 0, st>>>(net.part_w, net.part_w_rows, net.d_gcnt, net.d_tile_info,
-                                                                                             (const uint2*)net.d_slot_desc, net.facc, bias_fc0, h0, 128);
-        return;
-    }
-    if (net.fc0_fmt != FC0_F16) { // (FC0_MIXED: the full rows went through k_fc0_x3 above; the window tiles below run on fp6 difference rows)
-    k_fc0_mx<EPI_PARTIAL><<<dim3(fgrid, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.a_fc0, nsup, net.row_u4, hw / 32,
-                                                               (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, nullptr, cap_rows, net.part, net.d_gcnt + 3,
-                                                               max_count, net.d_gcnt + 98, nullptr, nullptr, net.n);
-    k_facc_reduce<<<512, 256, 0, st>>>(net.part, cap_rows, net.d_gcnt + 3, net.d_gcnt + 98, net.facc, (const uint2*)net.d_comp, net.d_gcnt + 96, (int)net.base_slots);
-    }
-    // window tiles: whole rounds of workgroups at full K, the tiles of the last partial round split over K (k_bin_prefix)
+    launch_fc0<EPI_PARTIAL, false>(net, net.fc0_fmt, fgrid, st, net.a_fc0, nsup, net.row_u4, bias_fc0, nullptr, cap_rows, net.part, cnt + NET_GCNT_FULL_ROWS, max_count,
+                                   cnt + NET_GCNT_FULL_WAYS);
+    k_facc_reduce<<<512, 256, 0, st>>>(net.part, cap_rows, cnt + NET_GCNT_FULL_ROWS, cnt + NET_GCNT_FULL_WAYS, net.facc, (const uint2*)net.d_comp, cnt + NET_GCNT_FULL_EVALS, (int)net.base_slots);
+    // window tiles, in the format of the difference rows (FC0_MIXED: fp6 behind f16 full rows): whole rounds of workgroups at full K, the tiles of the last partial round
+    // split over K (k_bin_prefix)
+    const int dfmt = (net.fc0_fmt != FC0_F16 || net.diff_fp6) ? FC0_FP6 : FC0_F16;
+    const size_t drow_u4 = dfmt == FC0_F16 ? SIBX_DROW_U4 : SIB_DROW_U4;
     const int wtiles_max = (tiles_max + SIB_BINS + 1 + 7) / 8 * 8 + 8; // (the XCD-aware tile mapping rounds an eighth of the tiles up)
-    k_fc0_mx<EPI_SPLIT, true><<<dim3((wtiles_max + 255) / 256 * 256, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.d_rows, 0, (size_t)SIB_DROW_U4, hw / 32,
-                                                                       (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, h0, 128, nullptr, net.d_gcnt, max_count,
-                                                                       net.d_tile_info, (const uint2*)net.d_slot_desc, net.facc, net.n);
+    launch_fc0<EPI_SPLIT, true>(net, dfmt, (wtiles_max + 255) / 256 * 256, st, net.d_rows, 0, drow_u4, bias_fc0, h0, 128, nullptr, cnt, max_count, net.d_tile_info, net.d_slot_desc,
+                                net.facc);
     const int stiles = wtiles_max < n_cu + 8 ? wtiles_max : n_cu + 8;
-    k_fc0_mx<EPI_PARTIAL, true><<<dim3(n_cu + 8, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.d_rows, 0, (size_t)SIB_DROW_U4, hw / 32,
-                                                                     (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, nullptr, net.part_w_rows, net.part_w, net.d_gcnt,
-                                                                     max_count, net.d_tile_info, (const uint2*)net.d_slot_desc, nullptr, net.n);
-    k_win_finish<<<(unsigned)(((size_t)stiles * GT_BS * 64 + 255) / 256), 256, 0, st>>>(net.part_w, net.part_w_rows, net.d_gcnt, net.d_tile_info,
-                                                                                         (const uint2*)net.d_slot_desc, net.facc, bias_fc0, h0, 128);
+    launch_fc0<EPI_PARTIAL, true>(net, dfmt, n_cu + 8, st, net.d_rows, 0, drow_u4, bias_fc0, nullptr, net.part_w_rows, net.part_w, cnt, max_count, net.d_tile_info, net.d_slot_desc);
+    k_win_finish<<<(unsigned)(((size_t)stiles * GT_BS * 64 + 255) / 256), 256, 0, st>>>(net.part_w, net.part_w_rows, cnt, net.d_tile_info, (const uint2*)net.d_slot_desc, net.facc,
+                                                                                         bias_fc0, h0, 128);
 }
 
 static int sib_env() { // OMOK_TRUNK_SIB: 0: every row through k_trunk, 1: copy path, 2: difference path
@@ -4289,6 +4199,36 @@ static void recover_handed_over_fill(Net& net, const Store& S, hipStream_t st, c
     launch_fill(S, net.fill_side, net.fill_k, st);
     net.fill_in_group = net.gcnt_zeroed = false;
 }
+// K split of the dense fc0 (plain rows, copy path).  Small batches (late plies of an episode) cannot fill the CUs with 128-sample tiles: K is split into fp32 partials
+// that a second kernel finishes, so that the workgroups fill whole waves of CUs (one workgroup per CU at a time: 144 KiB of LDS): with T tiles of 128 samples and
+// d-way split-K the launch takes ceil(T*d / CUs) / d units of time.  T = 300 (59 % of the games alive at 4096 x K = 16) costs 2 units unsplit and 1.2 with d = 5; late
+// plies (T << CUs) get their parallelism from d alone.  The fp32 partials of d splits must fit the slab.
+static int fc0_dense_nsplit(int rows, int nsup, int n_cu, size_t part_rows) {
+    const int tiles128 = (rows + GT_BS - 1) / GT_BS;
+    int nsplit = 1;
+    double best = 1e30;
+    // Up to 64 ways (round 4; 16 before): a thin round's few tiles then spread over all CUs -- per three plies at 16 / 32 / 64 live games: fp6 42.7 / 44.0 / 45.6 ->
+    // 38.0 / 39.3 / 42.3 ms, mixed (f16 rows) 48.0 / 49.1 / 51.5 -> 40.1 / 41.7 / 47.8 ms.  (Round 2 had measured 30 ways slower than 15 at 8 tiles; with the items
+    // dealt per XCD -- xcd_item -- it is the other way round.)
+    constexpr int dmax = 64;
+    for (int d = 1; d <= dmax; ++d) { // (uneven splits: ceil(nsup / d) super-steps per split, the last one shorter but never empty)
+        const int per = (nsup + d - 1) / d;
+        if ((d - 1) * per >= nsup) continue;
+        if (d > 1 && (size_t)d * (size_t)(tiles128 * GT_BS) > part_rows) continue;
+        const double waves = (double)(((size_t)tiles128 * d + n_cu - 1) / n_cu);
+        const double cost = waves * (per + 4) * (d > 1 ? 1.04 : 1.0); // (+ pipeline fill and epilogue of a workgroup; partials round trip)
+        if (cost < best - 1e-9) { best = cost; nsplit = d; }
+    }
+    return nsplit;
+}
+// K split of fc1 and the heads: 32 k-steps in a row per 128-sample tile; a batch of few tiles (thin rounds) leaves most CUs idle behind a chain of 32 dependent
+// stages, so K is split over blockIdx.y (a power of two of the 32 k-steps, >= 4 k-steps each) into the fp32 partial slab and finished as fc0 is
+static int tail_tsplit(int rows, int n_cu, size_t part_rows) {
+    const int tiles_t = (rows + GT_BS - 1) / GT_BS;
+    int tsplit = 1;
+    while (tsplit < 8 && tiles_t * tsplit * 2 <= n_cu && (size_t)(tsplit * 2) * (size_t)(tiles_t * GT_BS) <= part_rows) tsplit *= 2;
+    return tsplit;
+}
 static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32, hipStream_t st, Prof* prof, int sib_side = -1, bool skip_softmax = false) {
     const int hw = net.hw;
     const int use_sib = sib_env();
@@ -4313,80 +4253,26 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     uint4* h0 = (uint4*)net.h0;
     const size_t mb = ((size_t)net.max_b + GT_BS - 1) / GT_BS * GT_BS;
     uint4* h1 = h0 + mb * 128; // 32 k-steps * 4 uint4 per row
-    // fc0.  Small batches (late plies of an episode) cannot fill 256 CUs with 128-sample tiles: split K over
-    // blockIdx.y into fp32 partials and finish (sum in split order + bias + LeakyReLU + hi|lo) in a second kernel.
-    const MxScales sc{127 - net.mx_sw, 127 - (net.mx_sw + 11), 127 - MX_SA, 127 - (MX_SA + 11), ldexpf(1.0f, net.mx_sw), ldexpf(1.0f, MX_SA)};
     net.plan_path = sib ? (delta ? 2 : 1) : 0;
     net.plan_rows = max_count;
     net.plan_nsplit = 0;
-    if (delta) launch_fc0_delta(net, max_count, sc, bias_fc0, h0, st);
-    else {
-        const int nsup = hw * 2;
-        const int tiles128 = (max_count + GT_BS - 1) / GT_BS;
-        // Split K over blockIdx.y so that the workgroups fill whole waves of CUs (one workgroup per CU at a time: 144 KiB of
-        // LDS): with T tiles of 128 samples and d-way split-K the launch takes ceil(T*d / CUs) / d units of time.  T = 300
-        // (59 % of the games alive at 4096 x K = 16) costs 2 units unsplit and 1.2 with d = 5; late plies (T << CUs) get
-        // their parallelism from d alone.  d must divide the super-step count and its fp32 partials must fit the slab.
-        int nsplit = 1;
-        {
-            static int n_cu_dev[64] = {};
-            int& n_cu = n_cu_dev[net.device & 63];
-            if (!n_cu) {
-                hipDeviceProp_t prop;
-                n_cu = (hipGetDeviceProperties(&prop, net.device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-            }
-            double best = 1e30;
-            // Up to 64 ways (round 4; 16 before): a thin round's few tiles then spread over all CUs -- per three plies at 16 / 32 / 64 live games: fp6 42.7 / 44.0 / 45.6 ->
-            // 38.0 / 39.3 / 42.3 ms, mixed (f16 rows) 48.0 / 49.1 / 51.5 -> 40.1 / 41.7 / 47.8 ms.  (Round 2 had measured 30 ways slower than 15 at 8 tiles; with the items
-            // dealt per XCD -- xcd_item -- it is the other way round.)
-            constexpr int dmax = 64;
-            for (int d = 1; d <= dmax; ++d) { // (uneven splits: ceil(nsup / d) super-steps per split, the last one shorter but never empty)
-                const int per = (nsup + d - 1) / d;
-                if ((d - 1) * per >= nsup) continue;
-                if (d > 1 && (size_t)d * (size_t)(tiles128 * GT_BS) > net.part_rows) continue;
-                const double waves = (double)(((size_t)tiles128 * d + n_cu - 1) / n_cu);
-                const double cost = waves * (per + 4) * (d > 1 ? 1.04 : 1.0); // (+ pipeline fill and epilogue of a workgroup; partials round trip)
-                if (cost < best - 1e-9) { best = cost; nsplit = d; }
-            }
-        }
-        net.plan_nsplit = nsplit;
-        constexpr int LDS = 0; // static LDS objects: (2 + MXS_SLOTS) x 24 KiB
-        if (net.fc0_fmt == FC0_F16) {
-            const int lc = (hw % 32) ? (hw % 32) : 1;
-            if (nsplit == 1)
-                k_fc0_x3<EPI_SPLIT, false><<<dim3(tiles128, 1), 256, 0, st>>>((const uint4*)net.wt_fc0x, (const uint4*)net.a_fc0, nsup, net.row_u4, hw / 32, lc, bias_fc0, h0, 128,
-                                                                              nullptr, S.d_count, max_count, nullptr, nullptr, nullptr, net.n);
-            else {
-                const size_t cap_rows = (size_t)tiles128 * GT_BS;
-                k_fc0_x3<EPI_PARTIAL, false><<<dim3((tiles128 * nsplit + 7) / 8 * 8, 1), 256, 0, st>>>((const uint4*)net.wt_fc0x, (const uint4*)net.a_fc0, (nsup + nsplit - 1) / nsplit, net.row_u4,
-                                                                                     hw / 32, lc, bias_fc0, nullptr, cap_rows, net.part, S.d_count, max_count, nullptr, nullptr, nullptr, net.n);
-                const size_t threads = (size_t)max_count * 64;
-                k_splitk_finish<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(net.part, nsplit, cap_rows, bias_fc0, h0, 128, S.d_count, max_count);
-            }
-        } else
-        if (nsplit == 1) {
-            k_fc0_mx<EPI_SPLIT><<<dim3(tiles128, 1), 256, LDS, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.a_fc0, nsup, net.row_u4,
-                                                                     hw / 32, (hw % 32) ? (hw % 32) : 1, sc, bias_fc0, h0, 128, nullptr,
-                                                                     S.d_count, max_count, nullptr, nullptr, nullptr, net.n);
-        } else {
+    if (delta) launch_fc0_delta(net, max_count, bias_fc0, h0, st);
+    else { // dense fc0: whole K, or split K into fp32 partials + finish (sum in split order + bias + LeakyReLU + hi|lo)
+        const int nsup = hw * 2, tiles128 = (max_count + GT_BS - 1) / GT_BS;
+        const int nsplit = net.plan_nsplit = fc0_dense_nsplit(max_count, nsup, net.n_cu, net.part_rows);
+        if (nsplit == 1) launch_fc0<EPI_SPLIT, false>(net, net.fc0_fmt, tiles128, st, net.a_fc0, nsup, net.row_u4, bias_fc0, h0, 128, nullptr, S.d_count, max_count);
+        else {
             const size_t cap_rows = (size_t)tiles128 * GT_BS;
-            k_fc0_mx<EPI_PARTIAL><<<dim3((tiles128 * nsplit + 7) / 8 * 8, 1), 256, LDS, st>>>((const uint4*)net.wt_fc0, (const uint4*)net.a_fc0,
-                                                                            (nsup + nsplit - 1) / nsplit, net.row_u4, hw / 32, (hw % 32) ? (hw % 32) : 1, sc,
-                                                                            bias_fc0, nullptr, cap_rows, net.part, S.d_count, max_count, nullptr, nullptr,
-                                                                            nullptr, net.n);
-            const size_t threads = (size_t)max_count * 64;
-            k_splitk_finish<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(net.part, nsplit, cap_rows, bias_fc0, h0, 128, S.d_count,
-                                                                                max_count);
+            launch_fc0<EPI_PARTIAL, false>(net, net.fc0_fmt, (tiles128 * nsplit + 7) / 8 * 8, st, net.a_fc0, (nsup + nsplit - 1) / nsplit, net.row_u4, bias_fc0, nullptr, cap_rows,
+                                           net.part, S.d_count, max_count);
+            k_splitk_finish<<<(unsigned)(((size_t)max_count * 64 + 255) / 256), 256, 0, st>>>(net.part, nsplit, cap_rows, bias_fc0, h0, 128, S.d_count, max_count);
         }
     }
     if (prof) { prof->end(st); prof->begin(PC_TAIL, st); }
-    // fc1 and heads: 32 k-steps in a row per 128-sample tile; a batch of few tiles (thin rounds) leaves most CUs idle behind a chain of 32 dependent
-    // stages, so K is split over blockIdx.y (a power of two of the 32 k-steps, >= 4 k-steps each) into the fp32 partial slab and finished as fc0 is
+    // fc1 and heads: whole K, or K split over blockIdx.y (tail_tsplit)
     const int MT = heads_mt(hw);
     const int tiles_t = (max_count + GT_BS - 1) / GT_BS;
-    int tsplit = 1;
-    while (tsplit < 8 && tiles_t * tsplit * 2 <= net.n_cu_all && (size_t)(tsplit * 2) * (size_t)(tiles_t * GT_BS) <= net.part_rows) tsplit *= 2;
-    net.plan_tsplit = tsplit;
+    const int tsplit = net.plan_tsplit = tail_tsplit(max_count, net.n_cu, net.part_rows);
     const size_t cap_t = (size_t)tiles_t * GT_BS;
     const size_t fin_threads = (size_t)max_count * 64;
     if (tsplit == 1) {

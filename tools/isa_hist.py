@@ -41,12 +41,13 @@ def disassemble(src, extra, contract_off):
     cache = os.path.join(tempfile.gettempdir(), f"isa_hist_{key}.s")
     if os.path.exists(cache):
         return open(cache).read()
-    text = _disassemble(src, extra, contract_off)
+    text = objdump(compile_code_object(src, extra, contract_off))
     open(cache, "w").write(text)
     return text
 
 
-def _disassemble(src, extra, contract_off):
+def compile_code_object(src, extra="", contract_off=False):
+    """device-only compile with the Makefile's flags; path of the unbundled gfx950 code object"""
     tmp = tempfile.mkdtemp(prefix="isa_hist_")
     dev, co = os.path.join(tmp, "dev.o"), os.path.join(tmp, "k.co")
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fhip-fp32-correctly-rounded-divide-sqrt", "--cuda-device-only", "-w"]
@@ -56,6 +57,10 @@ def _disassemble(src, extra, contract_off):
     subprocess.check_call(cmd)
     subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + dev,
                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+    return co
+
+
+def objdump(co):
     return subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
 
 
