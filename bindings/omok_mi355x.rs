@@ -54,6 +54,8 @@ pub const OMOK_NET_F16X3_FP6: i32 = 3;
 pub const OMOK_NET_F16X3_F16: i32 = 4;
 pub const OMOK_NET_F16X3_MIXED: i32 = 5;
 pub const OMOK_MAX_ARENA: i32 = 16384;
+pub const OMOK_OPP_RANDOM: i32 = 0;
+pub const OMOK_OPP_NAIVE: i32 = 1;
 pub const OMOK_PLAN_INTS: i32 = 16;
 pub const OMOK_STAT_SIMS: i32 = 0;
 pub const OMOK_STAT_EVALS: i32 = 1;
@@ -138,6 +140,9 @@ pub mod ffi {
         pub fn omok_play_actions(e: *mut OmokEngine, actions: *const i32) -> c_int;
         pub fn omok_set_actions(e: *mut OmokEngine, actions: *const i32) -> c_int;
         pub fn omok_selfplay_run(e: *mut OmokEngine, count: i32, batch_size: i32, epsilon: f32, alpha: f32, temperature: f32, threshold: i32, max_plies: i32, stats: *mut f64) -> c_int;
+        pub fn omok_env_scripted_actions(e: *mut OmokEngine, kind: i32, boards: *const u8, turns: *const u8, batch: i32, forced_out: *mut i32) -> c_int;
+        pub fn omok_opponent_actions(e: *mut OmokEngine, kind: i32, actions: *mut i32) -> c_int;
+        pub fn omok_versus_run(e: *mut OmokEngine, kind: i32, opponent_side: i32, count: i32, batch_size: i32, epsilon: f32, alpha: f32, max_plies: i32, results: *mut i32, stats: *mut f64) -> c_int;
         pub fn omok_selfplay_run_slots(e: *mut OmokEngine, total_games: i32, count: i32, batch_size: i32, epsilon: f32, alpha: f32, temperature: f32, threshold: i32, records_dev: *mut c_void, cap_records: i64, game_offsets: *mut i64, game_lengths: *mut i32, game_status: *mut i32, n_records: *mut i64, stats: *mut f64) -> c_int;
         pub fn omok_round_generate(e: *mut OmokEngine, round: i32, batch_size: i32, epsilon: f32, alpha: f32, n_requests: *mut i32) -> c_int;
         pub fn omok_round_inputs(e: *mut OmokEngine, inputs: *mut f32) -> c_int;

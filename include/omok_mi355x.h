@@ -204,6 +204,39 @@ int omok_set_actions(omok_engine* e, const int32_t* actions);
 int omok_selfplay_run(omok_engine* e, int32_t count, int32_t batch_size, float epsilon, float alpha,
                       float temperature, int32_t threshold, int32_t max_plies, double* stats);
 
+/* ---- evaluation games against the scripted players of src/trainer.rs:380-394, 400-603 ---------
+ * OMOK_OPP_NAIVE: the "naive" player of play_against_naive_player (trainer.rs:508-534): the LOWEST empty cell at which a stone of the side
+ * to move, or a stone of the other side, ends the game -- place_stone(..).is_terminal() (environment/src/lib.rs:104-190): exactly five in a
+ * line (an overline does not count) or Draw (the last empty cell); the reference breaks at the first such cell, so a block at a lower index
+ * beats a win at a higher one.  Without such a cell it falls through to OMOK_OPP_RANDOM.
+ * OMOK_OPP_RANDOM: legal_moves[rng.gen_range(0..len)] (trainer.rs:452-455, :534): the r-th empty cell in ascending order, r = mulhi(x0,
+ * legal_move_count), x0 = word 0 of Philox(key of the episode, 0, the game's ply, 2 * (game_offset + game) + side to move, purpose 4)
+ * (DESIGN.md "RNG contract"). */
+#define OMOK_OPP_RANDOM 0
+#define OMOK_OPP_NAIVE 1
+/* the forced part of the rule on caller-held positions (boards [B][N*N] Stone bytes, turns [B]): forced_out[b] = the cell the NAIVE rule
+ * picks before its random fallback (trainer.rs:514-531), -1 if none (always -1 for RANDOM).  (The rule tries a stone of either colour at
+ * every empty cell, so the side to move does not change the answer: turns is read by no kernel.) */
+int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out);
+/* step-wise: the scripted player's move (trainer.rs:508-534 / :452-455) for the side to move of every live game, chosen on the device and
+ * staged like omok_set_actions (omok_mirror_* / omok_advance follow); actions [G] may be NULL, -1 for finished games.  OMOK_ERR_STATE in a
+ * match episode, OMOK_ERR_INVALID for an unknown kind. */
+int omok_opponent_actions(omok_engine* e, int32_t kind, int32_t* actions);
+/* Whole evaluation episode after a fresh omok_selfplay_reset: play_against_naive_player (trainer.rs:487-603: kind = OMOK_OPP_NAIVE,
+ * opponent_side = 0, the scripted player is Black and moves first) or _play_against_random_player (:400-485: OMOK_OPP_RANDOM, opponent_side =
+ * 1).  On plies where opponent_side (0 = Black, 1 = White) is to move: the scripted move as an external move (ensure_action_exists +
+ * play_action, :536-538).  On the others: omok_execute(count, batch_size, epsilon, alpha), sample_action(Best), play_action (:562-577).
+ * Runs until every game is over or max_plies (> 0) plies were played.  results [3] (may be NULL) = black wins, white wins, draws among the
+ * finished games (the reference's tuple, :602); stats as omok_selfplay_run.
+ * The net's agent is the engine's tree of side 1 - opponent_side: it receives exactly the calls the reference's single Agent receives.  The
+ * tree of side opponent_side is kept in step like with any external move (both agents of a game, see omok_play_actions); it is never
+ * searched, and costs one shared root-row evaluation per game and ply.  Transitions are recorded on the net's plies only (the moves
+ * omok_sample_actions chose): the replay buffer of an evaluation episode is not training data and is discarded by the next
+ * omok_selfplay_reset.  OMOK_ERR_STATE in a match episode or when the episode is not at ply 0, OMOK_ERR_INVALID for an unknown kind or
+ * opponent_side. */
+int omok_versus_run(omok_engine* e, int32_t kind, int32_t opponent_side, int32_t count, int32_t batch_size, float epsilon, float alpha,
+                    int32_t max_plies, int32_t* results, double* stats);
+
 /* Slots mode ("continuous refill"): plays `total_games` >= games games on the engine's `games` slots; a slot whose game is over takes the
    next game index instead of idling until the episode's longest game ends.  Per-game results are those of an episode of total_games
    games (omok_selfplay_run on an engine with games = total_games): a game's RNG streams are keyed by game_offset + index and its own

@@ -9,6 +9,7 @@ Names follow the reference so parity tests read like its own code:
   SelfPlay.run                     Trainer::train self-play phase, src/trainer.rs:95-205
   Engine.load_weights2 / load2     the second agent's AgentModel of benchmark/src/main.rs:14-108
   SelfPlay.match_reset             benchmark/src/main.rs: net 1 against net 2, half of the games per colour
+  SelfPlay.versus_run              Trainer::play_against_naive_player / _play_against_random_player, src/trainer.rs:400-603
 All compute happens in the HIP library; nothing here has a CPU path.
 """
 import ctypes as C
@@ -143,6 +144,16 @@ class Engine:
                                                B.iptr(actions), b, B.iptr(status)))
         return status
 
+    def env_scripted_actions(self, kind, boards, turns):
+        """the forced part of the scripted player's rule (src/trainer.rs:514-531) on caller-held positions: the lowest empty cell at
+        which a stone of either side ends the game, -1 where there is none (always -1 for B.OPP_RANDOM); int32 [B]"""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
+        turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
+        assert len(turns) == len(boards)
+        forced = np.zeros(len(boards), dtype=np.int32)
+        self._chk(B.lib().omok_env_scripted_actions(self.h, int(kind), B.u8ptr(boards), B.u8ptr(turns), len(boards), B.iptr(forced)))
+        return forced
+
     def encode_nn_input(self, boards, turns, mode=B.MODE_PLAYER):
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
         turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
@@ -256,6 +267,22 @@ class SelfPlay:
         a = np.ascontiguousarray(actions, dtype=np.int32)
         assert a.size == self.games
         self._chk(B.lib().omok_set_actions(self.h, B.iptr(a)))
+
+    def opponent_actions(self, kind):
+        """the scripted player's move (B.OPP_NAIVE / B.OPP_RANDOM, src/trainer.rs:508-534, 452-455) for the side to move of every live
+        game, chosen on the device and staged like set_actions (the mirror step / advance follow); -1 for finished games"""
+        a = np.zeros(self.games, dtype=np.int32)
+        self._chk(B.lib().omok_opponent_actions(self.h, int(kind), B.iptr(a)))
+        return a
+
+    def versus_run(self, kind, opponent_side, count, batch_size, epsilon=0.25, alpha=0.03, max_plies=0):
+        """Evaluation episode after reset() (omok_versus_run): the scripted player `kind` plays the colour opponent_side (0 = Black, moves
+        first: play_against_naive_player, src/trainer.rs:487-603; 1 = White: _play_against_random_player, :400-485), the net the other with
+        `count` simulations and sample_action(Best).  Returns ((black_win, white_win, draw), stats)."""
+        s = (C.c_double * len(B.STAT_NAMES))()
+        res = np.zeros(3, dtype=np.int32)
+        self._chk(B.lib().omok_versus_run(self.h, int(kind), int(opponent_side), count, batch_size, epsilon, alpha, max_plies, B.iptr(res), s))
+        return tuple(int(x) for x in res), dict(zip(B.STAT_NAMES, list(s)))
 
     def root_children(self, game, side):
         """(actions, n, w, p) of the root's children in insertion order"""

@@ -22,7 +22,7 @@ constexpr int KMAX = 64;
 constexpr float F32_EPS = 1.1920928955078125e-7f;
 
 enum { ST_IN_PROGRESS = 0, ST_DRAW = 1, ST_BLACK_WIN = 2, ST_WHITE_WIN = 3 };
-enum { RNG_EXPAND = 1, RNG_NOISE = 2, RNG_SAMPLE = 3 };
+enum { RNG_EXPAND = 1, RNG_NOISE = 2, RNG_SAMPLE = 3, RNG_OPPONENT = 4 };
 
 template <int N>
 struct Geo {
@@ -150,6 +150,11 @@ void launch_replay_pack(int n, const Store& S, const long long* offsets_dev, uin
 void launch_replay_offsets(int n, const Store& S, int per_transition, long long* offsets_dev /*[games + 1]*/, hipStream_t st);
 void launch_set_actions(int n, const Store& S, int side, const int32_t* actions_dev, uint32_t* d_flags /*[0] illegal, [1] missing*/, hipStream_t st);
 void launch_clear_actions(const Store& S, hipStream_t st);
+// the scripted players of the evaluation games (src/trainer.rs:400-603), kind 0 = random, 1 = naive: the move of the side to move of every live game, staged like
+// launch_set_actions (external) and copied to actions_dev [G] (-1: finished game)
+void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int32_t* actions_dev, hipStream_t st);
+// the forced part of the naive rule on caller-held positions: boards_dev [B][HW] Stone bytes -> forced_dev [B] (-1: none)
+void launch_env_scripted(int n, const uint8_t* boards_dev, int kind, int batch, int32_t* forced_dev, hipStream_t st);
 void launch_policy(int n, const Store& S, int side, float* pi_dev /*[G][HW]*/, uint8_t* has_dev /*[G]*/, hipStream_t st);
 void launch_env_place(int n, uint8_t* boards_dev, uint8_t* turns_dev, uint16_t* legal_dev, const int32_t* actions_dev, int batch,
                       int32_t* status_dev, hipStream_t st);

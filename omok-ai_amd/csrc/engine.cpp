@@ -1157,6 +1157,101 @@ extern "C" int omok_play_actions(omok_engine* e, const int32_t* actions) {
     return omok_advance(e);
 }
 
+// ---- evaluation games against the scripted players (src/trainer.rs:380-394, 400-603) -----------
+static int check_opponent_kind(omok_engine* e, int kind) {
+    if (kind != OMOK_OPP_RANDOM && kind != OMOK_OPP_NAIVE) return fail(e, OMOK_ERR_INVALID, "unknown scripted player %d (OMOK_OPP_RANDOM, OMOK_OPP_NAIVE)", kind);
+    return 0;
+}
+
+static void enqueue_opponent_move(omok_engine* e, int kind) {
+    e->prof.begin(PC_PLY, e->st);
+    launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, e->d_actions, e->st);
+    e->prof.end(e->st);
+}
+
+// the forced part of the naive player's rule (trainer.rs:514-531, rules of environment/src/lib.rs:104-190) on caller-held positions
+extern "C" int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out) {
+    if (!e || !boards || !turns || !forced_out || batch < 1) return OMOK_ERR_INVALID;
+    if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
+    ENTER(e);
+    // (the rule tests a stone of either colour at every empty cell, trainer.rs:518,524-527: the answer does not depend on the side to move)
+    uint8_t* d_boards = nullptr;
+    int32_t* d_forced = nullptr;
+    const size_t B = (size_t)batch;
+    HIPCHK(e, hipMalloc((void**)&d_boards, B * e->hw));
+    HIPCHK(e, hipMalloc((void**)&d_forced, B * 4));
+    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
+    launch_env_scripted(e->n, d_boards, kind, batch, d_forced, e->st);
+    hipMemcpyAsync(forced_out, d_forced, B * 4, hipMemcpyDeviceToHost, e->st);
+    const int rc = sync_and_check(e, "env_scripted_actions");
+    hipFree(d_boards); hipFree(d_forced);
+    return rc ? OMOK_ERR_HIP : OMOK_OK;
+}
+
+// the scripted player's move of every live game (trainer.rs:508-534 naive, :452-455 random), staged like omok_set_actions
+extern "C" int omok_opponent_actions(omok_engine* e, int32_t kind, int32_t* actions) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (need_reset(e)) return OMOK_ERR_STATE;
+    if (no_match(e, "omok_opponent_actions")) return OMOK_ERR_STATE;
+    if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
+    ENTER(e);
+    enqueue_opponent_move(e, kind);
+    if (actions) HIPCHK(e, hipMemcpyAsync(actions, e->d_actions, sizeof(int32_t) * e->cfg.games, hipMemcpyDeviceToHost, e->st));
+    if (sync_and_check(e, "opponent_actions")) return OMOK_ERR_HIP;
+    e->sampled = true;
+    return OMOK_OK;
+}
+
+// play_against_naive_player (trainer.rs:487-603; opponent_side 0) / _play_against_random_player (:400-485; opponent_side 1): the scripted
+// player's plies are external moves (ensure_action_exists + play_action, :536-538 / :457-459), the net's plies are execute + sample_action(Best)
+// + play_action (:562-577 / :416-431)
+extern "C" int omok_versus_run(omok_engine* e, int32_t kind, int32_t opponent_side, int32_t count, int32_t batch_size, float epsilon, float alpha,
+                               int32_t max_plies, int32_t* results, double* stats) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
+    if (no_match(e, "omok_versus_run")) return OMOK_ERR_STATE;
+    if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
+    if (opponent_side != 0 && opponent_side != 1) return fail(e, OMOK_ERR_INVALID, "opponent_side %d is neither 0 (Black) nor 1 (White)", opponent_side);
+    if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
+    if (e->ply != 0) return fail(e, OMOK_ERR_STATE, "omok_versus_run starts at ply 0: call omok_selfplay_reset first (the episode is at ply %d)", e->ply);
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    uint32_t bits = 0, alive = 0;
+    if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
+    int plies = 0;
+    while (alive > 0 && (max_plies <= 0 || plies < max_plies)) {
+        if ((e->ply & 1) == opponent_side) enqueue_opponent_move(e, kind);
+        else {
+            const int rounds = enqueue_execute(e, count, batch_size, epsilon, alpha, (int)alive);
+            enqueue_sample(e, 1.0f, 0); // threshold 0: sample_action(Best) on every ply (:576, :430)
+            e->sims += (double)rounds * batch_size * alive;
+        }
+        enqueue_mirror_and_advance(e, (int)alive);
+        e->ply_games += alive;
+        e->ply += 1;
+        plies += 1;
+        uint32_t after = 0;
+        if (read_status(e, &bits, &after)) return OMOK_ERR_HIP;
+        e->finished += (double)alive - (double)after;
+        alive = after;
+        if (tree_error(e, bits)) return bits & 1u ? OMOK_ERR_OVERFLOW : OMOK_ERR_ILLEGAL;
+    }
+    e->sampled = false;
+    if (results) {
+        std::vector<GameState> gs((size_t)e->cfg.games);
+        HIPCHK(e, hipMemcpyAsync(gs.data(), e->S.gs, sizeof(GameState) * gs.size(), hipMemcpyDeviceToHost, e->st));
+        if (sync_and_check(e, "versus_run")) return OMOK_ERR_HIP;
+        results[0] = results[1] = results[2] = 0;
+        for (const GameState& g : gs) {
+            if (g.alive) continue;
+            if (g.status == ST_BLACK_WIN) results[0] += 1;
+            else if (g.status == ST_WHITE_WIN) results[1] += 1;
+            else if (g.status == ST_DRAW) results[2] += 1;
+        }
+    }
+    if (stats) return omok_get_stats(e, stats);
+    return OMOK_OK;
+}
+
 // children of a root in insertion order (Node::children of MCTS::root, mcts/src/node.rs:10-21): action, n, w, p
 extern "C" int omok_root_children(omok_engine* e, int32_t game, int32_t side, int32_t* actions, uint32_t* n, float* w, float* p, int32_t cap) {
     if (!e || game < 0 || game >= e->cfg.games || (side != 0 && side != 1) || cap < 0) return OMOK_ERR_INVALID;

@@ -1848,6 +1848,106 @@ __global__ __launch_bounds__(256) void k_clear_actions(Store S) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The scripted players of the evaluation games (src/trainer.rs:400-603): the "naive" player of play_against_naive_player
+// (:508-534) and the uniformly random one of _play_against_random_player (:452-455).  Wave-cooperative: bb = black NW | white NW
+// words of the position (wave-uniform), all 64 lanes call, the results are wave-uniform.
+// ---------------------------------------------------------------------------------------------
+// The forced part of the naive rule (trainer.rs:514-531): the LOWEST empty cell at which a stone of the side to move, or a stone
+// of the other side, ends the game -- place_stone(..).is_terminal() (environment/src/lib.rs:104-166): exactly five in one of the
+// four line pairs (an overline is no win), or Draw, which either test returns for the last empty cell (:160-161).  The reference
+// breaks at the first cell that passes either test, so a block at a lower index beats a win at a higher one.  One ballot per
+// sweep of 64 cells, the first sweep with a hit decides.  -1: no such cell.
+template <int N>
+__device__ inline int scripted_forced_cell(const uint64_t* bb, int legal) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int lane = LANE;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        bool hit = a < G::HW && !(((bb[j] | bb[NW + j]) >> lane) & 1ULL);
+        if (hit && legal != 1) {
+            const int c = a < G::HW ? a : 0;
+            bool five = false;
+#pragma unroll
+            for (int pr = 0; pr < 4; ++pr) five = five || five_in_pair<N>(bb, c, pr) || five_in_pair<N>(bb + NW, c, pr);
+            hit = five;
+        }
+        const unsigned long long m = __ballot(hit);
+        if (m != 0ULL) return j * 64 + __ffsll((long long)m) - 1;
+    }
+    return -1;
+}
+
+// legal_moves[rng.gen_range(0..legal_moves.len())] (trainer.rs:455,534): the r-th empty cell in ascending order, r = mulhi(x0, legal)
+template <int N>
+__device__ inline int scripted_random_cell(const uint64_t* bb, int legal, uint32_t x0) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    int r = (int)__umulhi(x0, (uint32_t)legal);
+    int action = -1;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const unsigned long long valid = (j + 1) * 64 <= G::HW ? ~0ULL : ((1ULL << (G::HW - j * 64)) - 1ULL);
+        const unsigned long long empty = ~(bb[j] | bb[NW + j]) & valid;
+        const int c = __popcll(empty);
+        if (action < 0) {
+            if (r < c) action = j * 64 + nth_set_bit(empty, r);
+            else r -= c;
+        }
+    }
+    return action;
+}
+
+// k_opponent_move: the scripted player's move for the side to move of every live game, staged like k_set_actions (an external
+// move: nothing is recorded, both trees get ensure_action_exists in k_advance).  kind 1 = naive (forced cell, else random),
+// 0 = random.  Workgroup = one wave = one game; reads the root board of the side-to-move tree only.
+template <int N>
+__global__ __launch_bounds__(64) void k_opponent_move(Store S, int side, int kind, uint64_t seed, int64_t game_offset, int32_t* __restrict__ actions) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int g = blockIdx.x;
+    const int lane = LANE;
+    const GameState gs = S.gs[g];
+    if (!gs.alive) {
+        if (lane == 0) { actions[g] = -1; S.gs[g].last_action = -1; S.gs[g].external = 1; }
+        return;
+    }
+    const uint64_t* root = S.board + (size_t)(side * S.games + g) * (size_t)S.stride_nodes * (2 * NW); // root = node 0
+    uint64_t bb[2 * NW];
+    int legal = G::HW;
+#pragma unroll
+    for (int i = 0; i < 2 * NW; ++i) { bb[i] = root[i]; legal -= __popcll(bb[i]); }
+    int action = kind == 1 ? scripted_forced_cell<N>(bb, legal) : -1;
+    if (action < 0) {
+        const U4 o = philox(seed, 0u, (uint32_t)gs.plies, (uint32_t)((game_offset + gs.gid) * 2 + side), RNG_OPPONENT); // (the game's own ply and id, as k_sample)
+        action = scripted_random_cell<N>(bb, legal, o.x);
+    }
+    if (lane == 0) { actions[g] = action; S.gs[g].last_action = action; S.gs[g].external = 1; }
+}
+
+// the forced part of the rule on caller-held positions: boards [B][HW] Stone bytes -> forced [B] (-1: none; always -1 for kind 0)
+template <int N>
+__global__ __launch_bounds__(64) void k_env_scripted(const uint8_t* __restrict__ boards, int kind, int32_t* __restrict__ forced) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int b = blockIdx.x;
+    const int lane = LANE;
+    uint64_t bb[2 * NW];
+    int legal = G::HW;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
+        bb[j] = __ballot(s == 1);
+        bb[NW + j] = __ballot(s == 2);
+        legal -= __popcll(bb[j]) + __popcll(bb[NW + j]);
+    }
+    const int cell = kind == 1 ? scripted_forced_cell<N>(bb, legal) : -1;
+    if (lane == 0) forced[b] = cell;
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_mirror_scan: NN requests of ensure_action_exists (agent.rs:153-158) for every live game
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_mirror_scan(Store S, int side) {
@@ -2516,6 +2616,13 @@ void launch_set_actions(int n, const Store& S, int side, const int32_t* actions,
     DISPATCH_N(n, (k_set_actions<9><<<grid, 256, 0, st>>>(S, side, actions, flags)), (k_set_actions<15><<<grid, 256, 0, st>>>(S, side, actions, flags)));
 }
 void launch_clear_actions(const Store& S, hipStream_t st) { k_clear_actions<<<(S.games + 255) / 256, 256, 0, st>>>(S); }
+void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int32_t* actions, hipStream_t st) {
+    DISPATCH_N(n, (k_opponent_move<9><<<S.games, 64, 0, st>>>(S, side, kind, seed, game_offset, actions)),
+               (k_opponent_move<15><<<S.games, 64, 0, st>>>(S, side, kind, seed, game_offset, actions)));
+}
+void launch_env_scripted(int n, const uint8_t* boards, int kind, int batch, int32_t* forced, hipStream_t st) {
+    DISPATCH_N(n, (k_env_scripted<9><<<batch, 64, 0, st>>>(boards, kind, forced)), (k_env_scripted<15><<<batch, 64, 0, st>>>(boards, kind, forced)));
+}
 void launch_policy(int n, const Store& S, int side, float* pi, uint8_t* has, hipStream_t st) {
     DISPATCH_N(n, (k_policy<9><<<S.games, 64, 0, st>>>(S, side, pi, has)), (k_policy<15><<<S.games, 64, 0, st>>>(S, side, pi, has)));
 }

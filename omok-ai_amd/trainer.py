@@ -3,8 +3,9 @@
 Per iteration, like the reference: clear the replay memory (:77-78), play `episode_count` self-play games (:81-205, on
 the engine), back-fill z and augment (:207-324, on the device), cap the memory at `replay_memory_size` (:326-328), run
 `parameter_update_count` training steps on `parameter_update_batch_size` transitions (:329-357), save the model
-(`saves/<model_name>`, :375, ModelIO format).  Plots and the periodic games against the naive player (:371-400) are not
-part of this mirror.  Parameters and defaults: src/config.rs:83-110 (episode_count 50, evaluate_count 600, ...).
+(`saves/<model_name>`, :375, ModelIO format), and every `evaluate_every` iterations play `evaluate_games` games against the scripted
+naive player (:380-394, 487-603: `Trainer.evaluate`).  Plots (:371-376) are not part of this mirror.  Parameters and defaults:
+src/config.rs:83-110 (episode_count 50, evaluate_count 600, test_evaluate_count 800, ...).
 Multi-GPU: every rank plays its own `episode_count` games (global ids rank*episode_count + g) and trains data-parallel
 (gradients averaged per step), so all ranks hold identical weights after every iteration.
 """
@@ -31,6 +32,9 @@ class Parameters:  # src/config.rs:83-110
     temperature_threshold: int = 30
     parameter_update_count: int = 600
     parameter_update_batch_size: int = 128
+    test_evaluate_count: int = 800  # simulations per move of the net in the evaluation games (src/config.rs:31,103)
+    evaluate_every: int = 10        # `iteration % 10 == 0` (src/trainer.rs:380)
+    evaluate_games: int = 100       # play_against_naive_player(100, ..) (:384)
 
 
 class Trainer:
@@ -43,6 +47,8 @@ class Trainer:
         self.precision_rows = precision_rows  # independent check of the net outputs after every weight update (0 = off)
         self.precision_search_rounds = precision_search_rounds  # ... and of the search rounds' own path (sibling base + difference rows)
         self.last_precision = None
+        self.seed = seed
+        self.last_evaluation = None  # result of the last games against the naive player (evaluate)
         sims = -(-self.p.evaluate_count // self.p.evaluate_batch_size) * self.p.evaluate_batch_size
         max_nodes = max_nodes or min(16384, 4 * sims + 1024)
         self.engine = api.Engine(board_size=board_size, games=self.p.episode_count, max_nodes=max_nodes,
@@ -133,9 +139,39 @@ class Trainer:
                 os.replace(final + ".iteration.tmp", final + ".iteration")
                 self.engine.save(final + ".tmp")
                 os.replace(final + ".tmp", final)
+            versus = ""
+            if self.rank == 0 and p.evaluate_every > 0 and (self.iteration - 1) % p.evaluate_every == 0:  # `iteration % 10 == 0`, 0-based (:380)
+                try:  # like the precision check: a failure (e.g. no memory for the engine) is logged, never fatal
+                    black, white, draw = self.evaluate()
+                    versus = (f" | {p.evaluate_games} games against the naive player (naive = Black, net = White, {p.test_evaluate_count} simulations): "
+                              f"black_win={black} white_win={white} draw={draw}")
+                except Exception as ex:  # noqa: BLE001
+                    self.last_evaluation = {"iteration": self.iteration, "error": repr(ex)}
+                    log(f"[iter={self.iteration}] WARNING: the games against the naive player did not run: {ex!r}")
             log(f"[iter={self.iteration}] games={int(stats['finished'])} transitions={got} loss={loss:.4f} "
-                f"[v_loss={v_loss:.4f}, p_loss={p_loss:.4f}]")
+                f"[v_loss={v_loss:.4f}, p_loss={p_loss:.4f}]" + versus)
         return v_loss, p_loss, loss
+
+    def evaluate(self):
+        """play_against_naive_player (src/trainer.rs:487-603) with the weights just saved: `evaluate_games` games on an engine of its own
+        (arenas sized for `test_evaluate_count`), the scripted naive player is Black and moves first, the net answers as White with
+        `test_evaluate_count` simulations and sample_action(Best).  The reference prints Black's wins as "Win" although Black is the naive
+        player (:387-393); train() logs the three counts by colour, on the iteration's line.  Returns (black_win, white_win, draw)."""
+        p = self.p
+        sims = -(-p.test_evaluate_count // p.evaluate_batch_size) * p.evaluate_batch_size
+        max_nodes = min(16384, 4 * sims + 1024)
+        eng = api.Engine(board_size=self.n, games=p.evaluate_games, max_nodes=max_nodes, max_tables=max(256, max_nodes // 4),
+                         max_batch_k=p.evaluate_batch_size, device=self.local_rank, seed=self.seed + 1)  # (seed + 1: streams of its own, not the self-play games')
+        try:
+            eng.load(os.path.join(self.save_dir, p.model_name))
+            sp = api.SelfPlay(eng)
+            sp.set_episode(self.iteration - 1)
+            sp.reset()
+            (black, white, draw), _ = sp.versus_run(api.B.OPP_NAIVE, 0, p.test_evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha)
+        finally:
+            eng.close()
+        self.last_evaluation = {"iteration": self.iteration, "games": p.evaluate_games, "black_win": black, "white_win": white, "draw": draw}
+        return black, white, draw
 
     def close(self):
         self.engine.close()
