@@ -128,7 +128,9 @@ pub mod ffi {
         pub fn omok_env_play(e: *mut OmokEngine, moves: *const i32, batch: i32, len: i32, status_out: *mut i32, boards_out: *mut u8, turns_out: *mut u8, legal_out: *mut u16) -> c_int;
         pub fn omok_encode_nn_input(e: *mut OmokEngine, boards: *const u8, turns: *const u8, batch: i32, mode: i32, out: *mut f32) -> c_int;
         pub fn omok_env_place_stone(e: *mut OmokEngine, boards: *mut u8, turns: *mut u8, legal: *mut u16, actions: *const i32, batch: i32, status_out: *mut i32) -> c_int;
+        pub fn omok_env_check_positions(e: *mut OmokEngine, boards: *const u8, batch: i32, verdict_out: *mut i32, stones_out: *mut i32) -> c_int;
         pub fn omok_selfplay_reset(e: *mut OmokEngine) -> c_int;
+        pub fn omok_selfplay_reset_from(e: *mut OmokEngine, boards: *const u8) -> c_int;
         pub fn omok_match_reset(e: *mut OmokEngine, split: i32) -> c_int;
         pub fn omok_set_episode(e: *mut OmokEngine, episode: u64) -> c_int;
         pub fn omok_execute(e: *mut OmokEngine, count: i32, batch_size: i32, epsilon: f32, alpha: f32) -> c_int;
@@ -162,6 +164,7 @@ pub mod ffi {
         pub fn omok_game_info(e: *mut OmokEngine, alive: *mut u8, status: *mut u8, plies: *mut i32) -> c_int;
         pub fn omok_tree_dump(e: *mut OmokEngine, game: i32, side: i32, ints: *mut i32, floats: *mut f32, cap_nodes: i32) -> c_int;
         pub fn omok_tree_root(e: *mut OmokEngine, game: i32, side: i32, root_n: *mut u32, root_w: *mut f32, n_nodes: *mut i32, n_tables: *mut i32) -> c_int;
+        pub fn omok_root_stats(e: *mut OmokEngine, n: *mut u32, w: *mut f32) -> c_int;
         pub fn omok_root_children(e: *mut OmokEngine, game: i32, side: i32, actions: *mut i32, n: *mut u32, w: *mut f32, p: *mut f32, cap: i32) -> c_int;
         pub fn omok_replay_game(e: *mut OmokEngine, game: i32, boards: *mut u8, turns: *mut u8, pi: *mut f32, z: *mut f32, cap_plies: i32) -> c_int;
         pub fn omok_replay_pack_dev(e: *mut OmokEngine, dst_dev: *mut c_void, cap_records: i64) -> i64;

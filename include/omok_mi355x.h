@@ -134,12 +134,39 @@ int omok_encode_nn_input(omok_engine* e, const uint8_t* boards, const uint8_t* t
 int omok_env_place_stone(omok_engine* e, uint8_t* boards, uint8_t* turns, uint16_t* legal, const int32_t* actions,
                          int32_t batch, int32_t* status_out);
 
+/* Is a caller-supplied board a position a game can be in?  Extends Environment (environment/src/lib.rs:62-166), which can only be reached
+ * move by move from Environment::new() (:73-79): boards [B][N*N] bytes, verdict_out[b] = the first that applies of
+ *   1  a byte that is not a Stone (> 2);
+ *   2  stone counts that no alternating game from Environment::new() produces (neither black = white nor black = white + 1);
+ *   3  the position is already won: some stone, taken as the last one placed, gives a line total of exactly five in one of the four line
+ *      pairs -- the rule of place_stone (:151-159); a run of six or more is not a win;
+ *   4  no empty cell (Draw, :160-161);
+ *   0  a legal position of a game in progress.
+ * stones_out [B] (may be NULL) = the stone count; the side to move is stones & 1 (0 = Black).  Touches no engine state (the batched,
+ * caller-held form, like omok_env_scripted_actions). */
+int omok_env_check_positions(omok_engine* e, const uint8_t* boards, int32_t batch, int32_t* verdict_out, int32_t* stones_out);
+
 /* ---- self-play: G games x two agents (src/trainer.rs:81-205) ---------------------------- */
 /* Agent::new for both agents of every game (alpha-zero/src/agent.rs:16-35): root policy = raw
  * evaluate_p of the empty board.  Also clears the replay buffer.  Every reset is one trainer iteration
  * (src/trainer.rs:74-93, fresh thread_rng draws): it takes RNG stream `episode` and advances the counter; the first reset
  * after omok_create is episode 0. */
 int omok_selfplay_reset(omok_engine* e);
+/* Agent::new for both agents of every game (alpha-zero/src/agent.rs:16-35) on a GIVEN environment instead of Environment::new(): extends
+ * omok_selfplay_reset to opening books, tactical test positions, resume / take-back (gui/src/main.rs:42-47 can only restart from empty) and
+ * batched analysis.  boards [G][N*N] Stone bytes, the position of each game.  Root policy of both trees = evaluate_p of the position in
+ * Player mode (agent.rs:19-20; the G positions are evaluated as one batch in game order, bit-identical to omok_evaluate_pv of the same G
+ * rows) with every occupied cell set to 0 and, iff f32::EPSILON <= sum, scaled by 1 / sum -- the arithmetic of ensure_action_exists
+ * (agent.rs:166-171), which every policy the reference stores on a non-empty board went through.  Roots carry no history: n = 0, w = 0,
+ * no action.  The games' plies and omok_current_ply start at the stone count (side to move = stones & 1, RNG counters of DESIGN 5); the
+ * Boltzmann threshold of omok_sample_actions keeps counting the moves sampled (trainer.rs:139); the replay buffer is cleared and holds only
+ * moves sampled after the reset.  Episode counter and RNG stream as omok_selfplay_reset.
+ * OMOK_ERR_ILLEGAL if omok_env_check_positions gives a position a verdict other than 0, OMOK_ERR_INVALID if the stone counts differ (all
+ * games of an episode share the side to move, trainer.rs:96-97); the message names the first offending game.  A rejected call leaves the
+ * engine exactly as it was.  With no stone on any board this IS omok_selfplay_reset.
+ * Afterwards every self-play call works as after omok_selfplay_reset, omok_execute_shared(_recorded) on a one-game engine and
+ * omok_versus_run included; omok_selfplay_run_slots returns OMOK_ERR_STATE (refilled slots would start from the empty board). */
+int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards);
 /* Match episode: net 1 against net 2 (benchmark/src/main.rs:14-108).  Agent::new of every agent with its OWN net (agent.rs:16-35): in games
  * [0, split) net 1 plays Black (tree side 0) and net 2 White (side 1); in games [split, G) the colours are reversed (main.rs plays half of
  * its games each way).  0 <= split <= G.  RNG streams, the episode counter and the replay buffer as omok_selfplay_reset.  Until the next
@@ -232,8 +259,9 @@ int omok_opponent_actions(omok_engine* e, int32_t kind, int32_t* actions);
  * tree of side opponent_side is kept in step like with any external move (both agents of a game, see omok_play_actions); it is never
  * searched, and costs one shared root-row evaluation per game and ply.  Transitions are recorded on the net's plies only (the moves
  * omok_sample_actions chose): the replay buffer of an evaluation episode is not training data and is discarded by the next
- * omok_selfplay_reset.  OMOK_ERR_STATE in a match episode or when the episode is not at ply 0, OMOK_ERR_INVALID for an unknown kind or
- * opponent_side. */
+ * omok_selfplay_reset.  After omok_selfplay_reset_from the episode starts at the positions' ply: opponent_side still decides who moves on which
+ * ply (Black to move and opponent_side = 1: the first ply is a search).  OMOK_ERR_STATE in a match episode or when moves were played since the
+ * reset, OMOK_ERR_INVALID for an unknown kind or opponent_side. */
 int omok_versus_run(omok_engine* e, int32_t kind, int32_t opponent_side, int32_t count, int32_t batch_size, float epsilon, float alpha,
                     int32_t max_plies, int32_t* results, double* stats);
 
@@ -242,7 +270,7 @@ int omok_versus_run(omok_engine* e, int32_t kind, int32_t opponent_side, int32_t
    games (omok_selfplay_run on an engine with games = total_games): a game's RNG streams are keyed by game_offset + index and its own
    ply, trees are independent (bit for bit with board_size 9 or OMOK_NET_F16X3_ROWS / OMOK_NET_F32; in the default net mode at
    board_size 15 a row's p / v carry ~5e-5 of rounding that depends on the path a round takes, see OMOK_NET_F16X3_ROWS).  Call after
-   omok_selfplay_reset.  Finished games' transitions are appended to records_dev (device memory, cap_records records of
+   omok_selfplay_reset (OMOK_ERR_STATE after omok_selfplay_reset_from).  Finished games' transitions are appended to records_dev (device memory, cap_records records of
    omok_replay_record_bytes, the omok_replay_pack_dev format) in completion order; per game index: game_offsets[i] = first record,
    game_lengths[i] = records, game_status[i] = OMOK_STATUS_* (arrays of total_games, may be NULL); *n_records = records written.
    Extends src/trainer.rs:95-205 (the reference removes finished games from its agent list and lets the batch shrink). */
@@ -280,6 +308,9 @@ int omok_game_info(omok_engine* e, uint8_t* alive, uint8_t* status, int32_t* pli
 int omok_tree_dump(omok_engine* e, int32_t game, int32_t side, int32_t* ints, float* floats, int32_t cap_nodes);
 int omok_tree_root(omok_engine* e, int32_t game, int32_t side, uint32_t* root_n, float* root_w,
                    int32_t* n_nodes, int32_t* n_tables);
+/* MCTS::root's n and w (mcts/src/lib.rs:34-36, node.rs:10-21) of the side-to-move agent of every game, n [G], w [G]: omok_tree_root for all
+ * games in one kernel and one copy (0 for finished games).  With omok_compute_policy: what an analysis caller reads after omok_execute. */
+int omok_root_stats(omok_engine* e, uint32_t* n, float* w);
 /* Node::children of a root in insertion order (mcts/src/node.rs:10-21; MCTS::root, mcts/src/lib.rs:34-36): action, n, w and
  * p (= root.policy[action], which the reference keeps equal to child.p) of the first min(children, cap) children.  Returns
  * the number of children.  Any output may be NULL. */

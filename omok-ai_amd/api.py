@@ -10,6 +10,8 @@ Names follow the reference so parity tests read like its own code:
   Engine.load_weights2 / load2     the second agent's AgentModel of benchmark/src/main.rs:14-108
   SelfPlay.match_reset             benchmark/src/main.rs: net 1 against net 2, half of the games per colour
   SelfPlay.versus_run              Trainer::play_against_naive_player / _play_against_random_player, src/trainer.rs:400-603
+  Environment.check_positions      the rules of Environment::place_stone read backwards: is a given board a position of a game in progress?
+  SelfPlay.reset_from / analyze    Agent::new (agent.rs:16-35) on given positions instead of Environment::new()
 All compute happens in the HIP library; nothing here has a CPU path.
 """
 import ctypes as C
@@ -154,6 +156,15 @@ class Engine:
         self._chk(B.lib().omok_env_scripted_actions(self.h, int(kind), B.u8ptr(boards), B.u8ptr(turns), len(boards), B.iptr(forced)))
         return forced
 
+    def env_check_positions(self, boards):
+        """omok_env_check_positions on caller-held boards [B][HW] (bytes): (verdict int32 [B], stones int32 [B]); verdict 0 = a legal position
+        of a game in progress, 1 bad byte, 2 impossible stone counts, 3 already won, 4 full board; the side to move is stones & 1"""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
+        verdict = np.zeros(len(boards), dtype=np.int32)
+        stones = np.zeros(len(boards), dtype=np.int32)
+        self._chk(B.lib().omok_env_check_positions(self.h, B.u8ptr(boards), len(boards), B.iptr(verdict), B.iptr(stones)))
+        return verdict, stones
+
     def encode_nn_input(self, boards, turns, mode=B.MODE_PLAYER):
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
         turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
@@ -222,6 +233,11 @@ class Environment:
         s = int(self.eng.env_place_stone(self._board, self._turn, self._legal, [int(index)])[0])
         return None if s < 0 else s
 
+    @staticmethod
+    def check_positions(engine, boards):
+        """(verdict [B], stones [B]) of caller-supplied boards [B][HW]: Engine.env_check_positions"""
+        return engine.env_check_positions(boards)
+
     def encode_board(self, turn):
         """Environment::encode_board(turn): the first 2*HW floats of the NN input with that perspective."""
         t = np.array([turn], dtype=np.uint8)
@@ -239,6 +255,21 @@ class SelfPlay:
 
     def reset(self):
         self._chk(B.lib().omok_selfplay_reset(self.h))
+
+    def reset_from(self, boards):
+        """Agent::new for both agents of every game on the given positions (omok_selfplay_reset_from): boards [G][HW] Stone bytes, all with
+        the same stone count, each a legal position of a game in progress (Environment.check_positions).  The episode starts at ply =
+        stone count; a rejected call (OmokError -5 / -1) leaves the engine as it was."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1)
+        assert boards.size == self.games * self.hw
+        self._chk(B.lib().omok_selfplay_reset_from(self.h, B.u8ptr(boards)))
+
+    def root_stats(self):
+        """(root_n uint32 [G], root_w float32 [G]) of the side-to-move agents (omok_root_stats); 0 for finished games"""
+        n = np.zeros(self.games, dtype=np.uint32)
+        w = np.zeros(self.games, dtype=np.float32)
+        self._chk(B.lib().omok_root_stats(self.h, n.ctypes.data_as(C.POINTER(C.c_uint32)), B.fptr(w)))
+        return n, w
 
     def match_reset(self, split):
         """Match episode (omok_match_reset): in games [0, split) net 1 plays Black and net 2 White, in [split, G) the reverse; every
@@ -477,3 +508,15 @@ class SelfPlay:
         if n < 0:
             raise B.OmokError(int(n), B.lib().omok_last_error(self.h).decode())
         return int(n)
+
+
+def analyze(engine, boards, count, batch_size, epsilon=0.0, alpha=0.03):
+    """Batched analysis: searches the given positions (boards [G][HW] Stone bytes, G = the engine's games, equal stone counts) with `count`
+    simulations each, from fresh agents (SelfPlay.reset_from).  Returns (pi [G][HW] = Agent::compute_policy of the side to move, root_n [G],
+    root_w [G]).  epsilon = 0: no Dirichlet noise on the roots."""
+    sp = SelfPlay(engine)
+    sp.reset_from(boards)
+    sp.execute(count, batch_size, epsilon, alpha)
+    pi, _ = sp.compute_policy()
+    n, w = sp.root_stats()
+    return pi, n, w

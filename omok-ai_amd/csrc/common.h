@@ -109,6 +109,14 @@ struct RoundArgs {
 
 // ---- tree_kernels.hip launchers (all asynchronous on `st`) ---------------------------------
 void launch_reset(int n, const Store& S, const float* root_policy_dev /*ROWP*/, hipStream_t st);
+// Agent::new on caller-supplied positions (omok_selfplay_reset_from): boards_dev [G][HW] Stone bytes that passed launch_position_check,
+// p_dev [G][ROWP] = evaluate_p of the positions (Player mode, game order); both trees of game g start at position g
+void launch_reset_from(int n, const Store& S, const uint8_t* boards_dev, const float* p_dev, hipStream_t st);
+// boards_dev [B][HW] bytes -> verdict_dev [B] (0 legal and in progress, 1 bad byte, 2 impossible stone counts, 3 already won, 4 full board),
+// stones_dev [B] (may be NULL)
+void launch_position_check(int n, const uint8_t* boards_dev, int batch, int32_t* verdict_dev, int32_t* stones_dev, hipStream_t st);
+// root_n / root_w of the trees of `side` of every game (0 for finished games)
+void launch_root_stats(const Store& S, int side, uint32_t* n_dev, float* w_dev, hipStream_t st);
 // slots mode (omok_selfplay_run_slots): finished games are packed out (records appended at *out_count, per-game meta by game index) and their
 // slots restarted with the next game indices while any are left
 struct SlotMeta { long long offset; int32_t len; int32_t status; }; // per game index: first record, records, final GameStatus

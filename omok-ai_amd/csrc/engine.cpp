@@ -79,6 +79,7 @@ struct omok_engine {
     std::vector<void*> allocs;
     std::string err;
     int ply = 0;
+    int start_ply = 0;     // ply the episode started at: 0, or the stone count of the positions of omok_selfplay_reset_from
     bool reset_done = false;
     bool sampled = false;
     uint64_t episode = 0;  // index of the RNG stream the NEXT omok_selfplay_reset takes (one reset = one trainer iteration)
@@ -693,6 +694,7 @@ static int reset_episode(omok_engine* e, bool match, int split) {
     e->key = e->cfg.seed + e->episode * 0x9E3779B97F4A7C15ULL; // a fresh RNG stream per episode (the reference draws thread_rng anew, trainer.rs:71-93)
     e->episode += 1;
     e->ply = 0;
+    e->start_ply = 0;
     e->reset_done = true;
     e->sampled = false;
     e->round_reqs = e->mirror_reqs = -1;
@@ -716,6 +718,99 @@ extern "C" int omok_match_reset(omok_engine* e, int32_t split) {
     if (split < 0 || split > e->cfg.games) return fail(e, OMOK_ERR_INVALID, "split %d outside [0, games = %d]", split, e->cfg.games);
     HIPCHK(e, hipSetDevice(e->cfg.device));
     return reset_episode(e, true, split);
+}
+
+// ---- episodes from given positions ----------------------------------------------------------------
+static const char* verdict_text(int v) {
+    switch (v) {
+    case 1: return "a byte that is not a Stone (> 2)";
+    case 2: return "stone counts that no alternating game produces";
+    case 3: return "the position is already won";
+    case 4: return "no empty cell (Draw)";
+    default: return "legal";
+    }
+}
+
+// uploads `batch` boards and runs k_position_check on them; *d_boards_out (non-NULL: the caller frees it) keeps the device copy
+static int check_positions(omok_engine* e, const uint8_t* boards, int batch, int32_t* verdict_out, int32_t* stones_out, uint8_t** d_boards_out) {
+    uint8_t* d_boards = nullptr;
+    int32_t* d_out = nullptr; // [2][B] verdicts, stone counts
+    const size_t B = (size_t)batch;
+    HIPCHK(e, hipMalloc((void**)&d_boards, B * e->hw));
+    if (hipMalloc((void**)&d_out, 2 * B * 4) != hipSuccess) { hipFree(d_boards); return fail(e, OMOK_ERR_HIP, "position check: device allocation failed"); }
+    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
+    launch_position_check(e->n, d_boards, batch, d_out, d_out + B, e->st);
+    hipMemcpyAsync(verdict_out, d_out, B * 4, hipMemcpyDeviceToHost, e->st);
+    if (stones_out) hipMemcpyAsync(stones_out, d_out + B, B * 4, hipMemcpyDeviceToHost, e->st);
+    const int rc = sync_and_check(e, "position check");
+    hipFree(d_out);
+    if (rc || !d_boards_out) hipFree(d_boards);
+    else *d_boards_out = d_boards;
+    return rc ? OMOK_ERR_HIP : OMOK_OK;
+}
+
+// the rules of Environment::place_stone (environment/src/lib.rs:104-166) read backwards: can an alternating game from Environment::new() be in
+// this position, still in progress?
+extern "C" int omok_env_check_positions(omok_engine* e, const uint8_t* boards, int32_t batch, int32_t* verdict_out, int32_t* stones_out) {
+    if (!e || !boards || !verdict_out || batch < 1) return OMOK_ERR_INVALID;
+    ENTER(e);
+    return check_positions(e, boards, batch, verdict_out, stones_out, nullptr);
+}
+
+// Agent::new (agent.rs:16-35) for both agents of every game on a given environment: evaluate_p of the position in Player mode (:19-20), masked
+// and renormalised over its stones like every policy the reference stores on a non-empty board (ensure_action_exists, :166-171)
+extern "C" int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards) {
+    if (!e || !boards) return OMOK_ERR_INVALID;
+    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    ENTER(e);
+    const int G = e->cfg.games;
+    std::vector<int32_t> verdict((size_t)G), stones((size_t)G);
+    uint8_t* d_boards = nullptr;
+    if (check_positions(e, boards, G, verdict.data(), stones.data(), &d_boards)) return OMOK_ERR_HIP;
+    // nothing of the engine has been touched so far: a rejected call leaves trees, games, episode counter and replay buffer as they were
+    for (int g = 0; g < G; ++g)
+        if (verdict[g] != 0) {
+            hipFree(d_boards);
+            return fail(e, OMOK_ERR_ILLEGAL, "game %d: verdict %d (%s)", g, verdict[g], verdict_text(verdict[g]));
+        }
+    for (int g = 1; g < G; ++g)
+        if (stones[g] != stones[0]) {
+            hipFree(d_boards);
+            return fail(e, OMOK_ERR_INVALID, "game %d has %d stones, game 0 has %d: all games of an episode share the side to move", g, stones[g], stones[0]);
+        }
+    const int s0 = stones[0];
+    if (s0 == 0) { // Environment::new() everywhere: omok_selfplay_reset's own path (one empty-board row, nothing to mask)
+        hipFree(d_boards);
+        return reset_episode(e, false, 0);
+    }
+    auto done = [&](int rc) { hipFree(d_boards); return rc; };
+    uint8_t* d_turns = nullptr;
+    if (hipMalloc((void**)&d_turns, (size_t)G) != hipSuccess) return done(fail(e, OMOK_ERR_HIP, "reset_from: device allocation failed"));
+    // the G positions as plain rows in game order: the launch omok_evaluate_pv makes for the same rows (G <= the net batch)
+    hipMemsetAsync(d_turns, s0 & 1, (size_t)G, e->st);
+    hipMemcpyAsync(e->S.d_count, &G, sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+    e->prof.begin(PC_PLY, e->st);
+    launch_encode_boards(e->n, d_boards, d_turns, G, OMOK_MODE_PLAYER, e->net.in_f32, e->st);
+    e->prof.end(e->st);
+    net_forward_inputs(e->net, e->S, G, e->st, &e->prof);
+    e->prof.begin(PC_PLY, e->st);
+    launch_reset_from(e->n, e->S, d_boards, e->net.p, e->st);
+    e->prof.end(e->st);
+    invalidate_nets(e);
+    const int rc = sync_and_check(e, "selfplay_reset_from");
+    hipFree(d_turns);
+    if (rc) return done(OMOK_ERR_HIP);
+    e->evals += G;
+    e->key = e->cfg.seed + e->episode * 0x9E3779B97F4A7C15ULL; // as omok_selfplay_reset: every reset is one trainer iteration
+    e->episode += 1;
+    e->ply = s0; // a game's ply is its stone count: side = ply & 1, the RNG counters
+    e->start_ply = s0;
+    e->reset_done = true;
+    e->sampled = false;
+    e->round_reqs = e->mirror_reqs = -1;
+    e->match = false;
+    e->split = 0;
+    return done(OMOK_OK);
 }
 
 static int need_reset(omok_engine* e) {
@@ -1036,6 +1131,7 @@ extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int3
     if (total_games < G) return fail(e, OMOK_ERR_INVALID, "total_games (%d) must be >= the engine's game slots (%d)", total_games, G);
     if (!records_dev || cap_records < 1) return fail(e, OMOK_ERR_INVALID, "records buffer required (omok_replay_record_bytes per record)");
     if (no_match(e, "omok_selfplay_run_slots")) return OMOK_ERR_STATE;
+    if (e->start_ply != 0) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots after omok_selfplay_reset_from: refilled slots would start from the empty board");
     if (e->ply != 0) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots starts from a fresh omok_selfplay_reset (ply %d)", e->ply);
     ENTER(e);
     uint8_t* d_mask = nullptr;
@@ -1213,7 +1309,8 @@ extern "C" int omok_versus_run(omok_engine* e, int32_t kind, int32_t opponent_si
     if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
     if (opponent_side != 0 && opponent_side != 1) return fail(e, OMOK_ERR_INVALID, "opponent_side %d is neither 0 (Black) nor 1 (White)", opponent_side);
     if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
-    if (e->ply != 0) return fail(e, OMOK_ERR_STATE, "omok_versus_run starts at ply 0: call omok_selfplay_reset first (the episode is at ply %d)", e->ply);
+    if (e->ply != e->start_ply)
+        return fail(e, OMOK_ERR_STATE, "omok_versus_run starts at a fresh reset: %d move(s) were played since (the episode is at ply %d)", e->ply - e->start_ply, e->ply);
     HIPCHK(e, hipSetDevice(e->cfg.device));
     uint32_t bits = 0, alive = 0;
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
@@ -1541,6 +1638,23 @@ extern "C" int omok_tree_root(omok_engine* e, int32_t game, int32_t side, uint32
     if (root_w) *root_w = ts.root_w;
     if (n_nodes) *n_nodes = (int32_t)ts.n_nodes;
     if (n_tables) *n_tables = (int32_t)ts.n_tables;
+    return OMOK_OK;
+}
+
+// root_n / root_w of the side-to-move tree of every game: what an analysis caller reads beside omok_compute_policy
+extern "C" int omok_root_stats(omok_engine* e, uint32_t* n, float* w) {
+    if (!e || !n || !w) return OMOK_ERR_INVALID;
+    if (need_reset(e)) return OMOK_ERR_STATE;
+    ENTER(e);
+    const size_t G = (size_t)e->cfg.games;
+    uint32_t* d_n = (uint32_t*)e->d_pi; // (omok_compute_policy's staging buffer, [G][HW] f32: 2 G words fit)
+    float* d_w = e->d_pi + G;
+    launch_root_stats(e->S, e->ply & 1, d_n, d_w, e->st);
+    std::vector<uint32_t> host(2 * G);
+    HIPCHK(e, hipMemcpyAsync(host.data(), e->d_pi, 8 * G, hipMemcpyDeviceToHost, e->st));
+    if (sync_and_check(e, "root_stats")) return OMOK_ERR_HIP;
+    memcpy(n, host.data(), 4 * G);
+    memcpy(w, host.data() + G, 4 * G);
     return OMOK_OK;
 }
 

@@ -201,6 +201,26 @@ __device__ inline float seq_sum(const float* s, int n) {
     return acc;
 }
 
+// The mask-and-renormalise step of Agent::ensure_action_exists (agent.rs:166-171): s_row [ROWP] (LDS) = p_row with the occupied cells of bb
+// (black NW | white NW words), the cell `action` (the stone about to be placed; -1: none) and the pad cells set to 0; the sequential f32 sum
+// in ascending cell order decides the renormalisation: a stored element is renorm ? x * inv : x.  All 64 lanes call; renorm, inv wave-uniform.
+template <int N>
+__device__ inline void masked_policy_row(const uint64_t* bb, int action, const float* __restrict__ p_row, float* s_row, bool& renorm, float& inv) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int lane = LANE;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const bool empty = a < G::HW && !(((bb[j] | bb[NW + j]) >> lane) & 1ULL);
+        s_row[a] = (empty && a != action) ? p_row[a] : 0.0f; // agent.rs:166-171
+    }
+    __syncthreads();
+    const float sum = seq_sum(s_row, G::HW);
+    renorm = F32_EPS <= sum;
+    inv = renorm ? __fdiv_rn(1.0f, sum) : 1.0f;
+}
+
 // The same sequential sum over a row held in REGISTERS (x[j] of lane l = element 64 j + l): element by element through v_readlane,
 // ascending -- the same additions in the same order as seq_sum, without 225 dependent LDS round trips (~16 k cycles per row, the
 // whole run time of k_scatter_policy).  Wave-uniform result.
@@ -1579,6 +1599,69 @@ __global__ __launch_bounds__(64) void k_reset(Store S, const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_reset_from: Agent::new (agent.rs:16-35) for both trees of every game on a caller-supplied environment instead of Environment::new()
+// (omok_selfplay_reset_from; the boards passed k_position_check).  Workgroup = one wave = one tree.  boards [G][HW] Stone bytes,
+// P [G][ROWP] = evaluate_p of the positions in Player mode, game order.  The root is the node the reference holds after the position's moves
+// were played as external moves: a policy masked and renormalised over the position's stones (masked_policy_row), n = 0, w = 0 -- without
+// the history (action NONE).
+// ---------------------------------------------------------------------------------------------
+template <int N>
+__global__ __launch_bounds__(64) void k_reset_from(Store S, const uint8_t* __restrict__ boards, const float* __restrict__ P) {
+    using G = Geo<N>;
+    constexpr int ROWP = G::ROWP, NW = G::NW;
+    __shared__ float s_row[ROWP];
+    const int t = blockIdx.x;
+    const int g = t < S.games ? t : t - S.games;
+    const int lane = LANE;
+    const Tree<N> T(S, t);
+    uint64_t bb[2 * NW];
+    int stones = 0;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const int s = a < G::HW ? boards[(size_t)g * G::HW + a] : 0;
+        bb[j] = __ballot(s == 1);
+        bb[NW + j] = __ballot(s == 2);
+        stones += __popcll(bb[j]) + __popcll(bb[NW + j]);
+    }
+    bool renorm;
+    float inv;
+    masked_policy_row<N>(bb, -1, P + (size_t)g * ROWP, s_row, renorm, inv);
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const float x = s_row[a];
+        T.pol[a] = renorm ? x * inv : x;
+    }
+#pragma unroll
+    for (int i = 0; i < 2 * NW; ++i)
+        if (lane == i) T.board[i] = bb[i];
+    if (lane == 0) {
+        NodeHdr h;
+        h.parent = NONE16; h.table = NONE16; h.legal = (uint16_t)(G::HW - stones); h.nch = 0;
+        h.action = NONE8; h.status = ST_IN_PROGRESS; h.turn = (uint8_t)(stones & 1); h.has_policy = 1; h.pad = 0;
+        T.hdr[0] = h;
+        TreeState s{1u, 0u, 0u, 0.0f, 0u, 0u, 0u, 0u};
+        *T.ts = s;
+        if (t < S.games) {
+            GameState gs{};
+            gs.alive = 1; gs.status = ST_IN_PROGRESS; gs.plies = stones; gs.last_action = -1; gs.mirror_idx = -1; gs.gid = t;
+            S.gs[t] = gs;
+        }
+    }
+}
+
+// the side-to-move roots' visit count and value sum of every game (omok_root_stats): finished games report 0
+__global__ __launch_bounds__(256) void k_root_stats(Store S, int side, uint32_t* __restrict__ n, float* __restrict__ w) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= S.games) return;
+    const bool alive = S.gs[g].alive != 0;
+    const TreeState ts = S.ts[side * S.games + g];
+    n[g] = alive ? ts.root_n : 0u;
+    w[g] = alive ? ts.root_w : 0.0f;
+}
+
+// ---------------------------------------------------------------------------------------------
 // slots mode: harvest finished games, restart their slots (omok_selfplay_run_slots)
 // ---------------------------------------------------------------------------------------------
 // one workgroup: slots whose game is over and not yet harvested, in slot order -> record offsets (appended at *out_count), per-game meta
@@ -1947,6 +2030,51 @@ __global__ __launch_bounds__(64) void k_env_scripted(const uint8_t* __restrict__
     if (lane == 0) forced[b] = cell;
 }
 
+// k_position_check: is a caller-supplied board a position an alternating game from Environment::new() can be in, and still in progress?
+// boards [B][HW] bytes -> verdict [B], the first that applies: 1 a byte that is no Stone (> 2); 2 stone counts no alternating game produces
+// (neither black = white nor black = white + 1); 3 already won: some stone, taken as the last one placed, makes exactly five in one of the
+// four line pairs (place_stone, environment/src/lib.rs:151-159; a run of six or more is no win); 4 no empty cell (Draw, :160-161); 0 legal.
+// stones [B] (may be NULL) = Black + White bytes; the side to move is stones & 1.  Workgroup = one wave = one position.
+template <int N>
+__global__ __launch_bounds__(64) void k_position_check(const uint8_t* __restrict__ boards, int32_t* __restrict__ verdict, int32_t* __restrict__ stones) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int b = blockIdx.x;
+    const int lane = LANE;
+    uint64_t bb[2 * NW];
+    int nb = 0, nwh = 0;
+    bool bad = false, won = false;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
+        bb[j] = __ballot(s == 1);
+        bb[NW + j] = __ballot(s == 2);
+        bad = bad || __ballot(s > 2) != 0ULL;
+        nb += __popcll(bb[j]);
+        nwh += __popcll(bb[NW + j]);
+    }
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) { // (the rays of five_in_pair start next to the cell: `own` may hold the stone itself)
+        const int a = j * 64 + lane;
+        const int c = a < G::HW ? a : 0;
+        const bool isb = a < G::HW && ((bb[j] >> lane) & 1ULL), isw = a < G::HW && ((bb[NW + j] >> lane) & 1ULL);
+        bool five = false;
+#pragma unroll
+        for (int pr = 0; pr < 4; ++pr) five = five || (isb && five_in_pair<N>(bb, c, pr)) || (isw && five_in_pair<N>(bb + NW, c, pr));
+        won = won || __ballot(five) != 0ULL;
+    }
+    int v = 0;
+    if (bad) v = 1;
+    else if (nb != nwh && nb != nwh + 1) v = 2;
+    else if (won) v = 3;
+    else if (nb + nwh == G::HW) v = 4;
+    if (lane == 0) {
+        verdict[b] = v;
+        if (stones) stones[b] = nb + nwh;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_mirror_scan: NN requests of ensure_action_exists (agent.rs:153-158) for every live game
 // ---------------------------------------------------------------------------------------------
@@ -2144,16 +2272,9 @@ __device__ void ensure_action_exists(const Store& S, const Tree<N>& T, int actio
     uint64_t bb[2 * NW];
 #pragma unroll
     for (int i = 0; i < 2 * NW; ++i) bb[i] = T.board[i];
-#pragma unroll
-    for (int j = 0; j < G::IT; ++j) {
-        const int a = j * 64 + lane;
-        const bool empty = a < G::HW && !(((bb[j] | bb[NW + j]) >> lane) & 1ULL);
-        s_row[a] = (empty && a != action) ? p_row[a] : 0.0f; // agent.rs:166-171
-    }
-    __syncthreads();
-    const float sum = seq_sum(s_row, G::HW);
-    const bool renorm = F32_EPS <= sum;
-    const float inv = renorm ? __fdiv_rn(1.0f, sum) : 1.0f;
+    bool renorm;
+    float inv;
+    masked_policy_row<N>(bb, action, p_row, s_row, renorm, inv);
     const bool exists = h0.table != NONE16 && T.corder[(size_t)h0.table * ROWP + action] != NONE8;
     if (!exists) { // node.rs:69-71 returns None when the child is already there
         const TreeState ts = *T.ts;
@@ -2547,6 +2668,15 @@ size_t advance_lds_bytes(int cap_nodes, int cap_tables) {
 
 void launch_reset(int n, const Store& S, const float* rp, hipStream_t st) {
     DISPATCH_N(n, (k_reset<9><<<2 * S.games, 64, 0, st>>>(S, rp)), (k_reset<15><<<2 * S.games, 64, 0, st>>>(S, rp)));
+}
+void launch_reset_from(int n, const Store& S, const uint8_t* boards, const float* p, hipStream_t st) {
+    DISPATCH_N(n, (k_reset_from<9><<<2 * S.games, 64, 0, st>>>(S, boards, p)), (k_reset_from<15><<<2 * S.games, 64, 0, st>>>(S, boards, p)));
+}
+void launch_position_check(int n, const uint8_t* boards, int batch, int32_t* verdict, int32_t* stones, hipStream_t st) {
+    DISPATCH_N(n, (k_position_check<9><<<batch, 64, 0, st>>>(boards, verdict, stones)), (k_position_check<15><<<batch, 64, 0, st>>>(boards, verdict, stones)));
+}
+void launch_root_stats(const Store& S, int side, uint32_t* n_dev, float* w_dev, hipStream_t st) {
+    k_root_stats<<<(S.games + 255) / 256, 256, 0, st>>>(S, side, n_dev, w_dev);
 }
 void launch_round(int n, const Store& S, const RoundArgs& a, hipStream_t st) {
     DISPATCH_N(n, (k_round<9><<<S.games, 64, 0, st>>>(S, a)), (k_round<15><<<S.games, 64, 0, st>>>(S, a)));

@@ -152,11 +152,13 @@ class Trainer:
                 f"[v_loss={v_loss:.4f}, p_loss={p_loss:.4f}]" + versus)
         return v_loss, p_loss, loss
 
-    def evaluate(self):
+    def evaluate(self, openings=None):
         """play_against_naive_player (src/trainer.rs:487-603) with the weights just saved: `evaluate_games` games on an engine of its own
         (arenas sized for `test_evaluate_count`), the scripted naive player is Black and moves first, the net answers as White with
         `test_evaluate_count` simulations and sample_action(Best).  The reference prints Black's wins as "Win" although Black is the naive
-        player (:387-393); train() logs the three counts by colour, on the iteration's line.  Returns (black_win, white_win, draw)."""
+        player (:387-393); train() logs the three counts by colour, on the iteration's line.  openings: None = every game from the empty board
+        like the reference, or [evaluate_games, HW] Stone bytes = the position each game starts from (equal stone counts; the side the stone
+        count gives moves first, the naive player stays Black).  Returns (black_win, white_win, draw)."""
         p = self.p
         sims = -(-p.test_evaluate_count // p.evaluate_batch_size) * p.evaluate_batch_size
         max_nodes = min(16384, 4 * sims + 1024)
@@ -166,7 +168,10 @@ class Trainer:
             eng.load(os.path.join(self.save_dir, p.model_name))
             sp = api.SelfPlay(eng)
             sp.set_episode(self.iteration - 1)
-            sp.reset()
+            if openings is None:
+                sp.reset()
+            else:
+                sp.reset_from(np.ascontiguousarray(openings, dtype=np.uint8).reshape(p.evaluate_games, self.n * self.n))
             (black, white, draw), _ = sp.versus_run(api.B.OPP_NAIVE, 0, p.test_evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha)
         finally:
             eng.close()
