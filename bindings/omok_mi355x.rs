@@ -129,9 +129,11 @@ pub mod ffi {
         pub fn omok_encode_nn_input(e: *mut OmokEngine, boards: *const u8, turns: *const u8, batch: i32, mode: i32, out: *mut f32) -> c_int;
         pub fn omok_env_place_stone(e: *mut OmokEngine, boards: *mut u8, turns: *mut u8, legal: *mut u16, actions: *const i32, batch: i32, status_out: *mut i32) -> c_int;
         pub fn omok_env_check_positions(e: *mut OmokEngine, boards: *const u8, batch: i32, verdict_out: *mut i32, stones_out: *mut i32) -> c_int;
+        pub fn omok_env_random_positions(e: *mut OmokEngine, key: u64, first_game: i64, stones: i32, batch: i32, boards_out: *mut u8, ok_out: *mut u8) -> c_int;
         pub fn omok_selfplay_reset(e: *mut OmokEngine) -> c_int;
         pub fn omok_selfplay_reset_from(e: *mut OmokEngine, boards: *const u8) -> c_int;
         pub fn omok_match_reset(e: *mut OmokEngine, split: i32) -> c_int;
+        pub fn omok_match_reset_from(e: *mut OmokEngine, split: i32, boards: *const u8) -> c_int;
         pub fn omok_set_episode(e: *mut OmokEngine, episode: u64) -> c_int;
         pub fn omok_execute(e: *mut OmokEngine, count: i32, batch_size: i32, epsilon: f32, alpha: f32) -> c_int;
         pub fn omok_execute_shared(e: *mut OmokEngine, count: i32, batch_size: i32, epsilon: f32, alpha: f32, waves: i32) -> c_int;

@@ -146,6 +146,20 @@ int omok_env_place_stone(omok_engine* e, uint8_t* boards, uint8_t* turns, uint16
  * caller-held form, like omok_env_scripted_actions). */
 int omok_env_check_positions(omok_engine* e, const uint8_t* boards, int32_t batch, int32_t* verdict_out, int32_t* stones_out);
 
+/* Random openings on the device: an opening book without a file, for the match of benchmark/src/main.rs:14-108, which starts every game at
+ * Environment::new() and so plays (nearly) one game per colour assignment.  Position b of boards_out [batch][N*N] (Stone bytes) is the
+ * board after `stones` plies of the game with global id first_game + b in which BOTH sides are the OMOK_OPP_RANDOM player of
+ * _play_against_random_player (src/trainer.rs:452-455), with RNG key `key`: ply i (side i & 1, Black first) puts its stone on the r-th empty
+ * cell in ascending order, r = mulhi(x0, N*N - i), x0 = word 0 of Philox(key, 0, i, low 32 bits of 2 (first_game + b) + (i & 1), purpose 4)
+ * -- the draw omok_opponent_actions makes for that game and ply; no new RNG purpose.  If a placement ends the game
+ * (place_stone(..).is_terminal(), environment/src/lib.rs:104-166: exactly five in a line) placing stops, ok_out[b] = 0 and the board holds
+ * the stones up to and including that one; otherwise ok_out[b] = 1 and the board has verdict 0 under omok_env_check_positions with exactly
+ * `stones` stones.  0 <= stones < N*N and batch >= 1, else OMOK_ERR_INVALID.  Touches no engine state and needs no net (the batched,
+ * caller-held form, like omok_env_check_positions); a position depends on (key, first_game + b, stones) only, not on how a range of games
+ * is cut into calls. */
+int omok_env_random_positions(omok_engine* e, uint64_t key, int64_t first_game, int32_t stones, int32_t batch, uint8_t* boards_out,
+                              uint8_t* ok_out);
+
 /* ---- self-play: G games x two agents (src/trainer.rs:81-205) ---------------------------- */
 /* Agent::new for both agents of every game (alpha-zero/src/agent.rs:16-35): root policy = raw
  * evaluate_p of the empty board.  Also clears the replay buffer.  Every reset is one trainer iteration
@@ -180,6 +194,25 @@ int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards);
  * omok_selfplay_run_slots return OMOK_ERR_STATE in a match episode.  OMOK_ERR_STATE without a committed net 2, OMOK_ERR_INVALID for a
  * split outside [0, G]. */
 int omok_match_reset(omok_engine* e, int32_t split);
+/* omok_match_reset on a GIVEN environment, as omok_selfplay_reset_from is omok_selfplay_reset on one: a match from an opening book
+ * (benchmark/src/main.rs:14-108 can only start at Environment::new(); Agent::new of every agent with its own net, agent.rs:16-35).
+ * boards [G][N*N] Stone bytes, the position of each game; split as in omok_match_reset: in games [0, split) net 1 owns the Black tree (side
+ * 0) and net 2 the White tree, in [split, G) the reverse -- whichever side the position gives the move to.  Root policy of tree side * G + g
+ * = evaluate_p of position g in Player mode (agent.rs:19-20) computed by net side ^ (g >= split), with every occupied cell set to 0 and then
+ * scaled by 1.0f / sum iff f32::EPSILON <= sum (ensure_action_exists, agent.rs:166-171; the device function omok_selfplay_reset_from and
+ * omok_advance use).  The root has n = 0, w = 0, no parent, no table, no action; legal = N*N - stones, turn = stones & 1.  Every game has one
+ * tree of each net, so each net evaluates all G positions as one plain-row batch in game order: net 1's rows are bit-identical to
+ * omok_evaluate_pv of the same G rows on this engine, net 2's to omok_evaluate_pv on an engine that holds net 2's weights in slot 1 (same
+ * net_mode); omok_net2_info's evals count G rows for each net.  The games' plies, omok_current_ply and the ply the episode started at are
+ * the stone count; the count of moves sampled (Boltzmann threshold, replay length) is 0; episode counter and RNG key as in every reset; the
+ * replay buffer is cleared; the episode is a match with this split.
+ * Checked in this order: net 1 committed, else OMOK_ERR_STATE; net 2 committed, else OMOK_ERR_STATE; 0 <= split <= G, else
+ * OMOK_ERR_INVALID; every omok_env_check_positions verdict 0, else OMOK_ERR_ILLEGAL; equal stone counts, else OMOK_ERR_INVALID (the message
+ * names the first offending game).  A rejected call leaves the engine exactly as it was: trees, games, match / split, the episode counter
+ * and the replay buffer.  With no stone on any board this IS omok_match_reset.
+ * Afterwards every call behaves as after omok_match_reset: omok_play_actions, omok_execute_shared(_recorded), omok_selfplay_run_slots,
+ * omok_versus_run and omok_opponent_actions return OMOK_ERR_STATE. */
+int omok_match_reset_from(omok_engine* e, int32_t split, const uint8_t* boards);
 /* index of the RNG stream the NEXT omok_selfplay_reset uses (resuming a training run at iteration i: omok_set_episode(e, i)) */
 int omok_set_episode(omok_engine* e, uint64_t episode);
 /* ParallelMCTSExecutor::execute (alpha-zero/src/parallel_mcts_executor.rs:26-35) on the

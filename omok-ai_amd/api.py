@@ -12,6 +12,8 @@ Names follow the reference so parity tests read like its own code:
   SelfPlay.versus_run              Trainer::play_against_naive_player / _play_against_random_player, src/trainer.rs:400-603
   Environment.check_positions      the rules of Environment::place_stone read backwards: is a given board a position of a game in progress?
   SelfPlay.reset_from / analyze    Agent::new (agent.rs:16-35) on given positions instead of Environment::new()
+  SelfPlay.match_reset_from        the match of benchmark/src/main.rs from given positions (an opening book), each agent with its own net
+  Environment.random_positions     an opening book without a file: positions after s plies of _play_against_random_player's moves on both sides
 All compute happens in the HIP library; nothing here has a CPU path.
 """
 import ctypes as C
@@ -165,6 +167,15 @@ class Engine:
         self._chk(B.lib().omok_env_check_positions(self.h, B.u8ptr(boards), len(boards), B.iptr(verdict), B.iptr(stones)))
         return verdict, stones
 
+    def env_random_positions(self, key, first_game, stones, batch):
+        """omok_env_random_positions: (boards uint8 [batch][HW], ok uint8 [batch]); position b = `stones` plies of the game with global id
+        first_game + b, both sides the RANDOM scripted player under RNG key `key`; ok 0 = a placement ended the game and the board stops there"""
+        boards = np.zeros((int(batch), self.hw), dtype=np.uint8)
+        ok = np.zeros(int(batch), dtype=np.uint8)
+        self._chk(B.lib().omok_env_random_positions(self.h, int(key) & 0xFFFFFFFFFFFFFFFF, int(first_game), int(stones), int(batch),
+                                                    B.u8ptr(boards), B.u8ptr(ok)))
+        return boards, ok
+
     def encode_nn_input(self, boards, turns, mode=B.MODE_PLAYER):
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
         turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
@@ -238,6 +249,11 @@ class Environment:
         """(verdict [B], stones [B]) of caller-supplied boards [B][HW]: Engine.env_check_positions"""
         return engine.env_check_positions(boards)
 
+    @staticmethod
+    def random_positions(engine, key, first_game, stones, batch):
+        """(boards [batch][HW], ok [batch]) of random openings with `stones` stones: Engine.env_random_positions"""
+        return engine.env_random_positions(key, first_game, stones, batch)
+
     def encode_board(self, turn):
         """Environment::encode_board(turn): the first 2*HW floats of the NN input with that perspective."""
         t = np.array([turn], dtype=np.uint8)
@@ -263,6 +279,13 @@ class SelfPlay:
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1)
         assert boards.size == self.games * self.hw
         self._chk(B.lib().omok_selfplay_reset_from(self.h, B.u8ptr(boards)))
+
+    def match_reset_from(self, split, boards):
+        """Match episode on the given positions (omok_match_reset_from): boards [G][HW] as for reset_from, split as for match_reset (in games
+        [0, split) net 1 owns the Black tree, whichever side is to move).  A rejected call (OmokError -3 / -1 / -5) leaves the engine as it was."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1)
+        assert boards.size == self.games * self.hw
+        self._chk(B.lib().omok_match_reset_from(self.h, int(split), B.u8ptr(boards)))
 
     def root_stats(self):
         """(root_n uint32 [G], root_w float32 [G]) of the side-to-move agents (omok_root_stats); 0 for finished games"""

@@ -35,6 +35,7 @@ SYMBOLS = [
     "omok_compute_policy", "omok_play_actions", "omok_set_actions", "omok_root_children",
     "omok_env_scripted_actions", "omok_opponent_actions", "omok_versus_run",
     "omok_env_check_positions", "omok_selfplay_reset_from", "omok_root_stats",
+    "omok_match_reset_from", "omok_env_random_positions",
     "omok_sample_actions", "omok_advance", "omok_selfplay_run", "omok_selfplay_run_slots", "omok_round_generate", "omok_round_inputs",
     "omok_round_eval", "omok_round_outputs", "omok_round_logits", "omok_round_inject", "omok_round_scatter", "omok_mirror_generate",
     "omok_mirror_inputs", "omok_mirror_eval", "omok_mirror_outputs", "omok_mirror_inject", "omok_mirror_apply",
@@ -113,6 +114,8 @@ def lib():
     L.omok_versus_run.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, ip, C.POINTER(C.c_double)]
     L.omok_env_check_positions.argtypes = [H, u8p, C.c_int32, ip, ip]
     L.omok_selfplay_reset_from.argtypes = [H, u8p]
+    L.omok_match_reset_from.argtypes = [H, C.c_int32, u8p]
+    L.omok_env_random_positions.argtypes = [H, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, u8p, u8p]
     L.omok_root_stats.argtypes = [H, C.POINTER(C.c_uint32), fp]
     L.omok_root_children.argtypes = [H, C.c_int32, C.c_int32, ip, C.POINTER(C.c_uint32), fp, fp, C.c_int32]
     L.omok_execute.argtypes = [H, C.c_int32, C.c_int32, C.c_float, C.c_float]

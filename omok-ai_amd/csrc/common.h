@@ -110,8 +110,12 @@ struct RoundArgs {
 // ---- tree_kernels.hip launchers (all asynchronous on `st`) ---------------------------------
 void launch_reset(int n, const Store& S, const float* root_policy_dev /*ROWP*/, hipStream_t st);
 // Agent::new on caller-supplied positions (omok_selfplay_reset_from): boards_dev [G][HW] Stone bytes that passed launch_position_check,
-// p_dev [G][ROWP] = evaluate_p of the positions (Player mode, game order); both trees of game g start at position g
-void launch_reset_from(int n, const Store& S, const uint8_t* boards_dev, const float* p_dev, hipStream_t st);
+// p_dev [G][ROWP] = evaluate_p of the positions (Player mode, game order); both trees of game g start at position g.  p2_dev non-NULL
+// (omok_match_reset_from): the same rows from net 2; tree side * G + g takes the row of net side ^ (g >= split)
+void launch_reset_from(int n, const Store& S, const uint8_t* boards_dev, const float* p_dev, const float* p2_dev, int split, hipStream_t st);
+// random openings: position b = `stones` plies of the game with global id first_game + b, both sides the RANDOM scripted player drawing like
+// launch_opponent_move -> boards_dev [B][HW] Stone bytes, ok_dev [B] (0: a placement ended the game, the board stops there)
+void launch_random_positions(int n, uint64_t key, int64_t first_game, int stones, int batch, uint8_t* boards_dev, uint8_t* ok_dev, hipStream_t st);
 // boards_dev [B][HW] bytes -> verdict_dev [B] (0 legal and in progress, 1 bad byte, 2 impossible stone counts, 3 already won, 4 full board),
 // stones_dev [B] (may be NULL)
 void launch_position_check(int n, const uint8_t* boards_dev, int batch, int32_t* verdict_dev, int32_t* stones_dev, hipStream_t st);

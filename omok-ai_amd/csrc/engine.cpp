@@ -757,12 +757,12 @@ extern "C" int omok_env_check_positions(omok_engine* e, const uint8_t* boards, i
     return check_positions(e, boards, batch, verdict_out, stones_out, nullptr);
 }
 
-// Agent::new (agent.rs:16-35) for both agents of every game on a given environment: evaluate_p of the position in Player mode (:19-20), masked
-// and renormalised over its stones like every policy the reference stores on a non-empty board (ensure_action_exists, :166-171)
-extern "C" int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards) {
-    if (!e || !boards) return OMOK_ERR_INVALID;
-    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
-    ENTER(e);
+// Agent::new (agent.rs:16-35) for the agents of every game on a given environment: evaluate_p of the position in Player mode (:19-20), masked
+// and renormalised over its stones like every policy the reference stores on a non-empty board (ensure_action_exists, :166-171).  The part
+// omok_selfplay_reset_from and omok_match_reset_from share: check, upload, encode, one plain-row forward of the G positions per net, the root
+// kernel and the bookkeeping.  match: tree side * G + g takes the row of net side ^ (g >= split).  The caller has checked the nets and split.
+static int reset_from_positions(omok_engine* e, const uint8_t* boards, bool match, int split) {
+    const char* what = match ? "match_reset_from" : "selfplay_reset_from";
     const int G = e->cfg.games;
     std::vector<int32_t> verdict((size_t)G), stones((size_t)G);
     uint8_t* d_boards = nullptr;
@@ -779,28 +779,33 @@ extern "C" int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards) {
             return fail(e, OMOK_ERR_INVALID, "game %d has %d stones, game 0 has %d: all games of an episode share the side to move", g, stones[g], stones[0]);
         }
     const int s0 = stones[0];
-    if (s0 == 0) { // Environment::new() everywhere: omok_selfplay_reset's own path (one empty-board row, nothing to mask)
+    if (s0 == 0) { // Environment::new() everywhere: the ordinary reset's own path (one empty-board row per net, nothing to mask)
         hipFree(d_boards);
-        return reset_episode(e, false, 0);
+        return reset_episode(e, match, split);
     }
     auto done = [&](int rc) { hipFree(d_boards); return rc; };
     uint8_t* d_turns = nullptr;
-    if (hipMalloc((void**)&d_turns, (size_t)G) != hipSuccess) return done(fail(e, OMOK_ERR_HIP, "reset_from: device allocation failed"));
-    // the G positions as plain rows in game order: the launch omok_evaluate_pv makes for the same rows (G <= the net batch)
+    if (hipMalloc((void**)&d_turns, (size_t)G) != hipSuccess) return done(fail(e, OMOK_ERR_HIP, "%s: device allocation failed", what));
+    // the G positions as plain rows in game order: the launch omok_evaluate_pv makes for the same rows (G <= the net batch); in a match every
+    // game has one tree of each net, so each net evaluates all G rows
     hipMemsetAsync(d_turns, s0 & 1, (size_t)G, e->st);
     hipMemcpyAsync(e->S.d_count, &G, sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+    for (int i = 0; i < (match ? 2 : 1); ++i) {
+        Net& X = net_at(e, i);
+        e->prof.begin(PC_PLY, e->st);
+        launch_encode_boards(e->n, d_boards, d_turns, G, OMOK_MODE_PLAYER, X.in_f32, e->st);
+        e->prof.end(e->st);
+        net_forward_inputs(X, e->S, G, e->st, &e->prof);
+        if (match) k_add_evals<<<1, 64, 0, e->st>>>(e->S.d_count, e->d_mevals + i); // rows per net (omok_net2_info)
+    }
     e->prof.begin(PC_PLY, e->st);
-    launch_encode_boards(e->n, d_boards, d_turns, G, OMOK_MODE_PLAYER, e->net.in_f32, e->st);
-    e->prof.end(e->st);
-    net_forward_inputs(e->net, e->S, G, e->st, &e->prof);
-    e->prof.begin(PC_PLY, e->st);
-    launch_reset_from(e->n, e->S, d_boards, e->net.p, e->st);
+    launch_reset_from(e->n, e->S, d_boards, e->net.p, match ? e->net2->p : nullptr, split, e->st);
     e->prof.end(e->st);
     invalidate_nets(e);
-    const int rc = sync_and_check(e, "selfplay_reset_from");
+    const int rc = sync_and_check(e, what);
     hipFree(d_turns);
     if (rc) return done(OMOK_ERR_HIP);
-    e->evals += G;
+    e->evals += match ? 2 * G : G;
     e->key = e->cfg.seed + e->episode * 0x9E3779B97F4A7C15ULL; // as omok_selfplay_reset: every reset is one trainer iteration
     e->episode += 1;
     e->ply = s0; // a game's ply is its stone count: side = ply & 1, the RNG counters
@@ -808,9 +813,47 @@ extern "C" int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards) {
     e->reset_done = true;
     e->sampled = false;
     e->round_reqs = e->mirror_reqs = -1;
-    e->match = false;
-    e->split = 0;
+    e->match = match;
+    e->split = match ? split : 0;
     return done(OMOK_OK);
+}
+
+extern "C" int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards) {
+    if (!e || !boards) return OMOK_ERR_INVALID;
+    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    ENTER(e);
+    return reset_from_positions(e, boards, false, 0);
+}
+
+// omok_match_reset on given environments: an opening book for benchmark/src/main.rs:14-108, Agent::new of every agent with its own net
+extern "C" int omok_match_reset_from(omok_engine* e, int32_t split, const uint8_t* boards) {
+    if (!e || !boards) return OMOK_ERR_INVALID;
+    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    if (!e->net2 || !e->net2->committed) return fail(e, OMOK_ERR_STATE, "net 2 not loaded/committed (omok_net2_load x31 + omok_net2_commit)");
+    if (split < 0 || split > e->cfg.games) return fail(e, OMOK_ERR_INVALID, "split %d outside [0, games = %d]", split, e->cfg.games);
+    ENTER(e);
+    return reset_from_positions(e, boards, true, split);
+}
+
+// Random openings: the board after `stones` plies of a game both of whose sides are the RANDOM scripted player (src/trainer.rs:452-455), on
+// caller-held memory like omok_env_check_positions; ok = 0 where a placement ended the game (the board holds the stones up to that one)
+extern "C" int omok_env_random_positions(omok_engine* e, uint64_t key, int64_t first_game, int32_t stones, int32_t batch, uint8_t* boards_out,
+                                         uint8_t* ok_out) {
+    if (!e || !boards_out || !ok_out) return OMOK_ERR_INVALID;
+    if (stones < 0 || stones >= e->hw) return fail(e, OMOK_ERR_INVALID, "stones %d outside [0, %d)", stones, e->hw);
+    if (batch < 1) return fail(e, OMOK_ERR_INVALID, "batch %d < 1", batch);
+    ENTER(e);
+    uint8_t* d_out = nullptr; // [B][HW] boards, then [B] ok
+    const size_t B = (size_t)batch;
+    HIPCHK(e, hipMalloc((void**)&d_out, B * e->hw + B));
+    e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling: tools/reset_from_timing.py)
+    launch_random_positions(e->n, key, first_game, stones, batch, d_out, d_out + B * e->hw, e->st);
+    e->prof.end(e->st);
+    hipMemcpyAsync(boards_out, d_out, B * e->hw, hipMemcpyDeviceToHost, e->st);
+    hipMemcpyAsync(ok_out, d_out + B * e->hw, B, hipMemcpyDeviceToHost, e->st);
+    const int rc = sync_and_check(e, "env_random_positions");
+    hipFree(d_out);
+    return rc ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 static int need_reset(omok_engine* e) {

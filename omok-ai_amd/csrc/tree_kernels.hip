@@ -1603,16 +1603,19 @@ __global__ __launch_bounds__(64) void k_reset(Store S, const float* __restrict__
 // (omok_selfplay_reset_from; the boards passed k_position_check).  Workgroup = one wave = one tree.  boards [G][HW] Stone bytes,
 // P [G][ROWP] = evaluate_p of the positions in Player mode, game order.  The root is the node the reference holds after the position's moves
 // were played as external moves: a policy masked and renormalised over the position's stones (masked_policy_row), n = 0, w = 0 -- without
-// the history (action NONE).
+// the history (action NONE).  MATCH (omok_match_reset_from): P2 = the same rows from net 2; tree side * G + g takes the row of the net that
+// owns it, side ^ (g >= split), whichever side the position gives the move to.
 // ---------------------------------------------------------------------------------------------
-template <int N>
-__global__ __launch_bounds__(64) void k_reset_from(Store S, const uint8_t* __restrict__ boards, const float* __restrict__ P) {
+template <int N, bool MATCH>
+__global__ __launch_bounds__(64) void k_reset_from(Store S, const uint8_t* __restrict__ boards, const float* __restrict__ P, const float* __restrict__ P2,
+                                                   int split) {
     using G = Geo<N>;
     constexpr int ROWP = G::ROWP, NW = G::NW;
     __shared__ float s_row[ROWP];
     const int t = blockIdx.x;
     const int g = t < S.games ? t : t - S.games;
     const int lane = LANE;
+    if (MATCH) P = ((t < S.games ? 0 : 1) ^ (g >= split ? 1 : 0)) ? P2 : P;
     const Tree<N> T(S, t);
     uint64_t bb[2 * NW];
     int stones = 0;
@@ -2073,6 +2076,47 @@ __global__ __launch_bounds__(64) void k_position_check(const uint8_t* __restrict
         verdict[b] = v;
         if (stones) stones[b] = nb + nwh;
     }
+}
+
+// k_random_positions: random openings (omok_env_random_positions).  Position b = the board after `stones` plies of the game with global id
+// first_game + b in which BOTH sides are the RANDOM scripted player: ply i (side i & 1, Black first) makes k_opponent_move's draw -- word 0 of
+// Philox(key, 0, i, 2 id + side, RNG_OPPONENT) -> scripted_random_cell with HW - i empty cells.  A placement that ends the game
+// (place_stone(..).is_terminal(): exactly five through the new stone; stones < HW, so no Draw) stops the game: ok = 0 and the board holds the
+// stones up to that one.  Workgroup = one wave = one position; the bitboards stay in registers, one byte store of the board at the end.
+template <int N>
+__global__ __launch_bounds__(64) void k_random_positions(uint64_t key, int64_t first_game, int stones, uint8_t* __restrict__ boards, uint8_t* __restrict__ ok) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int b = blockIdx.x;
+    const int lane = LANE;
+    const int64_t id = first_game + b;
+    uint64_t bb[2 * NW];
+#pragma unroll
+    for (int i = 0; i < 2 * NW; ++i) bb[i] = 0ULL;
+    bool over = false;
+    for (int i = 0; i < stones && !over; ++i) {
+        const int side = i & 1;
+        const U4 o = philox(key, 0u, (uint32_t)i, (uint32_t)(id * 2 + side), RNG_OPPONENT);
+        const int cell = scripted_random_cell<N>(bb, G::HW - i, o.x);
+        // lanes 0..3: one line pair each; the rays start next to the cell, so the mover's words need not hold the new stone yet
+        const bool five = side == 0 ? five_in_pair<N>(bb, cell, lane & 3) : five_in_pair<N>(bb + NW, cell, lane & 3);
+        over = __ballot(lane < 4 && five) != 0ULL;
+        uint64_t stone[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) stone[w] = 0ULL;
+        set_bit<NW>(stone, cell);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            bb[w] |= side == 0 ? stone[w] : 0ULL;
+            bb[NW + w] |= side == 0 ? 0ULL : stone[w];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        if (a < G::HW) boards[(size_t)b * G::HW + a] = (uint8_t)(((bb[j] >> lane) & 1ULL) ? 1 : (((bb[NW + j] >> lane) & 1ULL) ? 2 : 0));
+    }
+    if (lane == 0) ok[b] = over ? 0 : 1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2669,8 +2713,17 @@ size_t advance_lds_bytes(int cap_nodes, int cap_tables) {
 void launch_reset(int n, const Store& S, const float* rp, hipStream_t st) {
     DISPATCH_N(n, (k_reset<9><<<2 * S.games, 64, 0, st>>>(S, rp)), (k_reset<15><<<2 * S.games, 64, 0, st>>>(S, rp)));
 }
-void launch_reset_from(int n, const Store& S, const uint8_t* boards, const float* p, hipStream_t st) {
-    DISPATCH_N(n, (k_reset_from<9><<<2 * S.games, 64, 0, st>>>(S, boards, p)), (k_reset_from<15><<<2 * S.games, 64, 0, st>>>(S, boards, p)));
+void launch_reset_from(int n, const Store& S, const uint8_t* boards, const float* p, const float* p2, int split, hipStream_t st) {
+    if (p2)
+        DISPATCH_N(n, (k_reset_from<9, true><<<2 * S.games, 64, 0, st>>>(S, boards, p, p2, split)),
+                   (k_reset_from<15, true><<<2 * S.games, 64, 0, st>>>(S, boards, p, p2, split)));
+    else
+        DISPATCH_N(n, (k_reset_from<9, false><<<2 * S.games, 64, 0, st>>>(S, boards, p, nullptr, 0)),
+                   (k_reset_from<15, false><<<2 * S.games, 64, 0, st>>>(S, boards, p, nullptr, 0)));
+}
+void launch_random_positions(int n, uint64_t key, int64_t first_game, int stones, int batch, uint8_t* boards, uint8_t* ok, hipStream_t st) {
+    DISPATCH_N(n, (k_random_positions<9><<<batch, 64, 0, st>>>(key, first_game, stones, boards, ok)),
+               (k_random_positions<15><<<batch, 64, 0, st>>>(key, first_game, stones, boards, ok)));
 }
 void launch_position_check(int n, const uint8_t* boards, int batch, int32_t* verdict, int32_t* stones, hipStream_t st) {
     DISPATCH_N(n, (k_position_check<9><<<batch, 64, 0, st>>>(boards, verdict, stones)), (k_position_check<15><<<batch, 64, 0, st>>>(boards, verdict, stones)));

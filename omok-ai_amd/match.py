@@ -6,6 +6,11 @@ Half of the games (games [0, G/2)) have the first net as Black, the other half t
 own tree with its own net, mirrors the opponent's move with its own net (ensure_action_exists, main.rs:79-82,99-102) and plays the
 most visited move (sample_action(Best) with EPSILON = 0, ALPHA = 1: benchmark/src/agent.rs:14-15,34-49).  Prints wins, losses and
 draws from the first net's side and returns them with the per-game results.
+
+From the empty board with Best moves the G games of a colour assignment are one game but for the expansion draws.  With an opening book
+(--openings FILE.npy, [M][HW] Stone bytes, or --random-openings S: M = games / 2 positions of S random stones made on the device from
+--seed) games i and i + M both start from opening i, once with each net as Black (omok_match_reset_from, split = M), and the result is
+also counted per opening (paired_tally).
 """
 import argparse
 import json
@@ -33,6 +38,9 @@ def parse_args(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--net-mode", default="NET_F16X3", help="binding constant of the net mode (NET_F16X3, NET_F16X3_ROWS, NET_F32, ...)")
     ap.add_argument("--json", action="store_true", help="print the result as one JSON line as well")
+    ap.add_argument("--openings", metavar="FILE.npy", help="opening book [M][HW] Stone bytes (equal stone counts), M = games / 2: each opening is played "
+                    "twice, once with each net as Black")
+    ap.add_argument("--random-openings", type=int, metavar="S", help="the same with games / 2 random positions of S stones made on the device from --seed")
     return ap.parse_args(argv)
 
 
@@ -46,11 +54,42 @@ def tally(status, split):
     return wins, losses, draws
 
 
-def run_match(eng, games, sims, batch, threshold=0, temperature=1.0):
-    """One match episode on an engine whose two net slots are loaded; returns (wins, losses, draws, status [G], stats)."""
+def paired_tally(status, m):
+    """(both, one_each, neither, drawn_pairs) over the M openings, from the first net's side: opening i was played as game i (first net Black)
+    and as game i + M (first net White).  both / neither: the first net won / lost both games; one_each: one win and one loss (the colour
+    decided); drawn_pairs: either game was a draw.  The four sum to M."""
+    status = np.asarray(status).reshape(-1)
+    assert status.size == 2 * m
+    as_black, as_white = status[:m], status[m:]
+    drawn = (as_black == api.DRAW) | (as_white == api.DRAW)
+    won = (as_black == api.BLACK_WIN).astype(np.int64) + (as_white == api.WHITE_WIN).astype(np.int64)
+    return tuple(int(np.sum(~drawn & (won == w))) for w in (2, 1, 0)) + (int(np.sum(drawn)),)
+
+
+def random_openings(eng, key, stones, count, chunk=None):
+    """`count` random openings of `stones` stones (Environment.random_positions under RNG key `key`): consecutive ranges of game ids from 0,
+    the positions of games still in progress kept in id order -- the book depends on (key, stones, count) only"""
+    chunk = chunk or max(64, 2 * count)
+    kept, first = [], 0
+    while sum(len(k) for k in kept) < count:
+        boards, ok = api.Environment.random_positions(eng, key, first, stones, chunk)
+        kept.append(boards[ok == 1])
+        first += chunk
+    return np.concatenate(kept)[:count]
+
+
+def run_match(eng, games, sims, batch, threshold=0, temperature=1.0, openings=None):
+    """One match episode on an engine whose two net slots are loaded; returns (wins, losses, draws, status [G], stats).  openings [M][HW]
+    (the engine has games = 2 M): games i and i + M start from opening i, the first net Black in the first half (split = M)."""
     sp = api.SelfPlay(eng)
     split = games // 2
-    sp.match_reset(split)
+    if openings is None:
+        sp.match_reset(split)
+    else:
+        openings = np.ascontiguousarray(openings, dtype=np.uint8).reshape(-1, eng.hw)
+        if games != 2 * len(openings) or eng.games != games:
+            raise ValueError(f"{len(openings)} openings need an engine of {2 * len(openings)} games, not {games}")
+        sp.match_reset_from(split, np.concatenate([openings, openings]))
     stats = sp.run(sims, batch, epsilon=EPSILON, alpha=ALPHA, temperature=temperature, threshold=threshold)
     alive, status, _ = sp.game_info()
     if alive.any():
@@ -61,13 +100,23 @@ def run_match(eng, games, sims, batch, threshold=0, temperature=1.0):
 
 def main(argv=None):
     a = parse_args(argv)
+    book = a.openings is not None or a.random_openings is not None
+    if a.openings is not None and a.random_openings is not None:
+        raise SystemExit("--openings and --random-openings exclude each other")
+    if book and a.games % 2:
+        raise SystemExit("--games must be even with openings: each opening is played once with each net as Black")
     max_nodes = a.max_nodes or min(16384, 4 * a.sims + 1024)
     eng = api.Engine(board_size=a.board, games=a.games, max_nodes=max_nodes, max_tables=max(256, max_nodes // 4), max_batch_k=a.batch,
                      device=a.device, net_mode=getattr(B, a.net_mode), seed=a.seed)
     try:
         eng.load(a.net1)
         eng.load2(a.net2)
-        w, l, d, status, stats = run_match(eng, a.games, a.sims, a.batch, a.threshold, a.temperature)
+        openings = None
+        if a.openings is not None:
+            openings = np.load(a.openings)
+        elif a.random_openings is not None:
+            openings = random_openings(eng, a.seed, a.random_openings, a.games // 2)
+        w, l, d, status, stats = run_match(eng, a.games, a.sims, a.batch, a.threshold, a.temperature, openings=openings)
         info = eng.net2_info()
     finally:
         eng.close()
@@ -75,8 +124,14 @@ def main(argv=None):
     print(f"{'':12s}{'wins':>8s}{'losses':>8s}{'draws':>8s}")
     print(f"{'first net':12s}{w:8d}{l:8d}{d:8d}")
     print(f"{'second net':12s}{l:8d}{w:8d}{d:8d}")
+    paired = paired_tally(status, a.games // 2) if book else None
+    if paired is not None:
+        print(f"{a.games // 2} openings, each played with both colours: the first net won both games of {paired[0]}, one of {paired[1]}, "
+              f"neither of {paired[2]}; {paired[3]} with a draw")
     result = {"games": a.games, "wins": w, "losses": l, "draws": d, "status": [int(s) for s in status],
               "fc0_format": [B.FC0_FORMATS[int(stats["fc0_format"])], info["fc0_format"]], "evals": list(info["evals"])}
+    if paired is not None:
+        result["paired"] = dict(zip(("both", "one_each", "neither", "drawn_pairs"), paired))
     if a.json:
         print(json.dumps({k: v for k, v in result.items() if k != "status"}))
     return result

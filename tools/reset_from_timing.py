@@ -1,5 +1,6 @@
 """omok_selfplay_reset_from beside omok_selfplay_reset at G = 4096, N = 15: HIP-event kernel time (the engine's own per-category events) and
-the wall-clock time of the blocking call (`python tools/reset_from_timing.py [OUT.txt]`)."""
+the wall-clock time of the blocking call (`python tools/reset_from_timing.py [--match] [OUT.txt]`).  --match: the same for
+omok_match_reset_from beside omok_match_reset (two random-init nets), and k_random_positions at 4096 positions of 8 and of 100 stones."""
 import os
 import sys
 import time
@@ -11,15 +12,21 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))  # (positions.quiet: the boards)
 import omok_ai_amd as oa
 import positions as P
 
+args = [a for a in sys.argv[1:] if a != "--match"]
+match = "--match" in sys.argv[1:]
 n, games, k = 15, 4096, 16
 eng = oa.Engine(board_size=n, games=games, max_nodes=64, max_tables=16, max_batch_k=k, seed=1)
 eng.load_random_weights(0)
+if match:
+    eng.load_weights2(oa.weights.init_random(n, seed=1))
 sp = oa.SelfPlay(eng)
 boards = P.quiet(n, games, 8, seed=1)
 eng.set_profiling(1)
 KEYS = ("ms_trunk", "ms_fc0", "ms_tail", "ms_ply")
 out = []
-for name, call in (("omok_selfplay_reset", sp.reset), ("omok_selfplay_reset_from", lambda: sp.reset_from(boards))):
+
+
+def timed(name, call, ply_label):
     for _ in range(3):
         call()
     wall, ev = [], []
@@ -33,9 +40,20 @@ for name, call in (("omok_selfplay_reset", sp.reset), ("omok_selfplay_reset_from
     med = {kk: float(np.median([e[kk] for e in ev])) for kk in KEYS}
     line = (f"{name}: wall-clock of the blocking call median {np.median(wall):.3f} ms (min {min(wall):.3f}, max {max(wall):.3f}); HIP events, median: "
             f"net forward {med['ms_trunk'] + med['ms_fc0'] + med['ms_tail']:.3f} ms (trunk {med['ms_trunk']:.3f}, fc0 {med['ms_fc0']:.3f}, tail {med['ms_tail']:.3f}), "
-            f"encode + k_reset_from {med['ms_ply']:.3f} ms")
+            f"{ply_label} {med['ms_ply']:.3f} ms")
     print(line)
     out.append(line)
-if len(sys.argv) > 1:
-    open(sys.argv[1], "w").write("\n".join(out) + "\n")
+
+
+if match:
+    split = games // 2
+    timed("omok_match_reset", lambda: sp.match_reset(split), "encode + k_reset_from")
+    timed("omok_match_reset_from", lambda: sp.match_reset_from(split, boards), "encode + k_reset_from")
+    for stones in (8, 100):
+        timed(f"omok_env_random_positions, {games} positions of {stones} stones", lambda: eng.env_random_positions(1, 0, stones, games), "k_random_positions")
+else:
+    timed("omok_selfplay_reset", sp.reset, "encode + k_reset_from")
+    timed("omok_selfplay_reset_from", lambda: sp.reset_from(boards), "encode + k_reset_from")
+if args:
+    open(args[0], "w").write("\n".join(out) + "\n")
 eng.close()
