@@ -161,6 +161,14 @@ pub mod ffi {
         pub fn omok_mirror_outputs(e: *mut OmokEngine, p: *mut f32) -> c_int;
         pub fn omok_mirror_inject(e: *mut OmokEngine, p: *const f32) -> c_int;
         pub fn omok_mirror_apply(e: *mut OmokEngine) -> c_int;
+        pub fn omok_train_begin(e: *mut OmokEngine, max_batch: i32) -> c_int;
+        pub fn omok_train_end(e: *mut OmokEngine) -> c_int;
+        pub fn omok_train_step(e: *mut OmokEngine, records_dev: *const c_void, n_records: i64, indices: *const i64, batch: i32, losses: *mut f32) -> c_int;
+        pub fn omok_train_losses(e: *mut OmokEngine, records_dev: *const c_void, n_records: i64, indices: *const i64, batch: i32, losses: *mut f32) -> c_int;
+        pub fn omok_train_batch_indices(e: *mut OmokEngine, n_records: i64, batch: i32, key: u64, step: i32, out: *mut i64) -> c_int;
+        pub fn omok_train_run(e: *mut OmokEngine, records_dev: *const c_void, n_records: i64, update_count: i32, batch_size: i32, key: u64, losses: *mut f32) -> c_int;
+        pub fn omok_debug_train_gradient(e: *mut OmokEngine, index: i32, out: *mut f32, count: i64) -> c_int;
+        pub fn omok_net_read(e: *mut OmokEngine, index: i32, out: *mut f32, count: i64) -> c_int;
         pub fn omok_alive_count(e: *mut OmokEngine) -> c_int;
         pub fn omok_current_ply(e: *mut OmokEngine) -> c_int;
         pub fn omok_game_info(e: *mut OmokEngine, alive: *mut u8, status: *mut u8, plies: *mut i32) -> c_int;

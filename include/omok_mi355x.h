@@ -331,6 +331,39 @@ int omok_mirror_outputs(omok_engine* e, float* p);
 int omok_mirror_inject(omok_engine* e, const float* p);
 int omok_mirror_apply(omok_engine* e);
 
+/* ---- training phase of Trainer::train (src/trainer.rs:329-357) on the device: AgentModel::train (alpha-zero/src/agent_model.rs:136-168) in plain fp32 on
+ *      the 31 raw tensors of net 1 -- the graph of network.rs:51-262, the losses of network.rs:249-253 / agent_model.rs:57-73, and the
+ *      AdadeltaOptimizer of agent_model.rs:24,75-82 (lr 0.01, rho 0.95, eps 1e-8, TensorFlow ApplyAdadelta: one zero-initialised accumulator pair per
+ *      variable).  Records are the packed replay records of omok_replay_augment_dev in device memory.  Every sum has a fixed order: the same calls on
+ *      the same inputs leave the same bits.  All of them: OMOK_ERR_STATE before omok_train_begin; OMOK_ERR_INVALID for batch < 1, batch > max_batch,
+ *      n_records < 1 or an index outside [0, n_records).  A rejected call leaves weights, accumulators and the committed state as they were. */
+/* The session's optimizer state (AdadeltaOptimizer::minimize creates the accumulators, agent_model.rs:75-82) plus gradients and activations for
+ * batches of up to max_batch (<= 4096) records.  Needs all 31 tensors loaded.  A second call starts a fresh optimizer. */
+int omok_train_begin(omok_engine* e, int32_t max_batch);
+/* frees them (omok_destroy does too) */
+int omok_train_end(omok_engine* e);
+/* One AgentModel::train (agent_model.rs:136-168) on records indices[0 .. batch) (a host array): encode_nn_input(Player) and encode_nn_targets
+ * (encoder.rs:10-68), one minimize run, THEN the three losses evaluated after the update.  losses [3] (may be NULL) = v_loss, p_loss, loss, the
+ * order of the reference's log line (trainer.rs:354-362).  Leaves net 1 uncommitted like omok_net_load: omok_net_commit before the next search. */
+int omok_train_step(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* indices, int32_t batch, float* losses);
+/* the forward and the three losses only (the fetches of agent_model.rs:150-166 without the minimize target): changes nothing; a held-out loss */
+int omok_train_losses(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* indices, int32_t batch, float* losses);
+/* The batch of step `step` of a run with RNG key `key`: choose_multiple of trainer.rs:329-350 (uniform, without replacement; the reference is
+ * unseeded).  k = min(batch, n_records) indices in draw order: index i is the mulhi(x0, n_records - i)-th record, 0-based and ascending, not among
+ * the first i drawn, x0 = word 0 of Philox4x32-10(key; i, step, 0, purpose 5).  out [k]; returns k. */
+int omok_train_batch_indices(omok_engine* e, int64_t n_records, int32_t batch, uint64_t key, int32_t step, int64_t* out);
+/* The update loop of trainer.rs:329-357: update_count steps, step s on the batch omok_train_batch_indices(n_records, batch_size, key, s) draws -- on
+ * the device, with no host synchronisation between steps.  losses [3] (may be NULL) = the means of the last min(update_count, 100) steps' v_loss,
+ * p_loss, loss (trainer.rs:354-362), summed on the device in step order.  Then commits net 1 as omok_net_commit does.  Weights and accumulators end
+ * bit for bit as after the loop of omok_train_batch_indices + omok_train_step. */
+int omok_train_run(omok_engine* e, const void* records_dev, int64_t n_records, int32_t update_count, int32_t batch_size, uint64_t key, float* losses);
+/* Debugging aid of the gradient tests (no reference counterpart): the gradient of tensor `index` the last omok_train_step / omok_train_run step
+ * applied, count = omok_net_tensor_size(index).  OMOK_ERR_STATE before the first step. */
+int omok_debug_train_gradient(omok_engine* e, int32_t index, float* out, int64_t count);
+/* The raw fp32 tensor `index` of net 1 as loaded or trained (Session::run fetch of a variable, model_io.rs:59-90 without the file),
+ * count = omok_net_tensor_size(index). */
+int omok_net_read(omok_engine* e, int32_t index, float* out, int64_t count);
+
 /* ---- inspection ------------------------------------------------------------------------ */
 int omok_alive_count(omok_engine* e);                  /* >= 0, or error */
 int omok_current_ply(omok_engine* e);

@@ -102,6 +102,63 @@ class Engine:
         self._chk(B.lib().omok_net2_info(self.h, C.byref(fmt), C.byref(outside), ev))
         return {"fc0_format": B.FC0_FORMATS[fmt.value], "probe_outside": outside.value, "evals": (ev[0], ev[1])}
 
+    # ---- native training step (AgentModel::train, agent_model.rs:136-168; Trainer::train's update loop, src/trainer.rs:329-357) ----
+    def read_weights(self):
+        """the 31 raw fp32 tensors of net 1 as loaded or trained (omok_net_read), flat, in the reference's variable order"""
+        out = []
+        for i in range(B.lib().omok_net_num_tensors()):
+            t = np.empty(int(B.lib().omok_net_tensor_size(self.h, i)), dtype=np.float32)
+            self._chk(B.lib().omok_net_read(self.h, i, B.fptr(t), t.size))
+            out.append(t)
+        return out
+
+    def train_begin(self, max_batch):
+        """a fresh AdadeltaOptimizer (zeroed accumulators) and the step's buffers for batches of up to max_batch records"""
+        self._chk(B.lib().omok_train_begin(self.h, int(max_batch)))
+
+    def train_end(self):
+        self._chk(B.lib().omok_train_end(self.h))
+
+    def _train_once(self, fn, records_ptr, n_records, indices):
+        idx = np.ascontiguousarray(indices, dtype=np.int64).ravel()
+        losses = np.zeros(3, dtype=np.float32)
+        self._chk(fn(self.h, C.c_void_p(int(records_ptr)), int(n_records), idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, B.fptr(losses)))
+        return float(losses[0]), float(losses[1]), float(losses[2])
+
+    def train_step(self, records_ptr, n_records, indices):
+        """one AgentModel::train on the packed replay records (device pointer) `indices` names: minimize, then (v_loss, p_loss, loss) after
+        the update.  Leaves the net uncommitted (commit() before searching)."""
+        return self._train_once(B.lib().omok_train_step, records_ptr, n_records, indices)
+
+    def train_losses(self, records_ptr, n_records, indices):
+        """(v_loss, p_loss, loss) of the current weights on those records; changes nothing"""
+        return self._train_once(B.lib().omok_train_losses, records_ptr, n_records, indices)
+
+    def train_batch_indices(self, n_records, batch, key, step):
+        """the record indices step `step` of train_run(key) draws: min(batch, n_records) distinct indices in draw order, int64"""
+        out = np.zeros(int(batch), dtype=np.int64)
+        k = self._chk(B.lib().omok_train_batch_indices(self.h, int(n_records), int(batch), int(key) & 0xFFFFFFFFFFFFFFFF, int(step),
+                                                       out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out[:k]
+
+    def train_run(self, records_ptr, n_records, update_count, batch_size, key):
+        """trainer.rs:329-357 in one blocking call: update_count steps on device-drawn batches, then the net is committed; returns the mean
+        (v_loss, p_loss, loss) of the last <= 100 steps"""
+        losses = np.zeros(3, dtype=np.float32)
+        self._chk(B.lib().omok_train_run(self.h, C.c_void_p(int(records_ptr)), int(n_records), int(update_count), int(batch_size),
+                                         int(key) & 0xFFFFFFFFFFFFFFFF, B.fptr(losses)))
+        return float(losses[0]), float(losses[1]), float(losses[2])
+
+    def train_gradient(self, index):
+        """gradient of tensor `index` the last step applied (omok_debug_train_gradient), flat"""
+        g = np.empty(int(B.lib().omok_net_tensor_size(self.h, index)), dtype=np.float32)
+        self._chk(B.lib().omok_debug_train_gradient(self.h, int(index), B.fptr(g), g.size))
+        return g
+
+    def commit(self):
+        """omok_net_commit: pack the raw tensors for the search (after train_step)"""
+        self._chk(B.lib().omok_net_commit(self.h))
+
     def evaluate_pv(self, inputs):
         x = np.ascontiguousarray(inputs, dtype=np.float32).reshape(-1, 3 * self.hw)
         b = x.shape[0]

@@ -42,6 +42,8 @@ SYMBOLS = [
     "omok_alive_count", "omok_current_ply", "omok_game_info", "omok_tree_dump", "omok_tree_root", "omok_replay_game",
     "omok_operand_row_bytes", "omok_debug_operand_rows", "omok_debug_set_base_cache", "omok_debug_set_children_kernel", "omok_debug_set_window_rects", "omok_debug_last_plan",
     "omok_replay_pack_dev", "omok_replay_record_bytes", "omok_replay_augment_dev", "omok_replay_augmented_game", "omok_get_stats", "omok_reset_stats", "omok_set_profiling",
+    "omok_train_begin", "omok_train_end", "omok_train_step", "omok_train_losses", "omok_train_batch_indices", "omok_train_run",
+    "omok_debug_train_gradient", "omok_net_read",
 ]
 
 
@@ -154,6 +156,15 @@ def lib():
     L.omok_get_stats.argtypes = [H, C.POINTER(C.c_double)]
     L.omok_reset_stats.argtypes = [H]
     L.omok_set_profiling.argtypes = [H, C.c_int32]
+    i64p = C.POINTER(C.c_int64)
+    L.omok_train_begin.argtypes = [H, C.c_int32]
+    L.omok_train_end.argtypes = [H]
+    L.omok_train_step.argtypes = [H, C.c_void_p, C.c_int64, i64p, C.c_int32, fp]
+    L.omok_train_losses.argtypes = [H, C.c_void_p, C.c_int64, i64p, C.c_int32, fp]
+    L.omok_train_batch_indices.argtypes = [H, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, i64p]
+    L.omok_train_run.argtypes = [H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, fp]
+    L.omok_debug_train_gradient.argtypes = [H, C.c_int32, fp, C.c_int64]
+    L.omok_net_read.argtypes = [H, C.c_int32, fp, C.c_int64]
     _lib = L
     return L
 

@@ -22,7 +22,7 @@ constexpr int KMAX = 64;
 constexpr float F32_EPS = 1.1920928955078125e-7f;
 
 enum { ST_IN_PROGRESS = 0, ST_DRAW = 1, ST_BLACK_WIN = 2, ST_WHITE_WIN = 3 };
-enum { RNG_EXPAND = 1, RNG_NOISE = 2, RNG_SAMPLE = 3, RNG_OPPONENT = 4 };
+enum { RNG_EXPAND = 1, RNG_NOISE = 2, RNG_SAMPLE = 3, RNG_OPPONENT = 4, RNG_TRAIN_BATCH = 5 };
 
 template <int N>
 struct Geo {

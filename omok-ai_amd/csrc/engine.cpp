@@ -9,7 +9,9 @@
 #include "../../include/omok_mi355x.h"
 #include "common.h"
 #include "net.h"
+#include "train.h"
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -108,6 +110,7 @@ struct omok_engine {
     int32_t* d_mcnt = nullptr;          // [0] rows of the first block (games < split), [1] of the second
     unsigned long long* d_mevals = nullptr; // [2] rows evaluated by net 1 / net 2 in match episodes
     float* d_root_policy2 = nullptr;
+    Train* train = nullptr;             // buffers and optimizer state of the native training step (omok_train_begin .. omok_train_end)
     // host-side stats
     double sims = 0, evals = 0, ply_games = 0, finished = 0;
     uint32_t peak_nodes = 0, peak_tables = 0;
@@ -197,6 +200,7 @@ extern "C" void omok_destroy(omok_engine* e) {
     e->prof.destroy();
     net_free(e->net);
     if (e->net2) { net_free(*e->net2); delete e->net2; }
+    if (e->train) { train_free(*e->train); delete e->train; }
     for (void* p : e->allocs) hipFree(p);
     if (e->st) hipStreamDestroy(e->st);
     delete e;
@@ -554,6 +558,124 @@ static int sync_and_check(omok_engine* e, const char* what) {
     hipError_t r = hipStreamSynchronize(e->st);
     if (r != hipSuccess) return fail(e, OMOK_ERR_HIP, "%s: %s", what, hipGetErrorString(r));
     return check_async(e, what);
+}
+
+// ---- native training step: AgentModel::train (alpha-zero/src/agent_model.rs:136-168), Trainer::train's update loop (src/trainer.rs:329-357) ----
+extern "C" int omok_net_read(omok_engine* e, int32_t index, float* out, int64_t count) {
+    if (!e || !out) return OMOK_ERR_INVALID;
+    if (index < 0 || index >= NET_TENSORS) return fail(e, OMOK_ERR_INVALID, "tensor index %d out of range", index);
+    if (count != e->net.wsize[index]) return fail(e, OMOK_ERR_INVALID, "tensor %d: expected %lld values, got %lld", index, (long long)e->net.wsize[index], (long long)count);
+    if (!e->net.loaded[index]) return fail(e, OMOK_ERR_STATE, "tensor %d was never loaded", index);
+    ENTER(e);
+    if (sync_and_check(e, "net_read")) return OMOK_ERR_HIP;
+    HIPCHK(e, hipMemcpy(out, e->net.w[index], sizeof(float) * (size_t)count, hipMemcpyDeviceToHost));
+    return OMOK_OK;
+}
+
+extern "C" int omok_train_end(omok_engine* e) {
+    ENTER(e);
+    if (!e->train) return OMOK_OK;
+    if (sync_and_check(e, "train_end")) return OMOK_ERR_HIP;
+    train_free(*e->train);
+    delete e->train;
+    e->train = nullptr;
+    return OMOK_OK;
+}
+
+extern "C" int omok_train_begin(omok_engine* e, int32_t max_batch) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (max_batch < 1 || max_batch > TRAIN_MAX_BATCH) return fail(e, OMOK_ERR_INVALID, "max_batch %d outside [1, %d]", max_batch, TRAIN_MAX_BATCH);
+    for (int i = 0; i < NET_TENSORS; ++i)
+        if (!e->net.loaded[i]) return fail(e, OMOK_ERR_STATE, "tensor %d was never loaded", i);
+    if (omok_train_end(e)) return OMOK_ERR_HIP; // (a second call starts a fresh optimizer)
+    Train* t = new Train();
+    if (train_alloc(*t, e->net, max_batch) == 0) { delete t; return fail(e, OMOK_ERR_HIP, "training buffers for batches of %d: allocation failed (hipMalloc)", max_batch); }
+    e->train = t;
+    return OMOK_OK;
+}
+
+// the checks the step entry points share
+static int train_check(omok_engine* e, const void* records_dev, int64_t n_records, int32_t batch) {
+    if (!e->train) return fail(e, OMOK_ERR_STATE, "no training state (omok_train_begin)");
+    for (int i = 0; i < NET_TENSORS; ++i)
+        if (!e->net.loaded[i]) return fail(e, OMOK_ERR_STATE, "tensor %d was never loaded", i);
+    if (!records_dev || ((uintptr_t)records_dev & 3)) return fail(e, OMOK_ERR_INVALID, "records_dev must be a 4-byte aligned device pointer");
+    if (n_records < 1 || n_records > 0x7fffffffLL) return fail(e, OMOK_ERR_INVALID, "n_records %lld outside [1, 2^31)", (long long)n_records);
+    if (batch < 1 || batch > e->train->max_b) return fail(e, OMOK_ERR_INVALID, "batch %d outside [1, max_batch = %d]", batch, e->train->max_b);
+    return 0;
+}
+
+static int train_fetch_losses(omok_engine* e, int first, int steps, float losses[3], const char* what) { // the sums of `steps` steps -> their means
+    float h[3];
+    HIPCHK(e, hipMemcpyAsync(h, e->train->losses + first, sizeof(h), hipMemcpyDeviceToHost, e->st));
+    if (sync_and_check(e, what)) return OMOK_ERR_HIP;
+    if (losses)
+        for (int i = 0; i < 3; ++i) losses[i] = h[i] / (float)steps;
+    return 0;
+}
+
+static int train_once(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* indices, int32_t batch, float losses[3], bool update) {
+    if (!e || !indices) return OMOK_ERR_INVALID;
+    if (int rc = train_check(e, records_dev, n_records, batch)) return rc;
+    for (int i = 0; i < batch; ++i)
+        if (indices[i] < 0 || indices[i] >= n_records) return fail(e, OMOK_ERR_INVALID, "indices[%d] = %lld outside [0, %lld)", i, (long long)indices[i], (long long)n_records);
+    ENTER(e);
+    Train& T = *e->train;
+    HIPCHK(e, hipMemcpyAsync(T.idx, indices, sizeof(int64_t) * (size_t)batch, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st)); // (the caller's array may go away)
+    if (update) e->net.committed = false;   // like omok_net_load: the packed operands no longer match Net::w[]
+    train_step(T, e->net, records_dev, batch, update, false, e->st);
+    return train_fetch_losses(e, 0, 1, losses, update ? "train_step" : "train_losses");
+}
+
+extern "C" int omok_train_step(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* indices, int32_t batch, float* losses) {
+    return train_once(e, records_dev, n_records, indices, batch, losses, true);
+}
+extern "C" int omok_train_losses(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* indices, int32_t batch, float* losses) {
+    return train_once(e, records_dev, n_records, indices, batch, losses, false);
+}
+
+extern "C" int omok_train_batch_indices(omok_engine* e, int64_t n_records, int32_t batch, uint64_t key, int32_t step, int64_t* out) {
+    if (!e || !out) return OMOK_ERR_INVALID;
+    if (!e->train) return fail(e, OMOK_ERR_STATE, "no training state (omok_train_begin)");
+    if (n_records < 1 || n_records > 0x7fffffffLL) return fail(e, OMOK_ERR_INVALID, "n_records %lld outside [1, 2^31)", (long long)n_records);
+    if (batch < 1 || batch > e->train->max_b) return fail(e, OMOK_ERR_INVALID, "batch %d outside [1, max_batch = %d]", batch, e->train->max_b);
+    if (step < 0) return fail(e, OMOK_ERR_INVALID, "step %d is negative", step);
+    ENTER(e);
+    const int k = (int)std::min<int64_t>(batch, n_records);
+    train_draw(*e->train, n_records, k, key, step, e->st);
+    HIPCHK(e, hipMemcpyAsync(out, e->train->idx, sizeof(int64_t) * (size_t)k, hipMemcpyDeviceToHost, e->st));
+    if (sync_and_check(e, "train_batch_indices")) return OMOK_ERR_HIP;
+    return k;
+}
+
+extern "C" int omok_train_run(omok_engine* e, const void* records_dev, int64_t n_records, int32_t update_count, int32_t batch_size, uint64_t key, float* losses) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (int rc = train_check(e, records_dev, n_records, batch_size)) return rc;
+    if (update_count < 0) return fail(e, OMOK_ERR_INVALID, "update_count %d is negative", update_count);
+    if (e->round_reqs >= 0 || e->mirror_reqs >= 0) return fail(e, OMOK_ERR_STATE, "omok_train_run while a round / mirror batch is pending (it commits the net)");
+    ENTER(e);
+    Train& T = *e->train;
+    const int k = (int)std::min<int64_t>(batch_size, n_records), counted = std::min(update_count, 100); // trainer.rs:354-362: the log line averages the last 100 steps
+    HIPCHK(e, hipMemsetAsync(T.losses, 0, sizeof(float) * 8, e->st));
+    if (update_count > 0) e->net.committed = false;
+    for (int s = 0; s < update_count; ++s) { // no host synchronisation between the steps: the draw, the step and the running sums stay on the device
+        train_draw(T, n_records, k, key, s, e->st);
+        train_step(T, e->net, records_dev, k, true, s >= update_count - counted, e->st);
+    }
+    if (int rc = train_fetch_losses(e, 4, std::max(counted, 1), losses, "train_run")) return rc;
+    return net_commit_slot(e, 1);
+}
+
+extern "C" int omok_debug_train_gradient(omok_engine* e, int32_t index, float* out, int64_t count) {
+    if (!e || !out) return OMOK_ERR_INVALID;
+    if (!e->train || !e->train->has_grad) return fail(e, OMOK_ERR_STATE, "no gradient yet (omok_train_begin + omok_train_step)");
+    if (index < 0 || index >= NET_TENSORS) return fail(e, OMOK_ERR_INVALID, "tensor index %d out of range", index);
+    if (count != e->net.wsize[index]) return fail(e, OMOK_ERR_INVALID, "tensor %d: expected %lld values, got %lld", index, (long long)e->net.wsize[index], (long long)count);
+    ENTER(e);
+    if (sync_and_check(e, "train_gradient")) return OMOK_ERR_HIP;
+    HIPCHK(e, hipMemcpy(out, e->train->grad + e->train->off[index], sizeof(float) * (size_t)count, hipMemcpyDeviceToHost));
+    return OMOK_OK;
 }
 
 extern "C" int omok_evaluate_pv(omok_engine* e, const float* in, int32_t batch, float* p, float* v) {

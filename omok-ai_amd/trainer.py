@@ -35,6 +35,7 @@ class Parameters:  # src/config.rs:83-110
     test_evaluate_count: int = 800  # simulations per move of the net in the evaluation games (src/config.rs:31,103)
     evaluate_every: int = 10        # `iteration % 10 == 0` (src/trainer.rs:380)
     evaluate_games: int = 100       # play_against_naive_player(100, ..) (:384)
+    train_backend: str = "torch"    # the training phase (:329-357): "torch" = autograd (train.py), "hip" = the engine's native step (omok_train_run)
 
 
 class Trainer:
@@ -42,6 +43,11 @@ class Trainer:
         self.p = params or Parameters()
         self.n = board_size
         self.rank, self.local_rank, self.world = dist.shard_info()
+        if self.p.train_backend not in ("torch", "hip"):
+            raise ValueError(f"train_backend {self.p.train_backend!r}: expected \"torch\" or \"hip\"")
+        if self.p.train_backend == "hip" and self.world > 1:
+            raise RuntimeError("train_backend=\"hip\" runs on one rank only: the native step does not average gradients over ranks "
+                               f"(world size {self.world}); use train_backend=\"torch\" for data-parallel training")
         self.device = f"cuda:{self.local_rank}"
         self.save_dir = save_dir
         self.precision_rows = precision_rows  # independent check of the net outputs after every weight update (0 = off)
@@ -62,6 +68,8 @@ class Trainer:
             tensors = weights.init_random(board_size, seed=seed)
             self.engine.load_weights(tensors)
         self.phase = T.TrainPhase(board_size, tensors, self.device)  # the optimizer state lives across iterations like the session's
+        if self.p.train_backend == "hip":  # ... here in the engine; self.phase.net only mirrors the variables (precision check, tests)
+            self.engine.train_begin(self.p.parameter_update_batch_size)
         self.selfplay = api.SelfPlay(self.engine)
         self.iteration = 0
         it_path = path + ".iteration"  # (not in the reference, whose thread_rng is fresh on every start): a resumed run must
@@ -93,9 +101,16 @@ class Trainer:
             records = buf[: got * rec].reshape(got, rec)
             if got > p.replay_memory_size:  # pop_front until the memory fits (:326-328)
                 records = records[got - p.replay_memory_size:]
-            v_loss, p_loss, loss = self.phase.run(records, p.parameter_update_count, p.parameter_update_batch_size,
-                                                  seed=self.iteration * 7919 + self.rank)
-            self.phase.push_to(self.engine)
+            if p.train_backend == "hip":  # the whole phase in one call on the engine's own fp32 variables; it commits them itself
+                v_loss, p_loss, loss = self.engine.train_run(records.data_ptr(), records.shape[0], p.parameter_update_count,
+                                                             p.parameter_update_batch_size, key=self.seed + self.iteration * 7919)
+                with torch.no_grad():
+                    for var, t in zip(self.phase.net.vars, self.engine.read_weights()):
+                        var.copy_(torch.from_numpy(t).reshape(var.shape))
+            else:
+                v_loss, p_loss, loss = self.phase.run(records, p.parameter_update_count, p.parameter_update_batch_size,
+                                                      seed=self.iteration * 7919 + self.rank)
+                self.phase.push_to(self.engine)
             # new weights -> omok_net_commit -> the engine re-measured fc0's operand format on its probe set; the probe's
             # figures are kept for the log, and the outputs are checked independently below (a probe is a measurement, not a proof)
             st = self.engine.stats()
