@@ -56,6 +56,7 @@ pub const OMOK_NET_F16X3_MIXED: i32 = 5;
 pub const OMOK_MAX_ARENA: i32 = 16384;
 pub const OMOK_OPP_RANDOM: i32 = 0;
 pub const OMOK_OPP_NAIVE: i32 = 1;
+pub const OMOK_TRAIN_MAX_RANKS: i32 = 64;
 pub const OMOK_PLAN_INTS: i32 = 16;
 pub const OMOK_STAT_SIMS: i32 = 0;
 pub const OMOK_STAT_EVALS: i32 = 1;
@@ -101,7 +102,8 @@ pub const OMOK_STAT_WORK_DIFF_FULL_RUNS: i32 = 46;
 pub const OMOK_STAT_WORK_WIN_PIXELS: i32 = 47;
 pub const OMOK_STAT_WORK_WIN_TILES: i32 = 48;
 pub const OMOK_STAT_WORK_FULL_TILES: i32 = 49;
-pub const OMOK_STAT_COUNT: i32 = 50;
+pub const OMOK_STAT_MS_TRAIN_APPLY: i32 = 50;
+pub const OMOK_STAT_COUNT: i32 = 51;
 
 /// The raw C ABI: every entry point of include/omok_mi355x.h (generated; do not edit by hand).
 pub mod ffi {
@@ -167,6 +169,9 @@ pub mod ffi {
         pub fn omok_train_losses(e: *mut OmokEngine, records_dev: *const c_void, n_records: i64, indices: *const i64, batch: i32, losses: *mut f32) -> c_int;
         pub fn omok_train_batch_indices(e: *mut OmokEngine, n_records: i64, batch: i32, key: u64, step: i32, out: *mut i64) -> c_int;
         pub fn omok_train_run(e: *mut OmokEngine, records_dev: *const c_void, n_records: i64, update_count: i32, batch_size: i32, key: u64, losses: *mut f32) -> c_int;
+        pub fn omok_train_gradient_count(e: *const OmokEngine) -> i64;
+        pub fn omok_train_backward(e: *mut OmokEngine, records_dev: *const c_void, n_records: i64, indices: *const i64, batch: i32, grad_dst_dev: *mut c_void) -> c_int;
+        pub fn omok_train_apply(e: *mut OmokEngine, grads_dev: *const c_void, ranks: i32, losses: *mut f32) -> c_int;
         pub fn omok_debug_train_gradient(e: *mut OmokEngine, index: i32, out: *mut f32, count: i64) -> c_int;
         pub fn omok_net_read(e: *mut OmokEngine, index: i32, out: *mut f32, count: i64) -> c_int;
         pub fn omok_alive_count(e: *mut OmokEngine) -> c_int;

@@ -357,8 +357,31 @@ int omok_train_batch_indices(omok_engine* e, int64_t n_records, int32_t batch, u
  * p_loss, loss (trainer.rs:354-362), summed on the device in step order.  Then commits net 1 as omok_net_commit does.  Weights and accumulators end
  * bit for bit as after the loop of omok_train_batch_indices + omok_train_step. */
 int omok_train_run(omok_engine* e, const void* records_dev, int64_t n_records, int32_t update_count, int32_t batch_size, uint64_t key, float* losses);
+/* ---- the same step in two halves, for data-parallel training (agent_model.rs:136-168 / trainer.rs:329-357 on several ranks; no reference counterpart:
+ *      the reference is one process).  The engine holds no collective library: it produces gradients into caller-owned device memory, the caller moves
+ *      them (an all-gather; omok_replay_pack_dev works the same way), and the engine sums the ranks' slabs IN RANK ORDER inside its Adadelta kernel, so
+ *      ranks that start from equal weights stay bit-equal whatever algorithm the collective used.  Exchange layout: one fp32 slab of
+ *      omok_train_gradient_count values without padding, tensor i at offset sum_{j<i} omok_net_tensor_size(j).
+ *      omok_train_backward + omok_train_apply(NULL, 1) leave weights, accumulators, losses and gradients bit for bit as omok_train_step does. */
+#define OMOK_TRAIN_MAX_RANKS 64
+/* floats of a gradient slab: the sum of omok_net_tensor_size over the 31 tensors (agent_model.rs:136-168 / trainer.rs:329-357: one gradient per
+ * variable).  A function of the board size only; needs no training state. */
+int64_t omok_train_gradient_count(const omok_engine* e);
+/* First half of omok_train_step (agent_model.rs:136-168 / trainer.rs:329-357): batch assembly, forward, the losses and the backward pass on records
+ * indices[0 .. batch).  Writes no weight and no accumulator; the 31 gradients stay readable by omok_debug_train_gradient and, if grad_dst_dev is not
+ * NULL, are also copied to that caller-owned device memory (omok_train_gradient_count floats, complete on return).  Checks and error codes of
+ * omok_train_step; a rejected call changes nothing.  Marks the step pending for omok_train_apply; omok_train_step, omok_train_losses, omok_train_run,
+ * omok_train_begin and omok_train_end clear that mark (they overwrite the batch). */
+int omok_train_backward(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* indices, int32_t batch, void* grad_dst_dev);
+/* Second half (agent_model.rs:136-168 / trainer.rs:329-357): TensorFlow ApplyAdadelta with the gradient g, then the forward and the three losses on the
+ * pending batch as omok_train_step does after its update (losses [3], may be NULL).  grads_dev == NULL (ranks must be 1): g = the engine's own
+ * gradient.  Else grads_dev = [ranks][omok_train_gradient_count] fp32 in device memory and, per element, g = s[0]; g += s[r] for r = 1 .. ranks - 1;
+ * g *= 1.0f / (float)ranks -- plain fp32 in that order; g is what omok_debug_train_gradient reads afterwards.  Leaves net 1 uncommitted and clears
+ * the pending mark.  OMOK_ERR_STATE without a pending omok_train_backward or before omok_train_begin; OMOK_ERR_INVALID for ranks < 1,
+ * ranks > OMOK_TRAIN_MAX_RANKS or NULL with ranks != 1; a rejected call changes nothing. */
+int omok_train_apply(omok_engine* e, const void* grads_dev, int32_t ranks, float* losses);
 /* Debugging aid of the gradient tests (no reference counterpart): the gradient of tensor `index` the last omok_train_step / omok_train_run step
- * applied, count = omok_net_tensor_size(index).  OMOK_ERR_STATE before the first step. */
+ * applied or the last omok_train_backward / omok_train_apply left, count = omok_net_tensor_size(index).  OMOK_ERR_STATE before the first step. */
 int omok_debug_train_gradient(omok_engine* e, int32_t index, float* out, int64_t count);
 /* The raw fp32 tensor `index` of net 1 as loaded or trained (Session::run fetch of a variable, model_io.rs:59-90 without the file),
  * count = omok_net_tensor_size(index). */
@@ -480,7 +503,8 @@ int omok_debug_last_plan(omok_engine* e, int32_t* out, int32_t cap);
 #define OMOK_STAT_WORK_WIN_PIXELS 47   /* window pixels walked by the fc0 window tiles (sum over tiles of their rectangles; K-split tiles: 49) */
 #define OMOK_STAT_WORK_WIN_TILES 48    /* fc0 window tiles (128 slots each) */
 #define OMOK_STAT_WORK_FULL_TILES 49   /* 128-row tiles of the difference path's full-row fc0 */
-#define OMOK_STAT_COUNT 50
+#define OMOK_STAT_MS_TRAIN_APPLY 50   /* HIP-event ms in omok_train_apply's Adadelta launch (under omok_set_profiling; tools/train_step_timing.py) */
+#define OMOK_STAT_COUNT 51
 int omok_get_stats(omok_engine* e, double* stats /* [OMOK_STAT_COUNT] */);
 int omok_reset_stats(omok_engine* e);
 /* Per-category HIP-event timing of the kernels on the engine's stream (off by default).  enabled = 1: every launch; enabled = N > 1:

@@ -149,6 +149,25 @@ class Engine:
                                          int(key) & 0xFFFFFFFFFFFFFFFF, B.fptr(losses)))
         return float(losses[0]), float(losses[1]), float(losses[2])
 
+    def train_gradient_count(self):
+        """floats of a gradient slab (omok_train_gradient_count): the 31 tensors back to back, a function of the board size only"""
+        return int(self._chk(B.lib().omok_train_gradient_count(self.h)))
+
+    def train_backward(self, records_ptr, n_records, indices, grad_dst_ptr=None):
+        """first half of train_step: the gradients of the batch `indices` names, no update.  They stay readable by train_gradient and, with
+        grad_dst_ptr (device memory of train_gradient_count() floats, e.g. a torch tensor's data_ptr()), are copied there before the call returns."""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).ravel()
+        dst = C.c_void_p(int(grad_dst_ptr)) if grad_dst_ptr else None
+        self._chk(B.lib().omok_train_backward(self.h, C.c_void_p(int(records_ptr)), int(n_records), idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, dst))
+
+    def train_apply(self, grads_ptr=None, ranks=1):
+        """second half: Adadelta with the engine's own gradient (grads_ptr None, ranks 1) or with the rank-order average of the [ranks, count] fp32
+        slabs at device pointer grads_ptr; then (v_loss, p_loss, loss) of the pending batch after the update.  Leaves the net uncommitted."""
+        losses = np.zeros(3, dtype=np.float32)
+        src = C.c_void_p(int(grads_ptr)) if grads_ptr else None
+        self._chk(B.lib().omok_train_apply(self.h, src, int(ranks), B.fptr(losses)))
+        return float(losses[0]), float(losses[1]), float(losses[2])
+
     def train_gradient(self, index):
         """gradient of tensor `index` the last step applied (omok_debug_train_gradient), flat"""
         g = np.empty(int(B.lib().omok_net_tensor_size(self.h, index)), dtype=np.float32)

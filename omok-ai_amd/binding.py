@@ -26,7 +26,7 @@ STAT_NAMES = ["sims", "evals", "ply_games", "finished", "ms_tree", "ms_trunk", "
               "probe_round_dp_fp6", "probe_round_dv_fp6", "probe_round_dlogit_fp6", "probe_round_dp_mixed", "probe_round_dv_mixed", "probe_round_dlogit_mixed",
               "probe_round_dp_f16", "probe_round_dv_f16", "probe_round_dlogit_f16", "probe_logit_limit", "probe_outside",
               "work_diff_runs", "work_diff_singles", "work_diff_children", "work_copy_runs", "work_copy_singles", "work_copy_children", "work_diff_full_runs",
-              "work_win_pixels", "work_win_tiles", "work_full_tiles"]
+              "work_win_pixels", "work_win_tiles", "work_full_tiles", "ms_train_apply"]
 
 # every symbol include/omok_mi355x.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -43,6 +43,7 @@ SYMBOLS = [
     "omok_operand_row_bytes", "omok_debug_operand_rows", "omok_debug_set_base_cache", "omok_debug_set_children_kernel", "omok_debug_set_window_rects", "omok_debug_last_plan",
     "omok_replay_pack_dev", "omok_replay_record_bytes", "omok_replay_augment_dev", "omok_replay_augmented_game", "omok_get_stats", "omok_reset_stats", "omok_set_profiling",
     "omok_train_begin", "omok_train_end", "omok_train_step", "omok_train_losses", "omok_train_batch_indices", "omok_train_run",
+    "omok_train_gradient_count", "omok_train_backward", "omok_train_apply",
     "omok_debug_train_gradient", "omok_net_read",
 ]
 
@@ -163,6 +164,10 @@ def lib():
     L.omok_train_losses.argtypes = [H, C.c_void_p, C.c_int64, i64p, C.c_int32, fp]
     L.omok_train_batch_indices.argtypes = [H, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, i64p]
     L.omok_train_run.argtypes = [H, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, fp]
+    L.omok_train_gradient_count.argtypes = [H]
+    L.omok_train_gradient_count.restype = C.c_int64
+    L.omok_train_backward.argtypes = [H, C.c_void_p, C.c_int64, i64p, C.c_int32, C.c_void_p]
+    L.omok_train_apply.argtypes = [H, C.c_void_p, C.c_int32, fp]
     L.omok_debug_train_gradient.argtypes = [H, C.c_int32, fp, C.c_int64]
     L.omok_net_read.argtypes = [H, C.c_int32, fp, C.c_int64]
     _lib = L

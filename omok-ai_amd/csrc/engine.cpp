@@ -621,6 +621,7 @@ static int train_once(omok_engine* e, const void* records_dev, int64_t n_records
         if (indices[i] < 0 || indices[i] >= n_records) return fail(e, OMOK_ERR_INVALID, "indices[%d] = %lld outside [0, %lld)", i, (long long)indices[i], (long long)n_records);
     ENTER(e);
     Train& T = *e->train;
+    T.pending = 0; // (the batch buffers of a pending omok_train_backward are overwritten)
     HIPCHK(e, hipMemcpyAsync(T.idx, indices, sizeof(int64_t) * (size_t)batch, hipMemcpyHostToDevice, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st)); // (the caller's array may go away)
     if (update) e->net.committed = false;   // like omok_net_load: the packed operands no longer match Net::w[]
@@ -656,6 +657,7 @@ extern "C" int omok_train_run(omok_engine* e, const void* records_dev, int64_t n
     if (e->round_reqs >= 0 || e->mirror_reqs >= 0) return fail(e, OMOK_ERR_STATE, "omok_train_run while a round / mirror batch is pending (it commits the net)");
     ENTER(e);
     Train& T = *e->train;
+    T.pending = 0;
     const int k = (int)std::min<int64_t>(batch_size, n_records), counted = std::min(update_count, 100); // trainer.rs:354-362: the log line averages the last 100 steps
     HIPCHK(e, hipMemsetAsync(T.losses, 0, sizeof(float) * 8, e->st));
     if (update_count > 0) e->net.committed = false;
@@ -665,6 +667,53 @@ extern "C" int omok_train_run(omok_engine* e, const void* records_dev, int64_t n
     }
     if (int rc = train_fetch_losses(e, 4, std::max(counted, 1), losses, "train_run")) return rc;
     return net_commit_slot(e, 1);
+}
+
+// ---- the step in two halves: a data-parallel host moves the gradient slabs between them (trainer.rs:329-357 on several ranks) ----
+extern "C" int64_t omok_train_gradient_count(const omok_engine* e) {
+    if (!e) return OMOK_ERR_INVALID;
+    int64_t count = 0;
+    for (int i = 0; i < NET_TENSORS; ++i) count += e->net.wsize[i];
+    return count;
+}
+
+extern "C" int omok_train_backward(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* indices, int32_t batch, void* grad_dst_dev) {
+    if (!e || !indices) return OMOK_ERR_INVALID;
+    if (int rc = train_check(e, records_dev, n_records, batch)) return rc;
+    for (int i = 0; i < batch; ++i)
+        if (indices[i] < 0 || indices[i] >= n_records) return fail(e, OMOK_ERR_INVALID, "indices[%d] = %lld outside [0, %lld)", i, (long long)indices[i], (long long)n_records);
+    if ((uintptr_t)grad_dst_dev & 3) return fail(e, OMOK_ERR_INVALID, "grad_dst_dev must be a 4-byte aligned device pointer (or NULL)");
+    ENTER(e);
+    Train& T = *e->train;
+    T.pending = 0;
+    HIPCHK(e, hipMemcpyAsync(T.idx, indices, sizeof(int64_t) * (size_t)batch, hipMemcpyHostToDevice, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st)); // (the caller's array may go away)
+    train_backward(T, e->net, records_dev, batch, e->st);
+    if (grad_dst_dev) HIPCHK(e, hipMemcpyAsync(grad_dst_dev, T.grad, sizeof(float) * (size_t)T.off[NET_TENSORS], hipMemcpyDeviceToDevice, e->st));
+    if (sync_and_check(e, "train_backward")) return OMOK_ERR_HIP; // the slab is complete on return: the caller's collective may run on any stream
+    T.pending = batch;
+    return OMOK_OK;
+}
+
+extern "C" int omok_train_apply(omok_engine* e, const void* grads_dev, int32_t ranks, float* losses) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (!e->train) return fail(e, OMOK_ERR_STATE, "no training state (omok_train_begin)");
+    if (e->train->pending < 1) return fail(e, OMOK_ERR_STATE, "no pending gradients (omok_train_backward, with no other omok_train_* call since)");
+    if (ranks < 1 || ranks > OMOK_TRAIN_MAX_RANKS) return fail(e, OMOK_ERR_INVALID, "ranks %d outside [1, %d]", ranks, OMOK_TRAIN_MAX_RANKS);
+    if (!grads_dev && ranks != 1) return fail(e, OMOK_ERR_INVALID, "grads_dev is NULL: the engine's own gradient is one rank's, not %d", ranks);
+    if ((uintptr_t)grads_dev & 3) return fail(e, OMOK_ERR_INVALID, "grads_dev must be a 4-byte aligned device pointer (or NULL)");
+    for (int i = 0; i < NET_TENSORS; ++i)
+        if (!e->net.loaded[i]) return fail(e, OMOK_ERR_STATE, "tensor %d was never loaded", i);
+    ENTER(e);
+    Train& T = *e->train;
+    const int k = T.pending;
+    T.pending = 0;
+    e->net.committed = false; // like omok_train_step
+    e->prof.begin(PC_TRAIN_APPLY, e->st);
+    train_update(T, e->net, (const float*)grads_dev, ranks, e->st);
+    e->prof.end(e->st);
+    train_evaluate(T, e->net, k, false, e->st);
+    return train_fetch_losses(e, 0, 1, losses, "train_apply");
 }
 
 extern "C" int omok_debug_train_gradient(omok_engine* e, int32_t index, float* out, int64_t count) {
@@ -2038,6 +2087,7 @@ extern "C" int omok_get_stats(omok_engine* e, double* stats) {
     stats[OMOK_STAT_MS_FC0] = e->prof.total_ms(PC_FC0);
     stats[OMOK_STAT_MS_TAIL] = e->prof.total_ms(PC_TAIL);
     stats[OMOK_STAT_MS_PLY] = e->prof.total_ms(PC_PLY);
+    stats[OMOK_STAT_MS_TRAIN_APPLY] = e->prof.total_ms(PC_TRAIN_APPLY);
     stats[OMOK_STAT_FC0_LAUNCHES] = e->prof.total_launches(PC_FC0);
     stats[OMOK_STAT_FC0_ROWS] = e->evals + (double)ev;
     stats[OMOK_STAT_TREE_BYTES] = (double)by;

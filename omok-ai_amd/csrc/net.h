@@ -181,7 +181,7 @@ size_t net_alloc(Net& net); // allocates buffers for net.max_b; returns bytes, 0
 void net_free(Net& net);
 
 // ---- tiny profiler: HIP-event pairs per category, resolved lazily ----
-enum { PC_ROUND = 0, PC_TREE_OTHER, PC_TRUNK, PC_FC0, PC_TAIL, PC_PLY, PC_COUNT };
+enum { PC_ROUND = 0, PC_TREE_OTHER, PC_TRUNK, PC_FC0, PC_TAIL, PC_PLY, PC_TRAIN_APPLY, PC_COUNT };
 constexpr int PC_COUNT_MAX = 8;
 // An event record between two kernels costs ~5 us of idle queue (measured: 10.6 us per category boundary = end + begin); with `every` = N > 1
 // only every Nth search round is timed and the stats scale the sampled sums by rounds seen / rounds timed (ply-level work is always timed).

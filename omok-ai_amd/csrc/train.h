@@ -19,6 +19,7 @@ struct Train {
     float* accu = nullptr;           // ... accumulated updates
     float* grad = nullptr;           // gradients of the last step
     bool has_grad = false;
+    int pending = 0;                 // batch of an omok_train_backward whose omok_train_apply is still due (its batch buffers are intact), 0 = none
     // the step's batch
     int64_t* idx = nullptr;          // [max_b] record indices (uploaded, or drawn on the device)
     float *x0 = nullptr, *pi = nullptr, *z = nullptr; // encode_nn_input(Player) [B][3 HW], targets [B][HW], [B]
@@ -45,5 +46,13 @@ void train_draw(Train& T, int64_t n_records, int k, uint64_t key, int step, hipS
 // One AgentModel::train on the k records T.idx names: forward + losses; update: backward, Adadelta on net.w[] in place, then forward + losses again.
 // T.losses[0..2] = v_loss, p_loss, loss; accumulate: also added to T.losses[4..6].
 void train_step(Train& T, Net& net, const void* records_dev, int k, bool update, bool accumulate, hipStream_t st);
+// The same step in two halves (omok_train_backward / omok_train_apply; agent_model.rs:136-168, trainer.rs:329-357 for data-parallel hosts).
+// train_backward: assemble, forward, losses with gradients, backward -> T.grad; writes no weight and no accumulator.
+void train_backward(Train& T, const Net& net, const void* records_dev, int k, hipStream_t st);
+// train_update: ApplyAdadelta on net.w[] with T.grad (grads_dev NULL), or with the rank-order average of grads_dev [ranks][T.off[31]], which it also
+// leaves in T.grad.  train_evaluate: forward + the three losses on the batch train_backward assembled -> T.losses[0..2]
+// (accumulate: also added to T.losses[4..6]).
+void train_update(Train& T, Net& net, const float* grads_dev, int ranks, hipStream_t st);
+void train_evaluate(Train& T, const Net& net, int k, bool accumulate, hipStream_t st);
 
 } // namespace omok

@@ -274,6 +274,38 @@ __global__ __launch_bounds__(256) void k_adadelta(AdadeltaArgs a, const float* _
         a.w[t][e] -= TRAIN_LEARNING_RATE * upd;
     }
 }
+// The data-parallel update (omok_train_apply): the same launch shape on the ranks' gradient slabs [ranks][count].  Per element the slabs are added in
+// rank order and the sum scaled by 1 / ranks -- plain fp32 adds and one multiply, nothing contracted into them, so every rank that holds the same slabs
+// forms the same bits whatever collective moved them -- the averaged gradient is kept in `grad` (omok_debug_train_gradient), then ApplyAdadelta as above.
+// Streaming: ranks x 4 B read, grad written, acc / accu / w read and written per element; tensor offsets are only 4-byte aligned (the head biases have HW
+// elements), so the accesses stay one dword per lane, 256 B per wave and instruction.
+__device__ inline float rank_average(const float* __restrict__ slabs, size_t s, int ranks, size_t count, float scale) {
+#pragma clang fp contract(off)
+    float g = slabs[s];
+    for (int r = 1; r < ranks; ++r) g += slabs[(size_t)r * count + s];
+    return g * scale;
+}
+__global__ __launch_bounds__(256) void k_adadelta_ranks(AdadeltaArgs a, const float* __restrict__ slabs, int ranks, float scale, float* __restrict__ grad,
+                                                        float* __restrict__ acc, float* __restrict__ accu) {
+    int t = 0;
+    while (t + 1 < NET_TENSORS && (int)blockIdx.x >= a.blk[t + 1]) ++t;
+    const long long size = a.off[t + 1] - a.off[t];
+    const long long e0 = (long long)((int)blockIdx.x - a.blk[t]) * 1024 + threadIdx.x;
+    const size_t count = (size_t)a.off[NET_TENSORS];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long e = e0 + 256 * j;
+        if (e >= size) break;
+        const size_t s = (size_t)(a.off[t] + e);
+        const float g = rank_average(slabs, s, ranks, count, scale);
+        grad[s] = g;
+        const float ac = TRAIN_RHO * acc[s] + (1.0f - TRAIN_RHO) * g * g; // (the lines of k_adadelta, which keeps its own device code)
+        const float upd = sqrtf(accu[s] + TRAIN_EPSILON) / sqrtf(ac + TRAIN_EPSILON) * g;
+        acc[s] = ac;
+        accu[s] = TRAIN_RHO * accu[s] + (1.0f - TRAIN_RHO) * upd * upd;
+        a.w[t][e] -= TRAIN_LEARNING_RATE * upd;
+    }
+}
 
 // ---- batch draw (src/trainer.rs:329-350 choose_multiple: uniform, without replacement) ------------------------------------------------
 // index i = the mulhi(x0, R - i)-th record, 0-based ascending, not among the first i drawn; x0 = word 0 of Philox4x32-10(key; i, step, 0,
@@ -432,7 +464,7 @@ static void backward(Train& T, const Net& net, int k, hipStream_t st) {
     launch_colsum(T, st, dy, rows, NC, gr[1]);
 }
 
-static void adadelta(Train& T, Net& net, hipStream_t st) {
+static AdadeltaArgs adadelta_args(const Train& T, const Net& net) {
     AdadeltaArgs a;
     a.blk[0] = 0;
     for (int i = 0; i < NET_TENSORS; ++i) {
@@ -441,19 +473,44 @@ static void adadelta(Train& T, Net& net, hipStream_t st) {
         a.blk[i + 1] = a.blk[i] + (int)((net.wsize[i] + 1023) / 1024);
     }
     a.off[NET_TENSORS] = T.off[NET_TENSORS];
+    return a;
+}
+
+static void adadelta(Train& T, Net& net, hipStream_t st) {
+    const AdadeltaArgs a = adadelta_args(T, net);
     k_adadelta<<<a.blk[NET_TENSORS], 256, 0, st>>>(a, T.grad, T.acc, T.accu);
 }
 
-void train_step(Train& T, Net& net, const void* records_dev, int k, bool update, bool accumulate, hipStream_t st) {
+// The step in two halves, where the gradients can leave and enter (omok_train_backward / omok_train_apply); train_step below runs the same halves.
+void train_backward(Train& T, const Net& net, const void* records_dev, int k, hipStream_t st) {
     k_assemble<<<k, 256, 0, st>>>((const uint8_t*)records_dev, T.idx, T.hw, T.rec, T.brd, T.x0, T.pi, T.z);
     forward(T, net, k, st);
-    losses(T, k, update, accumulate && !update, st);
-    if (!update) return;
+    losses(T, k, true, false, st);
     backward(T, net, k, st);
     T.has_grad = true;
-    adadelta(T, net, st);
+}
+
+void train_update(Train& T, Net& net, const float* grads_dev, int ranks, hipStream_t st) {
+    if (!grads_dev) { adadelta(T, net, st); return; }
+    const AdadeltaArgs a = adadelta_args(T, net);
+    k_adadelta_ranks<<<a.blk[NET_TENSORS], 256, 0, st>>>(a, grads_dev, ranks, 1.0f / (float)ranks, T.grad, T.acc, T.accu);
+    T.has_grad = true;
+}
+
+void train_evaluate(Train& T, const Net& net, int k, bool accumulate, hipStream_t st) {
     forward(T, net, k, st); // agent_model.rs:150-166: the three losses are fetched after the minimize run
     losses(T, k, false, accumulate, st);
+}
+
+void train_step(Train& T, Net& net, const void* records_dev, int k, bool update, bool accumulate, hipStream_t st) {
+    if (!update) {
+        k_assemble<<<k, 256, 0, st>>>((const uint8_t*)records_dev, T.idx, T.hw, T.rec, T.brd, T.x0, T.pi, T.z);
+        train_evaluate(T, net, k, accumulate, st);
+        return;
+    }
+    train_backward(T, net, records_dev, k, st);
+    train_update(T, net, nullptr, 1, st);
+    train_evaluate(T, net, k, accumulate, st);
 }
 
 } // namespace omok

@@ -3,8 +3,9 @@
 The reference is single-process; self-play games are independent
 (alpha-zero/src/parallel_mcts_executor.rs:200-205), so rank r simply owns games
 [r*G, (r+1)*G) (engine `game_offset`), and the RNG streams are keyed by the global game id, which
-makes results independent of the number of shards.  The only exchange is the optional episode-end
-gather of replay tuples (s, pi, z).  Works with any torch.distributed backend ("nccl" = RCCL over
+makes results independent of the number of shards.  The exchanges are the optional episode-end
+gather of replay tuples (s, pi, z) and, with the native data-parallel training step, one all-gather
+of gradient slabs per update (gather_gradients).  Works with any torch.distributed backend ("nccl" = RCCL over
 xGMI on the GPU box, "gloo" in the CPU tests).
 """
 import os
@@ -69,3 +70,39 @@ def gather_replay(records):
         for req in dist.batch_isend_irecv(ops):
             req.wait()
     return out, counts
+
+
+def gather_gradients(mine):
+    """All-gather of the ranks' gradient slabs for omok_train_apply: `mine` = this rank's [count] fp32 slab (omok_train_backward wrote it).
+    Returns [world, count] on mine's device, row r = rank r's slab: the engine adds the rows in that order, so every rank forms the same
+    bits whatever algorithm the collective runs.  World 1: mine[None], no collective.  A backend that cannot move device tensors (gloo)
+    is served through the host.  The result is a buffer this function reuses: it holds until the next call."""
+    if not (dist.is_initialized() and dist.get_world_size() > 1):
+        return mine[None]
+    world = dist.get_world_size()
+    mine = mine.contiguous()
+    staged = mine.device.type != "cpu" and dist.get_backend() == "gloo"
+    key = (world, mine.numel(), mine.dtype, str(mine.device), staged)
+    if _gather_buffers.get("key") != key:  # one update's slabs are consumed before the next gather: the buffers are reused from call to call
+        _gather_buffers.clear()
+        _gather_buffers.update(key=key, out=torch.empty(world * mine.numel(), dtype=mine.dtype, device=mine.device),
+                               host=torch.empty(world * mine.numel(), dtype=mine.dtype) if staged else None)
+    out = _gather_buffers["out"]  # (the concatenation of the ranks' slabs = the rows below)
+    if staged:
+        dist.all_gather_into_tensor(_gather_buffers["host"], mine.cpu())
+        out.copy_(_gather_buffers["host"])
+    else:
+        dist.all_gather_into_tensor(out, mine)
+    return out.view(world, -1)
+
+
+_gather_buffers = {}
+
+
+def min_over_ranks(value, device):
+    """the smallest of the ranks' integers (one tiny all-reduce; `device`: where a backend that needs device tensors finds one)"""
+    if not (dist.is_initialized() and dist.get_world_size() > 1):
+        return int(value)
+    t = torch.tensor([int(value)], dtype=torch.int64, device="cpu" if dist.get_backend() == "gloo" else device)
+    dist.all_reduce(t, op=dist.ReduceOp.MIN)
+    return int(t[0])

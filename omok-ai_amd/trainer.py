@@ -7,7 +7,8 @@ the engine), back-fill z and augment (:207-324, on the device), cap the memory a
 naive player (:380-394, 487-603: `Trainer.evaluate`).  Plots (:371-376) are not part of this mirror.  Parameters and defaults:
 src/config.rs:83-110 (episode_count 50, evaluate_count 600, test_evaluate_count 800, ...).
 Multi-GPU: every rank plays its own `episode_count` games (global ids rank*episode_count + g) and trains data-parallel
-(gradients averaged per step), so all ranks hold identical weights after every iteration.
+(gradients averaged per step: by the torch phase's all-reduce, or by the engine in rank order with train_backend="hip_dp"), so all ranks
+hold identical weights after every iteration.
 """
 import os
 from dataclasses import dataclass
@@ -35,7 +36,7 @@ class Parameters:  # src/config.rs:83-110
     test_evaluate_count: int = 800  # simulations per move of the net in the evaluation games (src/config.rs:31,103)
     evaluate_every: int = 10        # `iteration % 10 == 0` (src/trainer.rs:380)
     evaluate_games: int = 100       # play_against_naive_player(100, ..) (:384)
-    train_backend: str = "torch"    # the training phase (:329-357): "torch" = autograd (train.py), "hip" = the engine's native step (omok_train_run)
+    train_backend: str = "torch"    # the training phase (:329-357): "torch" = autograd (train.py), "hip" = the engine's native step (omok_train_run, one rank), "hip_dp" = the native step in two halves with the ranks' gradients averaged in between (any world size)
 
 
 class Trainer:
@@ -43,11 +44,11 @@ class Trainer:
         self.p = params or Parameters()
         self.n = board_size
         self.rank, self.local_rank, self.world = dist.shard_info()
-        if self.p.train_backend not in ("torch", "hip"):
-            raise ValueError(f"train_backend {self.p.train_backend!r}: expected \"torch\" or \"hip\"")
+        if self.p.train_backend not in ("torch", "hip", "hip_dp"):
+            raise ValueError(f"train_backend {self.p.train_backend!r}: expected \"torch\", \"hip\" or \"hip_dp\"")
         if self.p.train_backend == "hip" and self.world > 1:
             raise RuntimeError("train_backend=\"hip\" runs on one rank only: the native step does not average gradients over ranks "
-                               f"(world size {self.world}); use train_backend=\"torch\" for data-parallel training")
+                               f"(world size {self.world}); use train_backend=\"hip_dp\" or \"torch\" for data-parallel training")
         self.device = f"cuda:{self.local_rank}"
         self.save_dir = save_dir
         self.precision_rows = precision_rows  # independent check of the net outputs after every weight update (0 = off)
@@ -68,7 +69,7 @@ class Trainer:
             tensors = weights.init_random(board_size, seed=seed)
             self.engine.load_weights(tensors)
         self.phase = T.TrainPhase(board_size, tensors, self.device)  # the optimizer state lives across iterations like the session's
-        if self.p.train_backend == "hip":  # ... here in the engine; self.phase.net only mirrors the variables (precision check, tests)
+        if self.p.train_backend in ("hip", "hip_dp"):  # ... here in the engine; self.phase.net only mirrors the variables (precision check, tests)
             self.engine.train_begin(self.p.parameter_update_batch_size)
         self.selfplay = api.SelfPlay(self.engine)
         self.iteration = 0
@@ -83,6 +84,37 @@ class Trainer:
         tensors = model_file.load(tmp)[1]
         os.remove(tmp)
         return tensors
+
+    def _mirror_engine_weights(self):
+        with torch.no_grad():
+            for var, t in zip(self.phase.net.vars, self.engine.read_weights()):
+                var.copy_(torch.from_numpy(t).reshape(var.shape))
+
+    def _train_data_parallel(self, records):
+        """The update loop (:329-357) with the native step cut in two: every rank takes the gradients of a batch of ITS records (key = seed +
+        iteration * 7919 + rank: at rank 0 the key of "hip"), the ranks' slabs are all-gathered, and every engine applies their rank-order
+        average (omok_train_apply), so the replicas stay bit-equal.  Every rank runs parameter_update_count steps whatever its record count (>= 1),
+        so the collectives pair up; a rank without a single record (unreachable with episode_count >= 1: a game records its first move) is
+        found on ALL ranks before the loop, so that none is left waiting in a collective.  Returns the log line's means of the last <= 100 steps, summed in fp32 in step order like omok_train_run."""
+        p, eng = self.p, self.engine
+        n_records, key = records.shape[0], self.seed + self.iteration * 7919 + self.rank
+        if dist.min_over_ranks(n_records, self.device) < 1:
+            raise RuntimeError("train_backend=\"hip_dp\": a rank holds no replay record, so it cannot take part in the updates")
+        slab = torch.empty(eng.train_gradient_count(), dtype=torch.float32, device=self.device)
+        counted = min(p.parameter_update_count, 100)
+        sums = np.zeros(3, np.float32)
+        for s in range(p.parameter_update_count):
+            idx = eng.train_batch_indices(n_records, p.parameter_update_batch_size, key, s)
+            eng.train_backward(records.data_ptr(), n_records, idx, slab.data_ptr())
+            gathered = dist.gather_gradients(slab)
+            if gathered.is_cuda:
+                torch.cuda.current_stream(gathered.device).synchronize()  # the engine reads the slabs on its own stream
+            step = eng.train_apply(gathered.data_ptr(), self.world)
+            if s >= p.parameter_update_count - counted:
+                sums += np.asarray(step, np.float32)
+        eng.commit()
+        v_loss, p_loss, loss = (float(v) for v in sums / np.float32(max(counted, 1)))
+        return v_loss, p_loss, loss
 
     def train(self, iteration_count, log=print):
         p = self.p
@@ -104,9 +136,10 @@ class Trainer:
             if p.train_backend == "hip":  # the whole phase in one call on the engine's own fp32 variables; it commits them itself
                 v_loss, p_loss, loss = self.engine.train_run(records.data_ptr(), records.shape[0], p.parameter_update_count,
                                                              p.parameter_update_batch_size, key=self.seed + self.iteration * 7919)
-                with torch.no_grad():
-                    for var, t in zip(self.phase.net.vars, self.engine.read_weights()):
-                        var.copy_(torch.from_numpy(t).reshape(var.shape))
+                self._mirror_engine_weights()
+            elif p.train_backend == "hip_dp":
+                v_loss, p_loss, loss = self._train_data_parallel(records)
+                self._mirror_engine_weights()
             else:
                 v_loss, p_loss, loss = self.phase.run(records, p.parameter_update_count, p.parameter_update_batch_size,
                                                       seed=self.iteration * 7919 + self.rank)

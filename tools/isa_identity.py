@@ -2,7 +2,7 @@
 """tools/isa_identity.py OLD NEW
 
 Device code of two versions of the library, kernel by kernel.  OLD / NEW: a source tree (a directory that holds omok-ai_amd/csrc) or a git revision of this
-repository.  net_kernels.hip and tree_kernels.hip of both are compiled device-only with the Makefile's flags (tools/isa_hist.py: compile_code_object; tree_kernels.hip
+repository.  net_kernels.hip, tree_kernels.hip and train_kernels.hip of both are compiled device-only with the Makefile's flags (tools/isa_hist.py: compile_code_object; tree_kernels.hip
 with -ffp-contract=off) and the gfx950 code objects compared per demangled symbol:
   * the instruction sequence (mnemonics and operands; branch / call targets and address comments masked): identical or differing,
   * VGPR / AGPR / SGPR counts, LDS and scratch bytes from the code object's notes,
@@ -19,7 +19,7 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_hist  # noqa: E402
 
-FILES = (("net_kernels.hip", False), ("tree_kernels.hip", True))  # (source, -ffp-contract=off)
+FILES = (("net_kernels.hip", False), ("tree_kernels.hip", True), ("train_kernels.hip", False))  # (source, -ffp-contract=off)
 COUNTED = [  # first match wins
     ("mfma", re.compile(r"^v_s?mfma")),
     ("lds-dma", re.compile(r"^(global|buffer)_load_lds")),
