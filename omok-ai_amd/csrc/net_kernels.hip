@@ -19,6 +19,7 @@
 //             residual } with all weights LDS-resident -> fc0 operand rows (f16 hi | fp8 residual) in HBM
 //   k_fc0_mx  fc0: 512 features x 128 samples per workgroup, one wave per SIMD, LDS-DMA rings
 //   k_gemm_t  D^T[M x samples] = Wp[M x K] * Act^T, 8 waves, LDS ring: fc1, heads
+//   k_tail_fused  fc1 and the heads of a whole-K round in one launch: k_gemm_t's fc1 loop, h1 handed to the heads loop through LDS in chunks of 8 k-steps
 //   k_softmax policy softmax + value tanh
 //
 // OMOK_NET_F32: naive fp32 VALU kernels (k-ascending sums), debug / A-B reference on the GPU.
@@ -3135,12 +3136,13 @@ __global__ __launch_bounds__(256) void k_fc0_x3(const uint4* __restrict__ wp, co
 // Wp : [ksteps][MT][hi|lo][lane][8] f16 (1 KiB fragments), Act: rows of [ksteps][hi h0|hi h1|lo h0|lo h1]
 // 8 waves: wm = wave>>1 owns MT/4 m-tiles, ws = wave&1 owns 2 of the 4 sample tiles.
 
-template <int MT, int EPI, int TAG, int NST>
-__global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, const uint4* __restrict__ act, int ksteps,
-                                                size_t act_row_u4, int k_full, int last_cnt, int lo_off,
-                                                const float* __restrict__ bias, uint4* __restrict__ out_split,
-                                                size_t out_row_u4, float* __restrict__ out_logits, const int32_t* __restrict__ d_count,
-                                                int max_count) {
+// The main loop, shared by k_gemm_t and k_tail_fused's fc1 phase: k-steps [kbeg, kbeg + ksteps) of the workgroup's 128 samples through a ring of NST slots of
+// (MT * 2 + 8) KiB at `lds`, into acc[i][c] = m-tile wm * MT/4 + i, sample tile 2 ws + c.  The last NST - 1 k-steps stage nothing: behind their barriers
+// tail_issue(j), j = 0 .. NST - 2, may issue XT LDS-DMA instructions each for the caller's next phase (into ring slots whose last read that barrier proves); they are
+// younger than every k-step's pieces and still in flight on return (XT = 0: nothing is).
+template <int MT, int NST, int XT, class TailIssue>
+__device__ __forceinline__ void gemm_t_mainloop(uint4* lds, const uint4* __restrict__ wp, const uint4* __restrict__ act, int ksteps, int kbeg, size_t act_row_u4, int k_full,
+                                                int last_cnt, int lo_off, int b0, int wave, int lane, f32x16 (&acc)[MT / 4][2], TailIssue tail_issue) {
     constexpr int MTW = MT / 4;
     constexpr int WFR = MT * 2;            // weight fragments per k-step
     constexpr int NFR = WFR + 8;           // + 4 sample tiles x (hi, lo)
@@ -3148,14 +3150,7 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
     constexpr int STAGE_U4 = NFR * 64;
     // NST ring slots: NST-2 k-steps stay in flight behind the one being read
     static_assert(NFR % 8 == 0, "fragment count must split evenly over 8 waves");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint4* lds = (uint4*)smem;
-    int count = d_count[0];
-    if (count > max_count) count = max_count;
-    const int b0 = blockIdx.x * GT_BS;
-    if (b0 >= count) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    static_assert(XT == 0 || NST == 3 || NST == 4, "the counted waits of the last k-steps know these depths");
     const int wm = wave >> 1, ws = wave & 1;
     const int h = lane >> 5;
 
@@ -3177,8 +3172,6 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
             src[i] = act + row * act_row_u4 + (size_t)(part * lo_off + h);
         }
     }
-    // split-K (EPI_PARTIAL, small batches): blockIdx.y owns the k-steps [kbeg, kbeg + ksteps)
-    const int kbeg = EPI == EPI_PARTIAL ? (int)blockIdx.y * ksteps : 0;
     int kt = kbeg; // next k-step to stage
     int ko_cur = 0;
     auto issue_begin = [&]() { // uint4 offset of k-step kt inside an activation row: 4 per k-step; the k-steps of a
@@ -3195,7 +3188,6 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
         for (int i = 0; i < LPW; ++i) issue_one(i, slot);
         kt += 1;
     };
-    f32x16 acc[MTW][2];
 #pragma unroll
     for (int i = 0; i < MTW; ++i)
 #pragma unroll
@@ -3209,16 +3201,22 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
     int slot = 0, nslot = NST - 1;
     for (int t = 0; t < ksteps; ++t) {
         // retire k-step t (this wave's share; later k-steps stay in flight), then make every wave's share visible
+        // (with a tail_issue: its pieces behind the barriers of the k-steps before this one are younger still)
         const int rem = ksteps - 1 - t;
         if (rem >= NST - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW * (NST - 2)) : "memory");
-        else if (rem == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW) : "memory");
+        else if (rem == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW + (NST - 3) * XT) : "memory");
+        else if (XT != 0 && rem == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * XT) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // (a tail_issue overwrites the slot read one k-step ago: that k-step's ds_reads have returned, not merely been issued, before this wave says so at the barrier;
+        //  the staging of the steady state gets the same from the loop's back edge)
+        if (XT != 0 && rem <= NST - 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         // the staging of k-step t+NST-1 (its slot was last read at k-step t-1: safe behind the barrier) is
         // interleaved with the MFMAs so that the DMA issue cost hides under matrix-pipe time
         const bool stage = t + NST - 1 < ksteps;
         if (stage) issue_begin();
+        else if (XT != 0) tail_issue(NST - 2 - rem);
         const half8* L = (const half8*)(lds + slot * STAGE_U4);
         half8 bh[2], bl[2], ah[MTW], al[MTW];
 #pragma unroll
@@ -3248,6 +3246,29 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
         slot = slot + 1 == NST ? 0 : slot + 1;
         nslot = nslot + 1 == NST ? 0 : nslot + 1;
     }
+}
+
+template <int MT, int EPI, int TAG, int NST>
+__global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, const uint4* __restrict__ act, int ksteps,
+                                                size_t act_row_u4, int k_full, int last_cnt, int lo_off,
+                                                const float* __restrict__ bias, uint4* __restrict__ out_split,
+                                                size_t out_row_u4, float* __restrict__ out_logits, const int32_t* __restrict__ d_count,
+                                                int max_count) {
+    constexpr int MTW = MT / 4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint4* lds = (uint4*)smem;
+    int count = d_count[0];
+    if (count > max_count) count = max_count;
+    const int b0 = blockIdx.x * GT_BS;
+    if (b0 >= count) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, ws = wave & 1;
+    const int h = lane >> 5;
+    // split-K (EPI_PARTIAL, small batches): blockIdx.y owns the k-steps [kbeg, kbeg + ksteps)
+    const int kbeg = EPI == EPI_PARTIAL ? (int)blockIdx.y * ksteps : 0;
+    f32x16 acc[MTW][2];
+    gemm_t_mainloop<MT, NST, 0>(lds, wp, act, ksteps, kbeg, act_row_u4, k_full, last_cnt, lo_off, b0, wave, lane, acc, [](int) {});
 
     // ---- epilogue ----
 #pragma unroll
@@ -3292,6 +3313,173 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
                     for (int q = 0; q < 4; ++q) o[q] = y[4 * g + q];
                     *(f32x4*)(out_logits + (size_t)sample * (MT * 32) + 32 * mt + 8 * g + 4 * h) = o;
                 }
+            }
+        }
+    }
+}
+
+// ===============================================================================================
+// OMOK_NET_F16X3: fc1 and the heads in one launch (whole-K rounds): h1 stays on the CU
+// ===============================================================================================
+// fc1's accumulator tile IS the heads' B operand, in the same lane: EPI_SPLIT stores, for m-tile mt and half s, the lane's hi at row[(2 mt + s) 4 + h] and its lo at
+// row[(2 mt + s) 4 + 2 + h], and the heads' staging fetches row[4 ks + 2 part + h] of sample b0 + 32 ct + (lane & 31) into the same lane: k-step ks = 2 mt + s of the
+// heads is the register content of the wave that owns fc1 m-tile mt for sample tile ct.  The whole h1 tile (256 KiB) does not fit in LDS and never has to: the heads take
+// their k-steps in ascending order, which is the order of the fc1 waves' wm.
+//   fc1 phase    gemm_t_mainloop<16, 3> (k_gemm_t's loop: same ring, waits, wave-to-tile map and MFMA order), then bias, LeakyReLU and split8 as EPI_SPLIT does them,
+//                into registers (the 128 accumulator registers become 128 of hi|lo fragments)
+//   hand-over    chunk p = the heads' k-steps 8 p .. 8 p + 7 = what the two waves with wm == p hold: they write it as 1-KiB fragments [lane] (the image a k_gemm_t
+//                ring slot holds), barrier, all eight waves read the fragments of their own two sample tiles; a barrier in front of the next chunk's writes proves
+//                the last reads of this one
+//   heads phase  k_gemm_t<MTH>'s loop (wm owns MTH / 4 m-tiles, ws two sample tiles; hi x hi, lo x hi, hi x lo term-major) with only the weight fragments streamed:
+//                a ring of 3 slots of 2 MTH KiB, one barrier per k-step, counted vmcnt waits; slots 0 and 1 are issued behind the last two barriers of the fc1 phase
+// LDS (160 KiB): fc1 ring slots S0 S1 S2 of 40 KiB at 0, 40, 80 KiB.  fc1's last k-steps 29, 30, 31 sit in S2, S0, S1, so behind the barrier of k-step 30 S2 is free
+// (heads slot H0 at 80 KiB) and behind that of k-step 31 S0 is (H1 at 0, H2 behind it).  The chunk buffer is the 64 KiB from 96 KiB on: S2's upper part and the 40 KiB
+// the fc1 ring leaves unused, so chunk 0 is written while slower waves still read S1.
+// Every fc1 and heads accumulator sums the products k_gemm_t's sum in the same order, and the fragments are the same split8 of the same fp32 values: same bits.
+template <int MTH>
+__global__ __launch_bounds__(512) void k_tail_fused(const uint4* __restrict__ wp_fc1, const uint4* __restrict__ act, const float* __restrict__ bias_fc1,
+                                                    const uint4* __restrict__ wp_heads, const float* __restrict__ bias_heads, float* __restrict__ out_logits,
+                                                    const int32_t* __restrict__ d_count, int max_count) {
+    constexpr int MTW = MTH / 4;           // heads m-tiles per wave
+    constexpr int WFR = MTH * 2;           // heads weight fragments per k-step
+    constexpr int LPW = WFR / 8;           // LDS-DMA instructions per wave per heads k-step
+    constexpr int FC1_STAGE_U4 = 40 * 64;  // one fc1 ring slot
+    constexpr int H0_U4 = 2 * FC1_STAGE_U4, HST_U4 = WFR * 64; // heads ring: slot 0 at H0_U4, slots 1, 2 at 0 and HST_U4
+    constexpr int CHUNK_U4 = 96 * 64;      // chunk buffer: [k-step 8][sample tile 4][hi, lo][lane]
+    static_assert(WFR % 8 == 0 && 2 * HST_U4 <= FC1_STAGE_U4 && H0_U4 + HST_U4 <= CHUNK_U4, "heads ring inside the freed fc1 slots");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint4* lds = (uint4*)smem;
+    int count = d_count[0];
+    if (count > max_count) count = max_count;
+    const int b0 = blockIdx.x * GT_BS;
+    if (b0 >= count) return; // (workgroup-uniform: every barrier below is reached by all eight waves)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, ws = wave & 1;
+    const int h = lane >> 5;
+
+    const uint4* hsrc = wp_heads + (size_t)wave * 64 + lane; // this wave's heads weight fragments: f = wave + 8 i of every k-step
+    auto hslot = [&](int slot) { return lds + (slot == 0 ? H0_U4 : (slot - 1) * HST_U4); };
+    auto hissue_one = [&](int ks, int slot, int i) { dma16(hsrc + (size_t)ks * (WFR * 64) + i * 8 * 64, hslot(slot) + (wave + 8 * i) * 64); };
+    auto hissue = [&](int ks, int slot) {
+#pragma unroll
+        for (int i = 0; i < LPW; ++i) hissue_one(ks, slot, i);
+    };
+
+    // ---- fc1 phase ----
+    uint4 fr[4][2][2][2]; // h1 fragments of this wave: [m-tile i][sample tile c][half s = k-step 2 (4 wm + i) + s][hi, lo]
+    {
+        f32x16 acc[4][2];
+        gemm_t_mainloop<16, 3, LPW>(lds, wp_fc1, act, 32, 0, 128, 32, 1, 2, b0, wave, lane, acc, [&](int j) { hissue(j, j); });
+        // one m-tile at a time (its 16 bias values, then both sample tiles), so that the fragments take the accumulators' registers over as these die
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int mt = wm * 4 + i;
+            f32x4 bv[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) bv[g] = *(const f32x4*)(bias_fc1 + 32 * mt + 8 * g + 4 * h);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                float y[16];
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) y[4 * g + q] = acc[i][c][4 * g + q] + bv[g][q];
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    float v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = lrelu(y[8 * s + j]);
+                    half8 hi, lo;
+                    split8(v, hi, lo);
+                    fr[i][c][s][0] = *(const uint4*)&hi;
+                    fr[i][c][s][1] = *(const uint4*)&lo;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+
+    // ---- heads phase ----
+    f32x16 acc[MTW][2];
+#pragma unroll
+    for (int i = 0; i < MTW; ++i)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][c][r] = 0.0f;
+    uint4* chunk = lds + CHUNK_U4;
+    int slot = 0, nslot = 2;
+    for (int p = 0; p < 4; ++p) {
+        if (p) { // every wave has read the last k-step of chunk p - 1
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+        if (wm == p) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c)
+#pragma unroll
+                        for (int part = 0; part < 2; ++part) chunk[(((2 * i + s) * 4 + 2 * ws + c) * 2 + part) * 64 + lane] = fr[i][c][s][part];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the chunk's writes have left this wave before the barrier below
+        for (int kk = 0; kk < 8; ++kk) {
+            const int ks = 8 * p + kk;
+            // heads weights of k-step ks have landed (k-step ks + 1's stay in flight) and this wave's ds_reads of k-step ks - 1 have returned (the compiler moves MFMAs,
+            // not LDS reads, across the barrier: the slot they read is refilled behind it); then every wave's share and chunk p are visible
+            if (ks < 31) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LPW) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            const bool stage = ks + 2 < 32; // into the slot read at k-step ks - 1: free behind this barrier
+            const half8* L = (const half8*)hslot(slot);
+            const half8* C = (const half8*)chunk + (size_t)(kk * 8) * 64 + lane;
+            half8 bh[2], bl[2], ah[MTW], al[MTW];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                bh[c] = C[((2 * ws + c) * 2 + 0) * 64];
+                bl[c] = C[((2 * ws + c) * 2 + 1) * 64];
+            }
+#pragma unroll
+            for (int i = 0; i < MTW; ++i) {
+                ah[i] = L[((wm * MTW + i) * 2 + 0) * 64 + lane];
+                al[i] = L[((wm * MTW + i) * 2 + 1) * 64 + lane];
+            }
+#pragma unroll
+            for (int term = 0; term < 3; ++term)
+#pragma unroll
+                for (int i = 0; i < MTW; ++i) {
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) acc[i][c] = MFMA16(term == 1 ? al[i] : ah[i], term == 2 ? bl[c] : bh[c], acc[i][c]);
+                    if (stage && term == 0) {
+#pragma unroll
+                        for (int q = i; q < LPW; q += MTW) hissue_one(ks + 2, nslot, q);
+                    }
+                }
+            slot = slot + 1 == 3 ? 0 : slot + 1;
+            nslot = nslot + 1 == 3 ? 0 : nslot + 1;
+        }
+    }
+
+    // ---- epilogue (EPI_LOGITS) ----
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int sample = b0 + 32 * (2 * ws + c) + (lane & 31);
+        if (sample >= count) continue;
+#pragma unroll
+        for (int i = 0; i < MTW; ++i) {
+            const int mt = wm * MTW + i;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 bv = *(const f32x4*)(bias_heads + 32 * mt + 8 * g + 4 * h);
+                f32x4 o;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) o[q] = acc[i][c][4 * g + q] + bv[q];
+                *(f32x4*)(out_logits + (size_t)sample * (MTH * 32) + 32 * mt + 8 * g + 4 * h) = o;
             }
         }
     }
@@ -3948,13 +4136,6 @@ static void launch_trunk_fmt(Net& net, const Store& S, int max_count, hipStream_
     else launch_trunk<N, FROM_F32, BASE, DELTA, false>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2);
 }
 
-// ring depth of the full-round fc1 / heads launches (A-B knobs: same arithmetic, same bits)
-#ifndef FC1_NST
-#define FC1_NST 3
-#endif
-#ifndef HEADS_NST
-#define HEADS_NST 3
-#endif
 template <int MT, int EPI, int TAG, int NST = 3>
 static void launch_gemm(const void* wp, const void* act, int ksteps, size_t act_row_u4, int k_full, int last_cnt, int lo_off,
                         const float* bias, void* out_split, size_t out_row_u4, float* out_logits, const Store& S, int max_count,
@@ -3969,6 +4150,20 @@ static void launch_gemm(const void* wp, const void* act, int ksteps, size_t act_
     const dim3 grid((max_count + GT_BS - 1) / GT_BS, nsplit);
     kern<<<grid, 512, LDS, st>>>((const uint4*)wp, (const uint4*)act, ksteps, act_row_u4, k_full, last_cnt, lo_off, bias, (uint4*)out_split,
                                   out_row_u4, out_logits, S.d_count, max_count);
+}
+
+template <int MTH>
+static void launch_tail_fused(const void* wp_fc1, const void* act, const float* bias_fc1, const void* wp_heads, const float* bias_heads, float* out_logits, const Store& S,
+                              int max_count, hipStream_t st, int device) {
+    constexpr int LDS = 160 * 1024;
+    static bool attr_done[64] = {};
+    auto kern = k_tail_fused<MTH>;
+    if (!attr_done[device & 63]) {
+        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        attr_done[device & 63] = true;
+    }
+    kern<<<dim3((max_count + GT_BS - 1) / GT_BS), 512, LDS, st>>>((const uint4*)wp_fc1, (const uint4*)act, bias_fc1, (const uint4*)wp_heads, bias_heads, out_logits, S.d_count,
+                                                                 max_count);
 }
 
 template <int MT, int EPI>
@@ -4276,15 +4471,19 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     const size_t cap_t = (size_t)tiles_t * GT_BS;
     const size_t fin_threads = (size_t)max_count * 64;
     if (tsplit == 1) {
-        // whole-K launches: k_gemm_t; OMOK_GEMM_W=1 selects k_gemm_w (wave-private weight rings, one barrier per two k-steps; same bits, measured no faster: see the
-        // kernel) for A-B runs and the test that compares the two kernels' outputs bit for bit; the N = 9 heads (4 m-tiles: less than one per wave) stay on k_gemm_t
+        // whole-K rounds: k_tail_fused (fc1 and the heads in one launch, h1 is not written); OMOK_GEMM_W=1 selects the two k_gemm_w launches (wave-private weight rings,
+        // one barrier per two k-steps; same bits, measured no faster: see the kernel) for A-B runs and the tests that compare the outputs bit for bit; the N = 9 heads
+        // (4 m-tiles: less than one per wave) then stay on k_gemm_t
         const char* gw_env = getenv("OMOK_GEMM_W");
         const bool gw = gw_env && gw_env[0] == '1';
-        if (gw) launch_gemm_w<16, EPI_SPLIT>(net.wt_fc1, h0, 32, 128, bias_fc1, h1, 128, nullptr, S, max_count, st, net.device);
-        else launch_gemm<16, EPI_SPLIT, 1, FC1_NST>(net.wt_fc1, h0, 32, 128, 32, 1, 2, bias_fc1, h1, 128, nullptr, S, max_count, st, net.device);
-        if (MT == 8 && gw) launch_gemm_w<8, EPI_LOGITS>(net.wt_heads, h1, 32, 128, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
-        else if (MT == 8) launch_gemm<8, EPI_LOGITS, 2, HEADS_NST>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
-        else launch_gemm<4, EPI_LOGITS, 2>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
+        if (!gw) {
+            if (MT == 8) launch_tail_fused<8>(net.wt_fc1, h0, bias_fc1, net.wt_heads, bias_heads, net.s0, S, max_count, st, net.device);
+            else launch_tail_fused<4>(net.wt_fc1, h0, bias_fc1, net.wt_heads, bias_heads, net.s0, S, max_count, st, net.device);
+        } else {
+            launch_gemm_w<16, EPI_SPLIT>(net.wt_fc1, h0, 32, 128, bias_fc1, h1, 128, nullptr, S, max_count, st, net.device);
+            if (MT == 8) launch_gemm_w<8, EPI_LOGITS>(net.wt_heads, h1, 32, 128, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
+            else launch_gemm<4, EPI_LOGITS, 2>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
+        }
     } else {
         launch_gemm<16, EPI_PARTIAL, 1>(net.wt_fc1, h0, 32 / tsplit, 128, 32, 1, 2, bias_fc1, nullptr, cap_t, net.part, S, max_count, st, net.device, tsplit);
         k_splitk_finish<<<(unsigned)((fin_threads + 255) / 256), 256, 0, st>>>(net.part, tsplit, cap_t, bias_fc1, h1, 128, S.d_count, max_count);
