@@ -4,8 +4,8 @@
 // OMOK_NET_F16X3 (default): every contraction uses SPLIT operands: x = hi + lo with hi = f16(x), product =
 // hi*hi + lo*hi + hi*lo in an fp32 accumulator.  Trunk, fc1 and heads run the three terms on
 // v_mfma_f32_32x32x16_f16 (lo = f16(x - hi)); fc0 runs hi*hi on the f16 MFMA and the two correction terms on the
-// block-scaled fp8 MFMA (k_fc0_mx).  Plain fp16/bf16 inputs miss the 1e-3 parity bar on this net (random-init
-// logits have std ~9; tools/precision_study.py); the split lands at 1e-5 (f16 terms) .. 1e-4 (fp8 terms).
+// block-scaled fp6 MFMA (k_fc0_mx).  Plain fp16/bf16 inputs miss the 1e-3 parity bar on this net (random-init
+// logits have std ~9; tools/precision_study.py); the split lands at 1e-5 (f16 terms) .. 1e-4 (fp6 terms).
 //
 // Everything is computed TRANSPOSED: D[out-feature, column] = W^T[out, in] * X[in, column] with the
 // column (pixel in the trunk, sample in the fc layers) on the MFMA lane.  A 32x32 accumulator
@@ -16,7 +16,7 @@
 //
 //   k_trunk   one workgroup = one sample, one wave = one 32-pixel tile: conv_in (one MFMA k-step) ->
 //             3 x { 1x1 128->32, depthwise 3x3 through an LDS halo grid, 1x1 32->32, 1x1 32->128 +
-//             residual } with all weights LDS-resident -> fc0 operand rows (f16 hi | fp8 residual) in HBM
+//             residual } with all weights LDS-resident -> fc0 operand rows (f16 hi | fp6 residual) in HBM
 //   k_fc0_mx  fc0: 512 features x 128 samples per workgroup, one wave per SIMD, LDS-DMA rings
 //   k_gemm_t  D^T[M x samples] = Wp[M x K] * Act^T, 8 waves, LDS ring: fc1, heads
 //   k_tail_fused  fc1 and the heads of a whole-K round in one launch: k_gemm_t's fc1 loop, h1 handed to the heads loop through LDS in chunks of 8 k-steps
@@ -53,7 +53,6 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ inline void nt_store(const uint4& v, uint4* p) { __builtin_nontemporal_store(u32x4{v.x, v.y, v.z, v.w}, (u32x4*)p); }
 __device__ inline uint4 nt_load(const uint4* p) { const u32x4 v = __builtin_nontemporal_load((const u32x4*)p); return make_uint4(v[0], v[1], v[2], v[3]); }
-typedef short short2v __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x6 __attribute__((ext_vector_type(6)));
 typedef float f32x16v __attribute__((ext_vector_type(16)));
 typedef _Float16 half32 __attribute__((ext_vector_type(32)));
@@ -219,19 +218,22 @@ constexpr int TR_CONV_FRAGS = 8;
 constexpr int TR_SIDE_PER_BLOCK = 9 * NM + NM + NM + NC; // 480 floats
 constexpr int TR_SIDE_FLOATS = 3 * TR_SIDE_PER_BLOCK;    // 1440
 constexpr int GRID_STRIDE = 36; // floats per halo-grid row (32 + 4 pad: conflict-free b128 reads)
-// fc0 operand row: per (pixel tile, channel half q) one dense 6-KiB block = f16 part [32 pxl][128 B], then fp8 residual
+// fc0 operand row: per (pixel tile, channel half q) one dense 6-KiB block = f16 part [32 pxl][128 B], then residual
 // part [32 pxl][64 B] (uint4 units below)
 constexpr int OP_BLK_U4 = 384, OP_LO_U4 = 256;
 // FC0_F16 format of the same row (Net::fc0_fmt): the residual part of a block holds f16 residuals f16(x - hi) in the layout of the
 // hi part ([32 pxl][piece (2j+h) 8][16 B]) instead of fp6 codes + scales: blocks of 8 KiB
 constexpr int OPX_BLK_U4 = 512;
 constexpr int fmt_blk_u4(bool f16lo) { return f16lo ? OPX_BLK_U4 : OP_BLK_U4; }
+// The fc0 correction terms run on fp6 (e2m3) operands with per-lane E8M0 block scales ("MX6"; the fp8 format with global scales it replaced:
+// docs/experiments/r15_retired_fp8_format.diff).
 // MX6 block scales: 2^(floor(log2(amax * 32/31)) - 2).  With the plain floor(log2 amax) a block whose largest magnitude lies in [7.75, 8) x scale rounds up
 // past e2m3's largest code (7.5) and saturates: up to 6 % error on the block's largest element in ~6 % of the blocks -- the outliers a max-error probe sees.
+// The residual's scale comes from a block maximum of its own.  Taking it from the bound |x - f16(x)| <= 2^(floor(log2 |x|) - 11) instead saves 16 VALU per
+// block in the trunk epilogue (trunk -2 %) and moved N = 9 max|dv| from 3.6e-4 to 5.9e-4: not taken.
 constexpr float MX6_AMAX_ADJ = 32.0f / 31.0f;
-constexpr bool MX6 = true;   // fc0 correction terms on fp6 (e2m3) operands with per-lane E8M0 block scales (false: fp8, global scales)
-constexpr bool LO_SCALE_FROM_BOUND = false; // true: -16 VALU per block in the trunk epilogue (trunk -2 %), N = 9 max|dv| 3.6e-4 -> 5.9e-4
-constexpr int MX_SA = 2;        // fp8 copies of the fc0 operand are x * 2^MX_SA (|x| <= 112 representable; clamped beyond)
+constexpr int MX_SA = 2;        // (MxScales: global scales of the retired fp8 format.  Nothing on the device reads them any more; they stay only because k_fc0_mx's signature was not to change --
+                                //  a follow-up removes MX_SA, MxScales, fc0_scales and Net::mx_sw together with that parameter)
 
 // V2 children kernel (k_sib_children2, difference path): a base slot holds, PIXEL-major (a lane = (pixel, half h) of the MFMA accumulators reads its own
 // pixel's bytes, and the two halves' four 16-B pieces together use every byte of the pixel's lines: planes by piece -- adjacent pixels adjacent -- fetched
@@ -265,6 +267,272 @@ struct TrunkGeo {
     static constexpr int WG_THREADS = SPW * THREADS;
 };
 
+// ===============================================================================================
+// OMOK_NET_F16X3: the trunk's tile arithmetic, defined ONCE for k_trunk, k_sib_children and k_sib_children2
+// ===============================================================================================
+// The three kernels push a 32-pixel tile (one wave: pixel = lane & 31, h = lane >> 5 the accumulator half) through the same network, and the rows they
+// write must agree to the bit (the copy path's rows equal a full evaluation's; the two children kernels of the difference path are tested against each other).
+// So every piece of per-tile arithmetic lives here: the kernels differ in where a tile's pixels come from, in the depthwise between L0 and L1, and in where the
+// operand-row entries go.  Arguments are explicit and nothing is captured: ldsW / lside = the LDS-resident weights and side table, x = the tile's residual stream.
+// Two exceptions, each measured (profiles/r15_trunk_shared_kernel_stats.txt): k_trunk keeps L0 as inline text and k_sib_children2 its own base_fetch; the reasons stand there.
+
+// One-time prologue of a workgroup: conversions saturate (MODE.FP16_OVFL), trunk weights and side table into LDS (the caller zeroes its grids and synchronises).
+__device__ __forceinline__ void trunk_lds_prologue(unsigned char* smem, float* lside, const uint4* __restrict__ wt, const float* __restrict__ side, int tid) {
+    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1"); // fp6 / f16 conversions saturate (MODE.FP16_OVFL)
+    for (int i = tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
+    for (int i = tid; i < TR_SIDE_FLOATS; i += blockDim.x) lside[i] = side[i];
+}
+// The conv_in fragments of the children kernels: 32 registers that are only needed at the top of a pass.  They are fetched again at the END of every pass (from
+// L2, under the stores) instead of living through the blocks, where they pushed lane-constant addresses into scratch whose
+// reloads (a dozen dependent round trips in the store phase) cost more than the whole arithmetic of the pass
+__device__ __forceinline__ void load_conv_w(const half8* convW, int lane, half8 (&cwh)[4], half8 (&cwl)[4]) {
+    typedef const __attribute__((address_space(1))) half8* gptr_t; // (global, not generic: a flat load would also count as an LDS access)
+    unsigned long long cpv = (unsigned long long)convW;
+    asm volatile("" : "+s"(cpv)); // (opaque: keeps the loads inside the loop)
+    gptr_t cp = (gptr_t)cpv;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        cwh[m] = cp[m * 64 + lane];
+        cwl[m] = cp[(4 + m) * 64 + lane];
+    }
+}
+// The three input bits of board pixel px (flat encoder.rs layout, Player mode) from the position's words in LDS: wsrc[0..NW)
+// black, [NW..2 NW) white (one u64 each), turn = side to move
+template <int N>
+__device__ __forceinline__ void input_bits(const uint64_t* wsrc, int turn, int px, uint32_t (&bits)[3]) {
+    constexpr int HW = N * N, NW = Geo<N>::NW;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int m = 3 * px + c;
+        if (m >= 2 * HW) { bits[c] = turn == 0 ? 1u : 0u; continue; }   // encoder.rs:34-37
+        const int cell = m >> 1;
+        const bool want_black = ((m & 1) == 0) == (turn == 0);           // even slot = the side to move's stones (encoder.rs:24-27)
+        const uint64_t w = wsrc[(want_black ? 0 : NW) + (cell >> 6)];
+        bits[c] = (uint32_t)((w >> (cell & 63)) & 1ULL);
+    }
+}
+// conv_in's B operand from the pixel's three input bits, written down as f16 0 / 1 (1.0 = 0x3C00; no float conversion, no operand split):
+// k = (f0, f1, f2, 1) on lane-half 0, zeros on half 1 and in the remaining 12 k slots
+__device__ __forceinline__ half8 conv_in_operand(int h, uint32_t b0, uint32_t b1, uint32_t b2) {
+    union { uint32_t u[4]; half8 v; } Bq;
+    Bq.u[0] = h == 0 ? (b0 * 0x3C00u) | (b1 * 0x3C000000u) : 0u;
+    Bq.u[1] = h == 0 ? (b2 * 0x3C00u) | 0x3C000000u : 0u;
+    Bq.u[2] = 0u;
+    Bq.u[3] = 0u;
+    return Bq.v;
+}
+// conv_in 1x1 3->128 + bias + lrelu as one 16-deep k-step.  SPLIT_B: the inputs are floats with a residual bl (k_trunk<FROM_F32>); board inputs are 0 / 1 and
+// the bias 1: exact in f16, bl unused
+template <bool SPLIT_B>
+__device__ __forceinline__ void conv_in_tile(const half8 (&cwh)[4], const half8 (&cwl)[4], const half8& bh, const half8& bl, f32x16 (&x)[4]) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) x[m][i] = 0.0f;
+        x[m] = MFMA16(cwh[m], bh, x[m]);
+        x[m] = MFMA16(cwl[m], bh, x[m]);
+        if (SPLIT_B) x[m] = MFMA16(cwh[m], bl, x[m]);
+        LRELU16(x[m]);
+    }
+}
+// L0 of block blk: 1x1 128 -> 32, bias as the initial accumulator (the caller applies the LeakyReLU on the way to its depthwise grid)
+__device__ __forceinline__ void L0_tile(const half8* ldsW, const float* lside, int h, int lane, const f32x16 (&x)[4], int blk, f32x16& acc) {
+    const half8* W = ldsW + (size_t)blk * TR_FRAGS_PER_BLOCK * 64;
+    const float* b0 = lside + blk * TR_SIDE_PER_BLOCK + 9 * NM;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 bv = *(const f32x4*)(b0 + 8 * g + 4 * h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[4 * g + i] = bv[i];
+    }
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = x[ks >> 1][8 * (ks & 1) + j];
+        half8 bh, bl;
+        split8(v, bh, bl);
+        const half8 ah = W[(0 + ks) * 64 + lane], al = W[(8 + ks) * 64 + lane];
+        MFMA3(ah, al, bh, bl, acc);
+    }
+}
+// L1 and L2 of block blk from the pixel's depthwise outputs d[16]: pointwise 32 -> 32 + bias + lrelu, then 1x1 32 -> 128 + bias + residual (accumulated onto x), lrelu
+__device__ __forceinline__ void L1L2_tile(const half8* ldsW, const float* lside, int h, int lane, f32x16 (&x)[4], int blk, const float* d) {
+    const half8* W = ldsW + (size_t)blk * TR_FRAGS_PER_BLOCK * 64;
+    const float* sd = lside + blk * TR_SIDE_PER_BLOCK;
+    const float *b1 = sd + 10 * NM, *b2 = b1 + NM;
+    f32x16 accg;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 bv = *(const f32x4*)(b1 + 8 * g + 4 * h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) accg[4 * g + i] = bv[i];
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        half8 bh, bl;
+        split8(d + 8 * ks, bh, bl);
+        const half8 ah = W[(16 + ks) * 64 + lane], al = W[(18 + ks) * 64 + lane];
+        MFMA3(ah, al, bh, bl, accg);
+    }
+    float gv[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gv[i] = accg[i];
+    LRELU16(gv);
+    half8 gh[2], gl[2];
+    split8(gv, gh[0], gl[0]);
+    split8(gv + 8, gh[1], gl[1]);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 bv = *(const f32x4*)(b2 + 32 * m + 8 * g + 4 * h);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[m][4 * g + i] += bv[i];
+        }
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const half8 ah = W[(20 + m * 2 + ks) * 64 + lane], al = W[(28 + m * 2 + ks) * 64 + lane];
+            MFMA3(ah, al, gh[ks], gl[ks], x[m]);
+        }
+        LRELU16(x[m]);
+    }
+}
+// ---- fc0 operand-row entries of a pixel, the VALUE part (registers in, pieces out).  Per channel half q a lane holds 32 values of its pixel: x[2 q + mm][8 sx + j],
+//      and piece mm * 2 + sx is the 16 B of 8 f16 values the lane contributes to the pixel's 128-B f16 part.  Staging through LDS, read-back and the destination
+//      of the stores are each kernel's own. ----
+// FC0_F16 format: the four f16 hi pieces and the four f16 residual pieces f16(x - hi) of channel half q (split8: 1.5 VALU per value, no block maxima, no fp6 packing)
+__device__ __forceinline__ void entry_f16_pieces(const f32x16 (&x)[4], int q, half8 (&hi8)[4], half8 (&lo8)[4]) {
+#pragma unroll
+    for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+        for (int sx = 0; sx < 2; ++sx) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = x[2 * q + mm][8 * sx + j];
+            split8(v, hi8[mm * 2 + sx], lo8[mm * 2 + sx]);
+        }
+}
+// fp6 format, first half: f16 hi piece mm * 2 + sx of channel half q (round to nearest), its 8 residuals (one mixed-precision fma per value) into res[] at
+// their slots 16 mm + 8 sx + j, and the running block maxima of the values and of the residuals
+__device__ __forceinline__ uint4 entry_fp6_hi_piece(const f32x16 (&x)[4], int q, int mm, int sx, float (&res)[32], float& amax_v, float& amax_l) {
+    union { uint32_t u[4]; uint4 v; } H;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        const float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
+        const uint32_t ph = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v0, v1}, half2v));
+        H.u[jj] = ph;
+        float l0, l1;
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(ph), "v"(v0));
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(ph), "v"(v1));
+        const int slot = 16 * mm + 8 * sx + 2 * jj; // slot of v0
+        res[slot] = l0; res[slot + 1] = l1;
+        // (from asm: fmaxf() drags a canonicalising v_max per operand along under IEEE mode)
+        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_v) : "v"(v0), "v"(v1));
+        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_l) : "v"(l0), "v"(l1));
+    }
+    return H.v;
+}
+// fp6 format, second half: the E8M0 bytes of the two block scales 2^(floor(log2 max) - 2) (e2m3 emax = 2; hi copy | residual << 8) and the packed fp6 residuals
+// of the lane's 32 values (natural slot order 16 mm + reg)
+__device__ __forceinline__ u32x6 entry_fp6_residuals(const float (&res)[32], float amax_v, float amax_l, uint32_t& esc) {
+    int eh = (int)((__float_as_uint(amax_v * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2, el = (int)((__float_as_uint(amax_l * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2;
+    eh = eh < 1 ? 1 : eh;
+    el = el < 1 ? 1 : el;
+    esc = (uint32_t)eh | ((uint32_t)el << 8);
+    f32x16v ev, od; // v_cvt_scalef32_2xpk16_fp6_f32 interleaves its two sources: field 2i = ev[i], 2i+1 = od[i]
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { ev[i] = res[2 * i]; od[i] = res[2 * i + 1]; }
+    return __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, __uint_as_float((uint32_t)el << 23));
+}
+// fp6 format: the lane's share of the 64-B residual part of (pixel, q) into the pixel's staging row:
+// [h0 dwords 0..3][h1 dwords 0..3][h0 dwords 4,5 | h1 dwords 4,5][scale bytes h0, h1 | pad]
+__device__ __forceinline__ void entry_fp6_stage(uint4* stage_w, int q, int h, u32x6 lo6, uint32_t esc) {
+    stage_w[q * 4 + h] = make_uint4(lo6[0], lo6[1], lo6[2], lo6[3]);
+    ((uint2*)(stage_w + q * 4 + 2))[h] = make_uint2(lo6[4], lo6[5]);
+    ((uint16_t*)(stage_w + q * 4 + 3))[h] = (uint16_t)esc;
+}
+// ---- difference path: the BASE's operand entries of a lane's pixel (its own 4 f16 pieces and residual half per channel half q) and their subtraction from the
+//      child's finished residual stream, dequantised exactly as fc0 multiplies them ----
+struct BaseEntry {
+    uint4 hi[2][4]; // the lane's four f16 pieces per channel half q
+    u32x6 lo[2];    // fp6 format: its six dwords of packed fp6 residuals (one vector: as uint4 + uint2 members the compiler keeps them in scratch) ...
+    uint32_t sc[2]; // ... and its scale bytes
+};
+template <bool F16LO>
+__device__ __forceinline__ void base_fetch(BaseEntry& be, const uint4* frow, int px, int h) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * fmt_blk_u4(F16LO);
+#pragma unroll
+        for (int p4 = 0; p4 < 4; ++p4) be.hi[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
+        if (F16LO) continue; // (the f16 residual pieces: base_sub_f16lo, fetched behind the hi parts' subtraction -- 32 more registers do not fit beside L1L2)
+        const uint4* lp = bp + OP_LO_U4 + (px & 31) * 4;
+        const uint4 l4 = lp[h];
+        const uint2 l2 = ((const uint2*)(lp + 2))[h];
+        be.lo[q] = (u32x6){l4.x, l4.y, l4.z, l4.w, l2.x, l2.y};
+        be.sc[q] = ((const uint16_t*)(lp + 3))[h];
+    }
+}
+// x -= the f16 pieces `pc` (the lane's 4 pieces of channel half q: hi or residual part of the base's entries)
+__device__ __forceinline__ void sub_pieces(f32x16 (&x)[4], int q, const uint4 (&pc)[4]) {
+#pragma unroll
+    for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+        for (int sx = 0; sx < 2; ++sx) {
+            const uint4 hq = pc[mm * 2 + sx];
+            const uint32_t hu[4] = {hq.x, hq.y, hq.z, hq.w};
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
+                asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(hu[jj]));
+                asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(hu[jj]));
+                x[2 * q + mm][8 * sx + 2 * jj] = v0;
+                x[2 * q + mm][8 * sx + 2 * jj + 1] = v1;
+            }
+        }
+}
+// FC0_F16 rows: x - hi - lo, exactly the base as fc0 multiplies it
+__device__ __forceinline__ void base_sub_f16lo(f32x16 (&x)[4], const BaseEntry& be, const uint4* frow, int px, int h) {
+    uint4 lo[2][4];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * OPX_BLK_U4 + OP_LO_U4;
+#pragma unroll
+        for (int p4 = 0; p4 < 4; ++p4) lo[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) sub_pieces(x, q, be.hi[q]);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) sub_pieces(x, q, lo[q]);
+}
+// fp6 rows: x - hi - fp6 residual * 2^scale
+__device__ __forceinline__ void base_subtract(f32x16 (&x)[4], const BaseEntry& be) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        union { half32 v; uint32_t u[16]; } L; // residuals * 2^(scale - 127), element = slot 16 mm + reg (tools/probe/fp6_decode_probe.hip)
+        L.v = __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(be.lo[q], __uint_as_float((be.sc[q] >> 8) << 23));
+#pragma unroll
+        for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+            for (int sx = 0; sx < 2; ++sx) {
+                const uint4 hq = be.hi[q][mm * 2 + sx];
+                const uint32_t hu[4] = {hq.x, hq.y, hq.z, hq.w};
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
+                    const uint32_t ph = hu[jj], pl = L.u[8 * mm + 4 * sx + jj];
+                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(ph));
+                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(ph));
+                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(pl));
+                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(pl));
+                    x[2 * q + mm][8 * sx + 2 * jj] = v0;
+                    x[2 * q + mm][8 * sx + 2 * jj + 1] = v1;
+                }
+            }
+    }
+}
+
 template <int N, bool FROM_F32, bool BASE = false, bool DELTA = false, bool F16LO = false> // BASE: the base pass of the sibling path (see k_group / k_sib_children below), DELTA: the
                                                                                            // difference path, F16LO: operand rows in the FC0_F16 format (f16 residuals)
 __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_t* __restrict__ req_ref, const uint32_t* __restrict__ req_aux,
@@ -296,10 +564,8 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
     float* grid = (float*)(smem + TR_WBYTES) + slot * (TG::GRID_BYTES / 4);
     const float* lside = (const float*)(smem + TR_WBYTES + TG::SPW * TG::GRID_BYTES);
     const int h = lane >> 5;
-    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1"); // fp8 / f16 conversions saturate (MODE.FP16_OVFL)
     // ---- one-time: weights, side table, zero halo grid ----
-    for (int i = tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
-    for (int i = tid; i < TR_SIDE_FLOATS; i += blockDim.x) ((float*)lside)[i] = side[i];
+    trunk_lds_prologue(smem, (float*)lside, wt, side, tid);
     for (int i = tid; i < TG::SPW * (TG::GRID_BYTES / 4); i += blockDim.x) ((float*)(smem + TR_WBYTES))[i] = 0.0f;
     __syncthreads();
     int count = (row_list || BASE) ? d_nrows[0] : d_count[0];
@@ -412,7 +678,7 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
             // Board inputs are bits.  The flat layout puts (mine, theirs) of cell m >> 1 at m = 3 px + c (m < 2 HW) and the turn
             // plane behind it, so the 32 pixels of a tile touch the 48 consecutive cells from 48 * tile on: everything up to a
             // 48-bit window of each colour is wave-uniform (scalar unit), and a lane only picks its three bits out of the windows
-            // (lane-constant selectors, precomputed) and writes them down as f16 0 / 1: no float conversion, no operand split.
+            // (lane-constant selectors, precomputed) and writes them down as f16 0 / 1 (conv_in_operand).
             uint64_t bb[2 * NW];
 #pragma unroll
             for (int i = 0; i < 2 * NW; ++i) bb[i] = in.bb[i];
@@ -453,31 +719,15 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
                 const uint32_t bit = (src >> dec_shift[c]) & 1u;
                 bits[c] = dec_plane[c] ? tbit : bit;
             }
-            // f16 1.0 = 0x3C00; k = (f0, f1, f2, 1) on lane-half 0, zeros on half 1 and in the remaining 12 k slots
-            union { uint32_t u[4]; half8 v; } Bq;
-            Bq.u[0] = h == 0 ? (bits[0] * 0x3C00u) | (bits[1] * 0x3C000000u) : 0u;
-            Bq.u[1] = h == 0 ? (bits[2] * 0x3C00u) | 0x3C000000u : 0u;
-            Bq.u[2] = 0u;
-            Bq.u[3] = 0u;
-            bh = Bq.v;
+            bh = conv_in_operand(h, bits[0], bits[1], bits[2]);
             bl = bh; // (unused: the inputs are exact in f16)
         }
         f32x16 x[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) x[m][i] = 0.0f;
-            x[m] = MFMA16(cwh[m], bh, x[m]);
-            x[m] = MFMA16(cwl[m], bh, x[m]);
-            if (FROM_F32) x[m] = MFMA16(cwh[m], bl, x[m]); // (board inputs are 0 / 1 and the bias 1: exact in f16, bl = 0)
-            LRELU16(x[m]);
-        }
+        conv_in_tile<FROM_F32>(cwh, cwl, bh, bl, x);
         // ---- 3 bottleneck residual blocks ----
 #pragma unroll 1
         for (int blk = 0; blk < 3; ++blk) {
-            const half8* W = ldsW + (size_t)blk * TR_FRAGS_PER_BLOCK * 64;
-            const float* sd = lside + blk * TR_SIDE_PER_BLOCK;
-            const float *dwt = sd, *b0 = sd + 9 * NM, *b1 = b0 + NM, *b2 = b1 + NM;
+            const float* dwt = lside + blk * TR_SIDE_PER_BLOCK;
             const bool to_sib2 = BASE && DELTA && sib2 != nullptr && active && !single(bi) && valid;
             uint4* sb2 = nullptr;
             if (BASE && DELTA) sb2 = sib2 + (size_t)(to_sib2 ? groups[bi].y : 0u) * sib2_slot_u4(N);
@@ -488,23 +738,26 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
                     for (int g = 0; g < 4; ++g)
                         sb2[sib2_x2(HW, px, m, g, h)] = __builtin_bit_cast(uint4, (f32x4){x[m][4 * g], x[m][4 * g + 1], x[m][4 * g + 2], x[m][4 * g + 3]});
             }
-            // L0: 1x1 128 -> 32, bias as the initial accumulator
             f32x16 acc;
+            { // L0: 1x1 128 -> 32, bias as the initial accumulator.  L0_tile's text, inline: as a call k_trunk's N = 9 fp6 instantiations spill a conv_in fragment
+                const half8* W = ldsW + (size_t)blk * TR_FRAGS_PER_BLOCK * 64;
+                const float* b0 = lside + blk * TR_SIDE_PER_BLOCK + 9 * NM;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 bv = *(const f32x4*)(b0 + 8 * g + 4 * h);
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 bv = *(const f32x4*)(b0 + 8 * g + 4 * h);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) acc[4 * g + i] = bv[i];
-            }
+                    for (int i = 0; i < 4; ++i) acc[4 * g + i] = bv[i];
+                }
 #pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                float v[8];
+                for (int ks = 0; ks < 8; ++ks) {
+                    float v[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = x[ks >> 1][8 * (ks & 1) + j];
-                half8 bh, bl;
-                split8(v, bh, bl);
-                const half8 ah = W[(0 + ks) * 64 + lane], al = W[(8 + ks) * 64 + lane];
-                MFMA3(ah, al, bh, bl, acc);
+                    for (int j = 0; j < 8; ++j) v[j] = x[ks >> 1][8 * (ks & 1) + j];
+                    half8 bh, bl;
+                    split8(v, bh, bl);
+                    const half8 ah = W[(0 + ks) * 64 + lane], al = W[(8 + ks) * 64 + lane];
+                    MFMA3(ah, al, bh, bl, acc);
+                }
             }
             float d[16];
             // (no barrier here: a pixel's grid row is written below and was last read -- as depthwise output of the
@@ -578,54 +831,17 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
                 for (int i = 0; i < 4; ++i) d[4 * g + i] = dv[i];
                 if (to_sib2) sb2[sib2_grid(HW, blk, 1, px, g, h)] = __builtin_bit_cast(uint4, dv);
             }
-            // L1: pointwise 32 -> 32 + bias + lrelu
-            f32x16 accg;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 bv = *(const f32x4*)(b1 + 8 * g + 4 * h);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) accg[4 * g + i] = bv[i];
-            }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                half8 bh, bl;
-                split8(d + 8 * ks, bh, bl);
-                const half8 ah = W[(16 + ks) * 64 + lane], al = W[(18 + ks) * 64 + lane];
-                MFMA3(ah, al, bh, bl, accg);
-            }
-            // L2: 1x1 32 -> 128 + bias + residual (accumulated onto x), lrelu
-            float gv[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) gv[i] = accg[i];
-            LRELU16(gv);
-            half8 gh[2], gl[2];
-            split8(gv, gh[0], gl[0]);
-            split8(gv + 8, gh[1], gl[1]);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 bv = *(const f32x4*)(b2 + 32 * m + 8 * g + 4 * h);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) x[m][4 * g + i] += bv[i];
-                }
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const half8 ah = W[(20 + m * 2 + ks) * 64 + lane], al = W[(28 + m * 2 + ks) * 64 + lane];
-                    MFMA3(ah, al, gh[ks], gl[ks], x[m]);
-                }
-                LRELU16(x[m]);
-            }
+            L1L2_tile(ldsW, lside, h, lane, x, blk, d);
         }
         in = load_in(has_next ? b_next : b, ref_n, aux_n, single(has_next ? bi_next : bi)); // next sample's inputs first (see load_in)
         // ---- fc0 operand row (k_fc0_mx): per (tile, channel half q) one 6-KiB block: f16 hi pieces [pxl 32][piece
-        //      (2j+h) 8][16 B] with j = 2*(m&1)+s, then fp8 residual (x - hi)*2^(SA+11) pieces [pxl 32][piece (2h+e) 4][16 B]
-        //      (the fp8 copy of hi is derived inside k_fc0_mx).  One K=64 super-step of fc0 = one pixel of one block. ----
+        //      (2j+h) 8][16 B] with j = 2*(m&1)+s, then the 64-B residual part per pixel: packed fp6 (e2m3) codes of x - hi and the two E8M0 block scales (entry_fp6_stage)
+        //      (the fp6 copy of hi is derived inside k_fc0_mx).  One K=64 super-step of fc0 = one pixel of one block. ----
         //      Stores go through the sample's own halo-grid rows (free between the last depthwise read and the next
         //      sample's first write; a wave touches only its own pixels' interior rows, so no barrier): a lane holds six
         //      16-B pieces of ITS pixel, i.e. a direct store instruction touches 64 different cache lines with 16 B each
         //      (one texture-path cycle per line).  Transposed through LDS, 8 adjacent lanes write one pixel's 128-B run:
-        //      8 full lines per instruction.  Three passes of 128 B per pixel: f16 part of q = 0, of q = 1, both fp8 parts.
+        //      8 full lines per instruction.  Three passes of 128 B per pixel: f16 part of q = 0, of q = 1, both residual parts.
         //      (Lanes past the last pixel skip the LDS write; the read-back side then stores the clamped pixel's data into
         //      the pad slots of the row: no branch around the global stores, so the compiler counts them exactly.)
         // BASE: the row is stored into EVERY child row of the run (the rows fc0 reads must exist; k_sib_children then overwrites
@@ -640,19 +856,11 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
         uint4* stage_w = (uint4*)(grid + gi * GRID_STRIDE);          // this lane's pixel row (8 slots of 16 B)
         if constexpr (F16LO) {
             // FC0_F16: four passes of 128 B per pixel through the same staging rows -- per channel half q the f16 hi pieces, then the
-            // f16 residual pieces (split8: 1.5 VALU per value, no block maxima, no fp6 packing)
+            // f16 residual pieces
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 half8 hi8[4], lo8[4];
-#pragma unroll
-                for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-                    for (int sx = 0; sx < 2; ++sx) {
-                        float v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] = x[2 * q + mm][8 * sx + j];
-                        split8(v, hi8[mm * 2 + sx], lo8[mm * 2 + sx]);
-                    }
+                entry_f16_pieces(x, q, hi8, lo8);
 #pragma unroll
                 for (int part = 0; part < 2; ++part) {
                     if (valid) {
@@ -674,10 +882,8 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
                 }
             }
         } else {
-        const float sc_lo_inv = __uint_as_float((uint32_t)(127 - MX_SA - 11) << 23); // fp8 = (x - hi) / 2^-(SA+11)
-        uint32_t p8l[2][8];
-        u32x6 lo6[2];        // MX6: fp6 residuals of the lane's 32 values per channel half q, natural slot order 16*mm + reg
-        uint32_t esc[2];     // MX6: E8M0 bytes of the two block scales (hi copy | residual << 8)
+        u32x6 lo6[2];        // fp6 residuals of the lane's 32 values per channel half q
+        uint32_t esc[2];     // E8M0 bytes of the two block scales
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             float res[32], amax_v = 0.0f, amax_l = 0.0f;
@@ -685,43 +891,11 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
             for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
                 for (int sx = 0; sx < 2; ++sx) {
-                    union { uint32_t u[4]; uint4 v; } H;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
-                        // round-to-nearest hi; residual by one mixed-precision fma per value; scaled saturating
-                        // (MODE.FP16_OVFL) packed fp8 convert: 2 VALU per value
-                        const uint32_t ph = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v0, v1}, half2v));
-                        H.u[jj] = ph;
-                        float l0, l1;
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(ph), "v"(v0));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(ph), "v"(v1));
-                        const int slot = 16 * mm + 8 * sx + 2 * jj; // byte slot of v0
-                        const int w = slot >> 2;
-                        if (MX6) {
-                            res[slot] = l0; res[slot + 1] = l1;
-                            // (from asm: fmaxf() drags a canonicalising v_max per operand along under IEEE mode)
-                            asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_v) : "v"(v0), "v"(v1));
-                            if (!LO_SCALE_FROM_BOUND) asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_l) : "v"(l0), "v"(l1));
-                        } else if ((slot & 3) == 0)
-                            p8l[q][w] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(short2v{0, 0}, l0, l1, sc_lo_inv, false));
-                        else
-                            p8l[q][w] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(__builtin_bit_cast(short2v, p8l[q][w]), l0, l1, sc_lo_inv, true));
-                    }
-                    if (valid) stage_w[(mm * 2 + sx) * 2 + h] = H.v;
+                    const uint4 hv = entry_fp6_hi_piece(x, q, mm, sx, res, amax_v, amax_l);
+                    if (valid) stage_w[(mm * 2 + sx) * 2 + h] = hv;
                 }
             WAVE_LDS_FENCE();
-            if (MX6) { // block scales 2^(floor(log2 max) - 2) (e2m3 emax = 2) and the packed fp6 residuals
-                // (option: residual scale from the bound |x - f16(x)| <= 2^(floor(log2 |x|) - 11) instead of a second block maximum)
-                int eh = (int)((__float_as_uint(amax_v * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2, el = LO_SCALE_FROM_BOUND ? eh - 11 : (int)((__float_as_uint(amax_l * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2;
-                eh = eh < 1 ? 1 : eh;
-                el = el < 1 ? 1 : el;
-                esc[q] = (uint32_t)eh | ((uint32_t)el << 8);
-                f32x16v ev, od; // v_cvt_scalef32_2xpk16_fp6_f32 interleaves its two sources: field 2i = ev[i], 2i+1 = od[i]
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { ev[i] = res[2 * i]; od[i] = res[2 * i + 1]; }
-                lo6[q] = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, __uint_as_float((uint32_t)el << 23));
-            }
+            lo6[q] = entry_fp6_residuals(res, amax_v, amax_l, esc[q]);
             // read back: lanes 8i'..8i'+7 hold the 8 pieces of pixel 8i + i' of the tile
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -737,16 +911,7 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
         }
         if (valid) {
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                if (MX6) { // 64 B per (pixel, q): [h0 dwords 0..3][h1 dwords 0..3][h0 dwords 4,5 | h1 dwords 4,5][scale bytes h0, h1 | pad]
-                    stage_w[q * 4 + h] = make_uint4(lo6[q][0], lo6[q][1], lo6[q][2], lo6[q][3]);
-                    ((uint2*)(stage_w + q * 4 + 2))[h] = make_uint2(lo6[q][4], lo6[q][5]);
-                    ((uint16_t*)(stage_w + q * 4 + 3))[h] = (uint16_t)esc[q];
-                } else {
-                    stage_w[q * 4 + h * 2 + 0] = make_uint4(p8l[q][0], p8l[q][1], p8l[q][2], p8l[q][3]);
-                    stage_w[q * 4 + h * 2 + 1] = make_uint4(p8l[q][4], p8l[q][5], p8l[q][6], p8l[q][7]);
-                }
-            }
+            for (int q = 0; q < 2; ++q) entry_fp6_stage(stage_w, q, h, lo6[q], esc[q]);
         }
         WAVE_LDS_FENCE();
 #pragma unroll
@@ -1242,8 +1407,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
     constexpr int DROW_U4 = F16LO ? SIBX_DROW_U4 : SIB_DROW_U4;
     constexpr int SIB_HB_FLOATS = sib_hb_floats(N);
     constexpr int SWW = 4; // depthwise strips of the 7-wide window: 4 | 3 pixels
-    using TG = TrunkGeo<N>;
-    constexpr int HW = TG::HW, NW = Geo<N>::NW;
+    constexpr int NW = Geo<N>::NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const half8* ldsW = (const half8*)smem;
     float* grid = (float*)(smem + TR_WBYTES);                                       // four child grids
@@ -1251,9 +1415,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, l31 = lane & 31;
-    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");
-    for (int i = tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
-    for (int i = tid; i < TR_SIDE_FLOATS; i += blockDim.x) ((float*)lside)[i] = side[i];
+    trunk_lds_prologue(smem, (float*)lside, wt, side, tid);
     for (int i = tid; i < SIB_CGRID_BYTES; i += blockDim.x) grid[i] = 0.0f; // (4 grids x 11808 / 4 floats)
     // A child = a wave pair, and everything a pair writes in LDS is its own (child grid, staging rows, board words): the barriers below
     // are PAIR barriers (a flag per wave in LDS, the LDS executes a wave's accesses in order), not workgroup barriers.  The four pairs
@@ -1279,22 +1441,8 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
     for (int i = 0; i < (wv >> 1); ++i) __builtin_amdgcn_s_sleep(118); // (64 clocks per unit: a quarter of a ~30 k-cycle pass per pair index)
     const int nsib = d_cnt[NET_GCNT_ROWS_IN_RUNS];
     const half8* convW = (const half8*)(wt + TR_WBYTES / 16);
-    // conv_in fragments: 32 registers that are only needed at the top of a pass.  They are fetched again at the END of every pass (from
-    // L2, under the stores) instead of living through the blocks, where they pushed lane-constant addresses into scratch whose
-    // reloads (a dozen dependent round trips in the store phase) cost more than the whole arithmetic of the pass
-    half8 cwh[4], cwl[4];
-    auto load_conv_w = [&]() {
-        typedef const __attribute__((address_space(1))) half8* gptr_t; // (global, not generic: a flat load would also count as an LDS access)
-        unsigned long long cpv = (unsigned long long)convW;
-        asm volatile("" : "+s"(cpv)); // (opaque: keeps the loads inside the loop)
-        gptr_t cp = (gptr_t)cpv;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            cwh[m] = cp[m * 64 + lane];
-            cwl[m] = cp[(4 + m) * 64 + lane];
-        }
-    };
-    load_conv_w();
+    half8 cwh[4], cwl[4]; // conv_in fragments: fetched again at the end of every pass (load_conv_w)
+    load_conv_w(convW, lane, cwh, cwl);
     // wave pair = child, wave parity = window tile
     const int pair = wv >> 1, wt2 = wv & 1, ptid = tid & 127;
     const int c_w = 32 * wt2 + l31;            // window pixel of this lane, row-major in the 7x7 window
@@ -1304,97 +1452,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
     const int c_gi = (c_wy + 1) * SIB_GW + (c_wx + 1);
     float* cgrid = grid + pair * (SIB_CGRID_BYTES / 4);
 
-    // the shared per-tile arithmetic (k_trunk's, verbatim): operands are the tile's residual stream x and the LDS weights
-    auto L0_tile = [&](const f32x16 (&x)[4], int blk, f32x16& acc) {
-        const half8* W = ldsW + (size_t)blk * TR_FRAGS_PER_BLOCK * 64;
-        const float* b0 = lside + blk * TR_SIDE_PER_BLOCK + 9 * NM;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bv = *(const f32x4*)(b0 + 8 * g + 4 * h);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[4 * g + i] = bv[i];
-        }
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = x[ks >> 1][8 * (ks & 1) + j];
-            half8 bh, bl;
-            split8(v, bh, bl);
-            const half8 ah = W[(0 + ks) * 64 + lane], al = W[(8 + ks) * 64 + lane];
-            MFMA3(ah, al, bh, bl, acc);
-        }
-    };
-    auto L1L2_tile = [&](f32x16 (&x)[4], int blk, const float* d) {
-        const half8* W = ldsW + (size_t)blk * TR_FRAGS_PER_BLOCK * 64;
-        const float* sd = lside + blk * TR_SIDE_PER_BLOCK;
-        const float *b1 = sd + 10 * NM, *b2 = b1 + NM;
-        f32x16 accg;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bv = *(const f32x4*)(b1 + 8 * g + 4 * h);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) accg[4 * g + i] = bv[i];
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 bh, bl;
-            split8(d + 8 * ks, bh, bl);
-            const half8 ah = W[(16 + ks) * 64 + lane], al = W[(18 + ks) * 64 + lane];
-            MFMA3(ah, al, bh, bl, accg);
-        }
-        float gv[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) gv[i] = accg[i];
-        LRELU16(gv);
-        half8 gh[2], gl[2];
-        split8(gv, gh[0], gl[0]);
-        split8(gv + 8, gh[1], gl[1]);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 bv = *(const f32x4*)(b2 + 32 * m + 8 * g + 4 * h);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x[m][4 * g + i] += bv[i];
-            }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const half8 ah = W[(20 + m * 2 + ks) * 64 + lane], al = W[(28 + m * 2 + ks) * 64 + lane];
-                MFMA3(ah, al, gh[ks], gl[ks], x[m]);
-            }
-            LRELU16(x[m]);
-        }
-    };
-    auto conv_in_tile = [&](f32x16 (&x)[4], uint32_t b0, uint32_t b1, uint32_t b2) { // the pixel's three input bits
-        union { uint32_t u[4]; half8 v; } Bq;
-        Bq.u[0] = h == 0 ? (b0 * 0x3C00u) | (b1 * 0x3C000000u) : 0u;
-        Bq.u[1] = h == 0 ? (b2 * 0x3C00u) | 0x3C000000u : 0u;
-        Bq.u[2] = 0u;
-        Bq.u[3] = 0u;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) x[m][i] = 0.0f;
-            x[m] = MFMA16(cwh[m], Bq.v, x[m]);
-            x[m] = MFMA16(cwl[m], Bq.v, x[m]);
-            LRELU16(x[m]);
-        }
-    };
-    // the three input bits of board pixel px (flat encoder.rs layout, Player mode) from the position's words in LDS: wsrc[0..3]
-    // black, [4..7] white (one u64 each), turn = side to move
-    auto input_bits = [&](const uint64_t* wsrc, int turn, int px, uint32_t (&bits)[3]) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int m = 3 * px + c;
-            if (m >= 2 * HW) { bits[c] = turn == 0 ? 1u : 0u; continue; }   // encoder.rs:34-37
-            const int cell = m >> 1;
-            const bool want_black = ((m & 1) == 0) == (turn == 0);           // even slot = the side to move's stones (encoder.rs:24-27)
-            const uint64_t w = wsrc[(want_black ? 0 : NW) + (cell >> 6)];
-            bits[c] = (uint32_t)((w >> (cell & 63)) & 1ULL);
-        }
-    };
-    // operand-row entries of the tile's pixels (k_trunk's epilogue): channel half q of the lane's pixel staged at `stage_w`, then
+    // operand-row entries of the tile's pixels (staging and stores as in k_trunk's epilogue): channel half q of the lane's pixel staged at `stage_w`, then
     // the pixel `rp` whose 8 pieces lanes 8i..8i+7 read back from `rd_rows[i]` is stored at its place in `row`
     auto store_rows = [&](const f32x16 (&x)[4], uint4* row, bool lane_valid, float* stage_row, const int (&rd_gi)[4], const int (&rd_px)[4],
                           const bool (&rd_ok)[4], float* gbase) {
@@ -1403,15 +1461,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 half8 hi8[4], lo8[4];
-#pragma unroll
-                for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-                    for (int sx = 0; sx < 2; ++sx) {
-                        float v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] = x[2 * q + mm][8 * sx + j];
-                        split8(v, hi8[mm * 2 + sx], lo8[mm * 2 + sx]);
-                    }
+                entry_f16_pieces(x, q, hi8, lo8);
 #pragma unroll
                 for (int part = 0; part < 2; ++part) {
                     if (lane_valid) {
@@ -1441,31 +1491,11 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
             for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
                 for (int sx = 0; sx < 2; ++sx) {
-                    union { uint32_t u[4]; uint4 v; } H;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
-                        const uint32_t ph = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v0, v1}, half2v));
-                        H.u[jj] = ph;
-                        float l0, l1;
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(ph), "v"(v0));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(ph), "v"(v1));
-                        const int slot = 16 * mm + 8 * sx + 2 * jj;
-                        res[slot] = l0; res[slot + 1] = l1;
-                        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_v) : "v"(v0), "v"(v1));
-                        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_l) : "v"(l0), "v"(l1));
-                    }
-                    if (lane_valid) stage_w[(mm * 2 + sx) * 2 + h] = H.v;
+                    const uint4 hv = entry_fp6_hi_piece(x, q, mm, sx, res, amax_v, amax_l);
+                    if (lane_valid) stage_w[(mm * 2 + sx) * 2 + h] = hv;
                 }
             WAVE_LDS_FENCE();
-            int eh = (int)((__float_as_uint(amax_v * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2, el = (int)((__float_as_uint(amax_l * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2;
-            eh = eh < 1 ? 1 : eh;
-            el = el < 1 ? 1 : el;
-            esc[q] = (uint32_t)eh | ((uint32_t)el << 8);
-            f32x16v ev, od;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { ev[i] = res[2 * i]; od[i] = res[2 * i + 1]; }
-            lo6[q] = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, __uint_as_float((uint32_t)el << 23));
+            lo6[q] = entry_fp6_residuals(res, amax_v, amax_l, esc[q]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const uint4 v = *(const uint4*)(gbase + rd_gi[i] * GRID_STRIDE + 4 * (lane & 7));
@@ -1478,11 +1508,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
         }
         if (lane_valid) {
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                stage_w[q * 4 + h] = make_uint4(lo6[q][0], lo6[q][1], lo6[q][2], lo6[q][3]);
-                ((uint2*)(stage_w + q * 4 + 2))[h] = make_uint2(lo6[q][4], lo6[q][5]);
-                ((uint16_t*)(stage_w + q * 4 + 3))[h] = (uint16_t)esc[q];
-            }
+            for (int q = 0; q < 2; ++q) entry_fp6_stage(stage_w, q, h, lo6[q], esc[q]);
         }
         WAVE_LDS_FENCE();
 #pragma unroll
@@ -1539,81 +1565,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
         const int gx = cell < 9 ? cell : cell < 18 ? cell - 9 : cell < 25 ? 0 : SIB_GW - 1;
         ring_off[u] = (gy * SIB_GW + gx) * GRID_STRIDE + piece * 4;
     }
-    // DELTA: the base's operand entries of this lane's pixel (its own 4 f16 pieces and residual half per channel half q), fetched
-    // behind the last depthwise and subtracted from the finished residual stream
-    uint4 bs_hi[2][4], bs_lo[2];
-    uint2 bs_lt[2];
-    uint32_t bs_sc[2];
-    auto base_fetch = [&](const uint4* frow, int px) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * BLK_U4;
-#pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) bs_hi[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
-            if (F16LO) continue; // (the f16 residual pieces: base_sub_f16lo, fetched behind the hi parts' subtraction -- 32 more registers do not fit beside L1L2)
-            const uint4* lp = bp + OP_LO_U4 + (px & 31) * 4;
-            bs_lo[q] = lp[h];
-            bs_lt[q] = ((const uint2*)(lp + 2))[h];
-            bs_sc[q] = ((const uint16_t*)(lp + 3))[h];
-        }
-    };
-    // x -= the f16 pieces `pc` (the lane's 4 pieces of channel half q: hi or residual part of the base's entries)
-    auto sub_pieces = [&](f32x16 (&x)[4], int q, const uint4 (&pc)[4]) {
-#pragma unroll
-        for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-            for (int sx = 0; sx < 2; ++sx) {
-                const uint4 hq = pc[mm * 2 + sx];
-                const uint32_t hu[4] = {hq.x, hq.y, hq.z, hq.w};
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
-                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(hu[jj]));
-                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(hu[jj]));
-                    x[2 * q + mm][8 * sx + 2 * jj] = v0;
-                    x[2 * q + mm][8 * sx + 2 * jj + 1] = v1;
-                }
-            }
-    };
-    auto base_sub_f16lo = [&](f32x16 (&x)[4], const uint4* frow, int px) { // FC0_F16: x - hi - lo, exactly the base as fc0 multiplies it
-        uint4 lo[2][4];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * BLK_U4 + OP_LO_U4;
-#pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) lo[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) sub_pieces(x, q, bs_hi[q]);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) sub_pieces(x, q, lo[q]);
-    };
-    auto base_subtract = [&](f32x16 (&x)[4]) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const u32x6 r = {bs_lo[q].x, bs_lo[q].y, bs_lo[q].z, bs_lo[q].w, bs_lt[q].x, bs_lt[q].y};
-            union { half32 v; uint32_t u[16]; } L; // residuals * 2^(scale - 127), element = slot 16 mm + reg (tools/probe/fp6_decode_probe.hip)
-            L.v = __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(r, __uint_as_float((bs_sc[q] >> 8) << 23));
-#pragma unroll
-            for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-                for (int sx = 0; sx < 2; ++sx) {
-                    const uint4 hq = bs_hi[q][mm * 2 + sx];
-                    const uint32_t hu[4] = {hq.x, hq.y, hq.z, hq.w};
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
-                        const uint32_t ph = hu[jj], pl = L.u[8 * mm + 4 * sx + jj];
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(ph));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(ph));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(pl));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(pl));
-                        x[2 * q + mm][8 * sx + 2 * jj] = v0;
-                        x[2 * q + mm][8 * sx + 2 * jj + 1] = v1;
-                    }
-                }
-        }
-    };
+    BaseEntry be; // DELTA: the base's operand entries of this lane's pixel, fetched behind the last depthwise and subtracted from the finished residual stream
     uint4 ring[2];
     int wy0 = 0, wx0 = 0; // the current child's window
     const float* hb = hscr;
@@ -1621,7 +1573,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
     auto block_front = [&](int blk, float (&d)[16], bool fetch_next_ring) {
         const float* dwt = lside + blk * TR_SIDE_PER_BLOCK;
         f32x16 acc;
-        L0_tile(x, blk, acc);
+        L0_tile(ldsW, lside, h, lane, x, blk, acc);
         if (c_valid) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -1704,18 +1656,21 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
         const uint32_t slot_nn = fetch_slot(e0 + 2 * pass_stride);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         uint32_t bits[3];
-        input_bits(cw, turn, q, bits);
+        input_bits<N>(cw, turn, q, bits);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        conv_in_tile(x, bits[0], bits[1], bits[2]);
+        {
+            const half8 bq = conv_in_operand(h, bits[0], bits[1], bits[2]);
+            conv_in_tile<false>(cwh, cwl, bq, bq, x);
+        }
         float d[16];
 #pragma unroll 1
         for (int blk = 0; blk < 2; ++blk) {
             block_front(blk, d, true);
-            L1L2_tile(x, blk, d);
+            L1L2_tile(ldsW, lside, h, lane, x, blk, d);
         }
         block_front(2, d, false);
-        if (DELTA) base_fetch(a_out + (size_t)ent.y * row_u4, q);
-        L1L2_tile(x, 2, d);
+        if (DELTA) base_fetch<F16LO>(be, a_out + (size_t)ent.y * row_u4, q, h);
+        L1L2_tile(ldsW, lside, h, lane, x, 2, d);
         { // the window's 49 pixel entries: over the copied base row, or (DELTA) as differences into the slot's row
             int rd_gi[4], rd_px[4];
             bool rd_ok[4];
@@ -1730,8 +1685,8 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
                 rd_ok[i] = w < SIB_WPX && act;
             }
             if (DELTA) {
-                if constexpr (F16LO) base_sub_f16lo(x, a_out + (size_t)ent.y * row_u4, q);
-                else base_subtract(x);
+                if constexpr (F16LO) base_sub_f16lo(x, be, a_out + (size_t)ent.y * row_u4, q, h);
+                else base_subtract(x, be);
                 if (act && wt2 == 0 && lane == 0) slot_desc[slot] = make_uint2((uint32_t)crow, ent.y);
             }
             // the next pass's first halo ring before this pass's stores queue up behind it
@@ -1739,7 +1694,7 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
             ring_fetch(hscr + (size_t)ent_n.y * 3 * SIB_HB_FLOATS, 0, wy0, wx0, ring);
             store_rows(x, crow_p, c_valid, cgrid + c_gi * GRID_STRIDE, rd_gi, rd_px, rd_ok, cgrid);
         }
-        load_conv_w();
+        load_conv_w(convW, lane, cwh, cwl);
         ent_c = ent_n;
         ent_n = ent_nn;
         slot_c = slot_n;
@@ -1789,7 +1744,6 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             tp_last = now;
         }
     };
-    constexpr int BLK_U4 = fmt_blk_u4(F16LO);
     constexpr int DROW_U4 = OUT_F16 ? SIBX_DROW_U4 : SIB_DROW_U4;
     constexpr int HW = N * N, NW = Geo<N>::NW;
     constexpr size_t SLOT_U4 = sib2_slot_u4(N);
@@ -1800,9 +1754,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     float* wgrid = (float*)(smem + TR_WBYTES + TR_SIDE_FLOATS * 4) + wv * V2_WAVE_FLOATS; // this wave's cells
     const int h = lane >> 5;
-    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");
-    for (int i = tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
-    for (int i = tid; i < TR_SIDE_FLOATS; i += blockDim.x) ((float*)lside)[i] = side[i];
+    trunk_lds_prologue(smem, (float*)lside, wt, side, tid);
     for (int i = tid; i < 8 * V2_WAVE_FLOATS; i += blockDim.x) ((float*)(smem + TR_WBYTES + TR_SIDE_FLOATS * 4))[i] = 0.0f;
     // Round 6: the children of a workgroup are handed out from a counter in LDS instead of every wave taking every eighth entry.  The second wave of a SIMD (waves 4..7)
     // runs ~15 % slower than the first (issue arbitration favours the older wave: profiles/r05_children_store_order.txt, item 7), so with equal shares waves 0..3 end early
@@ -1817,109 +1769,10 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     for (int i = 0; i < (wv >> 2); ++i) __builtin_amdgcn_s_sleep(120); // the two waves of a SIMD (w, w + 4) start about half a pass apart
     const int nsib = d_cnt[NET_GCNT_ROWS_IN_RUNS];
     const half8* convW = (const half8*)(wt + TR_WBYTES / 16);
-    half8 cwh[4], cwl[4]; // conv_in fragments: fetched again at the end of every pass (see k_sib_children)
-    auto load_conv_w = [&]() {
-        typedef const __attribute__((address_space(1))) half8* gptr_t;
-        unsigned long long cpv = (unsigned long long)convW;
-        asm volatile("" : "+s"(cpv));
-        gptr_t cp = (gptr_t)cpv;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            cwh[m] = cp[m * 64 + lane];
-            cwl[m] = cp[(4 + m) * 64 + lane];
-        }
-    };
-    load_conv_w();
+    half8 cwh[4], cwl[4]; // conv_in fragments: fetched again at the end of every pass (load_conv_w)
+    load_conv_w(convW, lane, cwh, cwl);
 
-    // ---- the per-tile arithmetic of k_sib_children / k_trunk ----
-    auto L0_tile = [&](const f32x16 (&x)[4], int blk, f32x16& acc) {
-        const half8* W = ldsW + (size_t)blk * TR_FRAGS_PER_BLOCK * 64;
-        const float* b0 = lside + blk * TR_SIDE_PER_BLOCK + 9 * NM;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bv = *(const f32x4*)(b0 + 8 * g + 4 * h);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[4 * g + i] = bv[i];
-        }
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = x[ks >> 1][8 * (ks & 1) + j];
-            half8 bh, bl;
-            split8(v, bh, bl);
-            const half8 ah = W[(0 + ks) * 64 + lane], al = W[(8 + ks) * 64 + lane];
-            MFMA3(ah, al, bh, bl, acc);
-        }
-    };
-    auto L1L2_tile = [&](f32x16 (&x)[4], int blk, const float* d) {
-        const half8* W = ldsW + (size_t)blk * TR_FRAGS_PER_BLOCK * 64;
-        const float* sd = lside + blk * TR_SIDE_PER_BLOCK;
-        const float *b1 = sd + 10 * NM, *b2 = b1 + NM;
-        f32x16 accg;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 bv = *(const f32x4*)(b1 + 8 * g + 4 * h);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) accg[4 * g + i] = bv[i];
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 bh, bl;
-            split8(d + 8 * ks, bh, bl);
-            const half8 ah = W[(16 + ks) * 64 + lane], al = W[(18 + ks) * 64 + lane];
-            MFMA3(ah, al, bh, bl, accg);
-        }
-        float gv[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) gv[i] = accg[i];
-        LRELU16(gv);
-        half8 gh[2], gl[2];
-        split8(gv, gh[0], gl[0]);
-        split8(gv + 8, gh[1], gl[1]);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 bv = *(const f32x4*)(b2 + 32 * m + 8 * g + 4 * h);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x[m][4 * g + i] += bv[i];
-            }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const half8 ah = W[(20 + m * 2 + ks) * 64 + lane], al = W[(28 + m * 2 + ks) * 64 + lane];
-                MFMA3(ah, al, gh[ks], gl[ks], x[m]);
-            }
-            LRELU16(x[m]);
-        }
-    };
-    auto conv_in_tile = [&](f32x16 (&x)[4], uint32_t b0, uint32_t b1, uint32_t b2) {
-        union { uint32_t u[4]; half8 v; } Bq;
-        Bq.u[0] = h == 0 ? (b0 * 0x3C00u) | (b1 * 0x3C000000u) : 0u;
-        Bq.u[1] = h == 0 ? (b2 * 0x3C00u) | 0x3C000000u : 0u;
-        Bq.u[2] = 0u;
-        Bq.u[3] = 0u;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) x[m][i] = 0.0f;
-            x[m] = MFMA16(cwh[m], Bq.v, x[m]);
-            x[m] = MFMA16(cwl[m], Bq.v, x[m]);
-            LRELU16(x[m]);
-        }
-    };
-    auto input_bits = [&](const uint64_t* wsrc, int turn, int px, uint32_t (&bits)[3]) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int m = 3 * px + c;
-            if (m >= 2 * HW) { bits[c] = turn == 0 ? 1u : 0u; continue; }
-            const int cell = m >> 1;
-            const bool want_black = ((m & 1) == 0) == (turn == 0);
-            const uint64_t w = wsrc[(want_black ? 0 : NW) + (cell >> 6)];
-            bits[c] = (uint32_t)((w >> (cell & 63)) & 1ULL);
-        }
-    };
-    // difference-row entries of a tile's pixels: k_sib_children's store_rows<DELTA> (staging rows = this wave's cells 0..31)
+    // difference-row entries of a tile's pixels, in the layout of k_sib_children<DELTA>'s (staging rows = this wave's cells 0..31)
     // `far`: this lane's pixel lies outside the child's own region (P0 +- 3, clipped to the board -- at an edge that is less than the 7x7 window its bin shares): there the child
     // equals its base, and the lane stores EXACT zeros instead of the base row's quantisation remainder (~2^-22 of the activation), so that an fc0 window tile may skip the pixel
     // or not (k_bin_prefix: the tile's rectangle) without changing a bit of the row's sum.
@@ -1933,15 +1786,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 half8 hi8[4], lo8[4];
-#pragma unroll
-                for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-                    for (int sx = 0; sx < 2; ++sx) {
-                        float v[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] = x[2 * q + mm][8 * sx + j];
-                        split8(v, hi8[mm * 2 + sx], lo8[mm * 2 + sx]);
-                    }
+                entry_f16_pieces(x, q, hi8, lo8);
 #pragma unroll
                 for (int part = 0; part < 2; ++part) {
                     if (lane_valid) {
@@ -1968,31 +1813,11 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             for (int mm = 0; mm < 2; ++mm)
 #pragma unroll
                 for (int sx = 0; sx < 2; ++sx) {
-                    union { uint32_t u[4]; uint4 v; } H;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
-                        const uint32_t ph = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v0, v1}, half2v));
-                        H.u[jj] = ph;
-                        float l0, l1;
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(ph), "v"(v0));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(ph), "v"(v1));
-                        const int slot = 16 * mm + 8 * sx + 2 * jj;
-                        res[slot] = l0; res[slot + 1] = l1;
-                        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_v) : "v"(v0), "v"(v1));
-                        asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax_l) : "v"(l0), "v"(l1));
-                    }
-                    if (lane_valid) stage_w[(mm * 2 + sx) * 2 + h] = far ? make_uint4(0u, 0u, 0u, 0u) : H.v;
+                    const uint4 hv = entry_fp6_hi_piece(x, q, mm, sx, res, amax_v, amax_l);
+                    if (lane_valid) stage_w[(mm * 2 + sx) * 2 + h] = far ? make_uint4(0u, 0u, 0u, 0u) : hv;
                 }
             WAVE_LDS_FENCE();
-            int eh = (int)((__float_as_uint(amax_v * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2, el = (int)((__float_as_uint(amax_l * MX6_AMAX_ADJ) >> 23) & 0xFFu) - 2;
-            eh = eh < 1 ? 1 : eh;
-            el = el < 1 ? 1 : el;
-            esc[q] = (uint32_t)eh | ((uint32_t)el << 8);
-            f32x16v ev, od;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { ev[i] = res[2 * i]; od[i] = res[2 * i + 1]; }
-            lo6[q] = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(ev, od, __uint_as_float((uint32_t)el << 23));
+            lo6[q] = entry_fp6_residuals(res, amax_v, amax_l, esc[q]);
             if (far) lo6[q] = (u32x6){0u, 0u, 0u, 0u, 0u, 0u};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -2003,11 +1828,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         }
         if (lane_valid) {
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                stage_w[q * 4 + h] = make_uint4(lo6[q][0], lo6[q][1], lo6[q][2], lo6[q][3]);
-                ((uint2*)(stage_w + q * 4 + 2))[h] = make_uint2(lo6[q][4], lo6[q][5]);
-                ((uint16_t*)(stage_w + q * 4 + 3))[h] = (uint16_t)esc[q];
-            }
+            for (int q = 0; q < 2; ++q) entry_fp6_stage(stage_w, q, h, lo6[q], esc[q]);
         }
         WAVE_LDS_FENCE();
 #pragma unroll
@@ -2018,77 +1839,21 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         }
         WAVE_LDS_FENCE();
     };
-    // the base's operand entries of this lane's pixel, and their subtraction: k_sib_children's
-    uint4 bs_hi[2][4], bs_lo[2];
-    uint2 bs_lt[2];
-    uint32_t bs_sc[2];
-    auto base_fetch = [&](const uint4* frow, int px) {
+    BaseEntry be; // the base's operand entries of this lane's pixel
+    // base_fetch's text as a lambda of this kernel: called as the shared function, the fp6 instantiations no longer keep the entry's loads in flight under L1L2_tile
+    // (their counted vmcnt waits in base_subtract become one wait) and measured 1 % slower
+    auto base_fetch_here = [&](const uint4* frow, int px) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * BLK_U4;
+            const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * fmt_blk_u4(F16LO);
 #pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) bs_hi[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
+            for (int p4 = 0; p4 < 4; ++p4) be.hi[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
             if (F16LO) continue;
             const uint4* lp = bp + OP_LO_U4 + (px & 31) * 4;
-            bs_lo[q] = lp[h];
-            bs_lt[q] = ((const uint2*)(lp + 2))[h];
-            bs_sc[q] = ((const uint16_t*)(lp + 3))[h];
-        }
-    };
-    auto sub_pieces = [&](f32x16 (&x)[4], int q, const uint4 (&pc)[4]) {
-#pragma unroll
-        for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-            for (int sx = 0; sx < 2; ++sx) {
-                const uint4 hq = pc[mm * 2 + sx];
-                const uint32_t hu[4] = {hq.x, hq.y, hq.z, hq.w};
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
-                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(hu[jj]));
-                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(hu[jj]));
-                    x[2 * q + mm][8 * sx + 2 * jj] = v0;
-                    x[2 * q + mm][8 * sx + 2 * jj + 1] = v1;
-                }
-            }
-    };
-    auto base_sub_f16lo = [&](f32x16 (&x)[4], const uint4* frow, int px) {
-        uint4 lo[2][4];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const uint4* bp = frow + (size_t)((px >> 5) * 2 + q) * BLK_U4 + OP_LO_U4;
-#pragma unroll
-            for (int p4 = 0; p4 < 4; ++p4) lo[q][p4] = bp[(px & 31) * 8 + p4 * 2 + h];
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) sub_pieces(x, q, bs_hi[q]);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) sub_pieces(x, q, lo[q]);
-    };
-    auto base_subtract = [&](f32x16 (&x)[4]) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const u32x6 r = {bs_lo[q].x, bs_lo[q].y, bs_lo[q].z, bs_lo[q].w, bs_lt[q].x, bs_lt[q].y};
-            union { half32 v; uint32_t u[16]; } L;
-            L.v = __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(r, __uint_as_float((bs_sc[q] >> 8) << 23));
-#pragma unroll
-            for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-                for (int sx = 0; sx < 2; ++sx) {
-                    const uint4 hq = bs_hi[q][mm * 2 + sx];
-                    const uint32_t hu[4] = {hq.x, hq.y, hq.z, hq.w};
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        float v0 = x[2 * q + mm][8 * sx + 2 * jj], v1 = x[2 * q + mm][8 * sx + 2 * jj + 1];
-                        const uint32_t ph = hu[jj], pl = L.u[8 * mm + 4 * sx + jj];
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(ph));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(ph));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(v0) : "v"(pl));
-                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(v1) : "v"(pl));
-                        x[2 * q + mm][8 * sx + 2 * jj] = v0;
-                        x[2 * q + mm][8 * sx + 2 * jj + 1] = v1;
-                    }
-                }
+            const uint4 l4 = lp[h];
+            const uint2 l2 = ((const uint2*)(lp + 2))[h];
+            be.lo[q] = (u32x6){l4.x, l4.y, l4.z, l4.w, l2.x, l2.y};
+            be.sc[q] = ((const uint16_t*)(lp + 3))[h];
         }
     };
 
@@ -2167,8 +1932,11 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         const uint32_t slot_nn = sib_slot[entry_of(e_nn)];
         WAVE_LDS_FENCE();
         uint32_t bits[3];
-        input_bits(cw, turn, bpxA, bits);
-        conv_in_tile(x, bits[0], bits[1], bits[2]);
+        input_bits<N>(cw, turn, bpxA, bits);
+        {
+            const half8 bq = conv_in_operand(h, bits[0], bits[1], bits[2]);
+            conv_in_tile<false>(cwh, cwl, bq, bq, x);
+        }
         TP(0);
         // h_child - h_base of the tile -> the wave's cells; `hb` / `db`: the base's h and d pieces of this lane's pixel
         auto grid_write = [&](const f32x16& acc, const uint4 (&hb)[4]) {
@@ -2247,7 +2015,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 db[g] = sb[sib2_grid(HW, 0, 1, bpxA, g, h)];
             }
             f32x16 acc;
-            L0_tile(x, blk0, acc);
+            L0_tile(ldsW, lside, h, lane, x, blk0, acc);
             TP(1);
             if (at_p0) {
 #pragma unroll
@@ -2274,7 +2042,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             }
             WAVE_LDS_FENCE();
             TP(2);
-            L1L2_tile(x, blk0, d);
+            L1L2_tile(ldsW, lside, h, lane, x, blk0, d);
             TP(3);
         }
         { // ---- block 1: differences in the 3x3 around P0 ----
@@ -2287,12 +2055,12 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 db[g] = sb[sib2_grid(HW, 1, 1, bpxA, g, h)];
             }
             f32x16 acc;
-            L0_tile(x, blk1, acc);
+            L0_tile(ldsW, lside, h, lane, x, blk1, acc);
             TP(1);
             grid_write(acc, hb);
             strip_dw(lside + blk1 * TR_SIDE_PER_BLOCK, db);
             TP(2);
-            L1L2_tile(x, blk1, d);
+            L1L2_tile(ldsW, lside, h, lane, x, blk1, d);
             TP(3);
         }
         // ---- block 2: L0 on the tile; depthwise outputs on the tile AND the ring ----
@@ -2308,7 +2076,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 db[g] = sb[sib2_grid(HW, 2, 1, bpxA, g, h)];
             }
             f32x16 acc;
-            L0_tile(x, blk2, acc);
+            L0_tile(ldsW, lside, h, lane, x, blk2, acc);
             TP(1);
             grid_write(acc, hb);
             const float* dwt = lside + blk2 * TR_SIDE_PER_BLOCK;
@@ -2350,8 +2118,8 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             strip_dw(dwt, db);
         }
         TP(4);
-        base_fetch(frow, bpxA);
-        L1L2_tile(x, blk2, d);
+        base_fetch_here(frow, bpxA);
+        L1L2_tile(ldsW, lside, h, lane, x, blk2, d);
         TP(5);
         {
             int rd_px[4];
@@ -2364,8 +2132,8 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 rd_px[i] = (oy + tc / V2_TW) * SIB_WIN + ox + tc % V2_TW;
                 rd_ok[i] = t < V2_TPX;
             }
-            if constexpr (F16LO) base_sub_f16lo(x, frow, bpxA);
-            else base_subtract(x);
+            if constexpr (F16LO) base_sub_f16lo(x, be, frow, bpxA, h);
+            else base_subtract(x, be);
             if (lane == 0) slot_desc[slot] = make_uint2((uint32_t)crow, ent.y);
             TP(6);
             bool farA;
@@ -2387,11 +2155,11 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
 #pragma unroll
                 for (int i = 0; i < 4; ++i) x[m][4 * g + i] = v[i];
             }
-        base_fetch(frow, bpxB);
+        base_fetch_here(frow, bpxB);
 #pragma unroll
         for (int i = 0; i < 16; ++i) d[i] = dBk[i];
         TP(8);
-        L1L2_tile(x, blk2, d);
+        L1L2_tile(ldsW, lside, h, lane, x, blk2, d);
         TP(9);
         {
             int rd_px[4];
@@ -2405,8 +2173,8 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                 rd_px[i] = wy * SIB_WIN + wx;
                 rd_ok[i] = t < V2_RING;
             }
-            if constexpr (F16LO) base_sub_f16lo(x, frow, bpxB);
-            else base_subtract(x);
+            if constexpr (F16LO) base_sub_f16lo(x, be, frow, bpxB, h);
+            else base_subtract(x, be);
             TP(10);
             bool farB;
             {
@@ -2417,7 +2185,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             }
             store_rows(x, crow_p, (OL() & 31) < V2_RING, rd_px, rd_ok, farB);
         }
-        load_conv_w();
+        load_conv_w(convW, lane, cwh, cwl);
         ent_c = ent_n;
         ent_n = ent_nn;
         slot_c = slot_n;
@@ -2433,11 +2201,11 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
 #undef TILE_A
 #undef RING_B
 // ===============================================================================================
-// OMOK_NET_F16X3: fc0 with block-scaled fp6 (or fp8) correction terms
+// OMOK_NET_F16X3: fc0 with block-scaled fp6 correction terms
 // ===============================================================================================
 // x*w = hi*hi (f16 MFMA) + lo*hi + hi*lo.  The two correction terms are 2^-11 of the product, so 4 significant bits
 // keep the total at ~2^-15 relative: they run on v_mfma_scale_f32_32x32x64_f8f6f4 with fp6 (e2m3) operands and one E8M0
-// scale byte per lane and 32-element K block (MX6; the first version used fp8 e4m3 with global scales, MX6 = false).
+// scale byte per lane and 32-element K block (MX6; the first version used fp8 e4m3 with global scales).
 // Per K = 64 the matrix pipe executes 4 f16 + 2 fp6 MFMAs of 32 cycles instead of 12 f16 MFMAs.  Probed on the device:
 //   tools/probe/fp6_probe.hip  lane l = row/col l&31, k = 32*(l>>5) + i in bits [6i, 6i+5] of the lane's 192 bits; the lane's
 //                              scale byte (selected by opsel) scales exactly that block by 2^(byte-127); the packed converts
@@ -2455,12 +2223,6 @@ constexpr int MXS_SLOTS = 4;            // weight ring depth: three stages stay 
 
 struct MxScales { int wa_hi, wa_lo, ab_hi, ab_lo; float w_mul, a_mul; }; // E8M0 bytes (A = weights, B = samples) + 2^SW, 2^SA
 
-// fp8 (e4m3) copy of 8 f16 values * mul, as 2 dwords (the k-slots 8j..8j+7 of a lane).  The hi*lo / lo*hi correction
-// terms only need ~3 bits, so the fp8 "hi" operands are derived from the f16 fragments on the otherwise idle VALU
-// instead of being streamed (25 % fewer bytes through the LDS-DMA path, which bounds this kernel).
-__device__ inline v8i v8_from(const uint4& a, const uint4& b) {
-    return v8i{(int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y, (int)b.z, (int)b.w};
-}
 // LDS-DMA as inline asm: hipcc's waitcnt pass orders every later ds_read against builtin LDS-DMA with vmcnt(0),
 // which drains the whole prefetch ring once per stage; issued from asm the pass does not see it and the counted
 // waits below (also asm) are the only ordering.  m0 = LDS byte address of lane 0's 16 bytes.
@@ -2475,23 +2237,6 @@ __device__ inline void dma16s(const uint4* sbase, uint32_t voff, const uint4* ld
     if (NT) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(sbase), "s"(a) : "memory", "m0");
     else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(a) : "memory", "m0");
 }
-// v_cvt_scalef32_pk_fp8_f16: fp8(x / scale), RNE, two f16 (one dword) per instruction into one half of the destination
-// (tools/probe/cvt_probe.hip).  From asm so that the first convert of a dword does not drag a zeroing v_mov along for
-// the half it leaves alone (the builtin's tied "old" operand).
-__device__ inline uint32_t cvt_fp8_lo(uint32_t src2, float scale) {
-    uint32_t d;
-    asm("v_cvt_scalef32_pk_fp8_f16 %0, %1, %2" : "=v"(d) : "v"(src2), "v"(scale));
-    return d;
-}
-__device__ inline uint32_t cvt_fp8_hi(uint32_t d, uint32_t src2, float scale) {
-    asm("v_cvt_scalef32_pk_fp8_f16 %0, %1, %2 op_sel:[0,0,1]" : "+v"(d) : "v"(src2), "v"(scale));
-    return d;
-}
-__device__ inline void f16x8_to_fp8(const half8& v, float inv_mul, uint32_t& d0, uint32_t& d1) {
-    const uint4 q = __builtin_bit_cast(uint4, v);
-    d0 = cvt_fp8_hi(cvt_fp8_lo(q.x, inv_mul), q.y, inv_mul);
-    d1 = cvt_fp8_hi(cvt_fp8_lo(q.z, inv_mul), q.w, inv_mul);
-}
 
 // Workgroup = 4 waves (one per SIMD, each with the full 512-register file): wave w owns m-tile 4g+w of every
 // group g for ALL four sample tiles, i.e. 16 accumulator tiles (256 registers).  The sample operands of a
@@ -2499,7 +2244,9 @@ __device__ inline void f16x8_to_fp8(const half8& v, float inv_mul, uint32_t& d0,
 // exactly one wave.  LDS traffic per stage drops from 144 KiB (8-wave form) to ~48 KiB and the matrix pipe is fed
 // by one wave with 4 independent accumulator chains.
 constexpr bool A_NT = true;     // the sample-operand stream is read once: non-temporal, so it does not displace the weight stream in L2
-// MX6 helpers: fp6 (e2m3) copy of 32 f16 values (4 consecutive 8-element pieces, natural slot order) = x / 2^(E - 127)
+// fp6 (e2m3) copy of 32 f16 values (4 consecutive 8-element pieces, natural slot order) = x / 2^(E - 127).  The hi*lo / lo*hi correction
+// terms only need ~3 bits, so the fp6 "hi" operands are derived from the f16 fragments on the otherwise idle VALU
+// instead of being streamed (25 % fewer bytes through the LDS-DMA path, which bounds this kernel).
 __device__ inline v8i f16x32_to_fp6(const half8& p0, const half8& p1, const half8& p2, const half8& p3, uint32_t e8m0) {
     typedef _Float16 half16 __attribute__((ext_vector_type(16)));
     const half16 lo = __builtin_shufflevector(p0, p1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
@@ -2692,7 +2439,7 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     // (bn: board side, WIN only)  Static LDS objects, one per weight-ring slot: hipcc orders a ds_read after an LDS-DMA write by object (alias
     // scopes of distinct LDS variables), and with one dynamic array it drains ALL outstanding DMA (vmcnt(0)) before
     // the first LDS read of every stage.  With separate objects it waits exactly for the last DMA into the slot read.
-    __shared__ uint4 ldsA[2 * MXS_U4];        // [2]{ f16 [128 samples][8 pieces] | fp8 [128 samples][4 pieces] }
+    __shared__ uint4 ldsA[2 * MXS_U4];        // [2]{ f16 [128 samples][8 pieces] | fp6 residual part [128 samples][4 pieces] }
     __shared__ uint4 ldsW0[MXS_U4], ldsW1[MXS_U4], ldsW2[MXS_U4], ldsW3[MXS_U4]; // [4 i][6 frag][64] each
     auto ring = [&](int slot) -> uint4* { return slot == 0 ? ldsW0 : slot == 1 ? ldsW1 : slot == 2 ? ldsW2 : ldsW3; };
     Fc0Tile t;
@@ -2729,13 +2476,13 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     auto issue_w1 = [&](int uabs, int g, int slot, int k) { // fragment k of this wave's 6, stage g of absolute super-step uabs
         dma16s(wsrc + ((size_t)uabs * 4 + g) * MXS_U4 + k * 64, w_voff, ring(slot) + w_dma_off + k * 64);
     };
-    // Sample operands of a super-step: per sample 128 B of f16 pieces (2j+h) and 64 B of fp8 residual pieces (2h+e)
+    // Sample operands of a super-step: per sample 128 B of f16 pieces (2j+h) and 64 B of fp6 residuals and their scale bytes (read_lo6)
     // (two regions of the row's dense (tile, q) block).  The DMA reads them with ADJACENT LANES ON ADJACENT 16-B PIECES of one sample (8
-    // lanes = the 128-B f16 part, 4 lanes = the 64-B fp8 part): the texture path coalesces neighbouring lanes only,
+    // lanes = the 128-B f16 part, 4 lanes = the 64-B residual part): the texture path coalesces neighbouring lanes only,
     // and the MFMA lane order (lane = sample) made every lane its own 16-B request -- 64 requests per instruction
     // and as much address-path time for these 20 % of the bytes as for all the weights.  Wave w stages sample tile w:
-    // k = 0..3: f16 part of samples 8k..8k+7 of the tile, k = 4,5: fp8 part of samples 16(k-4)..+15.
-    // LDS image: f16 [128 samples][8 pieces], then fp8 [128 samples][4 pieces]; the piece index is XOR-swizzled with
+    // k = 0..3: f16 part of samples 8k..8k+7 of the tile, k = 4,5: residual part of samples 16(k-4)..+15.
+    // LDS image: f16 [128 samples][8 pieces], then the residual parts [128 samples][4 pieces]; the piece index is XOR-swizzled with
     // the sample index (on the global side, inside the contiguous segment) so that the ds_read_b128 of an MFMA
     // fragment (lane = sample, 128-B / 64-B stride) is bank-conflict free for its four 16-lane groups.
     const uint4* abase = act + (size_t)(b0 + 32 * wave) * act_row_u4; // wave-uniform
@@ -2752,7 +2499,7 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     }
     auto issue_a1 = [&](int uo, int buf, int k) {
         const int dst = k < 4 ? (wave * 4 + k) * 64 : 1024 + (wave * 2 + (k - 4)) * 64;
-        const int blk = uo >> 5, pl = uo & 31; // f16 part: 8 uint4 per pixel; fp8 part: 4 per pixel behind the 32 x 8
+        const int blk = uo >> 5, pl = uo & 31; // f16 part: 8 uint4 per pixel; residual part: 4 per pixel behind the 32 x 8
         if (WIN) {
             const int e = (uo & 1) * SIB_WPX + (uo >> 1); // difference row: [q][w] f16 parts, then [q][w] residual parts
             dma16s<A_NT>(abase + (k < 4 ? e * 8 : SIB_DLO_U4 + e * 4), a_voff[k], ldsA + buf * MXS_U4 + dst);
@@ -2761,12 +2508,10 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     };
     // LDS read offsets (uint4 units) of this lane's pieces inside sample tile 0; tile c adds 256 / 128
     const int sl = lane & 31;
-    int a_rd_hi[4], a_rd_lo[2];
+    int a_rd_hi[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) a_rd_hi[j] = sl * 8 + ((2 * j + h) ^ ((sl >> 1) & 7));
-#pragma unroll
-    for (int e = 0; e < 2; ++e) a_rd_lo[e] = 1024 + sl * 4 + ((2 * h + e) ^ ((sl >> 2) & 3));
-    // MX6: the 64 B of a sample's residual part = [h0 fp6 dwords 0..3][h1 dwords 0..3][h0 dwords 4,5 | h1 dwords 4,5][scale bytes | pad]
+    // the 64 B of a sample's residual part = [h0 fp6 dwords 0..3][h1 dwords 0..3][h0 dwords 4,5 | h1 dwords 4,5][scale bytes | pad]
     const int a_rd_lo6 = 1024 + sl * 4 + (h ^ ((sl >> 2) & 3));                          // uint4 index of this lane's first 16 B
     const int a_rd_tail = (1024 + sl * 4 + (2 ^ ((sl >> 2) & 3))) * 16 + 8 * h;         // byte offset of its last 8 B
     const int a_rd_esc = (1024 + sl * 4 + (3 ^ ((sl >> 2) & 3))) * 16 + 2 * h;          // byte offset of its two scale bytes (hi copy, residual)
@@ -2780,9 +2525,8 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
         e_hi |= (e & 0xFFu) << (8 * c);
         e_lo |= (e >> 8) << (8 * c);
     };
-    // fp8 conversions saturate to +-448 instead of producing NaN (MODE.FP16_OVFL, probed: tools/probe/cvt_probe.hip)
+    // conversions saturate instead of producing NaN (MODE.FP16_OVFL, probed: tools/probe/cvt_probe.hip)
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");
-    const float w_inv = 1.0f / sc.w_mul, a_inv = 1.0f / sc.a_mul; // powers of two
     f32x16 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -2815,10 +2559,7 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
 #pragma unroll
             for (int c = 0; c < 4; ++c) bh[c][j] = *(const half8*)(ldsA + c * 256 + a_rd_hi[j]);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (MX6) read_lo6(ldsA, c, a8l[c], sc_hi, sc_lo);
-            else a8l[c] = v8_from(ldsA[c * 128 + a_rd_lo[0]], ldsA[c * 128 + a_rd_lo[1]]);
-        }
+        for (int c = 0; c < 4; ++c) read_lo6(ldsA, c, a8l[c], sc_hi, sc_lo);
 #pragma unroll
         for (int k = 0; k < 6; ++k) wc[k] = ldsW0[w_rd_off + k * 64];
     }
@@ -2826,10 +2567,10 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
     // is issued in ITS gap (tools/probe/overlap_probe.hip: an 8-pass f16 MFMA hides ~4-5 single-issue instructions, a
     // trailing block of VALU hides nothing; one LDS-DMA costs ~60 cycles of issue).  So every MFMA below is followed by
     // its own small group of fillers and a scheduling barrier pins the group to the gap:
-    //   f16 MFMA gaps   : the fp8 derivations (one packed convert per weight pair; at g = 0 also the sample copies),
+    //   f16 MFMA gaps   : the fp6 derivations (one packed convert per 32 values: the weight block, at g = 0 also the sample tiles),
     //                     at g = 3 the LDS read that replaces the piece just consumed, at the end the next stage's
     //                     weight fragments LDS -> registers
-    //   scaled-fp8 gaps : one LDS-DMA each (16-pass MFMA = 64 cycles)
+    //   block-scaled gaps : one LDS-DMA each (16-pass MFMA = 64 cycles)
     // Stage q = (ul, g) lives in ring slot g.  The DMA of stage q+4 goes to slot g itself (its fragments were read into
     // registers during stage q-1): four stages of weights are in flight or resident.  Per block-scaled phase the DMA order is [2 sample pieces (g < 3)], 6 weights.
     // One workgroup barrier per super-step (top of g = 3): behind it the NEXT super-step's sample operands replace the
@@ -2844,12 +2585,11 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
             half8 ah[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) ah[j] = __builtin_bit_cast(half8, wc[j]);
-            const v8i w8l = MX6 ? v8i{(int)wc[4].x, (int)wc[4].y, (int)wc[4].z, (int)wc[4].w, (int)wc[5].x, (int)wc[5].y, 0, 0} : v8_from(wc[4], wc[5]);
-            const uint32_t wsc = wc[5].z; // MX6: E8M0 bytes of this lane's weight block (byte 0: fp6 copy of hi, byte 1: residual)
+            const v8i w8l = v8i{(int)wc[4].x, (int)wc[4].y, (int)wc[4].z, (int)wc[4].w, (int)wc[5].x, (int)wc[5].y, 0, 0};
+            const uint32_t wsc = wc[5].z; // E8M0 bytes of this lane's weight block (byte 0: fp6 copy of hi, byte 1: residual)
             // this stage's DMA refills ring slot g, the slot `wc` was read from one stage ago: those reads have returned
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            v8i w6h = {0, 0, 0, 0, 0, 0, 0, 0};
-            uint32_t w8[8]; // fp8 copy of ah[0..3]: dword 2j, 2j+1
+            v8i w6h = {0, 0, 0, 0, 0, 0, 0, 0}; // fp6 copy of ah[0..3]
             if (g == 3) { // every wave's share of A(ul+1) must have landed before anyone reads it: its last pieces were
                           // issued at the head of stage g = 1, with 6 + 6 weight pieces behind them
                 asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
@@ -2880,21 +2620,9 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     acc[g][c] = MFMA16(ah[j], bh[c][j], acc[g][c]);
-                    if (MX6) { // one packed convert per 32 values: the weight block in the first gap, sample tile c in gap (1, c) of g = 0
-                        if (j == 0 && c == 0) w6h = f16x32_to_fp6(ah[0], ah[1], ah[2], ah[3], wsc & 0xFFu);
-                        if (g == 0 && j == 1) a8h[c] = f16x32_to_fp6(bh[c][0], bh[c][1], bh[c][2], bh[c][3], (sc_hi >> (8 * c)) & 0xFFu);
-                    } else {
-                    { // weight pair c of piece j -> one half of dword 2j + (c >> 1)
-                        const uint4 aq = __builtin_bit_cast(uint4, ah[j]);
-                        const uint32_t src = c == 0 ? aq.x : c == 1 ? aq.y : c == 2 ? aq.z : aq.w;
-                        w8[2 * j + (c >> 1)] = (c & 1) ? cvt_fp8_hi(w8[2 * j + (c >> 1)], src, w_inv) : cvt_fp8_lo(src, w_inv);
-                    }
-                    if (g == 0) { // fp8 copy of this super-step's piece (c, j)
-                        uint32_t d0, d1;
-                        f16x8_to_fp8(bh[c][j], a_inv, d0, d1);
-                        a8h[c][2 * j] = (int)d0; a8h[c][2 * j + 1] = (int)d1;
-                    }
-                    }
+                    // one packed convert per 32 values: the weight block in the first gap, sample tile c in gap (1, c) of g = 0
+                    if (j == 0 && c == 0) w6h = f16x32_to_fp6(ah[0], ah[1], ah[2], ah[3], wsc & 0xFFu);
+                    if (g == 0 && j == 1) a8h[c] = f16x32_to_fp6(bh[c][0], bh[c][1], bh[c][2], bh[c][3], (sc_hi >> (8 * c)) & 0xFFu);
                     if (g == 3) bh[c][j] = *(const half8*)(LAn + c * 256 + a_rd_hi[j]); // next super-step's piece
                     if (j == 3) { // stage q+1's weights (issued during stage q-3): everything but the pieces of stages q-2, q-1
                                   // (8 each, 6 for a g = 2 stage) and the first 4 of this stage has landed
@@ -2911,29 +2639,21 @@ __global__ __launch_bounds__(256) void k_fc0_mx(const uint4* __restrict__ wp, co
                     GAP();
                 }
             }
-            v8i w8h;
-            if (MX6) w8h = w6h;
-            else w8h = v8i{(int)w8[0], (int)w8[1], (int)w8[2], (int)w8[3], (int)w8[4], (int)w8[5], (int)w8[6], (int)w8[7]};
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                if (MX6) acc[g][c] = MFMA6(w8h, a8l[c], acc[g][c], 0, wsc, c, sc_lo); // (fp6 copy of w) x (residual of x)
-                else acc[g][c] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w8h, a8l[c], acc[g][c], 0, 0, 0, sc.wa_hi, 0, sc.ab_lo);
+                acc[g][c] = MFMA6(w6h, a8l[c], acc[g][c], 0, wsc, c, sc_lo); // (fp6 copy of w) x (residual of x)
                 if (c == 0) dma_piece(5);
                 if (c == 3) dma_piece(6);
-                if (g == 3) {
-                    if (MX6) read_lo6(LAn, c, a8l[c], sc_hi_n, sc_lo_n);
-                    else a8l[c] = v8_from(LAn[c * 128 + a_rd_lo[0]], LAn[c * 128 + a_rd_lo[1]]);
-                }
+                if (g == 3) read_lo6(LAn, c, a8l[c], sc_hi_n, sc_lo_n);
                 GAP();
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                if (MX6) acc[g][c] = MFMA6(w8l, a8h[c], acc[g][c], 1, wsc, c, sc_hi); // (residual of w) x (fp6 copy of x)
-                else acc[g][c] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w8l, a8h[c], acc[g][c], 0, 0, 0, sc.wa_lo, 0, sc.ab_hi);
+                acc[g][c] = MFMA6(w8l, a8h[c], acc[g][c], 1, wsc, c, sc_hi); // (residual of w) x (fp6 copy of x)
                 if (c == 2) dma_piece(7);
                 GAP();
             }
-            if (MX6 && g == 3) { sc_hi = sc_hi_n; sc_lo = sc_lo_n; sc_hi_n = 0; sc_lo_n = 0; }
+            if (g == 3) { sc_hi = sc_hi_n; sc_lo = sc_lo_n; sc_hi_n = 0; sc_lo_n = 0; }
 #pragma unroll
             for (int k = 0; k < 6; ++k) wc[k] = wn[k];
         }
@@ -3745,31 +3465,6 @@ static void pack_A(std::vector<_Float16>& out, int ksteps, int MT, GetW getw, KI
                 }
 }
 
-// float -> OCP fp8 e4m3fn, round to nearest even, saturating at +-448
-static uint8_t to_e4m3(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    const uint8_t sign = (uint8_t)((u >> 24) & 0x80);
-    float a = fabsf(x);
-    if (!(a == a)) return 0x7f;
-    if (a >= 448.0f) return sign | 0x7e;
-    if (a < 0.0009765625f) return sign; // below half of the smallest subnormal (2^-9): rounds to 0
-    int e;
-    const float m = frexpf(a, &e); // a = m * 2^e, m in [0.5, 1)
-    int E = e - 1;                 // a = (2m) * 2^E, 2m in [1,2)
-    if (E < -6) { // subnormal: units of 2^-9
-        const float q = a * 512.0f;
-        int r = (int)lrintf(q);
-        if (r >= 8) return sign | 0x08; // rounds up to the smallest normal
-        return sign | (uint8_t)r;
-    }
-    const float frac = (2.0f * m - 1.0f) * 8.0f; // [0,8)
-    int r = (int)lrintf(frac);
-    if (r == 8) { r = 0; E += 1; }
-    if (E > 8 || (E == 8 && r > 6)) return sign | 0x7e;
-    return sign | (uint8_t)(((E + 7) << 3) | r);
-}
-
 // fp6 e2m3 (1 sign, 2 exponent, 3 mantissa; subnormal step 0.125, normals 1..7.5, no NaN / Inf): round to nearest even, saturating
 static uint8_t to_e2m3(float x) {
     const uint8_t sign = x < 0.0f ? 0x20 : 0x00;
@@ -4019,7 +3714,6 @@ static int net_pack(Net& net, hipStream_t st) {
                 for (int pl = 0; pl < 32 && tile * 32 + pl < hw; ++pl) { upx.push_back(tile * 32 + pl); uq.push_back(q); }
         const size_t nsup = upx.size();
         buf.assign((nsup * 4 + 4) * MXS_FR * 1024, 0);
-        const float s_lo = ldexpf(1.0f, SW + 11);
         for (size_t u = 0; u < nsup; ++u)
             for (int g = 0; g < 4; ++g)
                 for (int i = 0; i < 4; ++i) {
@@ -4027,7 +3721,7 @@ static int net_pack(Net& net, hipStream_t st) {
                     const int mt = 4 * g + i;
                     for (int l = 0; l < 64; ++l) {
                         const int r = l & 31, hh = l >> 5, n = 32 * mt + r;
-                        if (MX6) { // fragments 4, 5 = [lane][fp6 dwords 0..3] | [lane][fp6 dwords 4, 5 | scale bytes (hi copy, residual) | 0]
+                        { // fragments 4, 5 = [lane][fp6 dwords 0..3] | [lane][fp6 dwords 4, 5 | scale bytes (hi copy, residual) | 0]
                             float whf[32], wlf[32], ah = 0.0f, al = 0.0f;
                             for (int slot = 0; slot < 32; ++slot) {
                                 const int mm = slot >> 4, reg = slot & 15;
@@ -4056,10 +3750,8 @@ static int net_pack(Net& net, hipStream_t st) {
                             const size_t k = (size_t)upx[u] * NC + kperm(m, reg >> 3, hh, reg & 7);
                             const float wv = w[k * NF + n];
                             const _Float16 wh = (_Float16)wv;
-                            const float wl = wv - (float)wh;
                             const int j = 2 * mm + (reg >> 3), jj = reg & 7; // f16 piece j, element jj
                             memcpy(st + (size_t)j * 1024 + (size_t)l * 16 + jj * 2, &wh, 2);
-                            if (!MX6) st[(size_t)(4 + (slot >> 4)) * 1024 + (size_t)l * 16 + (slot & 15)] = to_e4m3(wl * s_lo);
                         }
                     }
                 }
