@@ -57,6 +57,8 @@ pub const OMOK_MAX_ARENA: i32 = 16384;
 pub const OMOK_OPP_RANDOM: i32 = 0;
 pub const OMOK_OPP_NAIVE: i32 = 1;
 pub const OMOK_TRAIN_MAX_RANKS: i32 = 64;
+pub const OMOK_MOVE_CELL: i32 = 255;
+pub const OMOK_MOVE_EXTERNAL: i32 = 256;
 pub const OMOK_PLAN_INTS: i32 = 16;
 pub const OMOK_STAT_SIMS: i32 = 0;
 pub const OMOK_STAT_EVALS: i32 = 1;
@@ -182,6 +184,9 @@ pub mod ffi {
         pub fn omok_root_stats(e: *mut OmokEngine, n: *mut u32, w: *mut f32) -> c_int;
         pub fn omok_root_children(e: *mut OmokEngine, game: i32, side: i32, actions: *mut i32, n: *mut u32, w: *mut f32, p: *mut f32, cap: i32) -> c_int;
         pub fn omok_replay_game(e: *mut OmokEngine, game: i32, boards: *mut u8, turns: *mut u8, pi: *mut f32, z: *mut f32, cap_plies: i32) -> c_int;
+        pub fn omok_game_log_enable(e: *mut OmokEngine, enabled: i32) -> c_int;
+        pub fn omok_game_log_read(e: *mut OmokEngine, first_game: i32, games: i32, start_boards: *mut u8, lengths: *mut i32, moves: *mut u16, root_n: *mut u32, root_w: *mut f32, child_n: *mut u32, child_w: *mut f32) -> c_int;
+        pub fn omok_env_replay(e: *mut OmokEngine, start_boards: *const u8, moves: *const u16, lengths: *const i32, batch: i32, stride: i32, upto: i32, boards_out: *mut u8, status_out: *mut i32, played_out: *mut i32) -> c_int;
         pub fn omok_replay_pack_dev(e: *mut OmokEngine, dst_dev: *mut c_void, cap_records: i64) -> i64;
         pub fn omok_replay_record_bytes(e: *const OmokEngine) -> i32;
         pub fn omok_replay_augment_dev(e: *mut OmokEngine, dst_dev: *mut c_void, cap_records: i64) -> i64;

@@ -408,6 +408,37 @@ int omok_root_children(omok_engine* e, int32_t game, int32_t side, int32_t* acti
  * time, before the back-fill of trainer.rs:207-214).  returns the ply count. */
 int omok_replay_game(omok_engine* e, int32_t game, uint8_t* boards, uint8_t* turns, float* pi, float* z,
                      int32_t cap_plies);
+/* ---- game records: every move of an episode with what the mover's search knew of it -----------
+ * The reference keeps a Transition for the moves the trainer sampled (src/trainer.rs:169-173) and nothing of an evaluation game or a match
+ * (trainer.rs:400-603, benchmark/src/main.rs:60-105 count results only).  The move log keeps, per game, the start position and for every
+ * move played since the last reset -- sampled (omok_advance, omok_selfplay_run, omok_versus_run, match episodes), scripted or supplied
+ * (omok_play_actions) -- the cell, whether it was external, MCTS::root's n and w of the mover's agent (mcts/src/lib.rs:34-36, as
+ * omok_root_stats returns them at that moment) and the n and w of the root's child for that cell (Node::children, mcts/src/node.rs:10-21, as
+ * omok_root_children returns them; 0 / 0.0f if the root has no such child: read BEFORE Agent::ensure_action_exists, alpha-zero/src/agent.rs:144-197,
+ * adds it, so a move the tree did not hold and the never-searched tree of a scripted side log what the search knew: nothing).  Written on the
+ * device in front of the re-rooting of every ply; off by default, and while off the engine makes the launches and allocations it makes without it. */
+#define OMOK_MOVE_CELL 255      /* 0xFF: moves[..] & OMOK_MOVE_CELL = the cell (N*N <= 225) */
+#define OMOK_MOVE_EXTERNAL 256  /* 0x100: the move was not sampled from the mover's own search */
+/* 1 = keep a move log from the next reset on (allocates 19 B per game and cell on first use), 0 = stop and free.  Changes no result.  Every
+ * successful omok_selfplay_reset(_from) / omok_match_reset(_from) sets the log's start (its boards, or Environment::new(), environment/src/lib.rs:73-79) and the lengths to 0; a rejected
+ * reset and a rejected omok_play_actions leave it as it was.  omok_selfplay_run_slots returns OMOK_ERR_STATE while the log is on (its games
+ * leave their slots). */
+int omok_game_log_enable(omok_engine* e, int32_t enabled);
+/* games [first_game, first_game + games): start_boards [games][N*N] Stone bytes, lengths [games] = moves since the reset (the game's plies - the
+ * ply the episode started at), moves [games][N*N] (entries at and beyond the length read 0xFFFF), root_n, root_w, child_n, child_w [games][N*N]
+ * (0 beyond the length); w in the perspective Node::propagate gives it (mcts/src/node.rs:83-99).  Every output may be NULL.  One synchronisation, one copy per array.
+ * OMOK_ERR_STATE while the log is off or before the first reset with it on; OMOK_ERR_INVALID for a range outside [0, G]. */
+int omok_game_log_read(omok_engine* e, int32_t first_game, int32_t games, uint8_t* start_boards, int32_t* lengths, uint16_t* moves,
+                       uint32_t* root_n, float* root_w, uint32_t* child_n, float* child_w);
+/* Batched replay on caller-held data (touches no engine state, needs no net; like omok_env_check_positions): from start_boards [batch][N*N]
+ * (NULL: Environment::new()) play moves[b][0 .. min(lengths[b], upto)) (upto < 0: all; cell = word & OMOK_MOVE_CELL; moves [batch][stride])
+ * by Environment::place_stone (environment/src/lib.rs:104-166), side to move = stones & 1.  Stops in front of the first move that is illegal
+ * (occupied, or cell >= N*N) and after a move that ends the game.  played_out[b] = moves placed, status_out[b] = GameStatus after the last
+ * one (0 if none), boards_out [batch][N*N] the position reached.  A start board whose omok_env_check_positions verdict v is not 0:
+ * played_out = -v, status_out = -1, board copied unchanged.  Outputs may be NULL.  batch >= 1, stride >= 1 and 0 <= lengths[b] <= stride,
+ * else OMOK_ERR_INVALID. */
+int omok_env_replay(omok_engine* e, const uint8_t* start_boards, const uint16_t* moves, const int32_t* lengths, int32_t batch,
+                    int32_t stride, int32_t upto, uint8_t* boards_out, int32_t* status_out, int32_t* played_out);
 /* replay tuples of all games packed on the device for an RCCL gather: record = board u8[N*N],
  * turn u8, zero pad to 4, pi f32[N*N], z f32; games in id order, transitions in play order (the same bytes on every run).
  * Writes at most cap_records to dst_dev (a device pointer the caller owns, e.g. a torch tensor) and returns the record

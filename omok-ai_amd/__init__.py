@@ -8,4 +8,5 @@ from . import dist  # noqa: F401
 from . import precision  # noqa: F401
 from . import model_file  # noqa: F401
 from . import match  # noqa: F401
+from . import records  # noqa: F401
 from .api import Engine, Environment, SelfPlay  # noqa: F401

@@ -14,6 +14,8 @@ Names follow the reference so parity tests read like its own code:
   SelfPlay.reset_from / analyze    Agent::new (agent.rs:16-35) on given positions instead of Environment::new()
   SelfPlay.match_reset_from        the match of benchmark/src/main.rs from given positions (an opening book), each agent with its own net
   Environment.random_positions     an opening book without a file: positions after s plies of _play_against_random_player's moves on both sides
+  SelfPlay.game_log / game_records every move of an episode with the mover's search statistics (the reference keeps sampled Transitions only, trainer.rs:169-173)
+  Engine.env_replay                Environment::place_stone move by move over a batch of records: a record back into a position
 All compute happens in the HIP library; nothing here has a CPU path.
 """
 import ctypes as C
@@ -252,6 +254,25 @@ class Engine:
                                                     B.u8ptr(boards), B.u8ptr(ok)))
         return boards, ok
 
+    def env_replay(self, start_boards, moves, lengths, upto=-1):
+        """omok_env_replay on caller-held records: from start_boards [B][HW] (None: empty boards) the moves moves[b][: min(lengths[b], upto)]
+        (upto < 0: all; uint16 words, cell = word & 0xFF) by Environment::place_stone, stopping in front of the first illegal move and after a
+        move that ends the game.  Returns (boards uint8 [B][HW], status int32 [B], played int32 [B]); a start board with a non-zero
+        env_check_positions verdict v comes back unchanged with status -1 and played -v."""
+        moves = np.ascontiguousarray(moves, dtype=np.uint16)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        batch = len(lengths)
+        moves = moves.reshape(batch, -1)
+        start = None
+        if start_boards is not None:
+            start = np.ascontiguousarray(start_boards, dtype=np.uint8).reshape(batch, self.hw)
+        boards = np.zeros((batch, self.hw), dtype=np.uint8)
+        status = np.zeros(batch, dtype=np.int32)
+        played = np.zeros(batch, dtype=np.int32)
+        self._chk(B.lib().omok_env_replay(self.h, None if start is None else B.u8ptr(start), moves.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                          B.iptr(lengths), batch, moves.shape[1], int(upto), B.u8ptr(boards), B.iptr(status), B.iptr(played)))
+        return boards, status, played
+
     def encode_nn_input(self, boards, turns, mode=B.MODE_PLAYER):
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
         turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
@@ -438,6 +459,29 @@ class SelfPlay:
         plies = np.zeros(self.games, dtype=np.int32)
         self._chk(B.lib().omok_game_info(self.h, B.u8ptr(alive), B.u8ptr(status), B.iptr(plies)))
         return alive, status, plies
+
+    def game_log(self, on=True):
+        """omok_game_log_enable: True = keep a move log from the next reset on (19 B per game and cell, allocated now), False = stop and free.
+        Changes no result; run_slots refuses while it is on."""
+        self._chk(B.lib().omok_game_log_enable(self.h, int(bool(on))))
+
+    def game_records(self, first_game=0, games=None, meta=None):
+        """the move log of games [first_game, first_game + games) since the last reset (omok_game_log_read) with their status and plies
+        (omok_game_info) as a records.GameRecords"""
+        from . import records as R
+        games = self.games - first_game if games is None else int(games)
+        rows = max(games, 0)  # (a range the library rejects is left to the library)
+        u32p = C.POINTER(C.c_uint32)
+        start = np.zeros((rows, self.hw), dtype=np.uint8)
+        lengths = np.zeros(rows, dtype=np.int32)
+        moves = np.zeros((rows, self.hw), dtype=np.uint16)
+        root_n, child_n = np.zeros((rows, self.hw), dtype=np.uint32), np.zeros((rows, self.hw), dtype=np.uint32)
+        root_w, child_w = np.zeros((rows, self.hw), dtype=np.float32), np.zeros((rows, self.hw), dtype=np.float32)
+        self._chk(B.lib().omok_game_log_read(self.h, int(first_game), games, B.u8ptr(start), B.iptr(lengths), moves.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                             root_n.ctypes.data_as(u32p), B.fptr(root_w), child_n.ctypes.data_as(u32p), B.fptr(child_w)))
+        _, status, plies = self.game_info()
+        return R.GameRecords.from_log(self.n, start, lengths, moves, root_n, root_w, child_n, child_w,
+                                      status[first_game:first_game + games], plies[first_game:first_game + games], meta)
 
     def execute(self, count, batch_size, epsilon=0.25, alpha=0.03):
         self._chk(B.lib().omok_execute(self.h, count, batch_size, epsilon, alpha))

@@ -45,6 +45,7 @@ SYMBOLS = [
     "omok_train_begin", "omok_train_end", "omok_train_step", "omok_train_losses", "omok_train_batch_indices", "omok_train_run",
     "omok_train_gradient_count", "omok_train_backward", "omok_train_apply",
     "omok_debug_train_gradient", "omok_net_read",
+    "omok_game_log_enable", "omok_game_log_read", "omok_env_replay",
 ]
 
 
@@ -170,6 +171,10 @@ def lib():
     L.omok_train_apply.argtypes = [H, C.c_void_p, C.c_int32, fp]
     L.omok_debug_train_gradient.argtypes = [H, C.c_int32, fp, C.c_int64]
     L.omok_net_read.argtypes = [H, C.c_int32, fp, C.c_int64]
+    u16p, u32p = C.POINTER(C.c_uint16), C.POINTER(C.c_uint32)
+    L.omok_game_log_enable.argtypes = [H, C.c_int32]
+    L.omok_game_log_read.argtypes = [H, C.c_int32, C.c_int32, u8p, ip, u16p, u32p, fp, u32p, fp]
+    L.omok_env_replay.argtypes = [H, u8p, u16p, ip, C.c_int32, C.c_int32, C.c_int32, u8p, ip, ip]
     _lib = L
     return L
 

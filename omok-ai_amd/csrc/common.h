@@ -119,6 +119,22 @@ void launch_random_positions(int n, uint64_t key, int64_t first_game, int stones
 // boards_dev [B][HW] bytes -> verdict_dev [B] (0 legal and in progress, 1 bad byte, 2 impossible stone counts, 3 already won, 4 full board),
 // stones_dev [B] (may be NULL)
 void launch_position_check(int n, const uint8_t* boards_dev, int batch, int32_t* verdict_dev, int32_t* stones_dev, hipStream_t st);
+// The move log of an engine (omok_game_log_enable): one allocation, [G][HW] each; entry i of game g = its move number i since the reset.
+// Not part of Store: the kernels that exist without the log keep their arguments.
+struct GameLog {
+    uint32_t* root_n;     // TreeState::root_n / root_w of the mover's tree when the move was made
+    float* root_w;
+    uint32_t* child_n;    // the root table's entry of the chosen cell (0 / 0.0f: the tree did not hold the move)
+    float* child_w;
+    uint16_t* move;       // cell | 0x100 if the move was external (GameState::external)
+    uint8_t* start_board; // Stone bytes of the position the episode started at
+};
+// entry gs.plies - start_ply of every game launch_advance is about to advance, read from the tree of `side` BEFORE ensure_action_exists
+void launch_log_move(int n, const Store& S, int side, int start_ply, const GameLog& L, hipStream_t st);
+// omok_env_replay: start_dev [B][HW] (NULL: empty boards) with their launch_position_check verdicts (NULL iff start_dev is), moves_dev [B][stride],
+// lengths_dev [B] -> boards_out [B][HW], status_out [B], played_out [B] (each may be NULL)
+void launch_replay(int n, const uint8_t* start_dev, const int32_t* verdict_dev, const uint16_t* moves_dev, const int32_t* lengths_dev, int batch, int stride,
+                   int upto, uint8_t* boards_out, int32_t* status_out, int32_t* played_out, hipStream_t st);
 // root_n / root_w of the trees of `side` of every game (0 for finished games)
 void launch_root_stats(const Store& S, int side, uint32_t* n_dev, float* w_dev, hipStream_t st);
 // slots mode (omok_selfplay_run_slots): finished games are packed out (records appended at *out_count, per-game meta by game index) and their

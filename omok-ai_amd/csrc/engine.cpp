@@ -111,6 +111,11 @@ struct omok_engine {
     unsigned long long* d_mevals = nullptr; // [2] rows evaluated by net 1 / net 2 in match episodes
     float* d_root_policy2 = nullptr;
     Train* train = nullptr;             // buffers and optimizer state of the native training step (omok_train_begin .. omok_train_end)
+    // move log (omok_game_log_enable): allocated on the first enable, freed by a disable
+    bool log_on = false;
+    bool log_started = false;           // a reset has set the log's start since it was enabled: moves are logged, omok_game_log_read answers
+    void* log_mem = nullptr;            // the one allocation GameLog points into
+    GameLog log{};
     // host-side stats
     double sims = 0, evals = 0, ply_games = 0, finished = 0;
     uint32_t peak_nodes = 0, peak_tables = 0;
@@ -201,6 +206,7 @@ extern "C" void omok_destroy(omok_engine* e) {
     net_free(e->net);
     if (e->net2) { net_free(*e->net2); delete e->net2; }
     if (e->train) { train_free(*e->train); delete e->train; }
+    if (e->log_mem) hipFree(e->log_mem);
     for (void* p : e->allocs) hipFree(p);
     if (e->st) hipStreamDestroy(e->st);
     delete e;
@@ -860,8 +866,10 @@ static int reset_episode(omok_engine* e, bool match, int split) {
     if (match && enqueue_root_policy(e, *e->net2, e->d_root_policy2)) return OMOK_ERR_HIP;
     launch_reset(e->n, e->S, e->d_root_policy, e->st);
     if (match) launch_match_roots(e->n, e->S, e->d_root_policy2, split, e->st);
+    if (e->log_on) hipMemsetAsync(e->log.start_board, 0, (size_t)e->cfg.games * e->hw, e->st); // the log starts at Environment::new()
     invalidate_nets(e);
     if (sync_and_check(e, match ? "match_reset" : "selfplay_reset")) return OMOK_ERR_HIP;
+    e->log_started = e->log_on;
     e->key = e->cfg.seed + e->episode * 0x9E3779B97F4A7C15ULL; // a fresh RNG stream per episode (the reference draws thread_rng anew, trainer.rs:71-93)
     e->episode += 1;
     e->ply = 0;
@@ -972,6 +980,7 @@ static int reset_from_positions(omok_engine* e, const uint8_t* boards, bool matc
     e->prof.begin(PC_PLY, e->st);
     launch_reset_from(e->n, e->S, d_boards, e->net.p, match ? e->net2->p : nullptr, split, e->st);
     e->prof.end(e->st);
+    if (e->log_on) hipMemcpyAsync(e->log.start_board, d_boards, (size_t)G * e->hw, hipMemcpyDeviceToDevice, e->st); // the log starts at the given positions
     invalidate_nets(e);
     const int rc = sync_and_check(e, what);
     hipFree(d_turns);
@@ -981,6 +990,7 @@ static int reset_from_positions(omok_engine* e, const uint8_t* boards, bool matc
     e->episode += 1;
     e->ply = s0; // a game's ply is its stone count: side = ply & 1, the RNG counters
     e->start_ply = s0;
+    e->log_started = e->log_on;
     e->reset_done = true;
     e->sampled = false;
     e->round_reqs = e->mirror_reqs = -1;
@@ -1261,6 +1271,12 @@ extern "C" int omok_sample_actions(omok_engine* e, float temperature, int32_t th
     return tree_error(e, bits);
 }
 
+// the move log's entry of this ply, directly in front of the re-rooting (k_advance) that forgets what the search knew of the move; nothing
+// is launched while the log is off
+static void enqueue_log_move(omok_engine* e, int side) {
+    if (e->log_on && e->log_started) launch_log_move(e->n, e->S, side, e->start_ply, e->log, e->st);
+}
+
 static void enqueue_mirror_and_advance(omok_engine* e, int alive) {
     const int side = e->ply & 1;
     e->prof.begin(PC_PLY, e->st);
@@ -1273,10 +1289,12 @@ static void enqueue_mirror_and_advance(omok_engine* e, int alive) {
             if (block_live(e, b)) match_forward(e, b, 1 - side, alive, -1, false);
         e->prof.begin(PC_PLY, e->st);
         match_join(e, 1 - side, true, alive);
+        enqueue_log_move(e, side);
         launch_advance(e->n, e->S, side, net_at(e, 1 - side).p, e->st);
     } else {
         net_forward_requests(e->net, e->S, alive, e->st, &e->prof);
         e->prof.begin(PC_PLY, e->st);
+        enqueue_log_move(e, side);
         launch_advance(e->n, e->S, side, e->net.p, e->st);
     }
     invalidate_nets(e);
@@ -1347,6 +1365,7 @@ extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int3
     if (no_match(e, "omok_selfplay_run_slots")) return OMOK_ERR_STATE;
     if (e->start_ply != 0) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots after omok_selfplay_reset_from: refilled slots would start from the empty board");
     if (e->ply != 0) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots starts from a fresh omok_selfplay_reset (ply %d)", e->ply);
+    if (e->log_on) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots with the move log on: its games leave their slots (omok_game_log_enable(e, 0) first)");
     ENTER(e);
     uint8_t* d_mask = nullptr;
     long long *d_slot_off = nullptr, *d_out = nullptr;
@@ -1807,8 +1826,12 @@ extern "C" int omok_mirror_apply(omok_engine* e) {
     if (read_status(e, &bits, &before)) return OMOK_ERR_HIP;
     if (e->match) {
         match_join(e, 1 - (e->ply & 1), true, e->cfg.games);
+        enqueue_log_move(e, e->ply & 1);
         launch_advance(e->n, e->S, e->ply & 1, net_at(e, 1 - (e->ply & 1)).p, e->st);
-    } else launch_advance(e->n, e->S, e->ply & 1, e->net.p, e->st);
+    } else {
+        enqueue_log_move(e, e->ply & 1);
+        launch_advance(e->n, e->S, e->ply & 1, e->net.p, e->st);
+    }
     invalidate_nets(e);
     if (read_status(e, &bits, &after)) return OMOK_ERR_HIP;
     e->ply_games += before;
@@ -1817,6 +1840,112 @@ extern "C" int omok_mirror_apply(omok_engine* e) {
     e->sampled = false;
     e->mirror_reqs = -1;
     return tree_error(e, bits);
+}
+
+// ---- game records: the move log and the batched replay ------------------------------------------------
+// One record per move of src/trainer.rs:95-205 / benchmark/src/main.rs:60-105 (the reference keeps the Transition of sampled moves only,
+// trainer.rs:169-173): allocated on the first enable, started by every successful reset, written by k_log_move in front of k_advance.
+extern "C" int omok_game_log_enable(omok_engine* e, int32_t enabled) {
+    if (!e) return OMOK_ERR_INVALID;
+    ENTER(e);
+    if (!enabled) {
+        if (e->log_mem) {
+            HIPCHK(e, hipStreamSynchronize(e->st));
+            hipFree(e->log_mem);
+            e->bytes -= (size_t)e->cfg.games * e->hw * 19;
+        }
+        e->log_mem = nullptr;
+        e->log = GameLog{};
+        e->log_on = e->log_started = false;
+        return OMOK_OK;
+    }
+    if (e->log_on) return OMOK_OK;
+    const size_t cells = (size_t)e->cfg.games * e->hw; // 4 + 4 + 4 + 4 + 2 + 1 = 19 B per cell, the widest arrays first: every one is aligned
+    hipError_t r = hipMalloc(&e->log_mem, cells * 19);
+    if (r != hipSuccess) { e->log_mem = nullptr; return fail(e, OMOK_ERR_HIP, "move log: hipMalloc(%zu bytes) failed: %s", cells * 19, hipGetErrorString(r)); }
+    uint8_t* p = (uint8_t*)e->log_mem;
+    e->log.root_n = (uint32_t*)p;
+    e->log.root_w = (float*)(p + cells * 4);
+    e->log.child_n = (uint32_t*)(p + cells * 8);
+    e->log.child_w = (float*)(p + cells * 12);
+    e->log.move = (uint16_t*)(p + cells * 16);
+    e->log.start_board = p + cells * 18;
+    e->bytes += cells * 19;
+    e->log_on = true;
+    e->log_started = false; // from the next reset on
+    return OMOK_OK;
+}
+
+extern "C" int omok_game_log_read(omok_engine* e, int32_t first_game, int32_t games, uint8_t* start_boards, int32_t* lengths, uint16_t* moves,
+                                  uint32_t* root_n, float* root_w, uint32_t* child_n, float* child_w) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (!e->log_on) return fail(e, OMOK_ERR_STATE, "the move log is off (omok_game_log_enable)");
+    if (!e->log_started) return fail(e, OMOK_ERR_STATE, "no reset since the move log was enabled: it starts at the next reset");
+    if (first_game < 0 || games < 0 || (int64_t)first_game + games > e->cfg.games)
+        return fail(e, OMOK_ERR_INVALID, "games [%d, %d + %d) outside [0, %d]", first_game, first_game, games, e->cfg.games);
+    if (games == 0) return OMOK_OK;
+    ENTER(e);
+    const size_t hw = (size_t)e->hw, off = (size_t)first_game * hw, cells = (size_t)games * hw;
+    std::vector<GameState> gs((size_t)games);
+    HIPCHK(e, hipMemcpyAsync(gs.data(), e->S.gs + first_game, sizeof(GameState) * gs.size(), hipMemcpyDeviceToHost, e->st));
+    if (start_boards) HIPCHK(e, hipMemcpyAsync(start_boards, e->log.start_board + off, cells, hipMemcpyDeviceToHost, e->st));
+    if (moves) HIPCHK(e, hipMemcpyAsync(moves, e->log.move + off, cells * 2, hipMemcpyDeviceToHost, e->st));
+    if (root_n) HIPCHK(e, hipMemcpyAsync(root_n, e->log.root_n + off, cells * 4, hipMemcpyDeviceToHost, e->st));
+    if (root_w) HIPCHK(e, hipMemcpyAsync(root_w, e->log.root_w + off, cells * 4, hipMemcpyDeviceToHost, e->st));
+    if (child_n) HIPCHK(e, hipMemcpyAsync(child_n, e->log.child_n + off, cells * 4, hipMemcpyDeviceToHost, e->st));
+    if (child_w) HIPCHK(e, hipMemcpyAsync(child_w, e->log.child_w + off, cells * 4, hipMemcpyDeviceToHost, e->st));
+    if (sync_and_check(e, "game_log_read")) return OMOK_ERR_HIP;
+    // a reset sets the lengths to 0 and leaves the arrays as they were: what lies at and beyond a game's length is blanked here
+    for (size_t g = 0; g < (size_t)games; ++g) {
+        int len = gs[g].plies - e->start_ply;
+        len = len < 0 ? 0 : (len > e->hw ? e->hw : len);
+        if (lengths) lengths[g] = len;
+        for (size_t i = g * hw + (size_t)len; i < (g + 1) * hw; ++i) {
+            if (moves) moves[i] = 0xFFFFu;
+            if (root_n) root_n[i] = 0u;
+            if (root_w) root_w[i] = 0.0f;
+            if (child_n) child_n[i] = 0u;
+            if (child_w) child_w[i] = 0.0f;
+        }
+    }
+    return OMOK_OK;
+}
+
+// Environment::place_stone (environment/src/lib.rs:104-166) move by move on caller-held records: touches no engine state, needs no net
+extern "C" int omok_env_replay(omok_engine* e, const uint8_t* start_boards, const uint16_t* moves, const int32_t* lengths, int32_t batch, int32_t stride,
+                               int32_t upto, uint8_t* boards_out, int32_t* status_out, int32_t* played_out) {
+    if (!e || !moves || !lengths) return OMOK_ERR_INVALID;
+    if (batch < 1) return fail(e, OMOK_ERR_INVALID, "batch %d < 1", batch);
+    if (stride < 1) return fail(e, OMOK_ERR_INVALID, "stride %d < 1", stride);
+    for (int b = 0; b < batch; ++b)
+        if (lengths[b] < 0 || lengths[b] > stride) return fail(e, OMOK_ERR_INVALID, "game %d: length %d outside [0, stride = %d]", b, lengths[b], stride);
+    ENTER(e);
+    const size_t B = (size_t)batch, hw = (size_t)e->hw;
+    uint8_t* d_start = nullptr;
+    std::vector<int32_t> host((size_t)2 * B); // verdicts | lengths
+    if (start_boards && check_positions(e, start_boards, batch, host.data(), nullptr, &d_start)) return OMOK_ERR_HIP;
+    memcpy(host.data() + B, lengths, B * 4);
+    // one allocation: verdicts, lengths, status, played (4 B each), moves (2 B), boards (1 B)
+    uint8_t* d = nullptr;
+    if (hipMalloc((void**)&d, B * 16 + B * stride * 2 + B * hw) != hipSuccess) {
+        if (d_start) hipFree(d_start);
+        return fail(e, OMOK_ERR_HIP, "env_replay: device allocation failed");
+    }
+    int32_t *d_verdict = (int32_t*)d, *d_len = d_verdict + B, *d_status = d_len + B, *d_played = d_status + B;
+    uint16_t* d_moves = (uint16_t*)(d + B * 16);
+    uint8_t* d_boards = d + B * 16 + B * stride * 2;
+    hipMemcpyAsync(d_verdict, host.data(), B * 8, hipMemcpyHostToDevice, e->st);
+    hipMemcpyAsync(d_moves, moves, B * stride * 2, hipMemcpyHostToDevice, e->st);
+    e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling: tools/game_log_timing.py)
+    launch_replay(e->n, d_start, d_start ? d_verdict : nullptr, d_moves, d_len, batch, stride, upto, d_boards, d_status, d_played, e->st);
+    e->prof.end(e->st);
+    if (boards_out) hipMemcpyAsync(boards_out, d_boards, B * hw, hipMemcpyDeviceToHost, e->st);
+    if (status_out) hipMemcpyAsync(status_out, d_status, B * 4, hipMemcpyDeviceToHost, e->st);
+    if (played_out) hipMemcpyAsync(played_out, d_played, B * 4, hipMemcpyDeviceToHost, e->st);
+    const int rc = sync_and_check(e, "env_replay");
+    hipFree(d);
+    if (d_start) hipFree(d_start);
+    return rc ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 // ---- inspection ----------------------------------------------------------------------------------

@@ -2120,6 +2120,103 @@ __global__ __launch_bounds__(64) void k_random_positions(uint64_t key, int64_t f
 }
 
 // ---------------------------------------------------------------------------------------------
+// game records (omok_game_log_enable / _read, omok_env_replay)
+// ---------------------------------------------------------------------------------------------
+// k_log_move: entry gs.plies - start_ply of the move log of every game k_advance is about to advance (the same condition: alive, a staged move).
+// Launched directly in front of k_advance, so the mover's tree is still rooted at the position the move was chosen in: root_n / root_w are
+// TreeState's (omok_root_stats), child_n / child_w the root table's entry of the cell (omok_root_children; 0 / 0.0f where the root has no table
+// or no child there -- ensure_action_exists has not run yet, so a move the tree does not hold logs what the search knew of it: nothing).
+// One thread per game; it reads the tree and writes the log only.
+template <int N>
+__global__ __launch_bounds__(256) void k_log_move(Store S, int side, int start_ply, GameLog L) {
+    using G = Geo<N>;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= S.games) return;
+    const GameState gs = S.gs[g];
+    if (!gs.alive || gs.last_action < 0) return;
+    const int i = gs.plies - start_ply, cell = gs.last_action;
+    if (i < 0 || i >= G::HW || cell >= G::HW) return; // (a legal game has at most HW - start_ply moves, all on the board)
+    const size_t t = (size_t)(side * S.games + g);
+    const TreeState ts = S.ts[t];
+    const NodeHdr h0 = S.hdr[t * (size_t)S.stride_nodes];
+    uint32_t cn = 0u;
+    float cw = 0.0f;
+    if (h0.table != NONE16) {
+        const size_t slot = (t * (size_t)S.stride_tables + h0.table) * G::ROWP + cell;
+        if (S.tcorder[slot] != NONE8) { cn = S.tcn[slot]; cw = S.tcw[slot]; }
+    }
+    const size_t o = (size_t)g * G::HW + i;
+    L.move[o] = (uint16_t)(cell | (gs.external ? 0x100 : 0));
+    L.root_n[o] = ts.root_n;
+    L.root_w[o] = ts.root_w;
+    L.child_n[o] = cn;
+    L.child_w[o] = cw;
+}
+
+// k_replay: a record back into a position (omok_env_replay).  From start board b (NULL: Environment::new()) the moves
+// moves[b][0 .. len) (cell = word & 0xFF), len = min(lengths[b], upto, stride), each by Environment::place_stone
+// (environment/src/lib.rs:104-166: place_and_status), side to move = stones & 1; it stops in front of the first illegal move (cell >= HW or
+// occupied) and after a move that ends the game.  verdict [B] = k_position_check's of the start boards (NULL with start == NULL): v != 0 ->
+// played = -v, status = -1, the bytes copied unchanged.  Workgroup = one wave = one game; the bitboards stay in registers, the moves are
+// loaded 64 at a time (one per lane) and handed round with v_readlane, so cell, status and every branch are wave-uniform; one byte store
+// of the board at the end.  Outputs may be NULL.
+template <int N>
+__global__ __launch_bounds__(64) void k_replay(const uint8_t* __restrict__ start, const int32_t* __restrict__ verdict, const uint16_t* __restrict__ moves,
+                                               const int32_t* __restrict__ lengths, int stride, int upto, uint8_t* __restrict__ boards_out,
+                                               int32_t* __restrict__ status_out, int32_t* __restrict__ played_out) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int b = blockIdx.x;
+    const int lane = LANE;
+    uint64_t bb[2 * NW];
+    int raw[G::IT]; // the start bytes as given: a rejected board goes out unchanged, whatever its bytes are
+    int stones = 0;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        raw[j] = (start && a < G::HW) ? start[(size_t)b * G::HW + a] : 0;
+        bb[j] = __ballot(raw[j] == 1);
+        bb[NW + j] = __ballot(raw[j] == 2);
+        stones += __popcll(bb[j]) + __popcll(bb[NW + j]);
+    }
+    const int v = verdict ? verdict[b] : 0;
+    int status = ST_IN_PROGRESS, played = 0;
+    if (v != 0) {
+        status = -1;
+        played = -v;
+    } else {
+        int len = lengths[b];
+        len = len < stride ? len : stride;
+        if (upto >= 0) len = len < upto ? len : upto;
+        bool stop = false;
+        for (int base = 0; base < len && !stop; base += 64) {
+            const int mine = base + lane < len ? (int)(moves[(size_t)b * stride + base + lane] & 0xFFu) : 0xFF;
+            const int cnt = len - base < 64 ? len - base : 64;
+            for (int j = 0; j < cnt && !stop; ++j) {
+                const int cell = __builtin_amdgcn_readlane(mine, j);
+                if (cell >= G::HW || get_bit<NW>(bb, cell) || get_bit<NW>(bb + NW, cell)) { stop = true; break; }
+                status = place_and_status<N>(bb, stones & 1, G::HW - stones, cell);
+                stones += 1;
+                played += 1;
+                stop = status != ST_IN_PROGRESS;
+            }
+        }
+    }
+    if (boards_out) {
+#pragma unroll
+        for (int j = 0; j < G::IT; ++j) {
+            const int a = j * 64 + lane;
+            const int s = ((bb[j] >> lane) & 1ULL) ? 1 : (((bb[NW + j] >> lane) & 1ULL) ? 2 : 0);
+            if (a < G::HW) boards_out[(size_t)b * G::HW + a] = (uint8_t)(v != 0 ? raw[j] : s);
+        }
+    }
+    if (lane == 0) {
+        if (status_out) status_out[b] = status;
+        if (played_out) played_out[b] = played;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_mirror_scan: NN requests of ensure_action_exists (agent.rs:153-158) for every live game
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_mirror_scan(Store S, int side) {
@@ -2727,6 +2824,15 @@ void launch_random_positions(int n, uint64_t key, int64_t first_game, int stones
 }
 void launch_position_check(int n, const uint8_t* boards, int batch, int32_t* verdict, int32_t* stones, hipStream_t st) {
     DISPATCH_N(n, (k_position_check<9><<<batch, 64, 0, st>>>(boards, verdict, stones)), (k_position_check<15><<<batch, 64, 0, st>>>(boards, verdict, stones)));
+}
+void launch_log_move(int n, const Store& S, int side, int start_ply, const GameLog& L, hipStream_t st) {
+    const int blocks = (S.games + 255) / 256;
+    DISPATCH_N(n, (k_log_move<9><<<blocks, 256, 0, st>>>(S, side, start_ply, L)), (k_log_move<15><<<blocks, 256, 0, st>>>(S, side, start_ply, L)));
+}
+void launch_replay(int n, const uint8_t* start, const int32_t* verdict, const uint16_t* moves, const int32_t* lengths, int batch, int stride, int upto,
+                   uint8_t* boards_out, int32_t* status_out, int32_t* played_out, hipStream_t st) {
+    DISPATCH_N(n, (k_replay<9><<<batch, 64, 0, st>>>(start, verdict, moves, lengths, stride, upto, boards_out, status_out, played_out)),
+               (k_replay<15><<<batch, 64, 0, st>>>(start, verdict, moves, lengths, stride, upto, boards_out, status_out, played_out)));
 }
 void launch_root_stats(const Store& S, int side, uint32_t* n_dev, float* w_dev, hipStream_t st) {
     k_root_stats<<<(S.games + 255) / 256, 256, 0, st>>>(S, side, n_dev, w_dev);

@@ -41,6 +41,7 @@ def parse_args(argv=None):
     ap.add_argument("--openings", metavar="FILE.npy", help="opening book [M][HW] Stone bytes (equal stone counts), M = games / 2: each opening is played "
                     "twice, once with each net as Black")
     ap.add_argument("--random-openings", type=int, metavar="S", help="the same with games / 2 random positions of S stones made on the device from --seed")
+    ap.add_argument("--save-games", metavar="FILE.npz", help="keep the move log and write every game's record there (python -m omok_ai_amd.records show FILE.npz --game i)")
     return ap.parse_args(argv)
 
 
@@ -78,11 +79,14 @@ def random_openings(eng, key, stones, count, chunk=None):
     return np.concatenate(kept)[:count]
 
 
-def run_match(eng, games, sims, batch, threshold=0, temperature=1.0, openings=None):
+def run_match(eng, games, sims, batch, threshold=0, temperature=1.0, openings=None, save_games=None, meta=None):
     """One match episode on an engine whose two net slots are loaded; returns (wins, losses, draws, status [G], stats).  openings [M][HW]
-    (the engine has games = 2 M): games i and i + M start from opening i, the first net Black in the first half (split = M)."""
+    (the engine has games = 2 M): games i and i + M start from opening i, the first net Black in the first half (split = M).  save_games: a
+    path = the move log is kept for this episode and the games' records (records.GameRecords, with `meta` and the split) written there."""
     sp = api.SelfPlay(eng)
     split = games // 2
+    if save_games is not None:
+        sp.game_log(True)
     if openings is None:
         sp.match_reset(split)
     else:
@@ -95,6 +99,9 @@ def run_match(eng, games, sims, batch, threshold=0, temperature=1.0, openings=No
     if alive.any():
         raise RuntimeError(f"{int(alive.sum())} game(s) still in progress after the match")
     w, l, d = tally(status, split)
+    if save_games is not None:
+        sp.game_records(meta=dict(meta or {}, kind="match", split=split, sims=sims, batch=batch, threshold=threshold)).save(save_games)
+        sp.game_log(False)
     return w, l, d, status, stats
 
 
@@ -116,7 +123,9 @@ def main(argv=None):
             openings = np.load(a.openings)
         elif a.random_openings is not None:
             openings = random_openings(eng, a.seed, a.random_openings, a.games // 2)
-        w, l, d, status, stats = run_match(eng, a.games, a.sims, a.batch, a.threshold, a.temperature, openings=openings)
+        meta = {"net1": a.net1, "net2": a.net2, "seed": a.seed, "board": a.board,
+                "openings": a.openings if a.openings is not None else (f"random:{a.random_openings}" if a.random_openings is not None else None)}
+        w, l, d, status, stats = run_match(eng, a.games, a.sims, a.batch, a.threshold, a.temperature, openings=openings, save_games=a.save_games, meta=meta)
         info = eng.net2_info()
     finally:
         eng.close()

@@ -1,0 +1,159 @@
+"""Game records: every move of an episode with what the mover's search knew of it, replayable.
+
+The reference keeps a Transition for the moves its trainer sampled (src/trainer.rs:169-173) and only counts the results of its evaluation
+games and matches (trainer.rs:400-603, benchmark/src/main.rs:60-105).  A GameRecords holds what the engine's move log kept of a batch of games
+(SelfPlay.game_log / game_records; include/omok_mi355x.h "game records"): the start position, every move with its `external` flag, and the
+root and chosen-child statistics of the mover's tree at the moment of the move.  Replaying goes through the engine's rules kernel
+(Engine.env_replay), never through a restatement of the rules here.
+
+    python -m omok_ai_amd.records show FILE.npz --game 3
+"""
+import argparse
+import json
+
+import numpy as np
+
+CELL_MASK, EXTERNAL = 0xFF, 0x100  # OMOK_MOVE_CELL, OMOK_MOVE_EXTERNAL
+STATUS_NAMES = {0: "in progress", 1: "draw", 2: "black wins", 3: "white wins"}
+_ARRAYS = ("start_boards", "lengths", "cells", "external", "root_n", "root_w", "child_n", "child_w", "status", "plies")
+
+
+class GameRecords:
+    """board size n; per game g: start_boards [G][HW] Stone bytes, lengths [G] moves since the start, cells int16 [G][HW] (-1 beyond the
+    length), external bool [G][HW], root_n uint32 / root_w float32 / child_n uint32 / child_w float32 [G][HW] (0 beyond the length), status
+    uint8 [G] and plies int32 [G] (omok_game_info: GameStatus, stones on the board); meta: a free dict (JSON-serialisable)."""
+
+    def __init__(self, n, start_boards, lengths, cells, external, root_n, root_w, child_n, child_w, status, plies, meta=None):
+        self.n, self.hw = int(n), int(n) * int(n)
+        g = len(lengths)
+        self.start_boards = np.ascontiguousarray(start_boards, dtype=np.uint8).reshape(g, self.hw)
+        self.lengths = np.ascontiguousarray(lengths, dtype=np.int32).reshape(g)
+        self.cells = np.ascontiguousarray(cells, dtype=np.int16).reshape(g, self.hw)
+        self.external = np.ascontiguousarray(external, dtype=bool).reshape(g, self.hw)
+        self.root_n = np.ascontiguousarray(root_n, dtype=np.uint32).reshape(g, self.hw)
+        self.root_w = np.ascontiguousarray(root_w, dtype=np.float32).reshape(g, self.hw)
+        self.child_n = np.ascontiguousarray(child_n, dtype=np.uint32).reshape(g, self.hw)
+        self.child_w = np.ascontiguousarray(child_w, dtype=np.float32).reshape(g, self.hw)
+        self.status = np.ascontiguousarray(status, dtype=np.uint8).reshape(g)
+        self.plies = np.ascontiguousarray(plies, dtype=np.int32).reshape(g)
+        self.meta = dict(meta or {})
+
+    @classmethod
+    def from_log(cls, n, start_boards, lengths, moves, root_n, root_w, child_n, child_w, status, plies, meta=None):
+        """from the arrays of omok_game_log_read: moves uint16 [G][HW], cell | 0x100 if external, 0xFFFF beyond the length"""
+        moves = np.asarray(moves, dtype=np.uint16)
+        lengths = np.asarray(lengths, dtype=np.int32).reshape(-1)
+        played = np.arange(moves.shape[1])[None, :] < lengths[:, None]
+        cells = np.where(played, (moves & CELL_MASK).astype(np.int16), np.int16(-1))
+        external = played & ((moves & EXTERNAL) != 0)
+        return cls(n, start_boards, lengths, cells, external, root_n, root_w, child_n, child_w, status, plies, meta)
+
+    games = property(lambda s: len(s.lengths))
+
+    def moves(self):
+        """the uint16 words of omok_game_log_read / omok_env_replay: cell | 0x100 if external, 0xFFFF beyond the length"""
+        words = (self.cells.astype(np.int32) & CELL_MASK) | np.where(self.external, EXTERNAL, 0)
+        return np.where(self.cells >= 0, words, 0xFFFF).astype(np.uint16)
+
+    def __eq__(self, other):
+        """every array bit for bit (the floats compared as their words) and the metadata"""
+        if not isinstance(other, GameRecords) or self.n != other.n or self.meta != other.meta:
+            return False
+        for name in _ARRAYS:
+            a, b = getattr(self, name), getattr(other, name)
+            if a.dtype != b.dtype or a.shape != b.shape or a.tobytes() != b.tobytes():
+                return False
+        return True
+
+    # ---- file ------------------------------------------------------------------------------------
+    def save(self, path):
+        """one .npz: the arrays, the board size and the metadata as JSON text"""
+        with open(path, "wb") as f:
+            np.savez_compressed(f, n=np.int32(self.n), meta=np.array(json.dumps(self.meta, sort_keys=True)),
+                                **{name: getattr(self, name) for name in _ARRAYS})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls(int(z["n"]), *[z[name] for name in _ARRAYS], meta=json.loads(str(z["meta"])))
+
+    # ---- replay (the engine's rules kernel) -------------------------------------------------------
+    def position_at(self, game, ply, engine):
+        """Stone bytes [HW] of game `game` after its first `ply` moves (0: the start position), through Engine.env_replay"""
+        assert 0 <= ply <= int(self.lengths[game])
+        boards, _, played = engine.env_replay(self.start_boards[game][None], self.moves()[game][None], self.lengths[game:game + 1], upto=int(ply))
+        assert int(played[0]) == ply, f"game {game}: the record stops being legal at move {int(played[0])}"
+        return boards[0]
+
+    def verify(self, engine):
+        """Replays every game and raises AssertionError unless, for each: every recorded move was placed (played == length), the replay's
+        GameStatus is the recorded one (in progress for an unfinished game) and the stones on the final board are the start's plus the
+        length -- which is also what omok_game_info counted (plies).  Returns the final boards [G][HW]."""
+        assert engine.n == self.n, f"records of board size {self.n}, engine of {engine.n}"
+        boards, status, played = engine.env_replay(self.start_boards, self.moves(), self.lengths)
+        stones = np.count_nonzero(boards, axis=1)
+        start = np.count_nonzero(self.start_boards, axis=1)
+        for g in range(self.games):
+            assert int(played[g]) == int(self.lengths[g]), f"game {g}: {int(played[g])} of {int(self.lengths[g])} moves replay"
+            assert int(status[g]) == int(self.status[g]), f"game {g}: replay ends with status {int(status[g])}, recorded {int(self.status[g])}"
+            assert int(stones[g]) == int(start[g]) + int(self.lengths[g]), f"game {g}: {int(stones[g])} stones after {int(start[g])} + {int(self.lengths[g])}"
+            assert int(self.plies[g]) == int(stones[g]), f"game {g}: plies {int(self.plies[g])}, stones {int(stones[g])}"
+        return boards
+
+    # ---- text --------------------------------------------------------------------------------------
+    def coordinate(self, cell):
+        """column letter (a = x 0) and row number (1 = y 0) of cell = y * n + x"""
+        return f"{chr(ord('a') + cell % self.n)}{cell // self.n + 1}"
+
+    def to_text(self, game):
+        """The final board of game `game` with move numbers (X / O: stones of the start position, Black / White), then one line per move:
+        ply (stones on the board before it), colour, coordinate, `ext` for an external move (scripted or supplied, not sampled from the mover's
+        search), root_n, child_n and q = child_w / child_n where child_n > 0.
+
+        Whose perspective w has (read from backup() in csrc/tree_kernels.hip, Node::propagate, mcts/src/node.rs:83-99): a simulation's value
+        is added to the slot of the node it reached and its sign flips at every step up the path; a terminal child that its mover won receives
+        +1 in its own slot, an evaluated leaf minus the net's value for the side to move in it.  So child_w / child_n is the mean value of
+        the move FOR THE SIDE THAT MADE IT (+1: the mover wins), and root_w, one step further up, has the other sign: root_w / root_n is the
+        mean value of the position for the mover's OPPONENT.  The board is the moves as recorded: no rule is applied here (verify does that)."""
+        n, length = self.n, int(self.lengths[game])
+        start = self.start_boards[game]
+        first = int(np.count_nonzero(start))
+        label = {c: {1: "X", 2: "O"}.get(int(s), "?") for c, s in enumerate(start) if s}
+        for i in range(length):
+            label.setdefault(int(self.cells[game, i]), str(i + 1))
+        width = max(3, len(str(length)) + 1)
+        out = [f"game {game}: {n} x {n}, {first} stones at the start, {length} moves, {STATUS_NAMES.get(int(self.status[game]), '?')}"]
+        out.append(" " * 3 + "".join(f"{chr(ord('a') + x):>{width}}" for x in range(n)))
+        for y in range(n):
+            out.append(f"{y + 1:>3}" + "".join(f"{label.get(y * n + x, '.'):>{width}}" for x in range(n)))
+        out.append("move  ply colour cell ext   root_n  child_n        q")
+        for i in range(length):
+            cell, cn = int(self.cells[game, i]), int(self.child_n[game, i])
+            q = f"{float(self.child_w[game, i]) / cn:+.4f}" if cn > 0 else "-"
+            out.append(f"{i + 1:>4} {first + i:>4} {'black' if (first + i) % 2 == 0 else 'white':>6} {self.coordinate(cell):>4} "
+                       f"{'ext' if self.external[game, i] else '':>3} {int(self.root_n[game, i]):>8} {cn:>8} {q:>8}")
+        return "\n".join(out)
+
+
+save = GameRecords.save
+load = GameRecords.load
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="omok_ai_amd.records", description="game records written by match.py --save-games / Trainer.evaluate(save_games=...)")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    show = sub.add_parser("show", help="print one game: the final board with move numbers and one line per move")
+    show.add_argument("file")
+    show.add_argument("--game", type=int, default=0)
+    args = ap.parse_args(argv)
+    rec = load(args.file)
+    if not 0 <= args.game < rec.games:
+        ap.error(f"--game {args.game} outside [0, {rec.games})")
+    if rec.meta:
+        print("meta: " + json.dumps(rec.meta, sort_keys=True))
+    print(rec.to_text(args.game))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

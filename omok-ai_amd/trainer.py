@@ -200,13 +200,15 @@ class Trainer:
                 f"[v_loss={v_loss:.4f}, p_loss={p_loss:.4f}]" + versus)
         return v_loss, p_loss, loss
 
-    def evaluate(self, openings=None):
+    def evaluate(self, openings=None, save_games=None):
         """play_against_naive_player (src/trainer.rs:487-603) with the weights just saved: `evaluate_games` games on an engine of its own
         (arenas sized for `test_evaluate_count`), the scripted naive player is Black and moves first, the net answers as White with
         `test_evaluate_count` simulations and sample_action(Best).  The reference prints Black's wins as "Win" although Black is the naive
         player (:387-393); train() logs the three counts by colour, on the iteration's line.  openings: None = every game from the empty board
         like the reference, or [evaluate_games, HW] Stone bytes = the position each game starts from (equal stone counts; the side the stone
-        count gives moves first, the naive player stays Black).  Returns (black_win, white_win, draw)."""
+        count gives moves first, the naive player stays Black).  save_games: a path = the games' records (records.GameRecords: every move, the
+        naive player's marked external, with the net's root and chosen-child statistics) are written there as one .npz; None = no move log is
+        kept.  Returns (black_win, white_win, draw)."""
         p = self.p
         sims = -(-p.test_evaluate_count // p.evaluate_batch_size) * p.evaluate_batch_size
         max_nodes = min(16384, 4 * sims + 1024)
@@ -216,11 +218,17 @@ class Trainer:
             eng.load(os.path.join(self.save_dir, p.model_name))
             sp = api.SelfPlay(eng)
             sp.set_episode(self.iteration - 1)
+            if save_games is not None:
+                sp.game_log(True)
             if openings is None:
                 sp.reset()
             else:
                 sp.reset_from(np.ascontiguousarray(openings, dtype=np.uint8).reshape(p.evaluate_games, self.n * self.n))
             (black, white, draw), _ = sp.versus_run(api.B.OPP_NAIVE, 0, p.test_evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha)
+            if save_games is not None:
+                sp.game_records(meta={"kind": "evaluate", "net": os.path.join(self.save_dir, p.model_name), "iteration": self.iteration,
+                                      "opponent": "naive", "opponent_side": 0, "sims": p.test_evaluate_count, "batch": p.evaluate_batch_size,
+                                      "seed": self.seed + 1, "openings": openings is not None}).save(save_games)
         finally:
             eng.close()
         self.last_evaluation = {"iteration": self.iteration, "games": p.evaluate_games, "black_win": black, "white_win": white, "draw": draw}
