@@ -105,6 +105,11 @@ struct RoundArgs {
     uint64_t seed; // Philox key of the current episode: cfg.seed + episode * 0x9E3779B97F4A7C15 (DESIGN.md "RNG contract")
     int64_t game_offset;
     const float* scatter_v; // non-NULL: the PREVIOUS round's backups (k_scatter with these values) run at the head of this round's kernel
+    // run-loop rounds on the sibling path (no k_scan: the net's k_group derives the request offsets itself): req_cnt[g] = the game's requests of this round
+    // (0 for a finished game), and workgroup 0 zeroes zero_ptr[0 .. zero_n) (the grouping counters the round's forward expects zeroed).  NULL: neither.
+    int32_t* req_cnt;
+    int32_t* zero_ptr;
+    int zero_n;
 };
 
 // ---- tree_kernels.hip launchers (all asynchronous on `st`) ---------------------------------

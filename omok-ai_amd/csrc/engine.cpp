@@ -93,6 +93,7 @@ struct omok_engine {
     int32_t* d_actions = nullptr;
     uint32_t* d_error = nullptr; // [0] error bits, [1] alive count
     unsigned long long* d_evals = nullptr;
+    int32_t* d_req_cnt = nullptr;       // [G] requests of every game in the current round (k_round -> k_group: run-loop rounds on the sibling path)
     uint16_t* d_sh_req = nullptr;       // [MAX_TREE_WAVES][KMAX] requests of the waves of a shared-tree round group
     uint32_t* d_sh_cnt = nullptr;       // [2 * KMAX] their counts | first-request offsets
     uint32_t* d_flags = nullptr;        // [0] illegal external moves, [1] live games without a move (omok_play_actions)
@@ -302,6 +303,7 @@ extern "C" int omok_create(const omok_config* cfg, omok_engine** out) {
     rc |= dalloc(e, &e->d_actions, G);
     rc |= dalloc(e, &e->d_error, 4);
     rc |= dalloc(e, &e->d_evals, 2);
+    rc |= dalloc(e, &e->d_req_cnt, G);
     rc |= dalloc(e, &e->d_sh_req, (size_t)MAX_TREE_WAVES * KMAX);
     rc |= dalloc(e, &e->d_sh_cnt, 2 * (size_t)KMAX);
     rc |= dalloc(e, &e->d_flags, 4);
@@ -1078,7 +1080,14 @@ static Net& backup_net(omok_engine* e, int side) { return e->match ? net_at(e, s
 static void enqueue_round(omok_engine* e, int round, int K, float eps, float alpha, bool eval_and_scatter, int alive, bool defer_backups = false,
                           bool pending_backups = false) {
     const int side = e->ply & 1;
-    RoundArgs a{side, round, K, e->ply, eps, alpha, e->key, e->cfg.game_offset, pending_backups ? backup_net(e, side).v : nullptr};
+    // run-loop rounds whose forward groups the requests by parent (sib_round): no k_scan and no k_fill.  k_round zeroes the grouping counters and leaves every
+    // game's request count; k_group derives the request offsets and the round's total from them and writes the dense request list.  The step-wise API and match
+    // episodes keep the separate kernels (the step-wise callers read the request list before the forward).
+    int max_req = alive * K;
+    if (max_req > e->net.max_b) max_req = e->net.max_b;
+    const bool sib_round = !e->match && eval_and_scatter && net_round_takes_sibling_path(e->net, max_req);
+    RoundArgs a{side, round, K, e->ply, eps, alpha, e->key, e->cfg.game_offset, pending_backups ? backup_net(e, side).v : nullptr,
+                sib_round ? e->d_req_cnt : nullptr, sib_round ? e->net.d_gcnt : nullptr, sib_round ? NET_GCNT_INTS : 0};
     e->prof.round_begin();
     e->prof.begin(PC_ROUND, e->st);
     launch_round(e->n, e->S, a, e->st);
@@ -1089,13 +1098,10 @@ static void enqueue_round(omok_engine* e, int round, int K, float eps, float alp
         e->prof.round_end();
         return;
     }
-    // run-loop rounds whose forward groups the requests by parent: k_scan zeroes the grouping counters, k_group writes the dense request list
-    // (two launches less per round); the step-wise API keeps the separate kernels (its callers read the request list before the forward)
-    int max_req = alive * K;
-    if (max_req > e->net.max_b) max_req = e->net.max_b;
-    const bool sib_round = eval_and_scatter && net_round_takes_sibling_path(e->net, max_req);
-    launch_scan(e->n, e->S, side, K, e->st, e->d_evals, sib_round ? e->net.d_gcnt : nullptr, NET_GCNT_INTS, !sib_round);
+    if (!sib_round) launch_scan(e->n, e->S, side, K, e->st, e->d_evals);
     e->net.gcnt_zeroed = e->net.fill_in_group = sib_round;
+    e->net.scan_cnt = sib_round ? e->d_req_cnt : nullptr;
+    e->net.scan_evals = e->d_evals;
     e->net.fill_side = side;
     e->net.fill_k = K;
     e->prof.end(e->st);
@@ -2172,7 +2178,7 @@ extern "C" int omok_debug_set_children_kernel(omok_engine* e, int32_t which) {
     return OMOK_OK;
 }
 
-// what the LAST forward of net 1 decided: the host's choices (Net::plan_*) + the counters k_group / k_bin_prefix left in d_gcnt (a sibling round's stay there until the
+// what the LAST forward of net 1 decided: the host's choices (Net::plan_*) + the counters k_group / bin_prefix_role left in d_gcnt (a sibling round's stay there until the
 // next round is generated)
 extern "C" int omok_debug_last_plan(omok_engine* e, int32_t* out, int32_t cap) {
     if (!e || !out || cap < 0) return OMOK_ERR_INVALID;
@@ -2240,7 +2246,7 @@ extern "C" int omok_get_stats(omok_engine* e, double* stats) {
     for (int i = 0; i < 9; ++i) stats[OMOK_STAT_PROBE_ROUND_FP6 + i] = e->net.probe[10 + i];
     stats[OMOK_STAT_PROBE_LOGIT_LIMIT] = NET_PROBE_LOGIT_LIMIT;
     stats[OMOK_STAT_PROBE_OUTSIDE] = (double)e->net.probe_outside;
-    if (e->net.d_work) { // executed-work counters of the sibling rounds (device side: k_group, k_bin_prefix)
+    if (e->net.d_work) { // executed-work counters of the sibling rounds (device side: k_group, bin_prefix_role)
         unsigned long long w[NET_WORK_COUNT];
         if (hipMemcpy(w, e->net.d_work, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return OMOK_ERR_HIP;
         for (int i = 0; i < 10; ++i) stats[OMOK_STAT_WORK_DIFF_RUNS + i] = (double)w[i];

@@ -58,7 +58,7 @@ struct Net {
     int32_t* d_singles = nullptr;
     void* d_sib_rows = nullptr; // (request row, run) of the rows inside runs
     int32_t* d_gcnt = nullptr;  // the sibling round's counters: [NET_GCNT_INTS], indexed by the NET_GCNT_* enum below
-    unsigned long long* d_work = nullptr; // [NET_WORK_COUNT] executed-work counters summed over the rounds since omok_reset_stats (k_group, k_bin_prefix add; only omok_get_stats reads)
+    unsigned long long* d_work = nullptr; // [NET_WORK_COUNT] executed-work counters summed over the rounds since omok_reset_stats (k_group, bin_prefix_role add; only omok_get_stats reads)
     float* sib_h = nullptr;     // [run][3 blocks][225][32] the base passes' depthwise inputs
     // difference path: a child's fc0 input = its run's base row + a 7x7-window difference row
     uint32_t* d_sib_slot = nullptr;  // per row inside a run: window bin << 24 | rank inside the bin
@@ -75,12 +75,16 @@ struct Net {
     float* facc = nullptr;           // [base_slots + max_b][512] fp32 fc0 rows: base slots, then the round's single rows
     int32_t* d_tags = nullptr;       // [games][2] (leaf node | slot << 16) of the bases in the game's slots (SIB_WAYS), most recently used first; -1 = none
     void* d_comp = nullptr;          // the round's positions to evaluate in full: (request row of the first child, base slot)
-    bool gcnt_zeroed = false;        // the engine's k_scan of this round has zeroed d_gcnt (launch_trunk_siblings then skips k_zero_ints)
-    bool fill_in_group = false;      // ... and left the dense request list to k_group (launch_scan(fill = false))
+    bool gcnt_zeroed = false;        // the engine's k_round of this round has zeroed d_gcnt (RoundArgs::zero_ptr; launch_trunk_siblings then skips k_zero_ints)
+    bool fill_in_group = false;      // ... and the engine left the dense request list to k_group (no k_fill)
     int fill_side = 0, fill_k = 0;   // ... for this side's trees and this K: a forward that does not group after all writes the list itself (launch_fill)
+    // ... and launched no k_scan at all: k_round left the games' request counts in scan_cnt [games], and k_group derives TreeState::req_base and the round's total
+    // (Store::d_count, scan_evals[0] += total) from them.  NULL: k_scan ran (step-wise rounds, match episodes).  One round's worth, as the two flags above.
+    const int32_t* scan_cnt = nullptr;
+    unsigned long long* scan_evals = nullptr;
     double children_launches[2] = {0.0, 0.0}; // sibling rounds by children kernel: [0] k_sib_children2, [1] k_sib_children
     bool sib_v2 = true;              // difference path: k_sib_children2 (one wave per child, growing windows) and the base-slot layout it reads
-    bool win_rects = true;           // fc0 window tiles walk only the rectangle of window pixels their rows can differ in (k_bin_prefix); false (omok_debug_set_window_rects): the whole 7x7 window -- same bits
+    bool win_rects = true;           // fc0 window tiles walk only the rectangle of window pixels their rows can differ in (bin_prefix_role); false (omok_debug_set_window_rects): the whole 7x7 window -- same bits
     bool base_cache = true;          // false (omok_debug_set_base_cache): every run's base is evaluated in full every round (A-B check: same p / v bit for bit)
     bool sib_cache_valid = false;    // false: the trees changed outside the search rounds (reset, advance, refill): tags are cleared first
     float* part_w = nullptr;         // fp32 partials of the K-split window tiles: [7][part_w_rows][512]
@@ -103,7 +107,7 @@ struct Net {
     // request rows are the engine's dense list minus grp_sub[0] (the rows of the games in front, NULL: none); grp_hi < 0: every game (self-play)
     int grp_lo = 0, grp_hi = -1;
     const int32_t* grp_sub = nullptr;
-    // what the LAST forward decided on the host (omok_debug_last_plan; the device-side choices of k_bin_prefix stay in d_gcnt): path 0 plain rows, 1 copy path,
+    // what the LAST forward decided on the host (omok_debug_last_plan; the device-side choices of bin_prefix_role stay in d_gcnt): path 0 plain rows, 1 copy path,
     // 2 difference path, 3 fp32 kernels (-1: no forward yet), its row bound, the dense fc0's K split (0: difference path / fp32) and the tail GEMMs' K split
     int plan_path = -1, plan_rows = 0, plan_nsplit = 0, plan_tsplit = 0;
 };
@@ -140,13 +144,13 @@ bool net_logits_cover_batch(const Net& net, int max_count);
 // true if net_forward_requests(net, S, max_count, ..., sibling_side >= 0) will group the requests by parent (k_group): the caller may then hand
 // the zeroing of net.d_gcnt and the request-list fill to it (Net::gcnt_zeroed, Net::fill_in_group)
 bool net_round_takes_sibling_path(const Net& net, int max_count);
-// Net::d_gcnt: what k_group counts, what k_bin_prefix derives from it on the device, and what the fc0 kernels of the difference path, k_win_finish, k_facc_reduce and
+// Net::d_gcnt: what k_group counts, what bin_prefix_role derives from it on the device, and what the fc0 kernels of the difference path, k_win_finish, k_facc_reduce and
 // the host (omok_debug_last_plan, OMOK_SIB_STATS) read
 enum {
     NET_GCNT_RUNS = 0,          // runs of sibling requests (k_group)
     NET_GCNT_SINGLES = 1,       // rows outside runs
     NET_GCNT_ROWS_IN_RUNS = 2,  // rows inside runs
-    NET_GCNT_FULL_ROWS = 3,     // difference path (k_bin_prefix, as everything up to NET_GCNT_BINS): rows evaluated in full = NET_GCNT_FULL_EVALS + NET_GCNT_SINGLES
+    NET_GCNT_FULL_ROWS = 3,     // difference path (bin_prefix_role, as everything up to NET_GCNT_BINS): rows evaluated in full = NET_GCNT_FULL_EVALS + NET_GCNT_SINGLES
     NET_GCNT_WIN_TILES = 4,     // fc0 window tiles
     NET_GCNT_SPLIT_TILE0 = 5,   // first tile of the K-split set (the tiles below it run the whole K)
     NET_GCNT_WIN_WAYS = 6,      // K splits of the tiles of that set
@@ -154,7 +158,7 @@ enum {
     NET_GCNT_BINS = 8,          // [+ b] children whose window is bin b (diagnostics; 81 bins, padded to 88 ints)
     NET_GCNT_FULL_EVALS = 96,   // runs whose base is evaluated in full (base-cache misses + uncacheable runs; k_group)
     NET_GCNT_UNCACHEABLE = 97,  // ... of them: runs that have no base slot of their game (k_group)
-    NET_GCNT_FULL_WAYS = 98,    // K splits of the full-row fc0 (k_bin_prefix)
+    NET_GCNT_FULL_WAYS = 98,    // K splits of the full-row fc0 (bin_prefix_role)
     NET_GCNT_FULL_STRIDE = 99,  // ... and the row stride of its partial slab (the kernels read the pair through one pointer: FULL_STRIDE follows FULL_WAYS)
     NET_GCNT_HEAD_INTS = 100    // ints in front of the padding and the per-pixel counts
 };

@@ -533,6 +533,20 @@ __device__ __forceinline__ void base_subtract(f32x16 (&x)[4], const BaseEntry& b
     }
 }
 
+// Difference path: the round's slot layout (bin starts, window tiles and their order, K splits: bin_prefix_role below, behind k_group) is derived by ONE workgroup from
+// k_group's counters.  It runs as workgroup 0 of the base pass's launch (k_trunk<.., BASE, DELTA>), whose sample workgroups read none of what it writes.
+struct BinPrefixArgs {
+    int32_t* cnt;            // Net::d_gcnt
+    int32_t* bin_start;      // [225] first slot of a P0's rows
+    int32_t* tile_info;      // [tile_cap] tiles, [tile_cap ..) the whole-K launch's order
+    uint2* slot_desc;        // the single rows' (request row, fp32 fc0 row)
+    const int32_t* singles;
+    unsigned long long* work; // Net::d_work
+    int n_cu, max_fways, max_wways, part_w_rows, facc_single_base, part_f_rows, nsup_full, bn, use_rects, tile_cap;
+};
+template <int NT> // NT = threads of the workgroup
+__device__ __forceinline__ void bin_prefix_role(unsigned char* lds, const BinPrefixArgs& a);
+
 template <int N, bool FROM_F32, bool BASE = false, bool DELTA = false, bool F16LO = false> // BASE: the base pass of the sibling path (see k_group / k_sib_children below), DELTA: the
                                                                                            // difference path, F16LO: operand rows in the FC0_F16 format (f16 residuals)
 __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_t* __restrict__ req_ref, const uint32_t* __restrict__ req_aux,
@@ -543,7 +557,8 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
                                                                     const int32_t* __restrict__ row_list, const int32_t* __restrict__ d_nrows,
                                                                     const uint2* __restrict__ groups, float* __restrict__ hscr,
                                                                     const int32_t* __restrict__ d_out_base, uint4* __restrict__ a_base,
-                                                                    const int32_t* __restrict__ d_nrows2, uint4* __restrict__ sib2) {
+                                                                    const int32_t* __restrict__ d_nrows2, uint4* __restrict__ sib2, BinPrefixArgs bp) {
+    // BASE && DELTA: workgroup 0 of the launch derives the round's slot layout (bin_prefix_role; bp, unused otherwise) and the sample workgroups are 1 .. gridDim.x - 1.
     // sib2 != NULL (BASE | DELTA only): the base's h and d grids and its residual stream in front of block 2 go to the base slot in the layout
     // k_sib_children2 reads (sib2_grid, sib2_x2) instead of the h grids to hscr.
     // row_list != NULL: the kernel evaluates the request rows row_list[0 .. d_nrows[0]) (the rows outside the sibling runs).
@@ -556,6 +571,14 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
     using TG = TrunkGeo<N>;
     constexpr int HW = TG::HW, NW = Geo<N>::NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int ROLE_WGS = (BASE && DELTA) ? 1 : 0;
+    if constexpr (ROLE_WGS != 0) {
+        if (blockIdx.x == 0) { // (the first workgroup dispatched; its tables take the LDS the trunk's weights would)
+            bin_prefix_role<TrunkGeo<N>::WG_THREADS>(smem, bp);
+            return;
+        }
+    }
+    const int wg = (int)blockIdx.x - ROLE_WGS, n_wg = (int)gridDim.x - ROLE_WGS; // sample workgroup, of how many
     const half8* ldsW = (const half8*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave index: uniform, and the compiler knows it (scalar loads / SALU below)
@@ -652,13 +675,13 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
         cwl[m] = convW[(4 + m) * 64 + lane];
     }
     auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-    const int b_first = (int)blockIdx.x * TG::SPW + slot;
-    const int b_stride = (int)gridDim.x * TG::SPW;
+    const int b_first = wg * TG::SPW + slot;
+    const int b_stride = n_wg * TG::SPW;
     uint32_t ref_n = 0, aux_n = 0xFFFFFFFFu;
     if (!FROM_F32 && b_first < count) { ref_n = refof(b_first); aux_n = auxof(b_first); }
     SampleIn in = load_in(b_first < count ? rowof(b_first) : 0, ref_n, aux_n, single(b_first));
 
-    for (int b0 = (int)blockIdx.x * TG::SPW; b0 < count; b0 += b_stride) { // uniform trip count over the workgroup (barriers inside)
+    for (int b0 = wg * TG::SPW; b0 < count; b0 += b_stride) { // uniform trip count over the workgroup (barriers inside)
         const int bi = b0 + slot;
         const bool active = bi < count; // a slot without a sample in the last pass runs along (for the barriers) and stores nothing
         const int b = active ? rowof(bi) : 0;
@@ -930,7 +953,7 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
 }
 
 // ===============================================================================================
-// OMOK_NET_F16X3: SIBLING requests of a search round (N = 15): k_group, k_bin_prefix, k_trunk<.., BASE>, k_sib_children, fc0 window tiles
+// OMOK_NET_F16X3: SIBLING requests of a search round (N = 15): k_group, bin_prefix_role, k_trunk<.., BASE>, k_sib_children, fc0 window tiles
 // ===============================================================================================
 // The K requests a tree contributes to a round are, almost always, children of ONE leaf (tree_kernels.hip: between two backups
 // the PUCT descent reaches the same leaf, and a round has no backups except terminal ones; measured over a configs[1] episode:
@@ -990,30 +1013,62 @@ __device__ inline void sib_window(int n, int action, int& wy0, int& wx0) { // th
 // One wave per tree, GROUP_TREES trees per workgroup: the workgroup counts in LDS and claims its ranges of the global lists with one
 // atomic per counter (per-row atomics on 3 + 81 addresses serialised in L2: 0.24 ms per round).
 // MATCH (match episodes, Net::grp_*): the games [g_lo, g_hi) only, request rows relative to row_sub[0] (the forward's own list; NULL: 0).
+// scan_cnt != NULL (!MATCH, run-loop rounds: no k_scan ran): the games' request counts of this round as k_round left them, dense (0 for a finished game).  The
+// workgroup derives what k_scan would have: the first request row of its trees = the counts of all games in front of its first one (every workgroup sums them for
+// itself, coalesced: no workgroup waits for another) + the prefix over its own trees, stored to TreeState::req_base of live trees; the workgroup of the last game
+// stores the round's total to S.d_count[0] and adds it to evals[0].
 constexpr int GROUP_TREES = 16;
 template <bool MATCH>
 __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, uint2* __restrict__ groups, int32_t* __restrict__ singles,
                                                              uint4* __restrict__ sib_rows, int32_t* __restrict__ cnt, uint32_t* __restrict__ sib_slot,
                                                              int32_t* __restrict__ tags, uint2* __restrict__ comp, int bn, int do_fill,
-                                                             unsigned long long* __restrict__ work, int g_lo, int g_hi, const int32_t* __restrict__ row_sub) {
+                                                             unsigned long long* __restrict__ work, int g_lo, int g_hi, const int32_t* __restrict__ row_sub,
+                                                             const int32_t* __restrict__ scan_cnt, unsigned long long* __restrict__ evals) {
     // Difference path (sib_slot != NULL): base slots.  The FIRST run of a tree uses one of the game's SIB_WAYS slots (SIB_WAYS g + way), whose content is
     // reused while a tag names the run's parent (a leaf is its tree's expansion target for ~14 rounds); further runs of the tree in the same
     // round (rare) take a slot behind the games' and are always evaluated.  comp[] lists the (first request row, slot) pairs to evaluate.
     constexpr int NP0 = 225, L_P0 = 3, L_FULL = L_P0 + NP0, L_UNC = L_FULL + 1, LC = L_UNC + 1; // [NET_GCNT_RUNS, _SINGLES, _ROWS_IN_RUNS] as in d_gcnt | [L_P0 +] children per net pixel of their stone (P0) | full evaluations, uncacheable runs
     static_assert(NET_GCNT_ROWS_IN_RUNS + 1 == L_P0 && NET_GCNT_UNCACHEABLE == NET_GCNT_FULL_EVALS + 1, "k_group's local counters mirror d_gcnt");
     __shared__ int l_cnt[LC], l_base[LC];
+    __shared__ int l_front[GROUP_TREES], l_n[GROUP_TREES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int g = (MATCH ? g_lo : 0) + blockIdx.x * GROUP_TREES + (tid >> 6);
     const int g_end = MATCH ? g_hi : S.games;
+    const bool scan = !MATCH && scan_cnt != nullptr;
+    if (scan) { // the requests of the games in front of the workgroup's first: a partial sum per wave
+        int s = 0;
+        for (int i = tid; i < (int)blockIdx.x * GROUP_TREES; i += 64 * GROUP_TREES) s += scan_cnt[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) l_front[tid >> 6] = s;
+    }
     if (tid < LC) l_cnt[tid] = 0;
     __syncthreads();
     int n = 0;
     TreeState ts{};
     const int t = side * S.games + (g < g_end ? g : 0);
-    if (g < g_end && S.gs[g].alive) {
+    const bool live = g < g_end && S.gs[g].alive;
+    if (live) {
         ts = S.ts[t];
         n = (int)ts.n_req;
         if (MATCH && row_sub) ts.req_base -= (uint32_t)row_sub[0];
+    }
+    if (scan) {
+        if (lane == 0) l_n[tid >> 6] = n;
+        __syncthreads();
+        int front = 0, mine = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < GROUP_TREES; ++w) {
+            front += l_front[w];
+            mine += w < (tid >> 6) ? l_n[w] : 0;
+            total += l_n[w];
+        }
+        ts.req_base = (uint32_t)(front + mine);
+        if (live && lane == 0) S.ts[t].req_base = ts.req_base;
+        if (blockIdx.x == gridDim.x - 1 && tid == 0) {
+            S.d_count[0] = front + total;
+            if (evals) evals[0] += (unsigned long long)(front + total); // (the evaluation counter of the stats)
+        }
     }
     int parent = -1 - lane; // distinct for the lanes beyond the list
     uint32_t tn = 0, ta = 0;
@@ -1101,7 +1156,7 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
     if (in_run) {
         if (sib_slot) {
             // slots are handed out per net PIXEL of the child's stone (P0), not per window bin: a bin's rows are then ordered by P0, and an fc0 window tile
-            // only has to walk the window pixels its own rows can differ in (k_bin_prefix: the tile's rectangle)
+            // only has to walk the window pixels its own rows can differ in (bin_prefix_role: the tile's rectangle)
             bin = (2 * (int)(ta >> 8) + 1) / 3;
             rank = atomicAdd(&l_cnt[L_P0 + bin], 1);
         }
@@ -1165,19 +1220,37 @@ __device__ inline void sib_p0_range(int bn, int o, int& lo, int& hi) { // net-pi
     lo = o == 0 ? 0 : o + SIB_WIN / 2;
     hi = o == bn - SIB_WIN ? bn - 1 : o + SIB_WIN / 2;
 }
-__host__ __device__ inline void tile_rect(int ti, int& y0, int& y1, int& x0, int& x1) { // the rectangle of window pixels in a tile_info word (k_bin_prefix packs it)
+__host__ __device__ inline void tile_rect(int ti, int& y0, int& y1, int& x0, int& x1) { // the rectangle of window pixels in a tile_info word (bin_prefix_role packs it)
     y0 = (ti >> 16) & 7; y1 = (ti >> 19) & 7; x0 = (ti >> 22) & 7; x1 = (ti >> 25) & 7;
 }
-constexpr int BP_THREADS = 256, BP_MAXT = 2048; // k_bin_prefix: threads, tiles of the whole-K launch it can order by cost (more: layout order)
-__global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__ cnt, int32_t* __restrict__ bin_start, int32_t* __restrict__ tile_info,
-                                                           uint2* __restrict__ slot_desc, const int32_t* __restrict__ singles, int n_cu, int max_fways,
-                                                           int max_wways, int part_w_rows, int facc_single_base, int part_f_rows, int nsup_full, int bn, int use_rects, int tile_cap,
-                                                           unsigned long long* __restrict__ work) {
-    __shared__ unsigned char cost[BP_MAXT];
-    __shared__ int hist[64], s_area;
-    __shared__ int tile0[SIB_BINS + 2], binc[SIB_BINS + 1], bcnt[SIB_BINS + 1], order[SIB_BINS + 1], start_at[SIB_BINS + 2], p0c[225], p0o[225], s_split, s_ntiles;
+constexpr int BP_MAXT = 2048; // bin_prefix_role: tiles of the whole-K launch it can order by cost (more: layout order)
+// ONE workgroup of NT threads (every loop strides by NT): workgroup 0 of the base pass's launch (k_trunk<.., BASE, DELTA>, 512 or 384 threads).  It reads k_group's
+// counters (P0 counts, singles, full evaluations) and the single rows' list, all complete at the launch's start; it writes the derived counters of d_gcnt, bin_start,
+// tile_info, the single rows' slot_desc and d_work -- none of which the launch's sample workgroups touch (they read d_comp, d_singles and the two counters
+// NET_GCNT_FULL_EVALS / _SINGLES); the first readers (k_sib_children2: bin_start; the fc0 launches) come behind the kernel boundary.
+// lds: the workgroup's dynamic LDS, of which the tables take the first BinPrefixLds bytes.
+struct BinPrefixLds {
+    int hist[64], s_area;
+    int tile0[SIB_BINS + 2], binc[SIB_BINS + 1], bcnt[SIB_BINS + 1], order[SIB_BINS + 1], start_at[SIB_BINS + 2], p0c[225], p0o[225], s_split, s_ntiles;
+    unsigned char cost[BP_MAXT];
+};
+static_assert(sizeof(BinPrefixLds) <= TrunkGeo<9>::LDS_BYTES && sizeof(BinPrefixLds) <= TrunkGeo<15>::LDS_BYTES, "the role's tables come out of the trunk workgroup's LDS");
+template <int NT>
+__device__ __forceinline__ void bin_prefix_role(unsigned char* lds, const BinPrefixArgs& a) {
+    int32_t* __restrict__ cnt = a.cnt;
+    int32_t* __restrict__ bin_start = a.bin_start;
+    int32_t* __restrict__ tile_info = a.tile_info;
+    uint2* __restrict__ slot_desc = a.slot_desc;
+    const int32_t* __restrict__ singles = a.singles;
+    unsigned long long* __restrict__ work = a.work;
+    const int n_cu = a.n_cu, max_fways = a.max_fways, max_wways = a.max_wways, part_w_rows = a.part_w_rows, facc_single_base = a.facc_single_base,
+              part_f_rows = a.part_f_rows, nsup_full = a.nsup_full, bn = a.bn, use_rects = a.use_rects, tile_cap = a.tile_cap;
+    BinPrefixLds& L = *(BinPrefixLds*)lds;
+    unsigned char* cost = L.cost;
+    int *hist = L.hist, &s_area = L.s_area, *tile0 = L.tile0, *binc = L.binc, *bcnt = L.bcnt, *order = L.order, *start_at = L.start_at, *p0c = L.p0c, *p0o = L.p0o,
+        &s_split = L.s_split, &s_ntiles = L.s_ntiles;
     const int tid = threadIdx.x;
-    for (int i = tid; i < 225; i += blockDim.x) p0c[i] = i < bn * bn ? cnt[NET_GCNT_P0 + i] : 0;
+    for (int i = tid; i < 225; i += NT) p0c[i] = i < bn * bn ? cnt[NET_GCNT_P0 + i] : 0;
     if (tid < 64) hist[tid] = 0;
     if (tid == 0) s_area = 0;
     __syncthreads();
@@ -1257,7 +1330,7 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
     // one thread per tile: its bin (layout position by a search over start_at), its live slots, its rectangle = union of the regions (P0 +- 3, clipped to the board) of
     // the P0s with rows in the tile, in window coordinates; cost = the rectangle's pixels
     const int ntiles = s_ntiles, t_split = s_split;
-    for (int T = tid; T < ntiles; T += blockDim.x) {
+    for (int T = tid; T < ntiles; T += NT) {
         int pos = 0;
         for (int step = 64; step > 0; step >>= 1)
             if (pos + step <= SIB_BINS && start_at[pos + step] <= T) pos += step;
@@ -1331,13 +1404,13 @@ __global__ __launch_bounds__(BP_THREADS) void k_bin_prefix(int32_t* __restrict__
                 if (T < n) tile_order[pos] = T;
             }
         }
-        for (int T = n + tid; T < t_split; T += blockDim.x) tile_order[T] = T; // (n = 0: more tiles than the table holds)
+        for (int T = n + tid; T < t_split; T += NT) tile_order[T] = T; // (n = 0: more tiles than the table holds)
     }
     const int nsing = cnt[NET_GCNT_SINGLES], s0 = tile0[SIB_BINS] * GT_BS;
-    for (int i = tid; i < nsing; i += blockDim.x) slot_desc[s0 + i] = make_uint2((uint32_t)singles[i], (uint32_t)(facc_single_base + i)); // (fp32 fc0 row index)
+    for (int i = tid; i < nsing; i += NT) slot_desc[s0 + i] = make_uint2((uint32_t)singles[i], (uint32_t)(facc_single_base + i)); // (fp32 fc0 row index)
 }
 
-// tiles of the K-split set (see k_bin_prefix): partials in split order + the slot's full row + bias, LeakyReLU, hi|lo operand row
+// tiles of the K-split set (see bin_prefix_role): partials in split order + the slot's full row + bias, LeakyReLU, hi|lo operand row
 __global__ __launch_bounds__(256) void k_win_finish(const float* __restrict__ part, size_t cap_rows, const int32_t* __restrict__ cnt,
                                                     const int32_t* __restrict__ tile_info, const uint2* __restrict__ slot_desc,
                                                     const float* __restrict__ facc, const float* __restrict__ bias, uint4* __restrict__ out_split,
@@ -1775,7 +1848,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     // difference-row entries of a tile's pixels, in the layout of k_sib_children<DELTA>'s (staging rows = this wave's cells 0..31)
     // `far`: this lane's pixel lies outside the child's own region (P0 +- 3, clipped to the board -- at an edge that is less than the 7x7 window its bin shares): there the child
     // equals its base, and the lane stores EXACT zeros instead of the base row's quantisation remainder (~2^-22 of the activation), so that an fc0 window tile may skip the pixel
-    // or not (k_bin_prefix: the tile's rectangle) without changing a bit of the row's sum.
+    // or not (bin_prefix_role: the tile's rectangle) without changing a bit of the row's sum.
     auto store_rows = [&](const f32x16 (&x)[4], uint4* row, bool lane_valid, const int (&rd_px)[4], const bool (&rd_ok)[4], bool far) {
         const int lq = OL();
         uint4* stage_w = (uint4*)(wgrid + (lq & 31) * GRID_STRIDE);
@@ -2279,7 +2352,7 @@ struct Fc0Tile {
     int split_y, part_row0;        // EPI_PARTIAL: K split index; WIN: first slot of the K-split set (partials are indexed by the slot inside it)
     size_t out_row_u4;             // EPI_SPLIT: output row stride; EPI_PARTIAL: rows of the partial slab per split
     int win_oy, win_ox;            // WIN: origin of the bin's 7x7 window on the board
-    int wr_y0, wr_x0, wr_w, wr_n, wr_inv; // WIN: the tile's rectangle of window pixels (k_bin_prefix): origin, width, super-steps (2 per pixel), 65536 / width + 1
+    int wr_y0, wr_x0, wr_w, wr_n, wr_inv; // WIN: the tile's rectangle of window pixels (bin_prefix_role): origin, width, super-steps (2 per pixel), 65536 / width + 1
     // WIN: super-step j of the tile's rectangle -> super-step u = 2 w + q of the 7x7 window (steps past the end -- prefetches -- re-read the last)
     __device__ __forceinline__ int win_u(int j) const {
         j = j < wr_n ? j : wr_n - 1;
@@ -2312,7 +2385,7 @@ __device__ __forceinline__ bool fc0_map_tile(Fc0Tile& t, int ksup, size_t out_ro
             tile = t_split + item / ways;
             t.part_row0 = t_split * GT_BS;
             out_row_u4 = (size_t)n_here * GT_BS; // partials: [split][slot inside the split set]
-        } else { // position p of the cost-sorted order (k_bin_prefix), dealt in rounds of 8 x 32 workgroups: XCD x = blockIdx & 7 takes chunk x of an even round and chunk
+        } else { // position p of the cost-sorted order (bin_prefix_role), dealt in rounds of 8 x 32 workgroups: XCD x = blockIdx & 7 takes chunk x of an even round and chunk
                  // 7 - x of an odd one (the XCD with the dearest tiles of round 1 gets the cheapest of round 2)
             const int per_x = (int)gridDim.x >> 3, cu_x = per_x < 32 ? per_x : 32, j = (int)blockIdx.x >> 3, r = j / cu_x; // (32 CUs per XCD)
             const int xc = (int)blockIdx.x & 7, p = r * (8 * cu_x) + ((r & 1) ? 7 - xc : xc) * cu_x + j % cu_x;
@@ -2322,7 +2395,7 @@ __device__ __forceinline__ bool fc0_map_tile(Fc0Tile& t, int ksup, size_t out_ro
         t.b0 = tile * GT_BS;
         const int ti = tile_info[tile], bin = ti & 0xFF;
         t.count = t.b0 + ((ti >> 8) & 0xFF);
-        // the tile's rectangle of window pixels (k_bin_prefix): rows wr_y0 .. y1, columns wr_x0 .. x1 of the 7x7 window; super-step j of the tile = pixel j / 2 of the rectangle in
+        // the tile's rectangle of window pixels (bin_prefix_role): rows wr_y0 .. y1, columns wr_x0 .. x1 of the 7x7 window; super-step j of the tile = pixel j / 2 of the rectangle in
         // row-major order, channel half j & 1
         int wr_y1, wr_x1;
         tile_rect(ti, t.wr_y0, wr_y1, t.wr_x0, wr_x1);
@@ -2339,7 +2412,7 @@ __device__ __forceinline__ bool fc0_map_tile(Fc0Tile& t, int ksup, size_t out_ro
         t.count = d_count[0];
         if (t.count > max_count) t.count = max_count;
         if (EPI == EPI_PARTIAL && tile_info) { // full rows of the difference path (d_count = d_gcnt + NET_GCNT_FULL_ROWS, tile_info = d_gcnt + NET_GCNT_FULL_WAYS): the number
-            // of K splits and the partial slab's row stride were chosen on the device (k_bin_prefix); uneven split.
+            // of K splits and the partial slab's row stride were chosen on the device (bin_prefix_role); uneven split.
             // 1-D grid over (split, tile) items dealt by xcd_item -- a (tiles_max x ways_max) grid of which a few dozen workgroups have work
             // costs more to dispatch (~65-100 workgroups per us) than the work takes
             const int ways = tile_info[0], per = (nsup + ways - 1) / ways;
@@ -3804,7 +3877,7 @@ static int net_pack(Net& net, hipStream_t st) {
 
 template <int N, bool FROM_F32, bool BASE = false, bool DELTA = false, bool F16LO = false>
 static void launch_trunk(Net& net, const Store& S, int max_count, hipStream_t st, const int32_t* row_list = nullptr, const int32_t* d_nrows = nullptr,
-                         const int32_t* d_out_base = nullptr, const int32_t* d_nrows2 = nullptr, bool v2 = false) {
+                         const int32_t* d_out_base = nullptr, const int32_t* d_nrows2 = nullptr, bool v2 = false, const BinPrefixArgs* role = nullptr) {
     using TG = TrunkGeo<N>;
     static bool attr_done[64] = {}; // per device: the attribute belongs to the device's copy of the code object
     auto kern = k_trunk<N, FROM_F32, BASE, DELTA, F16LO>;
@@ -3813,19 +3886,22 @@ static void launch_trunk(Net& net, const Store& S, int max_count, hipStream_t st
         attr_done[net.device & 63] = true;
     }
     const int wgs = (max_count + TG::SPW - 1) / TG::SPW;
-    const int grid = wgs < 256 ? wgs : 256;
+    // BASE && DELTA: workgroup 0 is bin_prefix_role (`role`: its arguments), the sample workgroups follow -- 256 workgroups in all as before, so that every one is
+    // resident from the start (the trunk's LDS allows one per CU): the role's CU idles behind it for the rest of the launch instead of a 257th workgroup starting late
+    constexpr int ROLE_WGS = (BASE && DELTA) ? 1 : 0;
+    const int grid = (wgs < 256 - ROLE_WGS ? wgs : 256 - ROLE_WGS) + ROLE_WGS;
     kern<<<grid, TG::WG_THREADS, TG::LDS_BYTES, st>>>(S.req_ref, S.req_aux, S.board, S.hdr, S.d_count, S.stride_nodes, net.in_f32, (const uint4*)net.wt_trunk, net.wt_first,
                                                        (uint4*)net.a_fc0, net.row_u4, max_count, row_list, d_nrows,
                                                        (BASE && DELTA) ? (const uint2*)net.d_comp : (const uint2*)net.d_groups, net.sib_h, d_out_base, (uint4*)net.a_base,
-                                                       d_nrows2, v2 ? (uint4*)net.sib_h : nullptr);
+                                                       d_nrows2, v2 ? (uint4*)net.sib_h : nullptr, role ? *role : BinPrefixArgs{});
 }
 
 // the same in the engine's current operand format (F16LO = FC0_F16 rows)
 template <int N, bool FROM_F32, bool BASE = false, bool DELTA = false>
 static void launch_trunk_fmt(Net& net, const Store& S, int max_count, hipStream_t st, const int32_t* row_list = nullptr, const int32_t* d_nrows = nullptr,
-                             const int32_t* d_out_base = nullptr, const int32_t* d_nrows2 = nullptr, bool v2 = false) {
-    if (net.fc0_fmt == FC0_F16) launch_trunk<N, FROM_F32, BASE, DELTA, true>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2);
-    else launch_trunk<N, FROM_F32, BASE, DELTA, false>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2);
+                             const int32_t* d_out_base = nullptr, const int32_t* d_nrows2 = nullptr, bool v2 = false, const BinPrefixArgs* role = nullptr) {
+    if (net.fc0_fmt == FC0_F16) launch_trunk<N, FROM_F32, BASE, DELTA, true>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2, role);
+    else launch_trunk<N, FROM_F32, BASE, DELTA, false>(net, S, max_count, st, row_list, d_nrows, d_out_base, d_nrows2, v2, role);
 }
 
 template <int MT, int EPI, int TAG, int NST = 3>
@@ -3873,7 +3949,7 @@ static void launch_gemm_w(const void* wp, const void* act, int ksteps, size_t ac
                                                                  S.d_count, max_count);
 }
 
-// K splits of the difference path's fc0 launches (chosen on the device, k_bin_prefix): the full rows up to 30 ways as far as the
+// K splits of the difference path's fc0 launches (chosen on the device, bin_prefix_role): the full rows up to 30 ways as far as the
 // partial slab holds ways x (the launch's row capacity); window tiles of the split set up to 14 ways (7 super-steps each)
 constexpr int SIB_MAX_WWAYS = 14;
 // (capped on the device by the slab: part_rows / (tiles of full rows x 128), and by CUs / tiles; 30 until round 4; per full round in the mixed format: k_fc0_x3 on the
@@ -3914,7 +3990,9 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
     const bool x16 = net.fc0_fmt == FC0_F16;
     if (!net.gcnt_zeroed) k_zero_ints<<<1, 128, 0, st>>>(net.d_gcnt, SIB_CNT_INTS); // (a hipMemsetAsync of these 448 bytes is a 13-us fill kernel)
     const int do_fill = net.fill_in_group ? 1 : 0;
+    const int32_t* scan_cnt = net.scan_cnt; // (non-NULL: no k_scan ran, k_group derives the request offsets)
     net.gcnt_zeroed = net.fill_in_group = false; // (one round's worth: the engine sets them per round)
+    net.scan_cnt = nullptr;
     if (delta && (!net.sib_cache_valid || !net.base_cache)) { // the trees changed since the last search round: no cached base is valid
         hipMemsetAsync(net.d_tags, 0xFF, sizeof(int32_t) * (size_t)net.games * SIB_WAYS, st);
         net.sib_cache_valid = true;
@@ -3923,11 +4001,11 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
         const int ng = net.grp_hi - net.grp_lo;
         k_group<true><<<ng > 0 ? (ng + GROUP_TREES - 1) / GROUP_TREES : 1, 64 * GROUP_TREES, 0, st>>>(S, side, (uint2*)net.d_groups, net.d_singles, (uint4*)net.d_sib_rows,
                                                                     net.d_gcnt, delta ? net.d_sib_slot : nullptr, net.d_tags, (uint2*)net.d_comp, net.n, do_fill,
-                                                                    net.d_work, net.grp_lo, net.grp_hi, net.grp_sub);
+                                                                    net.d_work, net.grp_lo, net.grp_hi, net.grp_sub, nullptr, nullptr);
     } else
         k_group<false><<<(S.games + GROUP_TREES - 1) / GROUP_TREES, 64 * GROUP_TREES, 0, st>>>(S, side, (uint2*)net.d_groups, net.d_singles, (uint4*)net.d_sib_rows, net.d_gcnt,
                                                                                      delta ? net.d_sib_slot : nullptr, net.d_tags, (uint2*)net.d_comp, net.n, do_fill, net.d_work,
-                                                                                     0, 0, nullptr);
+                                                                                     0, 0, nullptr, scan_cnt, net.scan_evals);
     if (!delta) {
         // (the copy path keeps the runs' h grids in sib_h[run index]: the slots the difference path caches bases in -- cached bases are void)
         net.sib_cache_valid = false;
@@ -3942,11 +4020,15 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
     static const int tprof_mode = getenv("OMOK_SIB_PROF") ? atoi(getenv("OMOK_SIB_PROF")) : 0; // timing experiments only (N = 15, fp6 format): 2 = k_sib_children2's phase profile
     const bool mixed = x16 && net.diff_fp6; // FC0_MIXED: full rows f16, difference rows fp6 (k_sib_children2 only)
     const bool v2 = net.sib_v2 || mixed;
-    // per-tile rectangles of window pixels (k_bin_prefix): only k_sib_children2 writes the exact zeros outside a child's own region that make a row's sum independent of its tile
+    // per-tile rectangles of window pixels (bin_prefix_role): only k_sib_children2 writes the exact zeros outside a child's own region that make a row's sum independent of its tile
     const bool rects = v2 && net.win_rects;
-    k_bin_prefix<<<1, BP_THREADS, 0, st>>>(net.d_gcnt, net.d_bin_start, net.d_tile_info, (uint2*)net.d_slot_desc, net.d_singles, net.n_cu,
-                                    SIB_MAX_FWAYS, SIB_MAX_WWAYS, (int)std::min<size_t>(net.part_w_rows * 7, (size_t)1 << 30), (int)net.base_slots,
-                                    (int)std::min<size_t>(net.part_rows, (size_t)1 << 30), 2 * net.hw, net.n, rects ? 1 : 0, (int)(net.d_slots / GT_BS), net.d_work);
+    // the round's slot layout (bin_prefix_role) is derived by workgroup 0 of the base pass's launch
+    const BinPrefixArgs role{net.d_gcnt, net.d_bin_start, net.d_tile_info, (uint2*)net.d_slot_desc, net.d_singles, net.d_work, net.n_cu,
+                             SIB_MAX_FWAYS, SIB_MAX_WWAYS, (int)std::min<size_t>(net.part_w_rows * 7, (size_t)1 << 30), (int)net.base_slots,
+                             (int)std::min<size_t>(net.part_rows, (size_t)1 << 30), 2 * net.hw, net.n, rects ? 1 : 0, (int)(net.d_slots / GT_BS)};
+    // runs without a cached base -> compact rows [0, misses) + their base slots; then the single rows -> compact rows [misses, misses + singles)
+    if (net.n == 9) launch_trunk_fmt<9, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + NET_GCNT_FULL_EVALS, nullptr, net.d_gcnt + NET_GCNT_SINGLES, v2, &role);
+    else launch_trunk_fmt<15, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + NET_GCNT_FULL_EVALS, nullptr, net.d_gcnt + NET_GCNT_SINGLES, v2, &role);
     static const bool stats = getenv("OMOK_SIB_STATS") && atoi(getenv("OMOK_SIB_STATS")); // diagnostics only: synchronises every round
     if (stats) {
         // per round: runs, runs evaluated in full (base-cache misses + uncacheable runs), singles, rows in runs, window tiles, first tile of the split set, its ways, full-row K split
@@ -3974,9 +4056,6 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
             for (int i = 0; i < 8; ++i) acc[i] = 0;
         }
     }
-    // runs without a cached base -> compact rows [0, misses) + their base slots; then the single rows -> compact rows [misses, misses + singles)
-    if (net.n == 9) launch_trunk_fmt<9, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + NET_GCNT_FULL_EVALS, nullptr, net.d_gcnt + NET_GCNT_SINGLES, v2);
-    else launch_trunk_fmt<15, false, true, true>(net, S, max_count, st, net.d_singles, net.d_gcnt + NET_GCNT_FULL_EVALS, nullptr, net.d_gcnt + NET_GCNT_SINGLES, v2);
     if (v2 && tprof_mode == 2 && !x16 && net.n == 15) {
         static unsigned long long* d_tp = nullptr;
         static unsigned long long acc[32] = {};
@@ -4033,14 +4112,14 @@ static void launch_fc0_delta(Net& net, int max_count, const float* bias_fc0, uin
     const int tiles_max = (max_count + GT_BS - 1) / GT_BS;
     const size_t cap_rows = (size_t)tiles_max * GT_BS;
     const int32_t* cnt = net.d_gcnt;
-    // full rows, in the format of full operand rows.  Their live count is only known on the device: k_bin_prefix chose the K split and the partial slab's row stride
+    // full rows, in the format of full operand rows.  Their live count is only known on the device: bin_prefix_role chose the K split and the partial slab's row stride
     // (NET_GCNT_FULL_WAYS, NET_GCNT_FULL_STRIDE)
     const int fgrid = ((tiles_max > n_cu ? tiles_max : n_cu) + 7) / 8 * 8; // (tiles x ways <= CUs by construction unless there are more tiles than CUs: then 1 way; whole eighths: xcd_item)
     launch_fc0<EPI_PARTIAL, false>(net, net.fc0_fmt, fgrid, st, net.a_fc0, nsup, net.row_u4, bias_fc0, nullptr, cap_rows, net.part, cnt + NET_GCNT_FULL_ROWS, max_count,
                                    cnt + NET_GCNT_FULL_WAYS);
     k_facc_reduce<<<512, 256, 0, st>>>(net.part, cap_rows, cnt + NET_GCNT_FULL_ROWS, cnt + NET_GCNT_FULL_WAYS, net.facc, (const uint2*)net.d_comp, cnt + NET_GCNT_FULL_EVALS, (int)net.base_slots);
     // window tiles, in the format of the difference rows (FC0_MIXED: fp6 behind f16 full rows): whole rounds of workgroups at full K, the tiles of the last partial round
-    // split over K (k_bin_prefix)
+    // split over K (bin_prefix_role)
     const int dfmt = (net.fc0_fmt != FC0_F16 || net.diff_fp6) ? FC0_FP6 : FC0_F16;
     const size_t drow_u4 = dfmt == FC0_F16 ? SIBX_DROW_U4 : SIB_DROW_U4;
     const int wtiles_max = (tiles_max + SIB_BINS + 1 + 7) / 8 * 8 + 8; // (the XCD-aware tile mapping rounds an eighth of the tiles up)
@@ -4083,8 +4162,10 @@ static void recover_handed_over_fill(Net& net, const Store& S, hipStream_t st, c
         fprintf(stderr, "omok_mi355x: internal inconsistency (recovered): the round's request-list fill was handed to the sibling path, but the forward (%s) does not take it; "
                         "the list is written here instead\n", where);
     }
-    launch_fill(S, net.fill_side, net.fill_k, st);
+    if (net.scan_cnt) launch_scan(net.n, S, net.fill_side, net.fill_k, st, net.scan_evals, nullptr, 0, true); // (no k_scan ran either: request offsets, then the list)
+    else launch_fill(S, net.fill_side, net.fill_k, st);
     net.fill_in_group = net.gcnt_zeroed = false;
+    net.scan_cnt = nullptr;
 }
 // K split of the dense fc0 (plain rows, copy path).  Small batches (late plies of an episode) cannot fill the CUs with 128-sample tiles: K is split into fp32 partials
 // that a second kernel finishes, so that the workgroups fill whole waves of CUs (one workgroup per CU at a time: 144 KiB of LDS): with T tiles of 128 samples and

@@ -963,10 +963,15 @@ __global__ __launch_bounds__(64, KROUND_WPS) void k_round(Store S, RoundArgs A) 
     __shared__ float s_row[G::ROWP];
     const int g = blockIdx.x;
     const int t = A.side * S.games + g;
+    if (A.zero_ptr && g == 0) // (before anything else: the counters of the round before stay readable until here)
+        for (int i = LANE; i < A.zero_n; i += 64) A.zero_ptr[i] = 0;
     const Tree<N> T(S, t);
     const GameState gs0 = S.gs[g];
     const TreeState ts = *T.ts; // (issued with the game's state, not behind it)
-    if (!gs0.alive) return;
+    if (!gs0.alive) {
+        if (A.req_cnt && LANE == 0) A.req_cnt[g] = 0;
+        return;
+    }
     Regs R{ts.n_nodes, ts.n_tables, ts.root_n, 0u, ts.error, ts.root_w, 0ull};
 #ifdef KROUND_PROF
     unsigned long long (&kp)[8] = R.kp;
@@ -992,6 +997,7 @@ __global__ __launch_bounds__(64, KROUND_WPS) void k_round(Store S, RoundArgs A) 
         o.n_nodes = R.n_nodes; o.n_tables = R.n_tables; o.root_n = R.root_n; o.root_w = R.root_w;
         o.error = R.error; o.n_req = R.n_req;
         *T.ts = o;
+        if (A.req_cnt) A.req_cnt[g] = (int32_t)R.n_req;
         atomicAdd(S.d_bytes, R.bytes);
 #ifdef KROUND_PROF
         const unsigned int L = (unsigned int)A.round & 63u;

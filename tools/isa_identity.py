@@ -8,6 +8,7 @@ with -ffp-contract=off) and the gfx950 code objects compared per demangled symbo
   * VGPR / AGPR / SGPR counts, LDS and scratch bytes from the code object's notes,
   * for differing kernels, side by side: the counts of MFMA, global / buffer loads and stores, LDS-DMA, ds_read, ds_write and s_barrier instructions and of
     s_waitcnt by immediate.
+A kernel whose parameter list changed (another mangled name) is compared with its namesake and marked "signature changed".
 Needs hipcc and the LLVM tools of ROCm, no GPU.  Exit status 0 whatever differs: the report is for reading."""
 import collections
 import os
@@ -97,10 +98,22 @@ def main():
     for src, contract_off in FILES:
         old = kernels_of(isa_hist.compile_code_object(os.path.join(old_dir, src), "", contract_off))
         new = kernels_of(isa_hist.compile_code_object(os.path.join(new_dir, src), "", contract_off))
+        # a symbol whose parameter list changed has another mangled name: it is compared with the old symbol of the same name in front of the parameter
+        # list (template arguments included) if there is exactly one on either side, and listed as "signature changed"
+        stem = lambda k: k.split("(")[0]
+        lone_old, lone_new = [k for k in old if k not in new], [k for k in new if k not in old]
+        resigned = []
+        for k in lone_new:
+            match = [o for o in lone_old if stem(o) == stem(k)]
+            if len(match) == 1 and sum(stem(x) == stem(k) for x in lone_new) == 1:
+                old[k] = old.pop(match[0])
+                resigned.append(k)
         same = [k for k in new if k in old and new[k] == old[k]]
         differ = [k for k in new if k in old and new[k] != old[k]]
         print(f"\n{src}: old {len(old)} kernels and device functions, new {len(new)}: identical {len(same)}, differing {len(differ)}, "
-              f"only in new {len(set(new) - set(old))}, only in old {len(set(old) - set(new))}")
+              f"only in new {len(set(new) - set(old))}, only in old {len(set(old) - set(new))}, signature changed {len(resigned)}")
+        for k in resigned:
+            print(f"   signature changed: {stem(k)}")
         for k in sorted(set(new) - set(old)):
             print(f"   only in new: {k[:150]}")
         for k in sorted(set(old) - set(new)):
