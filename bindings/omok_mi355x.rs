@@ -190,6 +190,7 @@ pub mod ffi {
         pub fn omok_replay_pack_dev(e: *mut OmokEngine, dst_dev: *mut c_void, cap_records: i64) -> i64;
         pub fn omok_replay_record_bytes(e: *const OmokEngine) -> i32;
         pub fn omok_replay_augment_dev(e: *mut OmokEngine, dst_dev: *mut c_void, cap_records: i64) -> i64;
+        pub fn omok_replay_augment_records_dev(e: *mut OmokEngine, records_dev: *const c_void, n_records: i64, game_offsets: *const i64, game_lengths: *const i32, games: i32, dst_dev: *mut c_void, cap_records: i64) -> i64;
         pub fn omok_replay_augmented_game(e: *mut OmokEngine, game: i32, boards: *mut u8, turns: *mut u8, pi: *mut f32, z: *mut f32, cap_records: i32) -> c_int;
         pub fn omok_operand_row_bytes(e: *const OmokEngine) -> i64;
         pub fn omok_debug_operand_rows(e: *mut OmokEngine, first_row: i32, rows: i32, out: *mut c_void) -> c_int;

@@ -451,6 +451,19 @@ int32_t omok_replay_record_bytes(const omok_engine* e);
  * rotate_90, rotate_180, rotate_270, flip_horizontal, flip_vertical of board and policy (src/utils.rs:1-64), turn and z
  * unchanged.  Records as in omok_replay_pack_dev.  Returns the record count 6 * sum(L) (records beyond cap are dropped). */
 int64_t omok_replay_augment_dev(omok_engine* e, void* dst_dev, int64_t cap_records);
+/* The same post-processing (src/trainer.rs:207-324, src/utils.rs:1-64) on caller-held packed records -- what omok_selfplay_run_slots hands back, or
+ * what another rank's omok_replay_pack_dev gathered -- when the engine no longer holds the games.  Touches no engine state and needs no net (like
+ * omok_env_replay); e supplies board size, device and stream.  records_dev: n_records records of omok_replay_record_bytes in device memory, z as recorded at
+ * play time; game i's game_lengths[i] transitions sit in play order at records [game_offsets[i], game_offsets[i] + game_lengths[i]) (host arrays of
+ * `games`, exactly omok_selfplay_run_slots' outputs; games may lie anywhere, in any order, with gaps).  Output to dst_dev in game INDEX order, per game
+ * the L back-filled transitions, then the 5L copies: byte for byte what omok_replay_augment_dev writes for an engine holding the same games in that
+ * order (z of transition p = z of the game's LAST record, negated when L - 1 - p is odd; pad bytes zero).  Returns 6 * sum(L); records at or beyond
+ * cap_records are dropped, never written.  `games` is not bounded by the engine's games.  records_dev and dst_dev are 4-byte aligned and do not
+ * overlap.  OMOK_ERR_INVALID, with nothing enqueued and dst_dev unwritten, for a NULL pointer, cap_records < 0, games < 1, a length outside [0, N*N] (a
+ * negative one is omok_selfplay_run_slots' fill of a game that never finished; length 0 contributes nothing) or a game with a positive length whose
+ * records are not inside [0, n_records): omok_last_error names the first such game. */
+int64_t omok_replay_augment_records_dev(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* game_offsets,
+                                        const int32_t* game_lengths, int32_t games, void* dst_dev, int64_t cap_records);
 /* the same for one game into host arrays ([6L][N*N] boards / pi, [6L] turns / z); returns 6L */
 int omok_replay_augmented_game(omok_engine* e, int32_t game, uint8_t* boards, uint8_t* turns, float* pi, float* z,
                                int32_t cap_records);

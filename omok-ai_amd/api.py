@@ -273,6 +273,21 @@ class Engine:
                                           B.iptr(lengths), batch, moves.shape[1], int(upto), B.u8ptr(boards), B.iptr(status), B.iptr(played)))
         return boards, status, played
 
+    def replay_augment_records(self, records_ptr, n_records, offsets, lengths, dst_ptr, cap_records):
+        """omok_replay_augment_records_dev on caller-held packed records (run_slots' output, or another rank's gathered records): z back-fill and
+        the five augmentations of Trainer::train (src/trainer.rs:207-324) into dst_ptr, games in the order of `offsets` / `lengths` (host arrays, one
+        entry per game: first record and record count in the device buffer records_ptr of n_records records).  Both pointers are device pointers
+        (e.g. a torch uint8 tensor's data_ptr()).  Returns 6 * sum(lengths); at most cap_records records are written."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if len(offsets) != len(lengths):
+            raise ValueError(f"{len(offsets)} offsets for {len(lengths)} lengths")
+        n = B.lib().omok_replay_augment_records_dev(self.h, C.c_void_p(records_ptr), int(n_records), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    B.iptr(lengths), len(lengths), C.c_void_p(dst_ptr), int(cap_records))
+        if n < 0:
+            raise B.OmokError(int(n), B.lib().omok_last_error(self.h).decode())
+        return int(n)
+
     def encode_nn_input(self, boards, turns, mode=B.MODE_PLAYER):
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
         turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)

@@ -46,6 +46,7 @@ SYMBOLS = [
     "omok_train_gradient_count", "omok_train_backward", "omok_train_apply",
     "omok_debug_train_gradient", "omok_net_read",
     "omok_game_log_enable", "omok_game_log_read", "omok_env_replay",
+    "omok_replay_augment_records_dev",
 ]
 
 
@@ -175,6 +176,8 @@ def lib():
     L.omok_game_log_enable.argtypes = [H, C.c_int32]
     L.omok_game_log_read.argtypes = [H, C.c_int32, C.c_int32, u8p, ip, u16p, u32p, fp, u32p, fp]
     L.omok_env_replay.argtypes = [H, u8p, u16p, ip, C.c_int32, C.c_int32, C.c_int32, u8p, ip, ip]
+    L.omok_replay_augment_records_dev.argtypes = [H, C.c_void_p, C.c_int64, i64p, ip, C.c_int32, C.c_void_p, C.c_int64]
+    L.omok_replay_augment_records_dev.restype = C.c_int64
     _lib = L
     return L
 

@@ -194,6 +194,11 @@ void launch_env_place(int n, uint8_t* boards_dev, uint8_t* turns_dev, uint16_t* 
 int set_advance_lds_attribute(int n, size_t bytes);
 void launch_replay_augment(int n, const Store& S, const long long* offsets_dev, int game_first, int game_count, long long base_sub,
                            uint8_t* dst_dev, long long cap_records, hipStream_t st);
+// the same on caller-held packed records: first_dev [m + 1] = exclusive scan of the lengths of the m non-empty games, span_dev [m] = each game's
+// first source record in src_dev and first destination record in dst_dev; `transitions` = first[m] waves
+struct AugSpan { long long src, dst; };
+void launch_replay_augment_records(int n, const uint8_t* src_dev, const long long* first_dev, const AugSpan* span_dev, int m, long long transitions,
+                                   uint8_t* dst_dev, long long cap_records, hipStream_t st);
 size_t advance_lds_bytes(int cap_nodes, int cap_tables);
 
 // match episodes (omok_match_reset; tree side * G + g is evaluated by net side ^ (g >= split)): the dense list of trees of `tree_side` in S.req_ref,

@@ -2111,12 +2111,53 @@ extern "C" int64_t omok_replay_pack_dev(omok_engine* e, void* dst_dev, int64_t c
 extern "C" int64_t omok_replay_augment_dev(omok_engine* e, void* dst_dev, int64_t cap_records) {
     if (!e || !dst_dev || cap_records < 0) return OMOK_ERR_INVALID;
     if (hipSetDevice(e->cfg.device) != hipSuccess) return OMOK_ERR_HIP;
+    e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling: tools/selfplay_slots_timing.py)
     launch_replay_offsets(e->n, e->S, 6, e->d_aug_offsets, e->st);
     launch_replay_augment(e->n, e->S, e->d_aug_offsets, 0, e->cfg.games, 0, (uint8_t*)dst_dev, cap_records, e->st);
+    e->prof.end(e->st);
     long long total = 0;
     if (hipMemcpyAsync(&total, e->d_aug_offsets + e->cfg.games, 8, hipMemcpyDeviceToHost, e->st) != hipSuccess) return OMOK_ERR_HIP;
     if (sync_and_check(e, "replay_augment")) return OMOK_ERR_HIP;
     return total;
+}
+
+// the same on caller-held packed records (slots mode, records gathered from other ranks): touches no engine state, needs no net
+extern "C" int64_t omok_replay_augment_records_dev(omok_engine* e, const void* records_dev, int64_t n_records, const int64_t* game_offsets,
+                                                   const int32_t* game_lengths, int32_t games, void* dst_dev, int64_t cap_records) {
+    if (!e) return OMOK_ERR_INVALID;
+    if (games < 1) return fail(e, OMOK_ERR_INVALID, "games %d < 1", games);
+    if (!records_dev || !game_offsets || !game_lengths || !dst_dev) return fail(e, OMOK_ERR_INVALID, "replay_augment_records: NULL pointer");
+    if (n_records < 0 || cap_records < 0) return fail(e, OMOK_ERR_INVALID, "n_records %lld / cap_records %lld < 0", (long long)n_records, (long long)cap_records);
+    if (((uintptr_t)records_dev | (uintptr_t)dst_dev) & 3) return fail(e, OMOK_ERR_INVALID, "records_dev and dst_dev must be 4-byte aligned");
+    // first [m + 1] = exclusive scan of the m non-empty games' lengths, then span [m] (k_replay_augment_records); destination bases = scan of 6 L
+    std::vector<long long> first(1, 0);
+    std::vector<AugSpan> span;
+    long long total = 0;
+    for (int i = 0; i < games; ++i) {
+        const long long L = game_lengths[i], off = game_offsets[i];
+        if (L < 0 || L > e->hw)
+            return fail(e, OMOK_ERR_INVALID, "game %d: length %lld outside [0, %d]%s", i, L, e->hw, L < 0 ? " (a game that never finished?)" : "");
+        if (L == 0) continue;
+        if (off < 0 || off > n_records - L)
+            return fail(e, OMOK_ERR_INVALID, "game %d: offset %lld + length %lld outside [0, n_records = %lld]", i, off, L, (long long)n_records);
+        span.push_back({off, 6 * total});
+        total += L;
+        first.push_back(total);
+    }
+    if (total == 0) return 0;
+    ENTER(e);
+    const size_t m = span.size(), first_bytes = (m + 1) * sizeof(long long);
+    uint8_t* d = nullptr;
+    if (hipMalloc((void**)&d, first_bytes + m * sizeof(AugSpan)) != hipSuccess) return fail(e, OMOK_ERR_HIP, "replay_augment_records: device allocation failed");
+    hipMemcpyAsync(d, first.data(), first_bytes, hipMemcpyHostToDevice, e->st);
+    hipMemcpyAsync(d + first_bytes, span.data(), m * sizeof(AugSpan), hipMemcpyHostToDevice, e->st);
+    e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling: tools/selfplay_slots_timing.py)
+    launch_replay_augment_records(e->n, (const uint8_t*)records_dev, (const long long*)d, (const AugSpan*)(d + first_bytes), (int)m, total,
+                                  (uint8_t*)dst_dev, cap_records, e->st);
+    e->prof.end(e->st);
+    const int rc = sync_and_check(e, "replay_augment_records");
+    hipFree(d);
+    return rc ? OMOK_ERR_HIP : 6 * total;
 }
 
 extern "C" int omok_replay_augmented_game(omok_engine* e, int32_t game, uint8_t* boards, uint8_t* turns, float* pi, float* z, int32_t cap_records) {

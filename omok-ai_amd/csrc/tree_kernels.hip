@@ -2639,11 +2639,16 @@ __global__ __launch_bounds__(256) void k_encode_boards(const uint8_t* __restrict
 // replay tuples packed for an RCCL gather: board u8[HW], turn u8, pad (zero) to 4, pi f32[HW], z f32; games in id order
 // (offsets = exclusive scan of the transition counts), transitions in play order: the packed buffer is deterministic
 template <int N>
+struct Rec { // the packed record (omok_replay_record_bytes): pi starts at byte BRD, z is the last dword
+    static constexpr int BRD = (Geo<N>::HW + 1 + 3) / 4 * 4, BYTES = BRD + 4 * Geo<N>::HW + 4;
+};
+
+template <int N>
 __global__ __launch_bounds__(64) void k_replay_pack(Store S, const long long* __restrict__ offsets, uint8_t* __restrict__ dst, long long cap,
                                                     const uint8_t* __restrict__ mask) {
     using G = Geo<N>;
     constexpr int NW = G::NW, ROWP = G::ROWP;
-    constexpr int BRD = (G::HW + 1 + 3) / 4 * 4, REC = BRD + 4 * G::HW + 4;
+    constexpr int BRD = Rec<N>::BRD, REC = Rec<N>::BYTES;
     const int g = blockIdx.x;
     const int lane = LANE;
     if (mask && !mask[g]) return; // (harvest: only the slots k_harvest_scan picked)
@@ -2704,7 +2709,7 @@ __global__ __launch_bounds__(64) void k_replay_augment(Store S, const long long*
                                                        uint8_t* __restrict__ dst, long long cap) {
     using G = Geo<N>;
     constexpr int NW = G::NW, ROWP = G::ROWP;
-    constexpr int BRD = (G::HW + 1 + 3) / 4 * 4, REC = BRD + 4 * G::HW + 4;
+    constexpr int BRD = Rec<N>::BRD, REC = Rec<N>::BYTES;
     const int g = game_first + blockIdx.y; // one wave per transition: grid = (HW plies, games)
     const int lane = LANE;
     const int L = S.gs[g].rp_len < G::HW ? S.gs[g].rp_len : G::HW;
@@ -2737,6 +2742,57 @@ __global__ __launch_bounds__(64) void k_replay_augment(Store S, const long long*
             }
             if (lane < BRD - G::HW) r[G::HW + lane] = lane == 0 ? turn : (uint8_t)0; // env.turn is cloned unchanged (:224); pad bytes zero
             if (lane == 0) ((float*)(r + BRD))[G::HW] = z;
+        }
+    }
+}
+
+// The same post-processing on caller-held packed records (omok_replay_augment_records_dev: the records of slots mode or of another rank, whose games
+// the engine no longer holds), one wave per SOURCE transition.  The wave stages its record in LDS once (whole dwords: the record size is a multiple
+// of 4) and writes its six destination records from there, every one as REC / 4 coalesced dword stores; a board dword is put together from four
+// permuted LDS bytes, a pi dword is one permuted LDS read.  first [m + 1] = exclusive scan of the lengths of the m non-empty games in game-index
+// order (built and uploaded by the host, which holds the lengths); span[i] = where game i's records come from and go.  The wave of transition t
+// finds the one i with first[i] <= t < first[i + 1] by bisection, so the launch shape decides nothing about the output.
+template <int N>
+__global__ __launch_bounds__(64) void k_replay_augment_records(const uint8_t* __restrict__ src, const long long* __restrict__ first,
+                                                               const AugSpan* __restrict__ span, int m, long long t0, uint8_t* __restrict__ dst,
+                                                               long long cap) {
+    using G = Geo<N>;
+    constexpr int BRD = Rec<N>::BRD, REC = Rec<N>::BYTES, BW = BRD / 4, RW = REC / 4;
+    __shared__ uint32_t s_rec[RW];
+    const int lane = LANE;
+    const long long t = t0 + blockIdx.x; // (the grid covers exactly the transitions [t0, t0 + gridDim.x) < first[m])
+    int lo = 0, hi = m - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (first[mid] <= t) lo = mid;
+        else hi = mid - 1;
+    }
+    const int L = (int)(first[lo + 1] - first[lo]), p = (int)(t - first[lo]);
+    const AugSpan sp = span[lo];
+    const uint32_t* rs = (const uint32_t*)(src + (size_t)(sp.src + p) * REC);
+    for (int d = lane; d < RW; d += 64) s_rec[d] = rs[d];
+    uint32_t z = ((const uint32_t*)(src + (size_t)(sp.src + L - 1) * REC))[RW - 1]; // z of the game's last record, as bits
+    if ((L - 1 - p) & 1) z ^= 0x80000000u; // transition.z = z; z = -z; (:211-214), incl. the sign of zero
+    __syncthreads();
+    const uint8_t* sb = (const uint8_t*)s_rec;
+    for (int k = 0; k < 6; ++k) {
+        const long long idx = k == 0 ? sp.dst + p : sp.dst + L + 5LL * p + (k - 1);
+        if (idx >= cap) continue;
+        uint32_t* r = (uint32_t*)(dst + (size_t)idx * REC);
+        for (int d = lane; d < RW; d += 64) {
+            uint32_t v = z;
+            if (d < BW) { // cells 4d .. 4d + 3, then the turn (cloned unchanged, :224) and zero pad bytes
+                v = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int a = 4 * d + c;
+                    const uint32_t b = a < G::HW ? sb[aug_src<N>(k, a)] : (a == G::HW ? sb[G::HW] : 0);
+                    v |= b << (8 * c);
+                }
+            } else if (d < BW + G::HW) {
+                v = s_rec[BW + aug_src<N>(k, d - BW)];
+            }
+            r[d] = v;
         }
     }
 }
@@ -2936,6 +2992,14 @@ void launch_replay_augment(int n, const Store& S, const long long* offsets, int 
     if (game_count <= 0) return;
     DISPATCH_N(n, (k_replay_augment<9><<<dim3(81, game_count), 64, 0, st>>>(S, offsets, game_first, base_sub, dst, cap)),
                (k_replay_augment<15><<<dim3(225, game_count), 64, 0, st>>>(S, offsets, game_first, base_sub, dst, cap)));
+}
+void launch_replay_augment_records(int n, const uint8_t* src, const long long* first, const AugSpan* span, int m, long long transitions, uint8_t* dst,
+                                   long long cap, hipStream_t st) {
+    for (long long t0 = 0; t0 < transitions; t0 += 1LL << 30) { // gridDim.x < 2^31: a wave per transition, 2^30 of them per launch
+        const unsigned grid = (unsigned)std::min(transitions - t0, 1LL << 30);
+        DISPATCH_N(n, (k_replay_augment_records<9><<<grid, 64, 0, st>>>(src, first, span, m, t0, dst, cap)),
+                   (k_replay_augment_records<15><<<grid, 64, 0, st>>>(src, first, span, m, t0, dst, cap)));
+    }
 }
 void launch_replay_pack(int n, const Store& S, const long long* offsets, uint8_t* dst, long long cap, hipStream_t st) {
     DISPATCH_N(n, (k_replay_pack<9><<<S.games, 64, 0, st>>>(S, offsets, dst, cap, nullptr)),

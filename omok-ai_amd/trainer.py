@@ -9,6 +9,10 @@ src/config.rs:83-110 (episode_count 50, evaluate_count 600, test_evaluate_count 
 Multi-GPU: every rank plays its own `episode_count` games (global ids rank*episode_count + g) and trains data-parallel
 (gradients averaged per step: by the torch phase's all-reduce, or by the engine in rank order with train_backend="hip_dp"), so all ranks
 hold identical weights after every iteration.
+Parameters.selfplay_slots = S > 0 plays the iteration's `episode_count` games in slots mode (omok_selfplay_run_slots) on an engine of
+min(S, episode_count) games: a slot whose game is over takes the next game index, so the trees resident in memory no longer grow with
+episode_count.  The raw records it hands back are back-filled and augmented on the device by omok_replay_augment_records_dev into the
+game-index order the episode path produces; everything after that is the same code.  0 (the default) is the episode path.
 """
 import os
 from dataclasses import dataclass
@@ -36,6 +40,7 @@ class Parameters:  # src/config.rs:83-110
     test_evaluate_count: int = 800  # simulations per move of the net in the evaluation games (src/config.rs:31,103)
     evaluate_every: int = 10        # `iteration % 10 == 0` (src/trainer.rs:380)
     evaluate_games: int = 100       # play_against_naive_player(100, ..) (:384)
+    selfplay_slots: int = 0         # 0 = one episode of episode_count games (omok_selfplay_run); S > 0 = the same games in slots mode on min(S, episode_count) slots (omok_selfplay_run_slots; no reference counterpart)
     train_backend: str = "torch"    # the training phase (:329-357): "torch" = autograd (train.py), "hip" = the engine's native step (omok_train_run, one rank), "hip_dp" = the native step in two halves with the ranks' gradients averaged in between (any world size)
 
 
@@ -49,6 +54,10 @@ class Trainer:
         if self.p.train_backend == "hip" and self.world > 1:
             raise RuntimeError("train_backend=\"hip\" runs on one rank only: the native step does not average gradients over ranks "
                                f"(world size {self.world}); use train_backend=\"hip_dp\" or \"torch\" for data-parallel training")
+        if self.p.selfplay_slots < 0:
+            raise ValueError(f"selfplay_slots {self.p.selfplay_slots}: expected 0 (episode) or a number of slots > 0")
+        self.slots = min(self.p.selfplay_slots, self.p.episode_count)  # 0 = the episode path
+        self._raw = None  # slots mode: the raw records of an iteration, episode_count * N * N at the most (allocated by the first iteration)
         self.device = f"cuda:{self.local_rank}"
         self.save_dir = save_dir
         self.precision_rows = precision_rows  # independent check of the net outputs after every weight update (0 = off)
@@ -58,7 +67,7 @@ class Trainer:
         self.last_evaluation = None  # result of the last games against the naive player (evaluate)
         sims = -(-self.p.evaluate_count // self.p.evaluate_batch_size) * self.p.evaluate_batch_size
         max_nodes = max_nodes or min(16384, 4 * sims + 1024)
-        self.engine = api.Engine(board_size=board_size, games=self.p.episode_count, max_nodes=max_nodes,
+        self.engine = api.Engine(board_size=board_size, games=self.slots or self.p.episode_count, max_nodes=max_nodes,
                                  max_tables=max_tables or max(256, max_nodes // 4), max_batch_k=self.p.evaluate_batch_size,
                                  device=self.local_rank, seed=seed, game_offset=dist.game_offset(self.rank, self.p.episode_count))
         path = os.path.join(save_dir, self.p.model_name)
@@ -124,12 +133,22 @@ class Trainer:
             self.iteration += 1
             self.engine.reset_stats()  # (per-iteration counters in the log line)
             self.selfplay.reset()  # fresh agents; the engine's replay buffer is cleared with them (:77-93)
-            stats = self.selfplay.run(p.evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha, p.temperature,
-                                      p.temperature_threshold, 0)
-            _, _, plies = self.selfplay.game_info()
-            total = 6 * int(plies.sum())
-            buf = torch.empty(max(total, 1) * rec, dtype=torch.uint8, device=self.device)
-            got = self.selfplay.replay_augment_into(buf.data_ptr(), total)
+            if self.slots:  # the same games by index (keyed by game_offset + index) on fewer slots; raw records in completion order
+                cap = p.episode_count * self.n * self.n
+                if self._raw is None:
+                    self._raw = torch.empty(cap * rec, dtype=torch.uint8, device=self.device)
+                stats, n_raw, offsets, lengths, _ = self.selfplay.run_slots(p.episode_count, p.evaluate_count, p.evaluate_batch_size, self._raw.data_ptr(), cap,
+                                                                            p.epsilon, p.alpha, p.temperature, p.temperature_threshold)
+                total = 6 * int(lengths.sum())
+                buf = torch.empty(max(total, 1) * rec, dtype=torch.uint8, device=self.device)
+                got = self.engine.replay_augment_records(self._raw.data_ptr(), n_raw, offsets, lengths, buf.data_ptr(), total)
+            else:
+                stats = self.selfplay.run(p.evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha, p.temperature,
+                                          p.temperature_threshold, 0)
+                _, _, plies = self.selfplay.game_info()
+                total = 6 * int(plies.sum())
+                buf = torch.empty(max(total, 1) * rec, dtype=torch.uint8, device=self.device)
+                got = self.selfplay.replay_augment_into(buf.data_ptr(), total)
             records = buf[: got * rec].reshape(got, rec)
             if got > p.replay_memory_size:  # pop_front until the memory fits (:326-328)
                 records = records[got - p.replay_memory_size:]
