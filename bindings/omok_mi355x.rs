@@ -152,6 +152,8 @@ pub mod ffi {
         pub fn omok_opponent_actions(e: *mut OmokEngine, kind: i32, actions: *mut i32) -> c_int;
         pub fn omok_versus_run(e: *mut OmokEngine, kind: i32, opponent_side: i32, count: i32, batch_size: i32, epsilon: f32, alpha: f32, max_plies: i32, results: *mut i32, stats: *mut f64) -> c_int;
         pub fn omok_selfplay_run_slots(e: *mut OmokEngine, total_games: i32, count: i32, batch_size: i32, epsilon: f32, alpha: f32, temperature: f32, threshold: i32, records_dev: *mut c_void, cap_records: i64, game_offsets: *mut i64, game_lengths: *mut i32, game_status: *mut i32, n_records: *mut i64, stats: *mut f64) -> c_int;
+        pub fn omok_selfplay_run_slots_logged(e: *mut OmokEngine, total_games: i32, count: i32, batch_size: i32, epsilon: f32, alpha: f32, temperature: f32, threshold: i32, records_dev: *mut c_void, cap_records: i64, log_dev: *mut c_void, game_offsets: *mut i64, game_lengths: *mut i32, game_status: *mut i32, n_records: *mut i64, stats: *mut f64) -> c_int;
+        pub fn omok_game_log_entry_bytes() -> i32;
         pub fn omok_round_generate(e: *mut OmokEngine, round: i32, batch_size: i32, epsilon: f32, alpha: f32, n_requests: *mut i32) -> c_int;
         pub fn omok_round_inputs(e: *mut OmokEngine, inputs: *mut f32) -> c_int;
         pub fn omok_round_eval(e: *mut OmokEngine) -> c_int;

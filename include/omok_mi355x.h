@@ -310,6 +310,21 @@ int omok_versus_run(omok_engine* e, int32_t kind, int32_t opponent_side, int32_t
 int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int32_t count, int32_t batch_size, float epsilon, float alpha,
                             float temperature, int32_t threshold, void* records_dev, int64_t cap_records, int64_t* game_offsets,
                             int32_t* game_lengths, int32_t* game_status, int64_t* n_records, double* stats);
+/* omok_selfplay_run_slots with the move log (omok_game_log_enable) packed out beside the records: the same games, the same records, the same
+ * stats, and for every record the move that followed it.  log_dev = device memory of cap_records entries of omok_game_log_entry_bytes (20);
+ * entry game_offsets[i] + p is move p of game index i, beside record game_offsets[i] + p (in slots mode every move is sampled, so a game has
+ * as many records as moves).  Entry, little-endian, by byte offset: 0 u32 root_n, 4 f32 root_w, 8 u32 child_n, 12 f32 child_w, 16 u16 move
+ * (cell | OMOK_MOVE_EXTERNAL, as omok_game_log_read), 18 u16 zero; the values are those omok_game_log_read returns for the same game of an
+ * episode of total_games games.  Needs the move log on and a reset since (OMOK_ERR_STATE otherwise: omok_game_log_enable, then
+ * omok_selfplay_reset); log_dev == NULL is OMOK_ERR_INVALID; every other check is omok_selfplay_run_slots', and all of them precede the
+ * first allocation or write.  The engine's per-slot log is the staging area: afterwards it describes no game, and omok_game_log_read returns
+ * OMOK_ERR_STATE until the next reset starts an ordinary log.  OMOK_ERR_OVERFLOW with *n_records = the count needed when the games do not
+ * fit cap_records: neither buffer is written beyond it. */
+int omok_selfplay_run_slots_logged(omok_engine* e, int32_t total_games, int32_t count, int32_t batch_size, float epsilon, float alpha,
+                                   float temperature, int32_t threshold, void* records_dev, int64_t cap_records, void* log_dev,
+                                   int64_t* game_offsets, int32_t* game_lengths, int32_t* game_status, int64_t* n_records, double* stats);
+/* bytes of one entry of omok_selfplay_run_slots_logged's log_dev: 20 */
+int32_t omok_game_log_entry_bytes(void);
 
 /* step-wise form of execute() for parity tests: generate -> (eval | inject) -> scatter */
 int omok_round_generate(omok_engine* e, int32_t round, int32_t batch_size, float epsilon, float alpha,
@@ -422,7 +437,7 @@ int omok_replay_game(omok_engine* e, int32_t game, uint8_t* boards, uint8_t* tur
 /* 1 = keep a move log from the next reset on (allocates 19 B per game and cell on first use), 0 = stop and free.  Changes no result.  Every
  * successful omok_selfplay_reset(_from) / omok_match_reset(_from) sets the log's start (its boards, or Environment::new(), environment/src/lib.rs:73-79) and the lengths to 0; a rejected
  * reset and a rejected omok_play_actions leave it as it was.  omok_selfplay_run_slots returns OMOK_ERR_STATE while the log is on (its games
- * leave their slots). */
+ * leave their slots: omok_selfplay_run_slots_logged packs their moves out with their records). */
 int omok_game_log_enable(omok_engine* e, int32_t enabled);
 /* games [first_game, first_game + games): start_boards [games][N*N] Stone bytes, lengths [games] = moves since the reset (the game's plies - the
  * ply the episode started at), moves [games][N*N] (entries at and beyond the length read 0xFFFF), root_n, root_w, child_n, child_w [games][N*N]

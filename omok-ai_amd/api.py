@@ -477,7 +477,7 @@ class SelfPlay:
 
     def game_log(self, on=True):
         """omok_game_log_enable: True = keep a move log from the next reset on (19 B per game and cell, allocated now), False = stop and free.
-        Changes no result; run_slots refuses while it is on."""
+        Changes no result; run_slots refuses while it is on (run_slots_logged is the slots-mode run that keeps the moves)."""
         self._chk(B.lib().omok_game_log_enable(self.h, int(bool(on))))
 
     def game_records(self, first_game=0, games=None, meta=None):
@@ -553,6 +553,37 @@ class SelfPlay:
                                                   ln.ctypes.data_as(C.POINTER(C.c_int32)), stt.ctypes.data_as(C.POINTER(C.c_int32)),
                                                   C.byref(n), s))
         return dict(zip(B.STAT_NAMES, list(s))), int(n.value), off, ln, stt
+
+    def run_slots_logged(self, total_games, count, batch_size, records_ptr, cap_records, log_ptr, epsilon=0.25, alpha=0.03, temperature=1.0, threshold=30):
+        """run_slots with the move log packed out beside the records (omok_selfplay_run_slots_logged; game_log(True) and a reset first):
+        `log_ptr` = device buffer of cap_records x 20 B, entry offsets[i] + p = move p of game index i (slots_game_records reads it).
+        Returns what run_slots returns; afterwards game_records() is refused until the next reset."""
+        s = (C.c_double * len(B.STAT_NAMES))()
+        off = np.zeros(total_games, dtype=np.int64)
+        ln = np.zeros(total_games, dtype=np.int32)
+        stt = np.zeros(total_games, dtype=np.int32)
+        n = C.c_int64()
+        self._chk(B.lib().omok_selfplay_run_slots_logged(self.h, total_games, count, batch_size, epsilon, alpha, temperature, threshold,
+                                                         C.c_void_p(records_ptr), cap_records, C.c_void_p(log_ptr), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                         ln.ctypes.data_as(C.POINTER(C.c_int32)), stt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         C.byref(n), s))
+        return dict(zip(B.STAT_NAMES, list(s))), int(n.value), off, ln, stt
+
+    def slots_game_records(self, log, n_records, offsets, lengths, status, meta=None):
+        """the games of a run_slots_logged as a records.GameRecords in game-index order: `log` = the log buffer (a torch uint8 tensor on
+        the device, or its device pointer), n_records / offsets / lengths / status = what the run returned.  One device-to-host copy."""
+        import torch
+        from . import records as R
+        nbytes = int(n_records) * R.ENTRY_BYTES
+        if isinstance(log, torch.Tensor):
+            host = log.reshape(-1)[:nbytes].cpu().numpy()
+        else:
+            host = np.empty(nbytes, dtype=np.uint8)
+            if nbytes:
+                err = C.CDLL("libamdhip64.so").hipMemcpy(C.c_void_p(host.ctypes.data), C.c_void_p(int(log)), C.c_size_t(nbytes), 2)  # 2 = hipMemcpyDeviceToHost
+                if int(err) != 0:
+                    raise RuntimeError(f"slots_game_records: the device-to-host copy of {nbytes} bytes failed ({err})")
+        return R.GameRecords.from_packed(self.n, host.reshape(int(n_records), R.ENTRY_BYTES), offsets, lengths, status, meta)
 
     # ---- step-wise (parity tests) -----------------------------------------------------------
     def round_generate(self, rnd, batch_size, epsilon=0.25, alpha=0.03):

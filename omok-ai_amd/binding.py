@@ -47,6 +47,7 @@ SYMBOLS = [
     "omok_debug_train_gradient", "omok_net_read",
     "omok_game_log_enable", "omok_game_log_read", "omok_env_replay",
     "omok_replay_augment_records_dev",
+    "omok_selfplay_run_slots_logged", "omok_game_log_entry_bytes",
 ]
 
 
@@ -131,6 +132,10 @@ def lib():
                                     C.POINTER(C.c_double)]
     L.omok_selfplay_run_slots.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int64,
                                           C.POINTER(C.c_int64), ip, ip, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.omok_selfplay_run_slots_logged.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.POINTER(C.c_int64), ip, ip, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.omok_game_log_entry_bytes.argtypes = []
+    L.omok_game_log_entry_bytes.restype = C.c_int32
     L.omok_round_generate.argtypes = [H, C.c_int32, C.c_int32, C.c_float, C.c_float, ip]
     L.omok_round_inputs.argtypes = [H, fp]
     L.omok_round_eval.argtypes = [H]

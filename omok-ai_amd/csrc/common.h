@@ -147,6 +147,12 @@ void launch_root_stats(const Store& S, int side, uint32_t* n_dev, float* w_dev, 
 struct SlotMeta { long long offset; int32_t len; int32_t status; }; // per game index: first record, records, final GameStatus
 void launch_harvest(int n, const Store& S, uint8_t* mask_dev /*[G]*/, long long* slot_off_dev /*[G]*/, long long* out_count_dev, SlotMeta* meta_dev,
                     uint8_t* dst_dev, long long cap_records, hipStream_t st);
+// omok_selfplay_run_slots_logged, directly after launch_harvest: log rows [0, len) of the slots its scan picked -> entries slot_off[g] + i of
+// log_dst_dev (LOG_ENTRY_BYTES each, little-endian: root_n u32 at byte 0, root_w f32 at 4, child_n u32 at 8, child_w f32 at 12, move u16 at
+// 16, zero u16 at 18), beside the records of the same indices; entries at or beyond cap_records are not written
+constexpr int LOG_ENTRY_BYTES = 20;
+void launch_harvest_log(int n, const Store& S, const GameLog& L, const uint8_t* mask_dev, const long long* slot_off_dev, uint8_t* log_dst_dev,
+                        long long cap_records, hipStream_t st);
 void launch_refill(int n, const Store& S, const float* root_policy_dev, int32_t* next_gid_dev, int total_games, int32_t* new_gid_dev /*[G]*/, hipStream_t st);
 void launch_round(int n, const Store& S, const RoundArgs& a, hipStream_t st);
 // evals_dev[0] += the round's requests; zero_ptr[0 .. zero_n) = 0 (counters the round's forward expects zeroed); fill = false: the dense

@@ -1358,9 +1358,13 @@ extern "C" int omok_selfplay_run(omok_engine* e, int32_t count, int32_t batch_si
 // is over takes the next index instead of idling until the longest game of the episode ends (the last 40 % of an episode's rounds
 // hold < 10 % of its rows).  Games start on even engine plies only (one `side` per ply: a slot may wait one ply), finished games'
 // transitions are packed out (k_replay_pack records) before their slot is reused.
-extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int32_t count, int32_t batch_size, float epsilon, float alpha,
-                                       float temperature, int32_t threshold, void* records_dev, int64_t cap_records, int64_t* game_offsets,
-                                       int32_t* game_lengths, int32_t* game_status, int64_t* n_records, double* stats) {
+// Both entry points: `logged` = omok_selfplay_run_slots_logged, which also packs the engine's per-slot move log (the staging area
+// enqueue_log_move fills as in any episode: a refilled slot starts at plies = 0 on an even engine ply, so entry gs.plies of the tree of
+// ply & 1 is the game's own move number and side) out to log_dev with every harvest.  Without it the launches are the ones they were.
+static int run_slots(omok_engine* e, bool logged, int32_t total_games, int32_t count, int32_t batch_size, float epsilon, float alpha, float temperature,
+                     int32_t threshold, void* records_dev, int64_t cap_records, void* log_dev, int64_t* game_offsets, int32_t* game_lengths,
+                     int32_t* game_status, int64_t* n_records, double* stats) {
+    const char* who = logged ? "omok_selfplay_run_slots_logged" : "omok_selfplay_run_slots";
     if (!e) return OMOK_ERR_INVALID;
     if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
     if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
@@ -1368,11 +1372,17 @@ extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int3
     const int G = e->cfg.games;
     if (total_games < G) return fail(e, OMOK_ERR_INVALID, "total_games (%d) must be >= the engine's game slots (%d)", total_games, G);
     if (!records_dev || cap_records < 1) return fail(e, OMOK_ERR_INVALID, "records buffer required (omok_replay_record_bytes per record)");
-    if (no_match(e, "omok_selfplay_run_slots")) return OMOK_ERR_STATE;
-    if (e->start_ply != 0) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots after omok_selfplay_reset_from: refilled slots would start from the empty board");
-    if (e->ply != 0) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots starts from a fresh omok_selfplay_reset (ply %d)", e->ply);
-    if (e->log_on) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots with the move log on: its games leave their slots (omok_game_log_enable(e, 0) first)");
+    if (logged && !log_dev) return fail(e, OMOK_ERR_INVALID, "log buffer required (cap_records entries of omok_game_log_entry_bytes)");
+    if (no_match(e, who)) return OMOK_ERR_STATE;
+    if (e->start_ply != 0) return fail(e, OMOK_ERR_STATE, "%s after omok_selfplay_reset_from: refilled slots would start from the empty board", who);
+    if (e->ply != 0) return fail(e, OMOK_ERR_STATE, "%s starts from a fresh omok_selfplay_reset (ply %d)", who, e->ply);
+    if (!logged && e->log_on)
+        return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots with the move log on: its games leave their slots (omok_selfplay_run_slots_logged packs their moves out, or omok_game_log_enable(e, 0) first)");
+    if (logged && !e->log_on) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots_logged needs the move log (omok_game_log_enable(e, 1), then the reset)");
+    if (logged && !e->log_started) return fail(e, OMOK_ERR_STATE, "omok_selfplay_run_slots_logged: no reset since the move log was enabled (omok_game_log_enable, then omok_selfplay_reset)");
     ENTER(e);
+    // a slot's rows hold one game after another: once the run has begun the per-slot log describes no game, whatever way the run ends
+    struct LogEnds { omok_engine* e; bool on; ~LogEnds() { if (on) e->log_started = false; } } log_ends{e, logged};
     uint8_t* d_mask = nullptr;
     long long *d_slot_off = nullptr, *d_out = nullptr;
     int32_t *d_next = nullptr, *d_new = nullptr;
@@ -1399,6 +1409,7 @@ extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int3
         e->ply += 1;
         e->prof.begin(PC_PLY, e->st);
         launch_harvest(e->n, e->S, d_mask, d_slot_off, d_out, d_meta, (uint8_t*)records_dev, cap_records, e->st);
+        if (logged) launch_harvest_log(e->n, e->S, e->log, d_mask, d_slot_off, (uint8_t*)log_dev, cap_records, e->st);
         if ((e->ply & 1) == 0) launch_refill(e->n, e->S, e->d_root_policy, d_next, total_games, d_new, e->st);
         invalidate_nets(e);
         e->prof.end(e->st);
@@ -1436,6 +1447,22 @@ extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int3
     if (stats) return omok_get_stats(e, stats);
     return OMOK_OK;
 }
+
+extern "C" int omok_selfplay_run_slots(omok_engine* e, int32_t total_games, int32_t count, int32_t batch_size, float epsilon, float alpha,
+                                       float temperature, int32_t threshold, void* records_dev, int64_t cap_records, int64_t* game_offsets,
+                                       int32_t* game_lengths, int32_t* game_status, int64_t* n_records, double* stats) {
+    return run_slots(e, false, total_games, count, batch_size, epsilon, alpha, temperature, threshold, records_dev, cap_records, nullptr, game_offsets,
+                     game_lengths, game_status, n_records, stats);
+}
+
+extern "C" int omok_selfplay_run_slots_logged(omok_engine* e, int32_t total_games, int32_t count, int32_t batch_size, float epsilon, float alpha,
+                                              float temperature, int32_t threshold, void* records_dev, int64_t cap_records, void* log_dev,
+                                              int64_t* game_offsets, int32_t* game_lengths, int32_t* game_status, int64_t* n_records, double* stats) {
+    return run_slots(e, true, total_games, count, batch_size, epsilon, alpha, temperature, threshold, records_dev, cap_records, log_dev, game_offsets,
+                     game_lengths, game_status, n_records, stats);
+}
+
+extern "C" int32_t omok_game_log_entry_bytes(void) { return LOG_ENTRY_BYTES; }
 
 extern "C" int omok_set_episode(omok_engine* e, uint64_t episode) {
     if (!e) return OMOK_ERR_INVALID;

@@ -2672,6 +2672,36 @@ __global__ __launch_bounds__(64) void k_replay_pack(Store S, const long long* __
     }
 }
 
+// k_harvest_log: the move log of the slots k_harvest_scan picked, packed out beside their records (omok_selfplay_run_slots_logged).  In slots
+// mode every move is sampled, so a game's record count (rp_len) is its move count (plies) and its slot's log rows [0, len) hold exactly the
+// moves of records [0, len): entry slot_off[g] + i of dst is the move of record slot_off[g] + i.  len = min(rp_len, HW) is the length the scan
+// summed, so the ranges of two slots cannot overlap.  Entry = 20 B: root_n u32, root_w f32, child_n u32, child_w f32, move u16, zero u16 (the
+// floats travel as their words).  Workgroup = one wave = one slot, lane = entry (64 at a time: every array is read coalesced); an entry at
+// or beyond cap is dropped, as k_replay_pack drops its record.
+template <int N>
+__global__ __launch_bounds__(64) void k_harvest_log(Store S, GameLog L, const uint8_t* __restrict__ mask, const long long* __restrict__ slot_off,
+                                                    uint8_t* __restrict__ dst, long long cap) {
+    using G = Geo<N>;
+    const int g = blockIdx.x;
+    const int lane = LANE;
+    if (!mask[g]) return;
+    const int len = S.gs[g].rp_len < G::HW ? S.gs[g].rp_len : G::HW;
+    const long long base = slot_off[g];
+    const uint32_t *root_w = (const uint32_t*)L.root_w, *child_w = (const uint32_t*)L.child_w;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int i = j * 64 + lane;
+        if (i >= len || base + i >= cap) continue;
+        const size_t o = (size_t)g * G::HW + i;
+        uint32_t* r = (uint32_t*)(dst + (size_t)(base + i) * LOG_ENTRY_BYTES);
+        r[0] = L.root_n[o];
+        r[1] = root_w[o];
+        r[2] = L.child_n[o];
+        r[3] = child_w[o];
+        r[4] = (uint32_t)L.move[o]; // bytes 18-19 = 0
+    }
+}
+
 // Replay post-processing of Trainer::train (src/trainer.rs:207-324) on the device, one wave per transition:
 //   z back-fill: walking the game backwards from its last transition, z alternates sign (:209-214);
 //   five augmented copies per transition, in the reference's order rotate_90, rotate_180, rotate_270, flip_horizontal,
@@ -3009,6 +3039,9 @@ void launch_harvest(int n, const Store& S, uint8_t* mask, long long* slot_off, l
                     hipStream_t st) {
     DISPATCH_N(n, (k_harvest_scan<9><<<1, 1024, 0, st>>>(S, mask, slot_off, out_count, meta)), (k_harvest_scan<15><<<1, 1024, 0, st>>>(S, mask, slot_off, out_count, meta)));
     DISPATCH_N(n, (k_replay_pack<9><<<S.games, 64, 0, st>>>(S, slot_off, dst, cap, mask)), (k_replay_pack<15><<<S.games, 64, 0, st>>>(S, slot_off, dst, cap, mask)));
+}
+void launch_harvest_log(int n, const Store& S, const GameLog& L, const uint8_t* mask, const long long* slot_off, uint8_t* dst, long long cap, hipStream_t st) {
+    DISPATCH_N(n, (k_harvest_log<9><<<S.games, 64, 0, st>>>(S, L, mask, slot_off, dst, cap)), (k_harvest_log<15><<<S.games, 64, 0, st>>>(S, L, mask, slot_off, dst, cap)));
 }
 void launch_match_split(const Store& S, int tree_side, int split, uint32_t* ref2, uint32_t* aux2, int32_t* cnt, unsigned long long* evals, int max_rows,
                         hipStream_t st) {

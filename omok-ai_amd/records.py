@@ -15,6 +15,7 @@ import numpy as np
 
 CELL_MASK, EXTERNAL = 0xFF, 0x100  # OMOK_MOVE_CELL, OMOK_MOVE_EXTERNAL
 STATUS_NAMES = {0: "in progress", 1: "draw", 2: "black wins", 3: "white wins"}
+ENTRY_BYTES = 20  # omok_game_log_entry_bytes: root_n u32, root_w f32, child_n u32, child_w f32, move u16, zero u16 (little-endian)
 _ARRAYS = ("start_boards", "lengths", "cells", "external", "root_n", "root_w", "child_n", "child_w", "status", "plies")
 
 
@@ -47,6 +48,47 @@ class GameRecords:
         cells = np.where(played, (moves & CELL_MASK).astype(np.int16), np.int16(-1))
         external = played & ((moves & EXTERNAL) != 0)
         return cls(n, start_boards, lengths, cells, external, root_n, root_w, child_n, child_w, status, plies, meta)
+
+    @classmethod
+    def from_packed(cls, n, entries, offsets, lengths, status, meta=None):
+        """from the packed move log of a slots-mode run (omok_selfplay_run_slots_logged): entries uint8 [n_records][20], entry offsets[i] + p =
+        move p of game index i (lengths[i] of them; the games may lie in any order, with gaps), status [games].  Games in game-index order,
+        start boards empty, plies = lengths; beyond a game's length the rows read as omok_game_log_read leaves them (0xFFFF / 0).  No engine.
+        ValueError for a length outside [0, HW], a game that reaches beyond the buffer, or a non-zero pad."""
+        hw = int(n) * int(n)
+        entries = np.ascontiguousarray(entries, dtype=np.uint8)
+        if entries.ndim != 2 or entries.shape[1] != ENTRY_BYTES:
+            raise ValueError(f"entries of shape {entries.shape}: expected [n_records, {ENTRY_BYTES}]")
+        offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        lengths = np.asarray(lengths, dtype=np.int32).reshape(-1)
+        status = np.asarray(status).reshape(-1)
+        g = len(lengths)
+        if len(offsets) != g or len(status) != g:
+            raise ValueError(f"{len(offsets)} offsets, {g} lengths, {len(status)} status values")
+        if g and (lengths.min() < 0 or lengths.max() > hw):
+            bad = int(np.flatnonzero((lengths < 0) | (lengths > hw))[0])
+            raise ValueError(f"game {bad}: length {int(lengths[bad])} outside [0, {hw}]")
+        played = np.arange(hw)[None, :] < lengths[:, None]
+        beyond = (lengths > 0) & ((offsets < 0) | (offsets + lengths > entries.shape[0]))
+        if beyond.any():
+            bad = int(np.flatnonzero(beyond)[0])
+            raise ValueError(f"game {bad}: entries [{int(offsets[bad])}, {int(offsets[bad])} + {int(lengths[bad])}) outside the buffer's {entries.shape[0]}")
+        rows = (offsets[:, None] + np.arange(hw)[None, :])[played]  # entry index of every played move, game-major
+        picked = entries[rows]
+        words = picked[:, :16].copy().view("<u4").reshape(-1, 4)
+        halves = picked[:, 16:].copy().view("<u2").reshape(-1, 2)
+        if halves[:, 1].any():
+            bad = int(rows[np.flatnonzero(halves[:, 1])[0]])
+            raise ValueError(f"entry {bad}: bytes 18-19 are not zero")
+        moves = np.full((g, hw), 0xFFFF, dtype=np.uint16)
+        moves[played] = halves[:, 0]
+        fields = []
+        for k in range(4):  # root_n, root_w, child_n, child_w: the floats are placed as their words
+            a = np.zeros((g, hw), dtype=np.uint32)
+            a[played] = words[:, k]
+            fields.append(a)
+        return cls.from_log(n, np.zeros((g, hw), dtype=np.uint8), lengths, moves, fields[0], fields[1].view(np.float32), fields[2],
+                            fields[3].view(np.float32), status.astype(np.uint8), lengths.copy(), meta)
 
     games = property(lambda s: len(s.lengths))
 
@@ -140,7 +182,7 @@ load = GameRecords.load
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog="omok_ai_amd.records", description="game records written by match.py --save-games / Trainer.evaluate(save_games=...)")
+    ap = argparse.ArgumentParser(prog="omok_ai_amd.records", description="game records written by match.py --save-games / Trainer.evaluate(save_games=...) / Trainer(save_selfplay_games=...)")
     sub = ap.add_subparsers(dest="cmd", required=True)
     show = sub.add_parser("show", help="print one game: the final board with move numbers and one line per move")
     show.add_argument("file")

@@ -13,6 +13,9 @@ Parameters.selfplay_slots = S > 0 plays the iteration's `episode_count` games in
 min(S, episode_count) games: a slot whose game is over takes the next game index, so the trees resident in memory no longer grow with
 episode_count.  The raw records it hands back are back-filled and augmented on the device by omok_replay_augment_records_dev into the
 game-index order the episode path produces; everything after that is the same code.  0 (the default) is the episode path.
+Trainer(save_selfplay_games=DIR) keeps every self-play game: each iteration writes DIR/selfplay_iter{iteration:06d}.rank{rank}.npz, a
+records.GameRecords (every move with the mover's root and chosen-child statistics; `python -m omok_ai_amd.records show FILE --game i`), from the
+engine's move log on the episode path and from omok_selfplay_run_slots_logged in slots mode: the same arrays either way, and the same weights as without it.
 """
 import os
 from dataclasses import dataclass
@@ -45,7 +48,8 @@ class Parameters:  # src/config.rs:83-110
 
 
 class Trainer:
-    def __init__(self, params=None, board_size=15, seed=0, save_dir="saves", max_nodes=None, max_tables=None, precision_rows=256, precision_search_rounds=True):
+    def __init__(self, params=None, board_size=15, seed=0, save_dir="saves", max_nodes=None, max_tables=None, precision_rows=256, precision_search_rounds=True,
+                 save_selfplay_games=None):
         self.p = params or Parameters()
         self.n = board_size
         self.rank, self.local_rank, self.world = dist.shard_info()
@@ -81,6 +85,10 @@ class Trainer:
         if self.p.train_backend in ("hip", "hip_dp"):  # ... here in the engine; self.phase.net only mirrors the variables (precision check, tests)
             self.engine.train_begin(self.p.parameter_update_batch_size)
         self.selfplay = api.SelfPlay(self.engine)
+        self.save_selfplay_games = save_selfplay_games  # a directory: every iteration's self-play games are written there (None = no move log is kept)
+        self._raw_log = None  # slots mode with the games kept: the packed move log beside _raw, 20 B per record
+        if save_selfplay_games is not None:
+            self.selfplay.game_log(True)  # from the next reset on: every iteration starts with one
         self.iteration = 0
         it_path = path + ".iteration"  # (not in the reference, whose thread_rng is fresh on every start): a resumed run must
         if os.path.exists(path) and os.path.exists(it_path):  # not replay the RNG streams of the iterations it has already played;
@@ -125,6 +133,18 @@ class Trainer:
         v_loss, p_loss, loss = (float(v) for v in sums / np.float32(max(counted, 1)))
         return v_loss, p_loss, loss
 
+    def _save_selfplay_games(self, read, log):
+        """this iteration's self-play games (read(meta) -> records.GameRecords) into save_selfplay_games; like the precision check, a failure
+        is logged, never fatal: the training state does not depend on the file"""
+        p = self.p
+        try:
+            os.makedirs(self.save_selfplay_games, exist_ok=True)
+            meta = {"kind": "selfplay", "iteration": self.iteration, "seed": self.seed, "sims": p.evaluate_count, "batch": p.evaluate_batch_size,
+                    "slots": self.slots, "game_offset": dist.game_offset(self.rank, p.episode_count)}
+            read(meta).save(os.path.join(self.save_selfplay_games, f"selfplay_iter{self.iteration:06d}.rank{self.rank}.npz"))
+        except Exception as ex:  # noqa: BLE001
+            log(f"[iter={self.iteration}] WARNING: the self-play games were not saved: {ex!r}")
+
     def train(self, iteration_count, log=print):
         p = self.p
         rec = self.selfplay.replay_record_bytes()
@@ -137,14 +157,24 @@ class Trainer:
                 cap = p.episode_count * self.n * self.n
                 if self._raw is None:
                     self._raw = torch.empty(cap * rec, dtype=torch.uint8, device=self.device)
-                stats, n_raw, offsets, lengths, _ = self.selfplay.run_slots(p.episode_count, p.evaluate_count, p.evaluate_batch_size, self._raw.data_ptr(), cap,
-                                                                            p.epsilon, p.alpha, p.temperature, p.temperature_threshold)
+                if self.save_selfplay_games is None:
+                    stats, n_raw, offsets, lengths, _ = self.selfplay.run_slots(p.episode_count, p.evaluate_count, p.evaluate_batch_size, self._raw.data_ptr(), cap,
+                                                                                p.epsilon, p.alpha, p.temperature, p.temperature_threshold)
+                else:
+                    if self._raw_log is None:
+                        self._raw_log = torch.empty(cap * api.B.lib().omok_game_log_entry_bytes(), dtype=torch.uint8, device=self.device)
+                    stats, n_raw, offsets, lengths, status = self.selfplay.run_slots_logged(p.episode_count, p.evaluate_count, p.evaluate_batch_size, self._raw.data_ptr(),
+                                                                                            cap, self._raw_log.data_ptr(), p.epsilon, p.alpha, p.temperature,
+                                                                                            p.temperature_threshold)
+                    self._save_selfplay_games(lambda meta: self.selfplay.slots_game_records(self._raw_log, n_raw, offsets, lengths, status, meta), log)
                 total = 6 * int(lengths.sum())
                 buf = torch.empty(max(total, 1) * rec, dtype=torch.uint8, device=self.device)
                 got = self.engine.replay_augment_records(self._raw.data_ptr(), n_raw, offsets, lengths, buf.data_ptr(), total)
             else:
                 stats = self.selfplay.run(p.evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha, p.temperature,
                                           p.temperature_threshold, 0)
+                if self.save_selfplay_games is not None:
+                    self._save_selfplay_games(lambda meta: self.selfplay.game_records(meta=meta), log)
                 _, _, plies = self.selfplay.game_info()
                 total = 6 * int(plies.sum())
                 buf = torch.empty(max(total, 1) * rec, dtype=torch.uint8, device=self.device)

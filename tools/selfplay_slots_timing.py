@@ -4,7 +4,10 @@ on one engine configuration (configs[1] by default: 4096 games, 15 x 15, 800 sim
 alternating -- 1 warm-up pair, then 3 pairs, medians -- then the post-processing of the slots run's raw records by
 omok_replay_augment_records_dev beside omok_replay_augment_dev on the episode engine's games: the kernels under the engine's HIP events
 (OMOK_STAT_MS_PLY with omok_set_profiling) and the wall clock of the blocking call, 3 warm-up calls, then 5, medians.  Both calls move about 7 records
-per transition (one read, six written)."""
+per transition (one read, six written).
+`--log` measures the move log in slots mode instead: on one engine of `--slots` slots, `--games` games with the log off (omok_selfplay_run_slots)
+and on (omok_selfplay_run_slots_logged), alternating, the same warm-up and pairs, games/s; then the device-to-host read-back of the packed
+log and records.GameRecords.from_packed of all games (SelfPlay.slots_game_records), wall clock, 1 warm-up call, then 5, median."""
 import os
 import sys
 import time
@@ -38,6 +41,52 @@ def engine(g):
     eng.load_random_weights(0)
     return eng, oa.SelfPlay(eng)
 
+
+def log_leg():
+    eng, sp = engine(slots)
+    rec, cap = sp.replay_record_bytes(), games * n * n
+    raw = torch.empty(cap * rec, dtype=torch.uint8, device="cuda")
+    log = torch.empty(cap * oa.records.ENTRY_BYTES, dtype=torch.uint8, device="cuda")
+
+    def run(logged):
+        sp.game_log(logged)  # (allocates / frees the per-slot log outside the timed part; it starts at the reset)
+        sp.reset()
+        eng.reset_stats()
+        t = time.perf_counter()
+        if logged:
+            res = sp.run_slots_logged(games, sims, k, raw.data_ptr(), cap, log.data_ptr())
+        else:
+            res = sp.run_slots(games, sims, k, raw.data_ptr(), cap)
+        return res[0]["finished"] / (time.perf_counter() - t), res
+
+    say(f"{games} games, {n} x {n}, {sims} simulations, K = {k}, slots mode on {slots} slots of one engine: move log off (omok_selfplay_run_slots) / on "
+        "(omok_selfplay_run_slots_logged), alternating; 1 warm-up pair, then 3 pairs")
+    run(False)
+    run(True)
+    rate = {"off": [], "on": []}
+    for pair in range(3):
+        rate["off"].append(run(False)[0])
+        r, (_, n_raw, off, ln, status) = run(True)
+        rate["on"].append(r)
+        say(f"pair {pair}: log off {rate['off'][-1]:.2f} games/s, log on {r:.2f} games/s")
+    for name in ("off", "on"):
+        say(f"log {name}: median {np.median(rate[name]):.2f} games/s (min {min(rate[name]):.2f}, max {max(rate[name]):.2f})")
+    say(f"log on / log off, medians: {np.median(rate['on']) / np.median(rate['off']):.4f}")
+    wall = []
+    for _ in range(6):
+        t = time.perf_counter()
+        games_rec = sp.slots_game_records(log, n_raw, off, ln, status)
+        wall.append((time.perf_counter() - t) * 1e3)
+    say(f"read-back of the packed log + GameRecords.from_packed, all {games_rec.games} games ({n_raw} moves, {n_raw * oa.records.ENTRY_BYTES / 1e6:.1f} MB): wall clock median "
+        f"{np.median(wall[1:]):.3f} ms (min {min(wall[1:]):.3f}, max {max(wall[1:]):.3f})")
+    eng.close()
+
+
+if "--log" in sys.argv:
+    log_leg()
+    if args:
+        open(args[0], "w").write("\n".join(out) + "\n")
+    raise SystemExit(0)
 
 e_eng, e_sp = engine(games)
 s_eng, s_sp = engine(slots)
