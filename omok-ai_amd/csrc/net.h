@@ -45,6 +45,7 @@ struct Net {
     // ---- OMOK_NET_F16X3: packed split-fp16 operands (see net_kernels.hip) ----
     void* wt_trunk = nullptr; // packed trunk weights (A-operand fragments, hi|lo)
     float* wt_first = nullptr; // conv_in weights/bias + all biases + depthwise taps, fp32
+    float* conv_tab = nullptr; // conv_in's output and block 0's first layer per 3-bit input pattern, rebuilt at every commit (k_conv_tables; k_sib_children2 reads them)
     void* wt_fc0 = nullptr;   // [kstep][ntile][hi|lo][lane][8] f16
     void* wt_fc1 = nullptr;
     void* wt_heads = nullptr;

@@ -282,7 +282,7 @@ __device__ __forceinline__ void trunk_lds_prologue(unsigned char* smem, float* l
     for (int i = tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
     for (int i = tid; i < TR_SIDE_FLOATS; i += blockDim.x) lside[i] = side[i];
 }
-// The conv_in fragments of the children kernels: 32 registers that are only needed at the top of a pass.  They are fetched again at the END of every pass (from
+// The conv_in fragments of k_sib_children (k_sib_children2 reads the conv tables instead; k_conv_tables fetches them once): 32 registers that are only needed at the top of a pass.  They are fetched again at the END of every pass (from
 // L2, under the stores) instead of living through the blocks, where they pushed lane-constant addresses into scratch whose
 // reloads (a dozen dependent round trips in the store phase) cost more than the whole arithmetic of the pass
 __device__ __forceinline__ void load_conv_w(const half8* convW, int lane, half8 (&cwh)[4], half8 (&cwl)[4]) {
@@ -354,6 +354,35 @@ __device__ __forceinline__ void L0_tile(const half8* ldsW, const float* lside, i
         split8(v, bh, bl);
         const half8 ah = W[(0 + ks) * 64 + lane], al = W[(8 + ks) * 64 + lane];
         MFMA3(ah, al, bh, bl, acc);
+    }
+}
+// Conv tables (Net::conv_tab): a board pixel's three input bits are f16 0 / 1 and k = 3 carries the bias, so conv_in's output of a pixel takes one of EIGHT values, and so
+// does block 0's L0 (a 1x1 layer on that output).  Both depend on the weights only, so they are computed once per commit and k_sib_children2 reads them instead of running
+// conv_in_tile and block 0's L0_tile in every pass.  Pattern = b0 | b1 << 1 | b2 << 2; fp32, rows padded so that lanes of different (pattern, h) read different 16-B slots:
+//   T0[pattern][CT_T0_STRIDE]  conv_in after LeakyReLU, channel 32 m + 8 g + 4 h + i = x[m][4 g + i]
+//   T1[pattern][CT_T1_STRIDE]  L0_tile's accumulator of block 0 (before LeakyReLU), channel 8 g + 4 h + i = acc[4 g + i]
+constexpr int CT_T0_STRIDE = NC + 8, CT_T1_STRIDE = NM + 8; // 136, 40 floats: slot (2 p + h) mod 16, (10 p + h) mod 16 -- distinct over p = 0..7, h = 0..1
+constexpr int CT_T1_OFF = 8 * CT_T0_STRIDE;
+constexpr int CT_FLOATS = CT_T1_OFF + 8 * CT_T1_STRIDE; // 1408 floats = 5632 B
+static_assert(NC == 128 && NM == 32 && CT_FLOATS % 4 == 0, "conv table layout");
+// One wave, at the end of net_pack: pixel p = 0..7 of the tile carries pattern p (the other pixels run along).  The device functions are the ones the trunk kernels call
+// (their weight pointers address global memory here), and an MFMA output column depends on its own B column only: an entry is the bit pattern any lane with that input computes.
+__global__ __launch_bounds__(64) void k_conv_tables(const uint4* __restrict__ wt, const float* __restrict__ side, float* __restrict__ tab) {
+    asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1"); // MODE.FP16_OVFL as in trunk_lds_prologue
+    const int lane = threadIdx.x, h = lane >> 5, pat = lane & 7;
+    half8 cwh[4], cwl[4];
+    load_conv_w((const half8*)(wt + TR_WBYTES / 16), lane, cwh, cwl);
+    const half8 bq = conv_in_operand(h, pat & 1, (pat >> 1) & 1, (pat >> 2) & 1);
+    f32x16 x[4], acc;
+    conv_in_tile<false>(cwh, cwl, bq, bq, x);
+    L0_tile((const half8*)wt, side, h, lane, x, 0, acc);
+    if ((lane & 31) >= 8) return;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+            *(f32x4*)(tab + pat * CT_T0_STRIDE + 32 * m + 8 * g + 4 * h) = (f32x4){x[m][4 * g], x[m][4 * g + 1], x[m][4 * g + 2], x[m][4 * g + 3]};
+        *(f32x4*)(tab + CT_T1_OFF + pat * CT_T1_STRIDE + 8 * g + 4 * h) = (f32x4){acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
     }
 }
 // L1 and L2 of block blk from the pixel's depthwise outputs d[16]: pointwise 32 -> 32 + bias + lrelu, then 1x1 32 -> 128 + bias + residual (accumulated onto x), lrelu
@@ -1791,12 +1820,16 @@ __global__ __launch_bounds__(512) void k_sib_children(const uint64_t* __restrict
 // pixel-major in the piece order of the accumulators (sib2_grid, sib2_x2).  Results are within rounding of k_sib_children's (a different summation order in the
 // depthwise) and need not be bit-identical -- on the rows the tests compare they are, every layer boundary re-quantising to ~22 bits -- so the difference path
 // is tolerance-checked; the copy path (rows bit-identical to a full evaluation by construction) keeps k_sib_children.
+// conv_in and block 0's L0 are not computed here: a pixel's three input bits select one of eight rows of the conv tables (k_conv_tables, once per commit; copied to
+// LDS in the prologue), which hold the bits conv_in_tile / L0_tile give for that input -- 168 MFMAs per child, and no conv_in fragments to keep or fetch again.
 constexpr int V2_TW = 5, V2_TPX = V2_TW * V2_TW;          // tile window side, pixels
 constexpr int V2_RING = SIB_WPX - V2_TPX;                 // 24
 constexpr int V2_ZERO_CELL = 32, V2_WORD_CELL = 33;       // cells 0..31: tile grid / staging rows
 constexpr int V2_CELLS = 34;
 constexpr int V2_WAVE_FLOATS = V2_CELLS * GRID_STRIDE;
-constexpr int V2_LDS = TR_WBYTES + TR_SIDE_FLOATS * 4 + 8 * V2_WAVE_FLOATS * 4;
+constexpr int V2_TAB_OFF = TR_WBYTES + TR_SIDE_FLOATS * 4 + 8 * V2_WAVE_FLOATS * 4; // the conv tables, behind the waves' cells
+constexpr int V2_LDS = V2_TAB_OFF + CT_FLOATS * 4;
+static_assert(V2_TAB_OFF % 16 == 0, "the conv tables are read as b128");
 static_assert(V2_LDS <= 160 * 1024, "k_sib_children2 LDS");
 #define OL() ({ int lq_ = lane; asm volatile("" : "+v"(lq_)); lq_; })
 #define TILE_A(LQ) (((LQ) & 31) < V2_TPX ? ((LQ) & 31) : V2_TPX - 1)
@@ -1808,7 +1841,8 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
                                                        uint4* __restrict__ a_out, size_t row_u4, const uint4* __restrict__ sib_rows,
                                                        const int32_t* __restrict__ d_cnt, const uint4* __restrict__ sib2,
                                                        const uint32_t* __restrict__ sib_slot, const int32_t* __restrict__ bin_start,
-                                                       uint4* __restrict__ d_rows, uint2* __restrict__ slot_desc, unsigned long long* __restrict__ tprof) {
+                                                       uint4* __restrict__ d_rows, uint2* __restrict__ slot_desc, unsigned long long* __restrict__ tprof,
+                                                       const uint4* __restrict__ conv_tab) {
     unsigned long long tp_acc[12] = {}, tp_last = 0;
     auto TP = [&](int phase) { // (phase = what ended here)
         if (TPROF) {
@@ -1829,6 +1863,8 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     const int h = lane >> 5;
     trunk_lds_prologue(smem, (float*)lside, wt, side, tid);
     for (int i = tid; i < 8 * V2_WAVE_FLOATS; i += blockDim.x) ((float*)(smem + TR_WBYTES + TR_SIDE_FLOATS * 4))[i] = 0.0f;
+    for (int i = tid; i < CT_FLOATS / 4; i += blockDim.x) ((uint4*)(smem + V2_TAB_OFF))[i] = conv_tab[i];
+    const float* ltab = (const float*)(smem + V2_TAB_OFF); // conv tables: T0 at 0, T1 at CT_T1_OFF
     // Round 6: the children of a workgroup are handed out from a counter in LDS instead of every wave taking every eighth entry.  The second wave of a SIMD (waves 4..7)
     // runs ~15 % slower than the first (issue arbitration favours the older wave: profiles/r05_children_store_order.txt, item 7), so with equal shares waves 0..3 end early
     // and the others finish alone; handed out on demand, all eight end together.  A child's arithmetic does not depend on the wave that takes it: same bits.
@@ -1841,9 +1877,6 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     __syncthreads(); // (the only workgroup barrier: from here on a wave touches read-only LDS and its own cells)
     for (int i = 0; i < (wv >> 2); ++i) __builtin_amdgcn_s_sleep(120); // the two waves of a SIMD (w, w + 4) start about half a pass apart
     const int nsib = d_cnt[NET_GCNT_ROWS_IN_RUNS];
-    const half8* convW = (const half8*)(wt + TR_WBYTES / 16);
-    half8 cwh[4], cwl[4]; // conv_in fragments: fetched again at the end of every pass (load_conv_w)
-    load_conv_w(convW, lane, cwh, cwl);
 
     // difference-row entries of a tile's pixels, in the layout of k_sib_children<DELTA>'s (staging rows = this wave's cells 0..31)
     // `far`: this lane's pixel lies outside the child's own region (P0 +- 3, clipped to the board -- at an edge that is less than the 7x7 window its bin shares): there the child
@@ -1994,6 +2027,18 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         uint4* crow_p = d_rows + (size_t)slot * DROW_U4;
         const uint4* sb = sib2 + (size_t)ent.y * SLOT_U4;
         const uint4* frow = a_out + (size_t)ent.y * row_u4;
+        // block 0's pieces of the base (h at P0 only, d): asked for first, so that their way from L2 passes under the input bits and the table reads (nothing else is left
+        // between the top of the pass and their use: block 0's L0, whose MFMAs covered it, is a table row now)
+        uint4 hb0[4], db0[4];
+        {
+            const bool p0 = (OL() & 31) == (py - vy0) * V2_TW + (pxx - vx0);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                hb0[g] = make_uint4(0u, 0u, 0u, 0u);
+                if (p0) hb0[g] = sb[sib2_grid(HW, 0, 0, bpxA, g, h)];
+                db0[g] = sb[sib2_grid(HW, 0, 1, bpxA, g, h)];
+            }
+        }
         uint64_t* cw = (uint64_t*)(wgrid + V2_WORD_CELL * GRID_STRIDE);
         if (lane < 2 * NW) cw[lane] = word_c;
         const uint64_t word_n = fetch_word(ent_n);
@@ -2006,9 +2051,17 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         WAVE_LDS_FENCE();
         uint32_t bits[3];
         input_bits<N>(cw, turn, bpxA, bits);
-        {
-            const half8 bq = conv_in_operand(h, bits[0], bits[1], bits[2]);
-            conv_in_tile<false>(cwh, cwl, bq, bq, x);
+        const int pat = (int)(bits[0] | bits[1] << 1 | bits[2] << 2);
+        { // conv_in of this lane's pixel: the row of its input pattern in the conv table (what conv_in_tile computes from these bits, bit for bit)
+            const float* t0 = ltab + pat * CT_T0_STRIDE + 4 * h;
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 v = *(const f32x4*)(t0 + 32 * m + 8 * g);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) x[m][4 * g + i] = v[i];
+                }
         }
         TP(0);
         // h_child - h_base of the tile -> the wave's cells; `hb` / `db`: the base's h and d pieces of this lane's pixel
@@ -2080,26 +2133,20 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             const int tP = (py - vy0) * V2_TW + (pxx - vx0); // P0's pixel index in the tile (wave-uniform)
             const int lq = OL(), tA = TILE_A(lq);
             const bool at_p0 = (lq & 31) == tP;
-            uint4 hb[4], db[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                hb[g] = make_uint4(0u, 0u, 0u, 0u);
-                if (at_p0) hb[g] = sb[sib2_grid(HW, 0, 0, bpxA, g, h)];
-                db[g] = sb[sib2_grid(HW, 0, 1, bpxA, g, h)];
-            }
-            f32x16 acc;
-            L0_tile(ldsW, lside, h, lane, x, blk0, acc);
-            TP(1);
-            if (at_p0) {
+            const uint4 (&hb)[4] = hb0, (&db)[4] = db0; // (fetched at the top of the pass)
+            if (at_p0) { // block 0's L0 is needed at P0 only: L0_tile's accumulator for the pixel's input pattern, from the conv table
+                const float* t1 = ltab + CT_T1_OFF + pat * CT_T1_STRIDE + 4 * h;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 b = __builtin_bit_cast(f32x4, hb[g]);
-                    const f32x2 r0 = lrelu2(acc[4 * g], acc[4 * g + 1]), r1 = lrelu2(acc[4 * g + 2], acc[4 * g + 3]);
+                    const f32x4 a4 = *(const f32x4*)(t1 + 8 * g);
+                    const f32x2 r0 = lrelu2(a4[0], a4[1]), r1 = lrelu2(a4[2], a4[3]);
                     f32x4 o;
                     o[0] = r0[0] - b[0]; o[1] = r0[1] - b[1]; o[2] = r1[0] - b[2]; o[3] = r1[1] - b[3];
                     *(f32x4*)(wgrid + 8 * g + 4 * h) = o; // cell 0
                 }
             }
+            TP(1); // (block 0's share of "L0 x3" is now the table read and P0's cell)
             WAVE_LDS_FENCE();
             const int ey = py - vy0 - tA / V2_TW + 1, ex = pxx - vx0 - tA % V2_TW + 1; // P0 as a tap of this lane's pixel: (ey, ex) in 0..2 if adjacent
             const bool adj = ey >= 0 && ey <= 2 && ex >= 0 && ex <= 2;
@@ -2258,7 +2305,6 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
             }
             store_rows(x, crow_p, (OL() & 31) < V2_RING, rd_px, rd_ok, farB);
         }
-        load_conv_w(convW, lane, cwh, cwl);
         ent_c = ent_n;
         ent_n = ent_nn;
         slot_c = slot_n;
@@ -3606,6 +3652,7 @@ size_t net_alloc(Net& net) {
         const size_t row_u4 = net.row_u4_fmt[FC0_F16]; // buffers are sized for the larger format: the format can change at every commit
         ok = ok && A(&net.wt_trunk, TR_WBYTES + TR_CONV_FRAGS * 1024);
         ok = ok && A((void**)&net.wt_first, sizeof(float) * (TR_SIDE_FLOATS + 2 * NF + heads_mt(net.hw) * 32));
+        ok = ok && A((void**)&net.conv_tab, sizeof(float) * CT_FLOATS);
         ok = ok && A(&net.wt_fc0, (ks0 + 4) * (size_t)MXS_FR * 1024); // hw*2 super-steps x 4 stages (= ks0) + 4 stages of padding (prefetch depth)
         ok = ok && A(&net.wt_fc0x, (2 * ks0 + 8) * (size_t)X3_FR * 1024); // FC0_F16: hw*4 half-steps x 4 stages + 8 stages of padding
         ok = ok && A(&net.wt_fc1, (size_t)32 * 16 * 2 * 1024);
@@ -3655,7 +3702,7 @@ void net_free(Net& net) {
         net.s0_x3 = net.s0_f32 = nullptr;
     }
     void** ptrs[] = {(void**)&net.p, (void**)&net.v, (void**)&net.vpre, (void**)&net.in_f32, (void**)&net.sx, (void**)&net.sh, (void**)&net.sd,
-                     (void**)&net.sg, (void**)&net.s0, (void**)&net.s1, &net.wt_trunk, (void**)&net.wt_first, &net.wt_fc0,
+                     (void**)&net.sg, (void**)&net.s0, (void**)&net.s1, &net.wt_trunk, (void**)&net.wt_first, (void**)&net.conv_tab, &net.wt_fc0,
                      &net.wt_fc0x, &net.wt_fc1, &net.wt_heads, &net.a_fc0, &net.h0, (void**)&net.part, (void**)&net.d_groups,
                      (void**)&net.d_singles, (void**)&net.d_gcnt, (void**)&net.d_work, (void**)&net.sib_h, (void**)&net.d_sib_rows, (void**)&net.d_sib_slot,
                      (void**)&net.d_bin_start, (void**)&net.d_tile_info, &net.d_slot_desc, &net.d_rows, (void**)&net.part_w, &net.a_base, (void**)&net.facc, (void**)&net.d_tags, &net.d_comp};
@@ -3871,6 +3918,7 @@ static int net_pack(Net& net, hipStream_t st) {
     }
     if (hipMemcpyAsync(net.wt_trunk, trunk.data(), trunk.size() * 2, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     if (hipMemcpyAsync(net.wt_first, side.data(), side.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    k_conv_tables<<<1, 64, 0, st>>>((const uint4*)net.wt_trunk, net.wt_first, net.conv_tab); // (behind the two uploads it reads)
     hipStreamSynchronize(st);
     return 0;
 }
@@ -3969,7 +4017,7 @@ static sib_kernel_t sib_kernel(bool delta, bool x16, int n) { // k_sib_children<
                  : (x16 ? k_sib_children<false, true, 15> : k_sib_children<false, false, 15>);
 }
 typedef void (*sib2_kernel_t)(const uint64_t*, const uint4*, const float*, uint4*, size_t, const uint4*, const int32_t*, const uint4*, const uint32_t*, const int32_t*,
-                              uint4*, uint2*, unsigned long long*);
+                              uint4*, uint2*, unsigned long long*, const uint4*);
 static sib2_kernel_t sib2_kernel(bool x16, int n, bool mixed = false) { // k_sib_children2<F16LO, N, false, OUT_F16>
     if (mixed) return n == 9 ? k_sib_children2<true, 9, false, false> : k_sib_children2<true, 15, false, false>;
     if (n == 9) return x16 ? k_sib_children2<true, 9> : k_sib_children2<false, 9>;
@@ -4063,12 +4111,12 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
         if (!d_tp) { hipMalloc(&d_tp, 256); hipMemset(d_tp, 0, 256); hipFuncSetAttribute((const void*)k_sib_children2<false, 15, true>, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS); }
         k_sib_children2<false, 15, true><<<256, 512, V2_LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4, (const uint4*)net.d_sib_rows,
                                                                    net.d_gcnt, (const uint4*)net.sib_h, net.d_sib_slot, net.d_bin_start, (uint4*)net.d_rows, (uint2*)net.d_slot_desc,
-                                                                   d_tp);
+                                                                   d_tp, (const uint4*)net.conv_tab);
         if (++launches % 100 == 0) {
             hipStreamSynchronize(st);
             hipMemcpy(acc, d_tp, 256, hipMemcpyDeviceToHost);
-            static const char* names[12] = {"inputs+conv_in", "L0 x3", "grid+strip dw+read d (blocks 0,1)", "L1L2 (blocks 0,1)", "block 2: grid + ring + tile dw", "L1L2 tile",
-                                            "base subtract tile", "stores tile", "x2 + base fetch ring", "L1L2 ring", "base subtract ring", "stores ring + conv w"};
+            static const char* names[12] = {"inputs+conv table", "P0's table row + L0 x2", "grid+strip dw+read d (blocks 0,1)", "L1L2 (blocks 0,1)", "block 2: grid + ring + tile dw", "L1L2 tile",
+                                            "base subtract tile", "stores tile", "x2 + base fetch ring", "L1L2 ring", "base subtract ring", "stores ring"};
             for (int w = 0; w < 2; ++w) {
                 double tot = 0;
                 for (int i = 0; i < 12; ++i) tot += (double)acc[16 * w + i];
@@ -4082,7 +4130,8 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
     net.children_launches[v2 ? 0 : 1] += 1.0;
     if (v2) {
         sib2_kernel(x16, net.n, mixed)<<<256, 512, V2_LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4, (const uint4*)net.d_sib_rows,
-                                                          net.d_gcnt, (const uint4*)net.sib_h, net.d_sib_slot, net.d_bin_start, (uint4*)net.d_rows, (uint2*)net.d_slot_desc, nullptr);
+                                                          net.d_gcnt, (const uint4*)net.sib_h, net.d_sib_slot, net.d_bin_start, (uint4*)net.d_rows, (uint2*)net.d_slot_desc, nullptr,
+                                                          (const uint4*)net.conv_tab);
         return;
     }
     sib_kernel(true, x16, net.n)<<<256, 512, LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4,
