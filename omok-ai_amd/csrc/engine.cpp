@@ -160,6 +160,25 @@ static int dalloc(omok_engine* e, Tp** p, size_t count) {
     return 0;
 }
 
+// Device scratch of one call (the engine-lifetime buffers are dalloc's): whatever get() handed out is freed when the holder goes out of scope,
+// on every return path.  get() returns nullptr and sets `failed` when an allocation fails; the caller reports it with fail().
+struct Scratch {
+    std::vector<void*> ptrs;
+    bool failed = false;
+    Scratch() = default;
+    Scratch(Scratch&&) = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { for (void* p : ptrs) hipFree(p); }
+    template <typename Tp>
+    Tp* get(size_t count) {
+        void* q = nullptr;
+        if (hipMalloc(&q, count * sizeof(Tp)) != hipSuccess) { failed = true; return nullptr; }
+        ptrs.push_back(q);
+        return (Tp*)q;
+    }
+};
+
 // tiny helper kernels --------------------------------------------------------------------------
 __global__ void k_count_alive(Store S, uint32_t* d_error, unsigned long long* d_evals) {
     __shared__ uint32_t s_cnt, s_err, s_mn, s_mt;
@@ -528,15 +547,30 @@ static Store block_view(const omok_engine* e, int b) { // the block's rows as a 
     else { V.req_ref = e->d_mref; V.req_aux = e->d_maux; V.d_count = e->d_mcnt + 1; }
     return V;
 }
-// one forward of block b's rows by its net (search rounds: sibling_side = the trees' side; its k_group takes the block's games only)
-static void match_forward(omok_engine* e, int b, int tree_side, int max_count, int sibling_side, bool skip_softmax) {
-    Net& X = net_at(e, tree_side ^ b);
-    X.grp_lo = b ? e->split : 0;
-    X.grp_hi = b ? e->cfg.games : e->split;
-    X.grp_sub = b ? e->d_mcnt : nullptr;
-    net_forward_requests(X, block_view(e, b), max_count, e->st, &e->prof, sibling_side, skip_softmax);
-    X.grp_hi = -1;
-    X.grp_sub = nullptr;
+// The evaluation blocks of a batch on the trees of `tree_side`: the rows one net evaluates, as a request list of their own.  Self-play has one, net 1 on
+// the whole list; a match the live ones of its two.  rows: the block's row count, or the bound the caller has for it (run loops: the count stays on the
+// device); pending: a match takes the counts of the pending step-wise batch (match_counts) instead.
+struct Block { Net* net; Store view; int rows, off, b; }; // off: the block's first row in the order of the whole list (pending batches)
+static int eval_blocks(omok_engine* e, int tree_side, int rows, bool pending, Block out[2]) {
+    if (!e->match) { out[0] = Block{&e->net, e->S, rows, 0, 0}; return 1; }
+    int n = 0;
+    for (int b = 0; b < 2; ++b)
+        if (block_live(e, b)) out[n++] = Block{&net_at(e, tree_side ^ b), block_view(e, b), pending ? e->match_cnt[b] : rows, b ? e->match_cnt[0] : 0, b};
+    return n;
+}
+// one forward of a block's rows by its net (search rounds: sibling_side = the trees' side; a match block's k_group takes the block's games only)
+static void block_forward(omok_engine* e, const Block& B, int max_count, int sibling_side = -1, bool skip_softmax = false) {
+    Net& X = *B.net;
+    if (e->match) {
+        X.grp_lo = B.b ? e->split : 0;
+        X.grp_hi = B.b ? e->cfg.games : e->split;
+        X.grp_sub = B.b ? e->d_mcnt : nullptr;
+    }
+    net_forward_requests(X, B.view, max_count, e->st, &e->prof, sibling_side, skip_softmax);
+    if (e->match) {
+        X.grp_hi = -1;
+        X.grp_sub = nullptr;
+    }
 }
 static void match_split(omok_engine* e, int tree_side, int max_rows) {
     launch_match_split(e->S, tree_side, e->split, e->d_mref, e->d_maux, e->d_mcnt, e->d_mevals, max_rows, e->st);
@@ -735,97 +769,78 @@ extern "C" int omok_debug_train_gradient(omok_engine* e, int32_t index, float* o
     return OMOK_OK;
 }
 
-extern "C" int omok_evaluate_pv(omok_engine* e, const float* in, int32_t batch, float* p, float* v) {
+// `rows` rows of src ([rows][stride]) as [rows][HW] into p, and as many values of vsrc into v (NULL: skipped), through net's staging buffer; no synchronisation
+static int rows_to_host(omok_engine* e, Net& net, const float* src, int stride, const float* vsrc, int rows, float* p, float* v) {
+    float* d_pack = net.in_f32; // (the forward is over: its input rows are free)
+    const size_t tot = (size_t)rows * e->hw;
+    k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(src, d_pack, e->hw, stride, rows);
+    HIPCHK(e, hipMemcpyAsync(p, d_pack, sizeof(float) * tot, hipMemcpyDeviceToHost, e->st));
+    if (v) HIPCHK(e, hipMemcpyAsync(v, vsrc, sizeof(float) * rows, hipMemcpyDeviceToHost, e->st));
+    return 0;
+}
+
+// omok_evaluate_pv, and with `logits` the debug / evidence entry point omok_evaluate_logits: the same forward, but the PRE-softmax policy logits and
+// the PRE-tanh value (network.rs:188-247 before the Tanh / Softmax ops), so that precision can be stated on logits as well as on the outputs the
+// reference API returns
+static int evaluate_inputs(omok_engine* e, bool logits, const float* in, int32_t batch, float* p, float* v) {
     if (!e || !in || !p || batch < 0) return OMOK_ERR_INVALID;
     if (need_net(e)) return OMOK_ERR_STATE;
     if (e->round_reqs >= 0 || e->mirror_reqs >= 0) // the forward reuses the request counter and the output rows of the pending batch
-        return fail(e, OMOK_ERR_STATE, "omok_evaluate_pv between omok_round_generate / omok_mirror_generate and their scatter / apply");
+        return fail(e, OMOK_ERR_STATE, logits ? "omok_evaluate_logits while a round / mirror batch is pending"
+                                              : "omok_evaluate_pv between omok_round_generate / omok_mirror_generate and their scatter / apply");
     HIPCHK(e, hipSetDevice(e->cfg.device));
+    Net& net = e->net;
     const size_t in_row = 3 * (size_t)e->hw;
-    float* d_pack = e->net.in_f32; // reused as the packed output staging after the forward
-    for (int32_t done = 0; done < batch; done += e->net.max_b) {
-        const int b = std::min<int32_t>(e->net.max_b, batch - done);
-        HIPCHK(e, hipMemcpyAsync(e->net.in_f32, in + (size_t)done * in_row, sizeof(float) * in_row * b, hipMemcpyHostToDevice, e->st));
-        HIPCHK(e, hipMemcpyAsync(e->S.d_count, &b, sizeof(int32_t), hipMemcpyHostToDevice, e->st));
-        net_forward_inputs(e->net, e->S, b, e->st, &e->prof);
-        const size_t tot = (size_t)b * e->hw;
-        k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(e->net.p, d_pack, e->hw, e->rowp, b);
-        HIPCHK(e, hipMemcpyAsync(p + (size_t)done * e->hw, d_pack, sizeof(float) * tot, hipMemcpyDeviceToHost, e->st));
-        if (v) HIPCHK(e, hipMemcpyAsync(v + done, e->net.v, sizeof(float) * b, hipMemcpyDeviceToHost, e->st));
-        if (sync_and_check(e, "evaluate_pv")) return OMOK_ERR_HIP;
-        e->evals += b;
-    }
-    return OMOK_OK;
-}
-
-// Debug / evidence entry point: the same forward, but the PRE-softmax policy logits and the PRE-tanh value (network.rs:188-247
-// before the Tanh / Softmax ops), so that precision can be stated on logits as well as on the outputs the reference API returns.
-extern "C" int omok_evaluate_logits(omok_engine* e, const float* in, int32_t batch, float* logits, float* vpre) {
-    if (!e || !in || !logits || batch < 0) return OMOK_ERR_INVALID;
-    if (need_net(e)) return OMOK_ERR_STATE;
-    if (e->round_reqs >= 0 || e->mirror_reqs >= 0) return fail(e, OMOK_ERR_STATE, "omok_evaluate_logits while a round / mirror batch is pending");
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    const size_t in_row = 3 * (size_t)e->hw;
-    const int piece = e->net.mode == OMOK_NET_F32 ? std::min(e->net.chunk, e->net.max_b) : e->net.max_b;
-    float* d_pack = e->net.in_f32;
+    const int piece = logits && net.mode == OMOK_NET_F32 ? std::min(net.chunk, net.max_b) : net.max_b; // (OMOK_NET_F32 keeps the logits of its last chunk only)
     for (int32_t done = 0; done < batch; done += piece) {
         const int b = std::min<int32_t>(piece, batch - done);
-        HIPCHK(e, hipMemcpyAsync(e->net.in_f32, in + (size_t)done * in_row, sizeof(float) * in_row * b, hipMemcpyHostToDevice, e->st));
+        HIPCHK(e, hipMemcpyAsync(net.in_f32, in + (size_t)done * in_row, sizeof(float) * in_row * b, hipMemcpyHostToDevice, e->st));
         HIPCHK(e, hipMemcpyAsync(e->S.d_count, &b, sizeof(int32_t), hipMemcpyHostToDevice, e->st));
-        net_forward_inputs(e->net, e->S, b, e->st, &e->prof);
-        int stride = 0;
-        const float* lg = net_logits(e->net, &stride);
-        const size_t tot = (size_t)b * e->hw;
-        k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(lg, d_pack, e->hw, stride, b);
-        HIPCHK(e, hipMemcpyAsync(logits + (size_t)done * e->hw, d_pack, sizeof(float) * tot, hipMemcpyDeviceToHost, e->st));
-        if (vpre) HIPCHK(e, hipMemcpyAsync(vpre + done, e->net.vpre, sizeof(float) * b, hipMemcpyDeviceToHost, e->st));
-        if (sync_and_check(e, "evaluate_logits")) return OMOK_ERR_HIP;
+        net_forward_inputs(net, e->S, b, e->st, &e->prof);
+        int stride = e->rowp;
+        const float* src = logits ? net_logits(net, &stride) : net.p;
+        if (rows_to_host(e, net, src, stride, logits ? net.vpre : net.v, b, p + (size_t)done * e->hw, v ? v + done : nullptr)) return OMOK_ERR_HIP;
+        if (sync_and_check(e, logits ? "evaluate_logits" : "evaluate_pv")) return OMOK_ERR_HIP;
         e->evals += b;
     }
     return OMOK_OK;
 }
+extern "C" int omok_evaluate_pv(omok_engine* e, const float* in, int32_t batch, float* p, float* v) { return evaluate_inputs(e, false, in, batch, p, v); }
+extern "C" int omok_evaluate_logits(omok_engine* e, const float* in, int32_t batch, float* logits, float* vpre) { return evaluate_inputs(e, true, in, batch, logits, vpre); }
 
 // ---- environment -------------------------------------------------------------------------------
 extern "C" int omok_env_play(omok_engine* e, const int32_t* moves, int32_t batch, int32_t len, int32_t* status_out,
                              uint8_t* boards_out, uint8_t* turns_out, uint16_t* legal_out) {
     if (!e || batch < 1 || len < 0 || (len > 0 && !moves)) return OMOK_ERR_INVALID;
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    int32_t *d_moves = nullptr, *d_status = nullptr;
-    uint8_t *d_boards = nullptr, *d_turns = nullptr;
-    uint16_t* d_legal = nullptr;
     const size_t ml = (size_t)batch * (size_t)(len > 0 ? len : 1);
-    HIPCHK(e, hipMalloc((void**)&d_moves, ml * 4));
-    HIPCHK(e, hipMalloc((void**)&d_status, ml * 4));
-    HIPCHK(e, hipMalloc((void**)&d_boards, (size_t)batch * e->hw));
-    HIPCHK(e, hipMalloc((void**)&d_turns, (size_t)batch));
-    HIPCHK(e, hipMalloc((void**)&d_legal, (size_t)batch * 2));
+    Scratch sc;
+    int32_t *d_moves = sc.get<int32_t>(ml), *d_status = sc.get<int32_t>(ml);
+    uint8_t *d_boards = sc.get<uint8_t>((size_t)batch * e->hw), *d_turns = sc.get<uint8_t>((size_t)batch);
+    uint16_t* d_legal = sc.get<uint16_t>((size_t)batch);
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_play: device allocation failed");
     if (len > 0) hipMemcpyAsync(d_moves, moves, ml * 4, hipMemcpyHostToDevice, e->st);
     launch_env_play(e->n, d_moves, batch, len, d_status, d_boards, d_turns, d_legal, e->st);
     if (status_out && len > 0) hipMemcpyAsync(status_out, d_status, ml * 4, hipMemcpyDeviceToHost, e->st);
     if (boards_out) hipMemcpyAsync(boards_out, d_boards, (size_t)batch * e->hw, hipMemcpyDeviceToHost, e->st);
     if (turns_out) hipMemcpyAsync(turns_out, d_turns, (size_t)batch, hipMemcpyDeviceToHost, e->st);
     if (legal_out) hipMemcpyAsync(legal_out, d_legal, (size_t)batch * 2, hipMemcpyDeviceToHost, e->st);
-    const int rc = sync_and_check(e, "env_play");
-    hipFree(d_moves); hipFree(d_status); hipFree(d_boards); hipFree(d_turns); hipFree(d_legal);
-    return rc ? OMOK_ERR_HIP : OMOK_OK;
+    return sync_and_check(e, "env_play") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 extern "C" int omok_encode_nn_input(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch,
                                     int32_t mode, float* out) {
     if (!e || !boards || !turns || !out || batch < 1 || (mode != 0 && mode != 1)) return OMOK_ERR_INVALID;
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    uint8_t *d_boards = nullptr, *d_turns = nullptr;
-    float* d_out = nullptr;
-    HIPCHK(e, hipMalloc((void**)&d_boards, (size_t)batch * e->hw));
-    HIPCHK(e, hipMalloc((void**)&d_turns, (size_t)batch));
-    HIPCHK(e, hipMalloc((void**)&d_out, (size_t)batch * 3 * e->hw * 4));
+    Scratch sc;
+    uint8_t *d_boards = sc.get<uint8_t>((size_t)batch * e->hw), *d_turns = sc.get<uint8_t>((size_t)batch);
+    float* d_out = sc.get<float>((size_t)batch * 3 * e->hw);
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "encode_nn_input: device allocation failed");
     hipMemcpyAsync(d_boards, boards, (size_t)batch * e->hw, hipMemcpyHostToDevice, e->st);
     hipMemcpyAsync(d_turns, turns, (size_t)batch, hipMemcpyHostToDevice, e->st);
     launch_encode_boards(e->n, d_boards, d_turns, batch, mode, d_out, e->st);
     hipMemcpyAsync(out, d_out, (size_t)batch * 3 * e->hw * 4, hipMemcpyDeviceToHost, e->st);
-    const int rc = sync_and_check(e, "encode_nn_input");
-    hipFree(d_boards); hipFree(d_turns); hipFree(d_out);
-    return rc ? OMOK_ERR_HIP : OMOK_OK;
+    return sync_and_check(e, "encode_nn_input") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 // ---- self-play ---------------------------------------------------------------------------------
@@ -863,6 +878,28 @@ static int enqueue_root_policy(omok_engine* e, Net& net, float* dst) {
     return 0;
 }
 
+// what the four reset entry points ask of the nets: net 1 committed; a match: net 2 too, and the split in range
+static int check_reset(omok_engine* e, bool match, int split) {
+    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    if (!match) return 0;
+    if (!e->net2 || !e->net2->committed) return fail(e, OMOK_ERR_STATE, "net 2 not loaded/committed (omok_net2_load x31 + omok_net2_commit)");
+    if (split < 0 || split > e->cfg.games) return fail(e, OMOK_ERR_INVALID, "split %d outside [0, games = %d]", split, e->cfg.games);
+    return 0;
+}
+
+// the host's bookkeeping of a successful reset; start_ply: the stone count of the positions (a game's ply is its stone count: side = ply & 1, the RNG counters)
+static void begin_episode(omok_engine* e, bool match, int split, int start_ply) {
+    e->key = e->cfg.seed + e->episode * 0x9E3779B97F4A7C15ULL; // a fresh RNG stream per episode (the reference draws thread_rng anew, trainer.rs:71-93)
+    e->episode += 1;                                           // (every reset is one trainer iteration)
+    e->ply = e->start_ply = start_ply;
+    e->log_started = e->log_on;
+    e->reset_done = true;
+    e->sampled = false;
+    e->round_reqs = e->mirror_reqs = -1;
+    e->match = match;
+    e->split = match ? split : 0;
+}
+
 static int reset_episode(omok_engine* e, bool match, int split) {
     if (enqueue_root_policy(e, e->net, e->d_root_policy)) return OMOK_ERR_HIP;
     if (match && enqueue_root_policy(e, *e->net2, e->d_root_policy2)) return OMOK_ERR_HIP;
@@ -871,22 +908,13 @@ static int reset_episode(omok_engine* e, bool match, int split) {
     if (e->log_on) hipMemsetAsync(e->log.start_board, 0, (size_t)e->cfg.games * e->hw, e->st); // the log starts at Environment::new()
     invalidate_nets(e);
     if (sync_and_check(e, match ? "match_reset" : "selfplay_reset")) return OMOK_ERR_HIP;
-    e->log_started = e->log_on;
-    e->key = e->cfg.seed + e->episode * 0x9E3779B97F4A7C15ULL; // a fresh RNG stream per episode (the reference draws thread_rng anew, trainer.rs:71-93)
-    e->episode += 1;
-    e->ply = 0;
-    e->start_ply = 0;
-    e->reset_done = true;
-    e->sampled = false;
-    e->round_reqs = e->mirror_reqs = -1;
-    e->match = match;
-    e->split = match ? split : 0;
+    begin_episode(e, match, split, 0);
     return OMOK_OK;
 }
 
 extern "C" int omok_selfplay_reset(omok_engine* e) {
     if (!e) return OMOK_ERR_INVALID;
-    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    if (int rc = check_reset(e, false, 0)) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     return reset_episode(e, false, 0);
 }
@@ -894,9 +922,7 @@ extern "C" int omok_selfplay_reset(omok_engine* e) {
 // benchmark/src/main.rs:14-108: net 1 against net 2, Agent::new of each agent with its own model (agent.rs:16-35)
 extern "C" int omok_match_reset(omok_engine* e, int32_t split) {
     if (!e) return OMOK_ERR_INVALID;
-    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
-    if (!e->net2 || !e->net2->committed) return fail(e, OMOK_ERR_STATE, "net 2 not loaded/committed (omok_net2_load x31 + omok_net2_commit)");
-    if (split < 0 || split > e->cfg.games) return fail(e, OMOK_ERR_INVALID, "split %d outside [0, games = %d]", split, e->cfg.games);
+    if (int rc = check_reset(e, true, split)) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     return reset_episode(e, true, split);
 }
@@ -912,22 +938,19 @@ static const char* verdict_text(int v) {
     }
 }
 
-// uploads `batch` boards and runs k_position_check on them; *d_boards_out (non-NULL: the caller frees it) keeps the device copy
-static int check_positions(omok_engine* e, const uint8_t* boards, int batch, int32_t* verdict_out, int32_t* stones_out, uint8_t** d_boards_out) {
-    uint8_t* d_boards = nullptr;
-    int32_t* d_out = nullptr; // [2][B] verdicts, stone counts
+// uploads `batch` boards into the caller's scratch and runs k_position_check on them; *d_boards_out (may be NULL) = the device copy
+static int check_positions(omok_engine* e, Scratch& sc, const uint8_t* boards, int batch, int32_t* verdict_out, int32_t* stones_out, uint8_t** d_boards_out) {
     const size_t B = (size_t)batch;
-    HIPCHK(e, hipMalloc((void**)&d_boards, B * e->hw));
-    if (hipMalloc((void**)&d_out, 2 * B * 4) != hipSuccess) { hipFree(d_boards); return fail(e, OMOK_ERR_HIP, "position check: device allocation failed"); }
+    uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
+    int32_t* d_out = sc.get<int32_t>(2 * B); // [2][B] verdicts, stone counts
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "position check: device allocation failed");
     hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
     launch_position_check(e->n, d_boards, batch, d_out, d_out + B, e->st);
     hipMemcpyAsync(verdict_out, d_out, B * 4, hipMemcpyDeviceToHost, e->st);
     if (stones_out) hipMemcpyAsync(stones_out, d_out + B, B * 4, hipMemcpyDeviceToHost, e->st);
-    const int rc = sync_and_check(e, "position check");
-    hipFree(d_out);
-    if (rc || !d_boards_out) hipFree(d_boards);
-    else *d_boards_out = d_boards;
-    return rc ? OMOK_ERR_HIP : OMOK_OK;
+    if (sync_and_check(e, "position check")) return OMOK_ERR_HIP;
+    if (d_boards_out) *d_boards_out = d_boards;
+    return OMOK_OK;
 }
 
 // the rules of Environment::place_stone (environment/src/lib.rs:104-166) read backwards: can an alternating game from Environment::new() be in
@@ -935,7 +958,8 @@ static int check_positions(omok_engine* e, const uint8_t* boards, int batch, int
 extern "C" int omok_env_check_positions(omok_engine* e, const uint8_t* boards, int32_t batch, int32_t* verdict_out, int32_t* stones_out) {
     if (!e || !boards || !verdict_out || batch < 1) return OMOK_ERR_INVALID;
     ENTER(e);
-    return check_positions(e, boards, batch, verdict_out, stones_out, nullptr);
+    Scratch sc;
+    return check_positions(e, sc, boards, batch, verdict_out, stones_out, nullptr);
 }
 
 // Agent::new (agent.rs:16-35) for the agents of every game on a given environment: evaluate_p of the position in Player mode (:19-20), masked
@@ -946,27 +970,19 @@ static int reset_from_positions(omok_engine* e, const uint8_t* boards, bool matc
     const char* what = match ? "match_reset_from" : "selfplay_reset_from";
     const int G = e->cfg.games;
     std::vector<int32_t> verdict((size_t)G), stones((size_t)G);
+    Scratch sc;
     uint8_t* d_boards = nullptr;
-    if (check_positions(e, boards, G, verdict.data(), stones.data(), &d_boards)) return OMOK_ERR_HIP;
+    if (check_positions(e, sc, boards, G, verdict.data(), stones.data(), &d_boards)) return OMOK_ERR_HIP;
     // nothing of the engine has been touched so far: a rejected call leaves trees, games, episode counter and replay buffer as they were
     for (int g = 0; g < G; ++g)
-        if (verdict[g] != 0) {
-            hipFree(d_boards);
-            return fail(e, OMOK_ERR_ILLEGAL, "game %d: verdict %d (%s)", g, verdict[g], verdict_text(verdict[g]));
-        }
+        if (verdict[g] != 0) return fail(e, OMOK_ERR_ILLEGAL, "game %d: verdict %d (%s)", g, verdict[g], verdict_text(verdict[g]));
     for (int g = 1; g < G; ++g)
-        if (stones[g] != stones[0]) {
-            hipFree(d_boards);
+        if (stones[g] != stones[0])
             return fail(e, OMOK_ERR_INVALID, "game %d has %d stones, game 0 has %d: all games of an episode share the side to move", g, stones[g], stones[0]);
-        }
     const int s0 = stones[0];
-    if (s0 == 0) { // Environment::new() everywhere: the ordinary reset's own path (one empty-board row per net, nothing to mask)
-        hipFree(d_boards);
-        return reset_episode(e, match, split);
-    }
-    auto done = [&](int rc) { hipFree(d_boards); return rc; };
-    uint8_t* d_turns = nullptr;
-    if (hipMalloc((void**)&d_turns, (size_t)G) != hipSuccess) return done(fail(e, OMOK_ERR_HIP, "%s: device allocation failed", what));
+    if (s0 == 0) return reset_episode(e, match, split); // Environment::new() everywhere: the ordinary reset's own path (one empty-board row per net, nothing to mask)
+    uint8_t* d_turns = sc.get<uint8_t>((size_t)G);
+    if (!d_turns) return fail(e, OMOK_ERR_HIP, "%s: device allocation failed", what);
     // the G positions as plain rows in game order: the launch omok_evaluate_pv makes for the same rows (G <= the net batch); in a match every
     // game has one tree of each net, so each net evaluates all G rows
     hipMemsetAsync(d_turns, s0 & 1, (size_t)G, e->st);
@@ -984,26 +1000,15 @@ static int reset_from_positions(omok_engine* e, const uint8_t* boards, bool matc
     e->prof.end(e->st);
     if (e->log_on) hipMemcpyAsync(e->log.start_board, d_boards, (size_t)G * e->hw, hipMemcpyDeviceToDevice, e->st); // the log starts at the given positions
     invalidate_nets(e);
-    const int rc = sync_and_check(e, what);
-    hipFree(d_turns);
-    if (rc) return done(OMOK_ERR_HIP);
+    if (sync_and_check(e, what)) return OMOK_ERR_HIP;
     e->evals += match ? 2 * G : G;
-    e->key = e->cfg.seed + e->episode * 0x9E3779B97F4A7C15ULL; // as omok_selfplay_reset: every reset is one trainer iteration
-    e->episode += 1;
-    e->ply = s0; // a game's ply is its stone count: side = ply & 1, the RNG counters
-    e->start_ply = s0;
-    e->log_started = e->log_on;
-    e->reset_done = true;
-    e->sampled = false;
-    e->round_reqs = e->mirror_reqs = -1;
-    e->match = match;
-    e->split = match ? split : 0;
-    return done(OMOK_OK);
+    begin_episode(e, match, split, s0);
+    return OMOK_OK;
 }
 
 extern "C" int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards) {
     if (!e || !boards) return OMOK_ERR_INVALID;
-    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
+    if (int rc = check_reset(e, false, 0)) return rc;
     ENTER(e);
     return reset_from_positions(e, boards, false, 0);
 }
@@ -1011,9 +1016,7 @@ extern "C" int omok_selfplay_reset_from(omok_engine* e, const uint8_t* boards) {
 // omok_match_reset on given environments: an opening book for benchmark/src/main.rs:14-108, Agent::new of every agent with its own net
 extern "C" int omok_match_reset_from(omok_engine* e, int32_t split, const uint8_t* boards) {
     if (!e || !boards) return OMOK_ERR_INVALID;
-    if (!e->net.committed) return fail(e, OMOK_ERR_STATE, "net not loaded/committed (omok_net_load x31 + omok_net_commit)");
-    if (!e->net2 || !e->net2->committed) return fail(e, OMOK_ERR_STATE, "net 2 not loaded/committed (omok_net2_load x31 + omok_net2_commit)");
-    if (split < 0 || split > e->cfg.games) return fail(e, OMOK_ERR_INVALID, "split %d outside [0, games = %d]", split, e->cfg.games);
+    if (int rc = check_reset(e, true, split)) return rc;
     ENTER(e);
     return reset_from_positions(e, boards, true, split);
 }
@@ -1026,17 +1029,16 @@ extern "C" int omok_env_random_positions(omok_engine* e, uint64_t key, int64_t f
     if (stones < 0 || stones >= e->hw) return fail(e, OMOK_ERR_INVALID, "stones %d outside [0, %d)", stones, e->hw);
     if (batch < 1) return fail(e, OMOK_ERR_INVALID, "batch %d < 1", batch);
     ENTER(e);
-    uint8_t* d_out = nullptr; // [B][HW] boards, then [B] ok
     const size_t B = (size_t)batch;
-    HIPCHK(e, hipMalloc((void**)&d_out, B * e->hw + B));
+    Scratch sc;
+    uint8_t* d_out = sc.get<uint8_t>(B * e->hw + B); // [B][HW] boards, then [B] ok
+    if (!d_out) return fail(e, OMOK_ERR_HIP, "env_random_positions: device allocation failed");
     e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling: tools/reset_from_timing.py)
     launch_random_positions(e->n, key, first_game, stones, batch, d_out, d_out + B * e->hw, e->st);
     e->prof.end(e->st);
     hipMemcpyAsync(boards_out, d_out, B * e->hw, hipMemcpyDeviceToHost, e->st);
     hipMemcpyAsync(ok_out, d_out + B * e->hw, B, hipMemcpyDeviceToHost, e->st);
-    const int rc = sync_and_check(e, "env_random_positions");
-    hipFree(d_out);
-    return rc ? OMOK_ERR_HIP : OMOK_OK;
+    return sync_and_check(e, "env_random_positions") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 static int need_reset(omok_engine* e) {
@@ -1044,47 +1046,35 @@ static int need_reset(omok_engine* e) {
     return 0;
 }
 
+// the net whose v holds the backups' values of a round on `side` (match episodes: the first block's, after match_join)
+static Net& backup_net(omok_engine* e, int side) { return e->match ? net_at(e, side) : e->net; }
+
+// a block's forward and the scatter of its policies (backups_inline: the scatter kernel runs the round's backups too)
+static void forward_and_scatter(omok_engine* e, const Block& B, int side, int rows_cap, bool backups_inline) {
+    Net& X = *B.net;
+    // the split-precision net hands over its logits: softmax / tanh run inside the policy scatter (no [requests][ROWP] round trip of p)
+    const bool fused = net_logits_cover_batch(X, rows_cap);
+    block_forward(e, B, rows_cap, side, fused);
+    e->prof.begin(PC_TREE_OTHER, e->st);
+    if (fused) {
+        int lrow = 0;
+        const float* lg = net_logits(X, &lrow);
+        launch_softmax_scatter(e->n, B.view, side, lg, lrow, X.v, X.vpre, rows_cap, e->st, backups_inline);
+    } else launch_scatter(e->n, B.view, side, X.p, X.v, rows_cap, e->st, backups_inline);
+    e->prof.end(e->st);
+}
+
 // defer_backups (run loops): this round's backups are not launched here; pending_backups: the previous round's run at the head of this round's
 // kernel.  The caller launches the last round's backups itself (launch_backups).
 // A round of a match episode: the one request list in two blocks, one forward per net on its own block, the policies scattered block by block,
 // then v of the second block joined behind the first's (in the first block's net, which the backups read).
-static void enqueue_match_round(omok_engine* e, int side, int K, bool eval_and_scatter, int alive, bool defer_backups) {
-    const int max_req = std::min(alive * K, e->net.max_b);
-    launch_scan(e->n, e->S, side, K, e->st, e->d_evals);
-    match_split(e, side, max_req);
-    e->prof.end(e->st);
-    if (!eval_and_scatter) return;
-    for (int b = 0; b < 2; ++b) {
-        if (!block_live(e, b)) continue;
-        Net& X = net_at(e, side ^ b);
-        const Store V = block_view(e, b);
-        const bool fused = net_logits_cover_batch(X, alive * K);
-        match_forward(e, b, side, alive * K, side, fused);
-        e->prof.begin(PC_TREE_OTHER, e->st);
-        if (fused) {
-            int lrow = 0;
-            const float* lg = net_logits(X, &lrow);
-            launch_softmax_scatter(e->n, V, side, lg, lrow, X.v, X.vpre, alive * K, e->st, false);
-        } else launch_scatter(e->n, V, side, X.p, X.v, alive * K, e->st, false);
-        e->prof.end(e->st);
-    }
-    e->prof.begin(PC_TREE_OTHER, e->st);
-    match_join(e, side, false, max_req);
-    if (!defer_backups) launch_backups(e->n, e->S, side, net_at(e, side).v, e->st);
-    e->prof.end(e->st);
-}
-
-// the net whose v holds the backups' values of a round on `side` (match episodes: the first block's, after match_join)
-static Net& backup_net(omok_engine* e, int side) { return e->match ? net_at(e, side) : e->net; }
-
 static void enqueue_round(omok_engine* e, int round, int K, float eps, float alpha, bool eval_and_scatter, int alive, bool defer_backups = false,
                           bool pending_backups = false) {
     const int side = e->ply & 1;
     // run-loop rounds whose forward groups the requests by parent (sib_round): no k_scan and no k_fill.  k_round zeroes the grouping counters and leaves every
     // game's request count; k_group derives the request offsets and the round's total from them and writes the dense request list.  The step-wise API and match
     // episodes keep the separate kernels (the step-wise callers read the request list before the forward).
-    int max_req = alive * K;
-    if (max_req > e->net.max_b) max_req = e->net.max_b;
+    const int max_req = std::min(alive * K, e->net.max_b);
     const bool sib_round = !e->match && eval_and_scatter && net_round_takes_sibling_path(e->net, max_req);
     RoundArgs a{side, round, K, e->ply, eps, alpha, e->key, e->cfg.game_offset, pending_backups ? backup_net(e, side).v : nullptr,
                 sib_round ? e->d_req_cnt : nullptr, sib_round ? e->net.d_gcnt : nullptr, sib_round ? NET_GCNT_INTS : 0};
@@ -1093,29 +1083,26 @@ static void enqueue_round(omok_engine* e, int round, int K, float eps, float alp
     launch_round(e->n, e->S, a, e->st);
     e->prof.end(e->st);
     e->prof.begin(PC_TREE_OTHER, e->st);
-    if (e->match) {
-        enqueue_match_round(e, side, K, eval_and_scatter, alive, defer_backups);
-        e->prof.round_end();
-        return;
-    }
     if (!sib_round) launch_scan(e->n, e->S, side, K, e->st, e->d_evals);
-    e->net.gcnt_zeroed = e->net.fill_in_group = sib_round;
-    e->net.scan_cnt = sib_round ? e->d_req_cnt : nullptr;
-    e->net.scan_evals = e->d_evals;
-    e->net.fill_side = side;
-    e->net.fill_k = K;
+    if (e->match) match_split(e, side, max_req);
+    else { // the hand-over to the forward of net 1
+        e->net.gcnt_zeroed = e->net.fill_in_group = sib_round;
+        e->net.scan_cnt = sib_round ? e->d_req_cnt : nullptr;
+        e->net.scan_evals = e->d_evals;
+        e->net.fill_side = side;
+        e->net.fill_k = K;
+    }
     e->prof.end(e->st);
     if (eval_and_scatter) {
-        // the split-precision net hands over its logits: softmax / tanh run inside the policy scatter (no [requests][ROWP] round trip of p)
-        const bool fused = net_logits_cover_batch(e->net, alive * K);
-        net_forward_requests(e->net, e->S, alive * K, e->st, &e->prof, side, fused);
-        e->prof.begin(PC_TREE_OTHER, e->st);
-        if (fused) {
-            int lrow = 0;
-            const float* lg = net_logits(e->net, &lrow);
-            launch_softmax_scatter(e->n, e->S, side, lg, lrow, e->net.v, e->net.vpre, alive * K, e->st, !defer_backups);
-        } else launch_scatter(e->n, e->S, side, e->net.p, e->net.v, alive * K, e->st, !defer_backups);
-        e->prof.end(e->st);
+        Block blk[2];
+        const int nb = eval_blocks(e, side, alive * K, false, blk);
+        for (int i = 0; i < nb; ++i) forward_and_scatter(e, blk[i], side, alive * K, !e->match && !defer_backups);
+        if (e->match) { // the blocks' scatters ran no backups: they read one v array in list order
+            e->prof.begin(PC_TREE_OTHER, e->st);
+            match_join(e, side, false, max_req);
+            if (!defer_backups) launch_backups(e->n, e->S, side, net_at(e, side).v, e->st);
+            e->prof.end(e->st);
+        }
     }
     e->prof.round_end();
 }
@@ -1143,10 +1130,17 @@ static int check_exec_args(omok_engine* e, int count, int K, float eps, float al
     return 0;
 }
 
+// what every entry point that searches asks first: the nets, an episode, the search arguments (temperature: the sampling of the run loops)
+static int check_search(omok_engine* e, int count, int K, float eps, float alpha, float temperature = 1.0f) {
+    if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
+    if (check_exec_args(e, count, K, eps, alpha)) return OMOK_ERR_INVALID;
+    if (!(temperature > 0.0f)) return fail(e, OMOK_ERR_INVALID, "temperature must be > 0");
+    return 0;
+}
+
 extern "C" int omok_execute(omok_engine* e, int32_t count, int32_t batch_size, float epsilon, float alpha) {
     if (!e) return OMOK_ERR_INVALID;
-    if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
-    if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
+    if (int rc = check_search(e, count, batch_size, epsilon, alpha)) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     uint32_t bits = 0, alive = 0;
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
@@ -1158,16 +1152,29 @@ extern "C" int omok_execute(omok_engine* e, int32_t count, int32_t batch_size, f
 
 // MCTSExecutor::run (alpha-zero/src/mcts_executor.rs:29-255): ONE tree, rounds as concurrent tasks.  `waves` rounds run at a time
 // on the shared tree of game 0 (one workgroup of `waves` wavefronts); their requests form one net batch.
-extern "C" int omok_execute_shared(omok_engine* e, int32_t count, int32_t batch_size, float epsilon, float alpha, int32_t waves) {
-    if (!e) return OMOK_ERR_INVALID;
-    if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
-    if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
-    if (no_match(e, "omok_execute_shared")) return OMOK_ERR_STATE;
-    if (e->cfg.games != 1) return fail(e, OMOK_ERR_INVALID, "omok_execute_shared searches ONE tree: create the engine with games = 1 (got %d)", e->cfg.games);
-    if (waves < 1 || waves > MAX_TREE_WAVES || waves * batch_size > e->net.max_b) // (cfg.max_tree_waves sizes the net batch: it binds through max_b)
+// With a RECORDED interleaving (rec, tests): every simulation and every backup of the scatter phase runs under the tree lock and the lock order is
+// written down, group by group, together with the net outputs of the group's requests -- everything a CPU restatement of MCTSExecutor::run needs
+// to replay the run exactly (tests/test_gpu_shared_tree.py).  Recording reads every group back: without it nothing here waits for the device.
+struct SharedRecording {
+    uint8_t *sim_order, *backup_order; // [groups][waves * batch_size] wave ids in lock order
+    int32_t* group_counts;             // [groups][3] simulations, backups, requests
+    float *p, *v;                      // [cap_requests][HW], [cap_requests]
+    int32_t cap_requests, *n_groups, *n_requests;
+};
+static int execute_shared(omok_engine* e, const char* who, int count, int K, float epsilon, float alpha, int waves, const SharedRecording* rec) {
+    if (int rc = check_search(e, count, K, epsilon, alpha)) return rc;
+    if (no_match(e, who)) return OMOK_ERR_STATE;
+    if (e->cfg.games != 1) return fail(e, OMOK_ERR_INVALID, "%s searches ONE tree: create the engine with games = 1 (got %d)", who, e->cfg.games);
+    if (waves < 1 || waves > MAX_TREE_WAVES || waves * K > e->net.max_b) // (cfg.max_tree_waves sizes the net batch: it binds through max_b)
         return fail(e, OMOK_ERR_INVALID, "waves must be in [1, %d] and waves * batch_size <= %d (the net batch, sized by max(games, max_tree_waves = %d) * max_batch_k)",
                     MAX_TREE_WAVES, e->net.max_b, e->cfg.max_tree_waves);
-    HIPCHK(e, hipSetDevice(e->cfg.device));
+    ENTER(e);
+    const size_t per = (size_t)waves * K;
+    Scratch sc;
+    uint8_t* d_rec = rec ? sc.get<uint8_t>(2 * per) : nullptr;  // [2][per] wave ids: simulations, backups
+    uint32_t* d_pos = rec ? sc.get<uint32_t>(2) : nullptr;      // [2]
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "recorded mode: device allocation failed");
+    std::vector<float> prow(rec ? per * e->rowp : 0);
     uint32_t bits = 0, alive = 0;
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
     const int side = e->ply & 1;
@@ -1175,92 +1182,76 @@ extern "C" int omok_execute_shared(omok_engine* e, int32_t count, int32_t batch_
     e->prof.begin(PC_ROUND, e->st);
     launch_round(e->n, e->S, a, e->st); // K = 0, round 0: the root's Dirichlet noise only (mcts_executor.rs:38-68)
     e->prof.end(e->st);
-    int exec_count = count / batch_size; // :70-74
-    if (exec_count * batch_size != count) exec_count += 1;
-    a.K = batch_size;
-    for (int group = 0; group * waves < exec_count; ++group) {
+    int exec_count = count / K; // :70-74
+    if (exec_count * K != count) exec_count += 1;
+    a.K = K;
+    int group = 0, total_req = 0;
+    for (; group * waves < exec_count; ++group) {
+        if (rec) {
+            hipMemsetAsync(d_rec, 0xFF, 2 * per, e->st);
+            hipMemsetAsync(d_pos, 0, 8, e->st);
+        }
         e->prof.begin(PC_ROUND, e->st);
-        launch_round_shared(e->n, e->S, a, exec_count, group, waves, e->d_sh_req, e->d_sh_cnt, e->st);
+        launch_round_shared(e->n, e->S, a, exec_count, group, waves, e->d_sh_req, e->d_sh_cnt, e->st, d_rec, d_pos);
         k_add_evals<<<1, 64, 0, e->st>>>(e->S.d_count, e->d_evals);
         e->prof.end(e->st);
-        net_forward_requests(e->net, e->S, waves * batch_size, e->st, &e->prof);
+        int32_t cnt = 0;
+        if (rec) {
+            if (hipMemcpyAsync(&cnt, e->S.d_count, 4, hipMemcpyDeviceToHost, e->st) != hipSuccess || sync_and_check(e, "execute_shared_recorded")) return OMOK_ERR_HIP;
+            if (total_req + cnt > rec->cap_requests) return fail(e, OMOK_ERR_INVALID, "recorded mode: more than cap_requests = %d requests", rec->cap_requests);
+        }
+        if (!rec || cnt > 0) net_forward_requests(e->net, e->S, waves * K, e->st, &e->prof); // (recorded: a group without requests has no forward)
+        if (cnt > 0) {
+            hipMemcpyAsync(prow.data(), e->net.p, sizeof(float) * (size_t)cnt * e->rowp, hipMemcpyDeviceToHost, e->st);
+            hipMemcpyAsync(rec->v + total_req, e->net.v, sizeof(float) * cnt, hipMemcpyDeviceToHost, e->st);
+        }
         e->prof.begin(PC_TREE_OTHER, e->st);
-        launch_scatter_shared(e->n, e->S, side, e->net.p, e->net.v, waves * batch_size, waves, e->d_sh_req, e->d_sh_cnt, e->st);
+        launch_scatter_shared(e->n, e->S, side, e->net.p, e->net.v, waves * K, waves, e->d_sh_req, e->d_sh_cnt, e->st, rec ? d_rec + per : nullptr, rec ? d_pos + 1 : nullptr);
         e->prof.end(e->st);
+        if (!rec) continue;
+        uint32_t pos[2] = {0, 0};
+        hipMemcpyAsync(rec->sim_order + (size_t)group * per, d_rec, per, hipMemcpyDeviceToHost, e->st);
+        hipMemcpyAsync(rec->backup_order + (size_t)group * per, d_rec + per, per, hipMemcpyDeviceToHost, e->st);
+        hipMemcpyAsync(pos, d_pos, 8, hipMemcpyDeviceToHost, e->st);
+        if (sync_and_check(e, "execute_shared_recorded")) return OMOK_ERR_HIP;
+        for (int r = 0; r < cnt; ++r) memcpy(rec->p + (size_t)(total_req + r) * e->hw, prow.data() + (size_t)r * e->rowp, sizeof(float) * e->hw);
+        rec->group_counts[3 * group] = (int32_t)pos[0];
+        rec->group_counts[3 * group + 1] = (int32_t)pos[1];
+        rec->group_counts[3 * group + 2] = cnt;
+        total_req += cnt;
     }
-    e->sims += (double)exec_count * batch_size * alive;
+    if (rec) {
+        *rec->n_groups = group;
+        *rec->n_requests = total_req;
+    }
+    e->sims += (double)exec_count * K * alive;
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
     return tree_error(e, bits);
 }
 
-// The same search with a RECORDED interleaving (tests): every simulation and every backup of the scatter phase runs under the tree lock and
-// the lock order is written down, group by group, together with the net outputs of the group's requests -- everything a CPU restatement of
-// MCTSExecutor::run needs to replay the run exactly (tests/test_gpu_shared_tree.py).
+extern "C" int omok_execute_shared(omok_engine* e, int32_t count, int32_t batch_size, float epsilon, float alpha, int32_t waves) {
+    if (!e) return OMOK_ERR_INVALID;
+    return execute_shared(e, "omok_execute_shared", count, batch_size, epsilon, alpha, waves, nullptr);
+}
+
 extern "C" int omok_execute_shared_recorded(omok_engine* e, int32_t count, int32_t batch_size, float epsilon, float alpha, int32_t waves,
                                             uint8_t* sim_order, uint8_t* backup_order, int32_t* group_counts, float* p, float* v,
                                             int32_t cap_requests, int32_t* n_groups, int32_t* n_requests) {
     if (!e || !sim_order || !backup_order || !group_counts || !p || !v || !n_groups || !n_requests) return OMOK_ERR_INVALID;
-    if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
-    if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
-    if (no_match(e, "omok_execute_shared_recorded")) return OMOK_ERR_STATE;
-    if (e->cfg.games != 1) return fail(e, OMOK_ERR_INVALID, "omok_execute_shared_recorded searches ONE tree: create the engine with games = 1 (got %d)", e->cfg.games);
-    if (waves < 1 || waves > MAX_TREE_WAVES || waves * batch_size > e->net.max_b) // (cfg.max_tree_waves sizes the net batch: it binds through max_b)
-        return fail(e, OMOK_ERR_INVALID, "waves must be in [1, %d] and waves * batch_size <= %d (the net batch, sized by max(games, max_tree_waves = %d) * max_batch_k)",
-                    MAX_TREE_WAVES, e->net.max_b, e->cfg.max_tree_waves);
-    ENTER(e);
-    const size_t per = (size_t)waves * batch_size;
-    uint8_t* d_rec = nullptr;   // [2][per] wave ids: simulations, backups
-    uint32_t* d_pos = nullptr;  // [2]
-    if (hipMalloc((void**)&d_rec, 2 * per) != hipSuccess || hipMalloc((void**)&d_pos, 8) != hipSuccess) {
-        if (d_rec) hipFree(d_rec);
-        return fail(e, OMOK_ERR_HIP, "recorded mode: device allocation failed");
-    }
-    auto done = [&](int rc) { hipFree(d_rec); hipFree(d_pos); return rc; };
-    uint32_t bits = 0, alive = 0;
-    if (read_status(e, &bits, &alive)) return done(OMOK_ERR_HIP);
-    const int side = e->ply & 1;
-    RoundArgs a{side, 0, 0, e->ply, epsilon, alpha, e->key, e->cfg.game_offset};
-    launch_round(e->n, e->S, a, e->st); // K = 0, round 0: the root's Dirichlet noise only (mcts_executor.rs:38-68)
-    int exec_count = count / batch_size; // :70-74
-    if (exec_count * batch_size != count) exec_count += 1;
-    a.K = batch_size;
-    int groups = 0, total_req = 0;
-    std::vector<float> prow((size_t)per * e->rowp);
-    for (int group = 0; group * waves < exec_count; ++group, ++groups) {
-        hipMemsetAsync(d_rec, 0xFF, 2 * per, e->st);
-        hipMemsetAsync(d_pos, 0, 8, e->st);
-        launch_round_shared(e->n, e->S, a, exec_count, group, waves, e->d_sh_req, e->d_sh_cnt, e->st, d_rec, d_pos);
-        k_add_evals<<<1, 64, 0, e->st>>>(e->S.d_count, e->d_evals);
-        int32_t cnt = 0;
-        if (hipMemcpyAsync(&cnt, e->S.d_count, 4, hipMemcpyDeviceToHost, e->st) != hipSuccess || sync_and_check(e, "execute_shared_recorded")) return done(OMOK_ERR_HIP);
-        if (total_req + cnt > cap_requests) return done(fail(e, OMOK_ERR_INVALID, "recorded mode: more than cap_requests = %d requests", cap_requests));
-        if (cnt > 0) {
-            net_forward_requests(e->net, e->S, waves * batch_size, e->st, &e->prof);
-            hipMemcpyAsync(prow.data(), e->net.p, sizeof(float) * (size_t)cnt * e->rowp, hipMemcpyDeviceToHost, e->st);
-            hipMemcpyAsync(v + total_req, e->net.v, sizeof(float) * cnt, hipMemcpyDeviceToHost, e->st);
-        }
-        launch_scatter_shared(e->n, e->S, side, e->net.p, e->net.v, waves * batch_size, waves, e->d_sh_req, e->d_sh_cnt, e->st, d_rec + per, d_pos + 1);
-        uint32_t pos[2] = {0, 0};
-        hipMemcpyAsync(sim_order + (size_t)group * per, d_rec, per, hipMemcpyDeviceToHost, e->st);
-        hipMemcpyAsync(backup_order + (size_t)group * per, d_rec + per, per, hipMemcpyDeviceToHost, e->st);
-        hipMemcpyAsync(pos, d_pos, 8, hipMemcpyDeviceToHost, e->st);
-        if (sync_and_check(e, "execute_shared_recorded")) return done(OMOK_ERR_HIP);
-        for (int r = 0; r < cnt; ++r) memcpy(p + (size_t)(total_req + r) * e->hw, prow.data() + (size_t)r * e->rowp, sizeof(float) * e->hw);
-        group_counts[3 * group] = (int32_t)pos[0];
-        group_counts[3 * group + 1] = (int32_t)pos[1];
-        group_counts[3 * group + 2] = cnt;
-        total_req += cnt;
-    }
-    *n_groups = groups;
-    *n_requests = total_req;
-    e->sims += (double)exec_count * batch_size * alive;
-    if (read_status(e, &bits, &alive)) return done(OMOK_ERR_HIP);
-    return done(tree_error(e, bits));
+    const SharedRecording rec{sim_order, backup_order, group_counts, p, v, cap_requests, n_groups, n_requests};
+    return execute_shared(e, "omok_execute_shared_recorded", count, batch_size, epsilon, alpha, waves, &rec);
 }
 
 static void enqueue_sample(omok_engine* e, float temperature, int threshold) {
     e->prof.begin(PC_PLY, e->st);
     launch_sample(e->n, e->S, e->ply & 1, e->ply, temperature, threshold, e->key, e->cfg.game_offset, e->d_actions, e->st);
+    e->prof.end(e->st);
+}
+
+// the scripted player's move of every live game (OMOK_OPP_*: the evaluation games further down), staged where the search's sample would be
+static void enqueue_opponent_move(omok_engine* e, int kind) {
+    e->prof.begin(PC_PLY, e->st);
+    launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, e->d_actions, e->st);
     e->prof.end(e->st);
 }
 
@@ -1283,6 +1274,16 @@ static void enqueue_log_move(omok_engine* e, int side) {
     if (e->log_on && e->log_started) launch_log_move(e->n, e->S, side, e->start_ply, e->log, e->st);
 }
 
+// the re-rooting of a ply whose mirror batch (at most max_rows rows) has been evaluated: the policies of the opponent's new roots in one array (a match: the
+// second block's behind the first's), the move log's entry, k_advance
+static void enqueue_advance(omok_engine* e, int max_rows) {
+    const int side = e->ply & 1;
+    if (e->match) match_join(e, 1 - side, true, max_rows);
+    enqueue_log_move(e, side);
+    launch_advance(e->n, e->S, side, backup_net(e, 1 - side).p, e->st);
+    invalidate_nets(e);
+}
+
 static void enqueue_mirror_and_advance(omok_engine* e, int alive) {
     const int side = e->ply & 1;
     e->prof.begin(PC_PLY, e->st);
@@ -1290,21 +1291,39 @@ static void enqueue_mirror_and_advance(omok_engine* e, int alive) {
     k_add_evals<<<1, 64, 0, e->st>>>(e->S.d_count, e->d_evals);
     if (e->match) match_split(e, 1 - side, alive); // ensure_action_exists on the opponent's tree: the opponent's net (benchmark/src/main.rs:79-82,99-102)
     e->prof.end(e->st);
-    if (e->match) {
-        for (int b = 0; b < 2; ++b)
-            if (block_live(e, b)) match_forward(e, b, 1 - side, alive, -1, false);
-        e->prof.begin(PC_PLY, e->st);
-        match_join(e, 1 - side, true, alive);
-        enqueue_log_move(e, side);
-        launch_advance(e->n, e->S, side, net_at(e, 1 - side).p, e->st);
-    } else {
-        net_forward_requests(e->net, e->S, alive, e->st, &e->prof);
-        e->prof.begin(PC_PLY, e->st);
-        enqueue_log_move(e, side);
-        launch_advance(e->n, e->S, side, e->net.p, e->st);
-    }
-    invalidate_nets(e);
+    Block blk[2];
+    const int nb = eval_blocks(e, 1 - side, alive, false, blk);
+    for (int i = 0; i < nb; ++i) block_forward(e, blk[i], alive);
+    e->prof.begin(PC_PLY, e->st);
+    enqueue_advance(e, alive);
     e->prof.end(e->st);
+}
+
+// ---- the ply driver: what the whole-episode calls and the step-wise ones share --------------------------------------------------------------
+struct Search { int count, K; float epsilon, alpha, temperature; int threshold; };
+
+// one ply up to its re-rooting, all enqueued: the move -- the search's (execute, sample) or, scripted >= 0, that scripted player's -- then the mirror step and the advance
+static void play_ply(omok_engine* e, const Search& s, int alive, int scripted = -1) {
+    if (scripted >= 0) enqueue_opponent_move(e, scripted);
+    else {
+        const int rounds = enqueue_execute(e, s.count, s.K, s.epsilon, s.alpha, alive);
+        enqueue_sample(e, s.temperature, s.threshold);
+        e->sims += (double)rounds * s.K * alive;
+    }
+    enqueue_mirror_and_advance(e, alive);
+}
+
+// ends a ply: the one status read-back and the host's accounting.  *alive: the games that moved -> the games still alive; count_finished: the difference
+// is games that ended (slots mode counts its games itself).  Returns the tree-error code.
+static int end_ply(omok_engine* e, uint32_t* alive, bool count_finished = true) {
+    uint32_t bits = 0, after = 0;
+    if (read_status(e, &bits, &after)) return OMOK_ERR_HIP;
+    e->ply_games += *alive;
+    if (count_finished) e->finished += (double)*alive - (double)after;
+    e->ply += 1;
+    e->sampled = false;
+    *alive = after;
+    return tree_error(e, bits);
 }
 
 extern "C" int omok_advance(omok_engine* e) {
@@ -1312,46 +1331,28 @@ extern "C" int omok_advance(omok_engine* e) {
     if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
     if (!e->sampled) return fail(e, OMOK_ERR_STATE, "omok_sample_actions must precede omok_advance");
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    uint32_t bits = 0, before = 0, after = 0;
-    if (read_status(e, &bits, &before)) return OMOK_ERR_HIP;
-    enqueue_mirror_and_advance(e, (int)before);
-    if (read_status(e, &bits, &after)) return OMOK_ERR_HIP;
-    e->ply_games += before;
-    e->finished += (double)before - (double)after;
-    e->ply += 1;
-    e->sampled = false;
-    return tree_error(e, bits);
+    uint32_t bits = 0, alive = 0;
+    if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
+    enqueue_mirror_and_advance(e, (int)alive);
+    return end_ply(e, &alive);
 }
 
 extern "C" int omok_selfplay_run(omok_engine* e, int32_t count, int32_t batch_size, float epsilon, float alpha,
                                  float temperature, int32_t threshold, int32_t max_plies, double* stats) {
     if (!e) return OMOK_ERR_INVALID;
-    if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
-    if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
-    if (!(temperature > 0.0f)) return fail(e, OMOK_ERR_INVALID, "temperature must be > 0");
+    if (int rc = check_search(e, count, batch_size, epsilon, alpha, temperature)) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
+    const Search s{count, batch_size, epsilon, alpha, temperature, threshold};
     uint32_t bits = 0, alive = 0;
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
-    int plies = 0;
-    while (alive > 0 && (max_plies <= 0 || plies < max_plies)) { // trainer.rs:95
-        const int rounds = enqueue_execute(e, count, batch_size, epsilon, alpha, (int)alive);
-        enqueue_sample(e, temperature, threshold);
-        enqueue_mirror_and_advance(e, (int)alive);
-        e->sims += (double)rounds * batch_size * alive;
-        e->ply_games += alive;
-        e->ply += 1;
-        plies += 1;
-        uint32_t after = 0;
-        if (read_status(e, &bits, &after)) return OMOK_ERR_HIP;
-        e->finished += (double)alive - (double)after;
-        alive = after;
-        if (tree_error(e, bits)) return bits & 1u ? OMOK_ERR_OVERFLOW : OMOK_ERR_ILLEGAL;
+    for (int plies = 0; alive > 0 && (max_plies <= 0 || plies < max_plies); ++plies) { // trainer.rs:95
+        play_ply(e, s, (int)alive);
+        if (int rc = end_ply(e, &alive)) return rc;
     }
-    e->sampled = false;
+    e->sampled = false; // (also where no ply was played)
     if (stats) return omok_get_stats(e, stats);
     return OMOK_OK;
 }
-
 
 // Slots mode: the engine's `games` slots are kept full.  Same games, same results as an episode of `total_games` games (every game
 // is keyed by its index: RNG streams by cfg.game_offset + index and the game's own ply; trees are independent), but a slot whose game
@@ -1366,9 +1367,7 @@ static int run_slots(omok_engine* e, bool logged, int32_t total_games, int32_t c
                      int32_t* game_status, int64_t* n_records, double* stats) {
     const char* who = logged ? "omok_selfplay_run_slots_logged" : "omok_selfplay_run_slots";
     if (!e) return OMOK_ERR_INVALID;
-    if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
-    if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
-    if (!(temperature > 0.0f)) return fail(e, OMOK_ERR_INVALID, "temperature must be > 0");
+    if (int rc = check_search(e, count, batch_size, epsilon, alpha, temperature)) return rc;
     const int G = e->cfg.games;
     if (total_games < G) return fail(e, OMOK_ERR_INVALID, "total_games (%d) must be >= the engine's game slots (%d)", total_games, G);
     if (!records_dev || cap_records < 1) return fail(e, OMOK_ERR_INVALID, "records buffer required (omok_replay_record_bytes per record)");
@@ -1383,40 +1382,30 @@ static int run_slots(omok_engine* e, bool logged, int32_t total_games, int32_t c
     ENTER(e);
     // a slot's rows hold one game after another: once the run has begun the per-slot log describes no game, whatever way the run ends
     struct LogEnds { omok_engine* e; bool on; ~LogEnds() { if (on) e->log_started = false; } } log_ends{e, logged};
-    uint8_t* d_mask = nullptr;
-    long long *d_slot_off = nullptr, *d_out = nullptr;
-    int32_t *d_next = nullptr, *d_new = nullptr;
-    SlotMeta* d_meta = nullptr;
-    auto cleanup = [&]() { for (void* p : {(void*)d_mask, (void*)d_slot_off, (void*)d_out, (void*)d_next, (void*)d_new, (void*)d_meta}) if (p) hipFree(p); };
-    if (hipMalloc(&d_mask, G) != hipSuccess || hipMalloc(&d_slot_off, sizeof(long long) * G) != hipSuccess || hipMalloc(&d_out, 8) != hipSuccess ||
-        hipMalloc(&d_next, 4) != hipSuccess || hipMalloc(&d_new, sizeof(int32_t) * G) != hipSuccess ||
-        hipMalloc(&d_meta, sizeof(SlotMeta) * (size_t)total_games) != hipSuccess) {
-        cleanup();
-        return fail(e, OMOK_ERR_HIP, "slots mode: device allocation failed");
-    }
+    Scratch sc;
+    uint8_t* d_mask = sc.get<uint8_t>(G);
+    long long *d_slot_off = sc.get<long long>(G), *d_out = sc.get<long long>(1);
+    int32_t *d_next = sc.get<int32_t>(1), *d_new = sc.get<int32_t>(G);
+    SlotMeta* d_meta = sc.get<SlotMeta>((size_t)total_games);
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "slots mode: device allocation failed");
     hipMemsetAsync(d_out, 0, 8, e->st);
     hipMemsetAsync(d_meta, 0xFF, sizeof(SlotMeta) * (size_t)total_games, e->st);
     hipMemcpyAsync(d_next, &G, 4, hipMemcpyHostToDevice, e->st); // the reset started games 0 .. G-1
+    const Search s{count, batch_size, epsilon, alpha, temperature, threshold};
     uint32_t bits = 0, alive = 0;
-    if (read_status(e, &bits, &alive)) { cleanup(); return OMOK_ERR_HIP; }
+    if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
     int rc = OMOK_OK;
     while (alive > 0) {
-        const int rounds = enqueue_execute(e, count, batch_size, epsilon, alpha, (int)alive);
-        enqueue_sample(e, temperature, threshold);
-        enqueue_mirror_and_advance(e, (int)alive);
-        e->sims += (double)rounds * batch_size * alive;
-        e->ply_games += alive;
-        e->ply += 1;
+        play_ply(e, s, (int)alive);
         e->prof.begin(PC_PLY, e->st);
         launch_harvest(e->n, e->S, d_mask, d_slot_off, d_out, d_meta, (uint8_t*)records_dev, cap_records, e->st);
         if (logged) launch_harvest_log(e->n, e->S, e->log, d_mask, d_slot_off, (uint8_t*)log_dev, cap_records, e->st);
-        if ((e->ply & 1) == 0) launch_refill(e->n, e->S, e->d_root_policy, d_next, total_games, d_new, e->st);
+        if (e->ply & 1) launch_refill(e->n, e->S, e->d_root_policy, d_next, total_games, d_new, e->st); // (the ply that ends here is odd: the next one is even)
         invalidate_nets(e);
         e->prof.end(e->st);
-        uint32_t after = 0;
-        if (read_status(e, &bits, &after)) { cleanup(); return OMOK_ERR_HIP; }
-        alive = after;
-        if (tree_error(e, bits)) { rc = bits & 1u ? OMOK_ERR_OVERFLOW : OMOK_ERR_ILLEGAL; break; }
+        rc = end_ply(e, &alive, false);
+        if (rc == OMOK_ERR_HIP) return rc;
+        if (rc != OMOK_OK) break;
         if (alive == 0 && (e->ply & 1)) { // every slot is waiting for an even ply with games left to start: let the ply pass
             int32_t next = 0;
             hipMemcpy(&next, d_next, 4, hipMemcpyDeviceToHost);
@@ -1424,10 +1413,10 @@ static int run_slots(omok_engine* e, bool logged, int32_t total_games, int32_t c
             e->ply += 1;
             launch_refill(e->n, e->S, e->d_root_policy, d_next, total_games, d_new, e->st);
             invalidate_nets(e);
-            if (read_status(e, &bits, &alive)) { cleanup(); return OMOK_ERR_HIP; }
+            if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
         }
     }
-    e->sampled = false;
+    e->sampled = false; // (also where no ply was played)
     long long out = 0;
     hipMemcpy(&out, d_out, 8, hipMemcpyDeviceToHost);
     if (n_records) *n_records = out;
@@ -1442,7 +1431,6 @@ static int run_slots(omok_engine* e, bool logged, int32_t total_games, int32_t c
         }
     }
     e->finished += (double)total_games;
-    cleanup();
     if (rc != OMOK_OK) return rc;
     if (stats) return omok_get_stats(e, stats);
     return OMOK_OK;
@@ -1525,29 +1513,21 @@ static int check_opponent_kind(omok_engine* e, int kind) {
     return 0;
 }
 
-static void enqueue_opponent_move(omok_engine* e, int kind) {
-    e->prof.begin(PC_PLY, e->st);
-    launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, e->d_actions, e->st);
-    e->prof.end(e->st);
-}
-
 // the forced part of the naive player's rule (trainer.rs:514-531, rules of environment/src/lib.rs:104-190) on caller-held positions
 extern "C" int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out) {
     if (!e || !boards || !turns || !forced_out || batch < 1) return OMOK_ERR_INVALID;
     if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
     ENTER(e);
     // (the rule tests a stone of either colour at every empty cell, trainer.rs:518,524-527: the answer does not depend on the side to move)
-    uint8_t* d_boards = nullptr;
-    int32_t* d_forced = nullptr;
     const size_t B = (size_t)batch;
-    HIPCHK(e, hipMalloc((void**)&d_boards, B * e->hw));
-    HIPCHK(e, hipMalloc((void**)&d_forced, B * 4));
+    Scratch sc;
+    uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
+    int32_t* d_forced = sc.get<int32_t>(B);
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_scripted_actions: device allocation failed");
     hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
     launch_env_scripted(e->n, d_boards, kind, batch, d_forced, e->st);
     hipMemcpyAsync(forced_out, d_forced, B * 4, hipMemcpyDeviceToHost, e->st);
-    const int rc = sync_and_check(e, "env_scripted_actions");
-    hipFree(d_boards); hipFree(d_forced);
-    return rc ? OMOK_ERR_HIP : OMOK_OK;
+    return sync_and_check(e, "env_scripted_actions") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 // the scripted player's move of every live game (trainer.rs:508-534 naive, :452-455 random), staged like omok_set_actions
@@ -1570,35 +1550,21 @@ extern "C" int omok_opponent_actions(omok_engine* e, int32_t kind, int32_t* acti
 extern "C" int omok_versus_run(omok_engine* e, int32_t kind, int32_t opponent_side, int32_t count, int32_t batch_size, float epsilon, float alpha,
                                int32_t max_plies, int32_t* results, double* stats) {
     if (!e) return OMOK_ERR_INVALID;
-    if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
+    if (int rc = check_search(e, count, batch_size, epsilon, alpha)) return rc;
     if (no_match(e, "omok_versus_run")) return OMOK_ERR_STATE;
     if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
     if (opponent_side != 0 && opponent_side != 1) return fail(e, OMOK_ERR_INVALID, "opponent_side %d is neither 0 (Black) nor 1 (White)", opponent_side);
-    if (check_exec_args(e, count, batch_size, epsilon, alpha)) return OMOK_ERR_INVALID;
     if (e->ply != e->start_ply)
         return fail(e, OMOK_ERR_STATE, "omok_versus_run starts at a fresh reset: %d move(s) were played since (the episode is at ply %d)", e->ply - e->start_ply, e->ply);
     HIPCHK(e, hipSetDevice(e->cfg.device));
+    const Search s{count, batch_size, epsilon, alpha, 1.0f, 0}; // threshold 0: sample_action(Best) on every ply of the net (:576, :430)
     uint32_t bits = 0, alive = 0;
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
-    int plies = 0;
-    while (alive > 0 && (max_plies <= 0 || plies < max_plies)) {
-        if ((e->ply & 1) == opponent_side) enqueue_opponent_move(e, kind);
-        else {
-            const int rounds = enqueue_execute(e, count, batch_size, epsilon, alpha, (int)alive);
-            enqueue_sample(e, 1.0f, 0); // threshold 0: sample_action(Best) on every ply (:576, :430)
-            e->sims += (double)rounds * batch_size * alive;
-        }
-        enqueue_mirror_and_advance(e, (int)alive);
-        e->ply_games += alive;
-        e->ply += 1;
-        plies += 1;
-        uint32_t after = 0;
-        if (read_status(e, &bits, &after)) return OMOK_ERR_HIP;
-        e->finished += (double)alive - (double)after;
-        alive = after;
-        if (tree_error(e, bits)) return bits & 1u ? OMOK_ERR_OVERFLOW : OMOK_ERR_ILLEGAL;
+    for (int plies = 0; alive > 0 && (max_plies <= 0 || plies < max_plies); ++plies) {
+        play_ply(e, s, (int)alive, (e->ply & 1) == opponent_side ? kind : -1); // the scripted player's plies search nothing: no sims
+        if (int rc = end_ply(e, &alive)) return rc;
     }
-    e->sampled = false;
+    e->sampled = false; // (also where no ply was played)
     if (results) {
         std::vector<GameState> gs((size_t)e->cfg.games);
         HIPCHK(e, hipMemcpyAsync(gs.data(), e->S.gs, sizeof(GameState) * gs.size(), hipMemcpyDeviceToHost, e->st));
@@ -1655,15 +1621,12 @@ extern "C" int omok_env_place_stone(omok_engine* e, uint8_t* boards, uint8_t* tu
                                     int32_t batch, int32_t* status_out) {
     if (!e || !boards || !turns || !legal || !actions || !status_out || batch < 1) return OMOK_ERR_INVALID;
     ENTER(e);
-    uint8_t *d_boards = nullptr, *d_turns = nullptr;
-    uint16_t* d_legal = nullptr;
-    int32_t *d_act = nullptr, *d_status = nullptr;
     const size_t B = (size_t)batch;
-    HIPCHK(e, hipMalloc((void**)&d_boards, B * e->hw));
-    HIPCHK(e, hipMalloc((void**)&d_turns, B));
-    HIPCHK(e, hipMalloc((void**)&d_legal, B * 2));
-    HIPCHK(e, hipMalloc((void**)&d_act, B * 4));
-    HIPCHK(e, hipMalloc((void**)&d_status, B * 4));
+    Scratch sc;
+    uint8_t *d_boards = sc.get<uint8_t>(B * e->hw), *d_turns = sc.get<uint8_t>(B);
+    uint16_t* d_legal = sc.get<uint16_t>(B);
+    int32_t *d_act = sc.get<int32_t>(B), *d_status = sc.get<int32_t>(B);
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_place_stone: device allocation failed");
     hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
     hipMemcpyAsync(d_turns, turns, B, hipMemcpyHostToDevice, e->st);
     hipMemcpyAsync(d_legal, legal, B * 2, hipMemcpyHostToDevice, e->st);
@@ -1673,9 +1636,7 @@ extern "C" int omok_env_place_stone(omok_engine* e, uint8_t* boards, uint8_t* tu
     hipMemcpyAsync(turns, d_turns, B, hipMemcpyDeviceToHost, e->st);
     hipMemcpyAsync(legal, d_legal, B * 2, hipMemcpyDeviceToHost, e->st);
     hipMemcpyAsync(status_out, d_status, B * 4, hipMemcpyDeviceToHost, e->st);
-    const int rc = sync_and_check(e, "env_place_stone");
-    hipFree(d_boards); hipFree(d_turns); hipFree(d_legal); hipFree(d_act); hipFree(d_status);
-    return rc ? OMOK_ERR_HIP : OMOK_OK;
+    return sync_and_check(e, "env_place_stone") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 // ---- step-wise API (parity tests) --------------------------------------------------------------
@@ -1706,11 +1667,7 @@ static int requests_to_inputs(omok_engine* e, int cnt, float* inputs) {
 
 static int outputs_to_host(omok_engine* e, Net& net, int cnt, float* p, float* v) {
     if (cnt <= 0) return OMOK_OK;
-    float* d_pack = net.in_f32;
-    const size_t tot = (size_t)cnt * e->hw;
-    k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(net.p, d_pack, e->hw, e->rowp, cnt);
-    HIPCHK(e, hipMemcpyAsync(p, d_pack, sizeof(float) * tot, hipMemcpyDeviceToHost, e->st));
-    if (v) HIPCHK(e, hipMemcpyAsync(v, net.v, sizeof(float) * cnt, hipMemcpyDeviceToHost, e->st));
+    if (rows_to_host(e, net, net.p, e->rowp, net.v, cnt, p, v)) return OMOK_ERR_HIP;
     return sync_and_check(e, "outputs") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
@@ -1724,15 +1681,19 @@ static int inject_outputs(omok_engine* e, Net& net, int cnt, const float* p, con
     return sync_and_check(e, "inject") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
-// the step-wise rows of a match episode, block by block (the list's row order): block b's rows are in its net's buffers
-static int match_outputs_to_host(omok_engine* e, int tree_side, float* p, float* v) {
-    for (int b = 0, off = 0; b < 2; off += e->match_cnt[b], ++b)
-        if (outputs_to_host(e, net_at(e, tree_side ^ b), e->match_cnt[b], p + (size_t)off * e->hw, v ? v + off : nullptr)) return OMOK_ERR_HIP;
+// the rows of the pending step-wise batch on the trees of `side`, block by block (the list's row order: block i's rows start at blk[i].off and are in its net's buffers)
+static int pending_outputs(omok_engine* e, int side, int rows, float* p, float* v) {
+    Block blk[2];
+    const int nb = eval_blocks(e, side, rows, true, blk);
+    for (int i = 0; i < nb; ++i)
+        if (outputs_to_host(e, *blk[i].net, blk[i].rows, p + (size_t)blk[i].off * e->hw, v ? v + blk[i].off : nullptr)) return OMOK_ERR_HIP;
     return OMOK_OK;
 }
-static int match_inject(omok_engine* e, int tree_side, const float* p, const float* v) {
-    for (int b = 0, off = 0; b < 2; off += e->match_cnt[b], ++b)
-        if (inject_outputs(e, net_at(e, tree_side ^ b), e->match_cnt[b], p + (size_t)off * e->hw, v ? v + off : nullptr)) return OMOK_ERR_HIP;
+static int pending_inject(omok_engine* e, int side, int rows, const float* p, const float* v) {
+    Block blk[2];
+    const int nb = eval_blocks(e, side, rows, true, blk);
+    for (int i = 0; i < nb; ++i)
+        if (inject_outputs(e, *blk[i].net, blk[i].rows, p + (size_t)blk[i].off * e->hw, v ? v + blk[i].off : nullptr)) return OMOK_ERR_HIP;
     return OMOK_OK;
 }
 
@@ -1747,39 +1708,34 @@ extern "C" int omok_round_eval(omok_engine* e) {
     if (need_net(e)) return OMOK_ERR_STATE;
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
     if (e->round_reqs == 0) return OMOK_OK;
-    if (e->match) {
-        for (int b = 0; b < 2; ++b)
-            if (e->match_cnt[b] > 0) match_forward(e, b, e->ply & 1, e->round_cap, e->ply & 1, false);
-    } else net_forward_requests(e->net, e->S, e->round_cap, e->st, &e->prof, e->ply & 1);
+    Block blk[2];
+    const int nb = eval_blocks(e, e->ply & 1, e->round_reqs, true, blk);
+    for (int i = 0; i < nb; ++i)
+        if (blk[i].rows > 0) block_forward(e, blk[i], e->round_cap, e->ply & 1);
     return sync_and_check(e, "round_eval") ? OMOK_ERR_HIP : OMOK_OK;
 }
 extern "C" int omok_round_outputs(omok_engine* e, float* p, float* v) {
     if (!e || !p) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
-    if (e->match) return match_outputs_to_host(e, e->ply & 1, p, v);
-    return outputs_to_host(e, e->net, e->round_reqs, p, v);
+    return pending_outputs(e, e->ply & 1, e->round_reqs, p, v);
 }
 // the pre-softmax policy logits and the pre-tanh value of the pending round's evaluation (precision evidence for the path the search rounds take)
 extern "C" int omok_round_logits(omok_engine* e, float* logits, float* vpre) {
     if (!e || !logits) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
-    if (e->round_reqs == 0) return OMOK_OK;
-    const int blocks = e->match ? 2 : 1;
-    for (int b = 0, off = 0; b < blocks; off += e->match_cnt[b], ++b) { // (match episodes: block by block, each from its own net)
-        Net& net = e->match ? net_at(e, (e->ply & 1) ^ b) : e->net;
-        const int rows = e->match ? e->match_cnt[b] : e->round_reqs;
+    Block blk[2];
+    const int nb = eval_blocks(e, e->ply & 1, e->round_reqs, true, blk);
+    for (int i = 0; i < nb; ++i) { // (match episodes: block by block, each from its own net)
+        Net& net = *blk[i].net;
+        const int rows = blk[i].rows, off = blk[i].off;
         if (rows == 0) continue;
         if (net.mode == OMOK_NET_F32 && rows > net.chunk)
             return fail(e, OMOK_ERR_STATE, "omok_round_logits: OMOK_NET_F32 keeps the logits of its last chunk of %d rows only", net.chunk);
         int stride = 0;
         const float* lg = net_logits(net, &stride);
-        float* d_pack = net.in_f32;
-        const size_t tot = (size_t)rows * e->hw;
-        k_pack_rows<<<(unsigned)((tot + 255) / 256), 256, 0, e->st>>>(lg, d_pack, e->hw, stride, rows);
-        HIPCHK(e, hipMemcpyAsync(logits + (size_t)off * e->hw, d_pack, sizeof(float) * tot, hipMemcpyDeviceToHost, e->st));
-        if (vpre) HIPCHK(e, hipMemcpyAsync(vpre + off, net.vpre, sizeof(float) * rows, hipMemcpyDeviceToHost, e->st));
+        if (rows_to_host(e, net, lg, stride, net.vpre, rows, logits + (size_t)off * e->hw, vpre ? vpre + off : nullptr)) return OMOK_ERR_HIP;
         if (sync_and_check(e, "round_logits")) return OMOK_ERR_HIP;
     }
     return OMOK_OK;
@@ -1788,21 +1744,20 @@ extern "C" int omok_round_inject(omok_engine* e, const float* p, const float* v)
     if (!e || !p || !v) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
-    if (e->match) return match_inject(e, e->ply & 1, p, v);
-    return inject_outputs(e, e->net, e->round_reqs, p, v);
+    return pending_inject(e, e->ply & 1, e->round_reqs, p, v);
 }
 extern "C" int omok_round_scatter(omok_engine* e) {
     ENTER(e);
     if (e->round_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated round");
     const int side = e->ply & 1;
-    if (e->round_reqs > 0 && e->match) {
-        for (int b = 0; b < 2; ++b) {
-            Net& X = net_at(e, side ^ b);
-            if (e->match_cnt[b] > 0) launch_scatter(e->n, block_view(e, b), side, X.p, X.v, e->match_cnt[b], e->st, false);
-        }
+    Block blk[2];
+    const int nb = eval_blocks(e, side, e->round_reqs, true, blk);
+    for (int i = 0; i < nb; ++i)
+        if (blk[i].rows > 0) launch_scatter(e->n, blk[i].view, side, blk[i].net->p, blk[i].net->v, blk[i].rows, e->st, !e->match);
+    if (e->match && e->round_reqs > 0) { // the blocks' scatters ran no backups: they read one v array in list order
         match_join(e, side, false, e->round_reqs);
         launch_backups(e->n, e->S, side, net_at(e, side).v, e->st);
-    } else if (e->round_reqs > 0) launch_scatter(e->n, e->S, side, e->net.p, e->net.v, e->round_reqs, e->st);
+    }
     e->round_reqs = -1;
     return sync_and_check(e, "round_scatter") ? OMOK_ERR_HIP : OMOK_OK;
 }
@@ -1832,47 +1787,32 @@ extern "C" int omok_mirror_eval(omok_engine* e) {
     ENTER(e);
     if (need_net(e)) return OMOK_ERR_STATE;
     if (e->mirror_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated mirror batch");
-    if (e->mirror_reqs > 0 && e->match) {
-        for (int b = 0; b < 2; ++b)
-            if (e->match_cnt[b] > 0) match_forward(e, b, 1 - (e->ply & 1), e->match_cnt[b], -1, false);
-    } else if (e->mirror_reqs > 0) net_forward_requests(e->net, e->S, e->mirror_reqs, e->st, &e->prof);
+    Block blk[2];
+    const int nb = eval_blocks(e, 1 - (e->ply & 1), e->mirror_reqs, true, blk);
+    for (int i = 0; i < nb; ++i)
+        if (blk[i].rows > 0) block_forward(e, blk[i], blk[i].rows);
     return sync_and_check(e, "mirror_eval") ? OMOK_ERR_HIP : OMOK_OK;
 }
 extern "C" int omok_mirror_outputs(omok_engine* e, float* p) {
     if (!e || !p) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->mirror_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated mirror batch");
-    if (e->match) return match_outputs_to_host(e, 1 - (e->ply & 1), p, nullptr);
-    return outputs_to_host(e, e->net, e->mirror_reqs, p, nullptr);
+    return pending_outputs(e, 1 - (e->ply & 1), e->mirror_reqs, p, nullptr);
 }
 extern "C" int omok_mirror_inject(omok_engine* e, const float* p) {
     if (!e || !p) return OMOK_ERR_INVALID;
     ENTER(e);
     if (e->mirror_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated mirror batch");
-    if (e->match) return match_inject(e, 1 - (e->ply & 1), p, nullptr);
-    return inject_outputs(e, e->net, e->mirror_reqs, p, nullptr);
+    return pending_inject(e, 1 - (e->ply & 1), e->mirror_reqs, p, nullptr);
 }
 extern "C" int omok_mirror_apply(omok_engine* e) {
     ENTER(e);
     if (e->mirror_reqs < 0) return fail(e, OMOK_ERR_STATE, "no generated mirror batch");
-    uint32_t bits = 0, before = 0, after = 0;
-    if (read_status(e, &bits, &before)) return OMOK_ERR_HIP;
-    if (e->match) {
-        match_join(e, 1 - (e->ply & 1), true, e->cfg.games);
-        enqueue_log_move(e, e->ply & 1);
-        launch_advance(e->n, e->S, e->ply & 1, net_at(e, 1 - (e->ply & 1)).p, e->st);
-    } else {
-        enqueue_log_move(e, e->ply & 1);
-        launch_advance(e->n, e->S, e->ply & 1, e->net.p, e->st);
-    }
-    invalidate_nets(e);
-    if (read_status(e, &bits, &after)) return OMOK_ERR_HIP;
-    e->ply_games += before;
-    e->finished += (double)before - (double)after;
-    e->ply += 1;
-    e->sampled = false;
+    uint32_t bits = 0, alive = 0;
+    if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
+    enqueue_advance(e, e->cfg.games);
     e->mirror_reqs = -1;
-    return tree_error(e, bits);
+    return end_ply(e, &alive);
 }
 
 // ---- game records: the move log and the batched replay ------------------------------------------------
@@ -1954,16 +1894,14 @@ extern "C" int omok_env_replay(omok_engine* e, const uint8_t* start_boards, cons
         if (lengths[b] < 0 || lengths[b] > stride) return fail(e, OMOK_ERR_INVALID, "game %d: length %d outside [0, stride = %d]", b, lengths[b], stride);
     ENTER(e);
     const size_t B = (size_t)batch, hw = (size_t)e->hw;
+    Scratch sc;
     uint8_t* d_start = nullptr;
     std::vector<int32_t> host((size_t)2 * B); // verdicts | lengths
-    if (start_boards && check_positions(e, start_boards, batch, host.data(), nullptr, &d_start)) return OMOK_ERR_HIP;
+    if (start_boards && check_positions(e, sc, start_boards, batch, host.data(), nullptr, &d_start)) return OMOK_ERR_HIP;
     memcpy(host.data() + B, lengths, B * 4);
     // one allocation: verdicts, lengths, status, played (4 B each), moves (2 B), boards (1 B)
-    uint8_t* d = nullptr;
-    if (hipMalloc((void**)&d, B * 16 + B * stride * 2 + B * hw) != hipSuccess) {
-        if (d_start) hipFree(d_start);
-        return fail(e, OMOK_ERR_HIP, "env_replay: device allocation failed");
-    }
+    uint8_t* d = sc.get<uint8_t>(B * 16 + B * stride * 2 + B * hw);
+    if (!d) return fail(e, OMOK_ERR_HIP, "env_replay: device allocation failed");
     int32_t *d_verdict = (int32_t*)d, *d_len = d_verdict + B, *d_status = d_len + B, *d_played = d_status + B;
     uint16_t* d_moves = (uint16_t*)(d + B * 16);
     uint8_t* d_boards = d + B * 16 + B * stride * 2;
@@ -1975,10 +1913,7 @@ extern "C" int omok_env_replay(omok_engine* e, const uint8_t* start_boards, cons
     if (boards_out) hipMemcpyAsync(boards_out, d_boards, B * hw, hipMemcpyDeviceToHost, e->st);
     if (status_out) hipMemcpyAsync(status_out, d_status, B * 4, hipMemcpyDeviceToHost, e->st);
     if (played_out) hipMemcpyAsync(played_out, d_played, B * 4, hipMemcpyDeviceToHost, e->st);
-    const int rc = sync_and_check(e, "env_replay");
-    hipFree(d);
-    if (d_start) hipFree(d_start);
-    return rc ? OMOK_ERR_HIP : OMOK_OK;
+    return sync_and_check(e, "env_replay") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 // ---- inspection ----------------------------------------------------------------------------------
@@ -2174,17 +2109,16 @@ extern "C" int64_t omok_replay_augment_records_dev(omok_engine* e, const void* r
     if (total == 0) return 0;
     ENTER(e);
     const size_t m = span.size(), first_bytes = (m + 1) * sizeof(long long);
-    uint8_t* d = nullptr;
-    if (hipMalloc((void**)&d, first_bytes + m * sizeof(AugSpan)) != hipSuccess) return fail(e, OMOK_ERR_HIP, "replay_augment_records: device allocation failed");
+    Scratch sc;
+    uint8_t* d = sc.get<uint8_t>(first_bytes + m * sizeof(AugSpan));
+    if (!d) return fail(e, OMOK_ERR_HIP, "replay_augment_records: device allocation failed");
     hipMemcpyAsync(d, first.data(), first_bytes, hipMemcpyHostToDevice, e->st);
     hipMemcpyAsync(d + first_bytes, span.data(), m * sizeof(AugSpan), hipMemcpyHostToDevice, e->st);
     e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling: tools/selfplay_slots_timing.py)
     launch_replay_augment_records(e->n, (const uint8_t*)records_dev, (const long long*)d, (const AugSpan*)(d + first_bytes), (int)m, total,
                                   (uint8_t*)dst_dev, cap_records, e->st);
     e->prof.end(e->st);
-    const int rc = sync_and_check(e, "replay_augment_records");
-    hipFree(d);
-    return rc ? OMOK_ERR_HIP : 6 * total;
+    return sync_and_check(e, "replay_augment_records") ? OMOK_ERR_HIP : 6 * total;
 }
 
 extern "C" int omok_replay_augmented_game(omok_engine* e, int32_t game, uint8_t* boards, uint8_t* turns, float* pi, float* z, int32_t cap_records) {
