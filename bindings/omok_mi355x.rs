@@ -54,6 +54,8 @@ pub const OMOK_NET_F16X3_FP6: i32 = 3;
 pub const OMOK_NET_F16X3_F16: i32 = 4;
 pub const OMOK_NET_F16X3_MIXED: i32 = 5;
 pub const OMOK_MAX_ARENA: i32 = 16384;
+pub const OMOK_ALPHA_MAX: i32 = 33; // alpha in (0, 33]
+pub const OMOK_TEMPERATURE_INV_MAX: i32 = 80; // 1 / temperature <= 80
 pub const OMOK_OPP_RANDOM: i32 = 0;
 pub const OMOK_OPP_NAIVE: i32 = 1;
 pub const OMOK_TRAIN_MAX_RANKS: i32 = 64;

@@ -217,7 +217,15 @@ int omok_match_reset_from(omok_engine* e, int32_t split, const uint8_t* boards);
 int omok_set_episode(omok_engine* e, uint64_t episode);
 /* ParallelMCTSExecutor::execute (alpha-zero/src/parallel_mcts_executor.rs:26-35) on the
  * side-to-move agents of all live games: rounds of `batch_size` simulations per tree, one net
- * forward per round, ordered scatter; simulations round up to a multiple of batch_size. */
+ * forward per round, ordered scatter; simulations round up to a multiple of batch_size.
+ * The search arguments, here and in every entry point below that takes them (else OMOK_ERR_INVALID, nothing changed):
+ *   count >= 1, 1 <= batch_size <= max_batch_k, 0 <= epsilon <= 1 (epsilon = 0 still renormalises the root row, pme.rs:63-68; epsilon = 1
+ *   leaves pure noise),
+ *   0 < alpha <= OMOK_ALPHA_MAX: the Dirichlet noise is normalised Gamma(alpha) draws, alpha = k + f with k = min((int)alpha, 32) unit
+ *   exponentials and an Ahrens-Dieter GS draw for f.  GS samples Gamma(f) only for f <= 1, so alpha = 33 (k = 32, f = 1) is the largest value
+ *   drawn from the right distribution: above it the clamp leaves f > 1 (the mean of "Gamma(40)" comes out near 33.9), and alpha = inf has no
+ *   integer part at all.  The reference hands alpha to rand_distr's Dirichlet, which has no such limit; its default is 0.03 (src/config.rs:94). */
+#define OMOK_ALPHA_MAX 33
 int omok_execute(omok_engine* e, int32_t count, int32_t batch_size, float epsilon, float alpha);
 /* MCTSExecutor::run (alpha-zero/src/mcts_executor.rs:29-255; the executor of gui/src/agent.rs and benchmark/src/agent.rs) on an
  * engine with games = 1: ONE tree searched by `waves` wavefronts.  The reference runs its ceil(count / batch_size) rounds as
@@ -239,7 +247,15 @@ int omok_execute_shared_recorded(omok_engine* e, int32_t count, int32_t batch_si
 /* Agent::sample_action for every live game (agent.rs:83-137) with the trainer's mode rule
  * (trainer.rs:138-146): Boltzmann(temperature) while the game's ply < threshold, else Best.
  * Records the transition (env before the move, pi) like trainer.rs:150-173.
- * actions [G]: chosen cell, -1 for finished games.  May be NULL. */
+ * actions [G]: chosen cell, -1 for finished games.  May be NULL.
+ * temperature (here and in omok_selfplay_run / _run_slots / _run_slots_logged): 1 / temperature <= OMOK_TEMPERATURE_INV_MAX in fp32, that
+ * is temperature >= 0.0125, and not NaN; else OMOK_ERR_INVALID, nothing changed.  The heated weights exp(pi / T) and their sum are fp32
+ * (agent.rs:119-120): pi <= 1 and at most 225 cells, so with 1 / T <= 80 the sum is at most 225 * exp(80) = 1.2e37 < FLT_MAX = 3.4e38.  The
+ * first possible overflow is at 1 / T = ln(FLT_MAX) - ln(225) = 88.72 - 5.42 = 83.3.  Once a weight or the sum is inf, every normalised weight is 0 or
+ * NaN and the reference panics (WeightedIndex::new(..).unwrap(), agent.rs:130); there is no move to reproduce.  temperature = +inf is
+ * legal: 1 / T = 0, every visited cell weighs exp(0) = 1, the draw is uniform over the visited cells -- exactly what agent.rs:110-128
+ * computes with temperature.recip() = 0. */
+#define OMOK_TEMPERATURE_INV_MAX 80
 int omok_sample_actions(omok_engine* e, float temperature, int32_t threshold, int32_t* actions);
 /* Agent::play_action on the mover's tree, then ensure_action_exists + play_action on the
  * opponent's tree (agent.rs:144-232, trainer.rs:156-167), finished games retire

@@ -1125,8 +1125,16 @@ static int enqueue_execute(omok_engine* e, int count, int K, float eps, float al
 static int check_exec_args(omok_engine* e, int count, int K, float eps, float alpha) {
     if (count < 1) return fail(e, OMOK_ERR_INVALID, "count must be >= 1");
     if (K < 1 || K > e->cfg.max_batch_k) return fail(e, OMOK_ERR_INVALID, "batch_size %d outside [1, max_batch_k=%d]", K, e->cfg.max_batch_k);
-    if (!(alpha > 0.0f)) return fail(e, OMOK_ERR_INVALID, "alpha must be > 0");
+    if (!(alpha > 0.0f && alpha <= (float)OMOK_ALPHA_MAX)) return fail(e, OMOK_ERR_INVALID, "alpha must be in (0, %d]", OMOK_ALPHA_MAX);
     if (!(eps >= 0.0f && eps <= 1.0f)) return fail(e, OMOK_ERR_INVALID, "epsilon must be in [0,1]");
+    return 0;
+}
+
+// Boltzmann(temperature) of omok_sample_actions: the heated weights exp(pi / T) and their fp32 sum must stay finite (omok_mi355x.h); NaN fails both
+// comparisons, +inf passes (1 / T = 0: uniform over the visited cells, as in the reference)
+static int check_temperature(omok_engine* e, float temperature) {
+    if (!(temperature > 0.0f && 1.0f / temperature <= (float)OMOK_TEMPERATURE_INV_MAX))
+        return fail(e, OMOK_ERR_INVALID, "temperature must be >= 1 / %d", OMOK_TEMPERATURE_INV_MAX);
     return 0;
 }
 
@@ -1134,8 +1142,7 @@ static int check_exec_args(omok_engine* e, int count, int K, float eps, float al
 static int check_search(omok_engine* e, int count, int K, float eps, float alpha, float temperature = 1.0f) {
     if (need_net(e) || need_reset(e)) return OMOK_ERR_STATE;
     if (check_exec_args(e, count, K, eps, alpha)) return OMOK_ERR_INVALID;
-    if (!(temperature > 0.0f)) return fail(e, OMOK_ERR_INVALID, "temperature must be > 0");
-    return 0;
+    return check_temperature(e, temperature);
 }
 
 extern "C" int omok_execute(omok_engine* e, int32_t count, int32_t batch_size, float epsilon, float alpha) {
@@ -1258,7 +1265,7 @@ static void enqueue_opponent_move(omok_engine* e, int kind) {
 extern "C" int omok_sample_actions(omok_engine* e, float temperature, int32_t threshold, int32_t* actions) {
     if (!e) return OMOK_ERR_INVALID;
     if (need_reset(e)) return OMOK_ERR_STATE;
-    if (!(temperature > 0.0f)) return fail(e, OMOK_ERR_INVALID, "temperature must be > 0");
+    if (check_temperature(e, temperature)) return OMOK_ERR_INVALID;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     enqueue_sample(e, temperature, threshold);
     if (actions) HIPCHK(e, hipMemcpyAsync(actions, e->d_actions, sizeof(int32_t) * e->cfg.games, hipMemcpyDeviceToHost, e->st));

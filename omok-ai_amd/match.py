@@ -33,7 +33,7 @@ def parse_args(argv=None):
     ap.add_argument("--board", type=int, default=15, choices=(9, 15))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--threshold", type=int, default=0, help="plies played with temperature sampling before Best (0: Best throughout, as main.rs)")
-    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--temperature", type=float, default=1.0, help="Boltzmann temperature of those plies; the engine takes 1 / temperature <= 80 (>= 0.0125)")
     ap.add_argument("--max-nodes", type=int, default=0, help="tree arena (0: sized from --sims)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--net-mode", default="NET_F16X3", help="binding constant of the net mode (NET_F16X3, NET_F16X3_ROWS, NET_F32, ...)")

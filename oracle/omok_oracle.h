@@ -72,6 +72,9 @@ void orc_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c
 double orc_det_log(double x);
 double orc_det_exp(double x);
 float orc_det_expf(float x);
+/* Gamma(alpha) for 0 < alpha <= 33 only: k = min((int)alpha, 32) unit exponentials + Ahrens-Dieter GS for f = alpha - k, which samples
+ * Gamma(f) only for f <= 1.  The engine rejects alpha outside (0, 33]; this function does not check (it restates the kernel's arithmetic, and
+ * tests/test_oracle_net_rng.py shows what alpha = 40 gives). */
 float orc_gamma(float alpha, uint64_t seed, uint32_t cell, uint32_t ply, uint32_t tree_global);
 
 /* ---- net (alpha-zero/src/network.rs) ---- */
@@ -113,7 +116,9 @@ void orc_sp_round_scatter(orc_sp* sp, const float* p, const float* v);
 /* request r of the last generated round: tree (game) index and node index */
 void orc_sp_request_info(const orc_sp* sp, int r, int* game, int* node);
 /* trainer.rs:131-161: sample_action for every alive game, records the transition.
- * actions[g] = -1 for finished games. */
+ * actions[g] = -1 for finished games.  Meaningful for 1 / temperature <= 80 (fp32) only, the range the engine accepts: the heated weights
+ * exp(pi / T) and their sum are fp32, and once one of them is inf every normalised weight is 0 or NaN, the scan finds nothing and cell 0 comes
+ * out, where the reference panics (agent.rs:130).  Not checked here, nor in lit_sample: the oracles keep the arithmetic, the tests show the defect. */
 void orc_sp_sample(orc_sp* sp, float temperature, int threshold, int32_t* actions /*G*/);
 /* trainer.rs:163-166 part 1: NN inputs (Opponent mode) for ensure_action_exists of every
  * alive game, in game order; returns the count */

@@ -1,4 +1,4 @@
-"""Shared helpers of the parity tests (no GPU, no product code)."""
+"""Shared helpers of the parity tests (the drivers import the product and the oracle when they are called)."""
 import numpy as np
 
 
@@ -41,6 +41,209 @@ def random_positions(n, count, seed):
             env.place_stone(int(c))
         out[i] = env.encode_nn_input(int(rng.integers(0, 2)))
     return out
+
+
+def compare_trees(sp, osp, games, tag):
+    for g in range(games):
+        for side in (0, 1):
+            gi, gf = sp.tree_dump(g, side)
+            oi, of = osp.tree_dump(g, side)
+            assert gi.shape == oi.shape, f"{tag}: game {g} side {side}: {gi.shape[0]} vs {oi.shape[0]} nodes"
+            assert np.array_equal(gi, oi), f"{tag}: node records differ (game {g} side {side})"
+            assert np.array_equal(gf.view(np.uint32), of.view(np.uint32)), f"{tag}: w/policy bits differ (game {g} side {side})"
+            assert sp.tree_root(g, side)[0] == osp.tree_root(g, side)[0]
+            assert np.float32(sp.tree_root(g, side)[1]).tobytes() == np.float32(osp.tree_root(g, side)[1]).tobytes()
+
+
+def drive_selfplay_vs_oracle(n, games, count, k, max_plies, mode, threshold=6, max_nodes=2048, max_tables=1024, seed=7,
+                             game_offset=5, weight_seed=0, epsilon=0.25, alpha=0.03, temperature=1.0, on_sample=None):
+    """Plays `games` games step by step on the engine and on the oracle (the oracle consumes the GPU net's p / v, so the
+    comparison isolates the tree arithmetic) and compares canonical tree dumps, request boards, moves and replay tuples bit
+    for bit.  Returns the shape of the deepest search seen by the ORACLE: (fully expanded nodes, fully expanded non-root
+    nodes, max depth, max tables) so that a test can prove it left the shallow root-plus-one-layer regime.
+    on_sample(ply, pi [games][hw], has [games], actions [games]): called with the engine's compute_policy read BEFORE the
+    ply's sample_actions and the moves that call chose."""
+    import omok_ai_amd as oa
+    from oracle import oracle as O
+    tensors = oa.weights.init_random(n, seed=weight_seed)
+    eng = oa.Engine(board_size=n, games=games, max_nodes=max_nodes, max_tables=max_tables, max_batch_k=k, seed=seed,
+                    game_offset=game_offset, net_mode=mode)
+    eng.load_weights(tensors)
+    sp = oa.SelfPlay(eng)
+    sp.reset()
+    root_p = eng.evaluate_p(O.Environment(n).encode_nn_input(0)[None]).reshape(-1)
+    osp = O.SelfPlay(n, games, cap_nodes=max_nodes, cap_tables=max_tables, seed=seed, game_offset=game_offset)
+    osp.reset(root_p)
+    compare_trees(sp, osp, games, "reset")
+    shape = [0, 0, 0, 0]
+    ply = 0
+    rounds = (count + k - 1) // k
+    while osp.alive_count > 0 and (max_plies == 0 or ply < max_plies):
+        for rnd in range(rounds):
+            nreq = sp.round_generate(rnd, k, epsilon, alpha)
+            oin = osp.round_generate(rnd, k, epsilon, alpha)
+            assert nreq == len(oin), f"ply {ply} round {rnd}: request count"
+            assert np.array_equal(sp.round_inputs(), oin), f"ply {ply} round {rnd}: request boards"
+            if rnd == 0 or (rounds > 20 and rnd % 16 == 15):  # pending children of the round are in the dump as well
+                compare_trees(sp, osp, games, f"ply {ply} after generate of round {rnd}")
+            p, v = sp.round_eval()
+            sp.round_scatter()
+            osp.round_scatter(p, v)
+        compare_trees(sp, osp, games, f"ply {ply} after execute")
+        assert osp.error == 0
+        for g in range(games):
+            if osp.game_alive(g):
+                full, full_nr, depth = tree_shape(osp.tree_dump(g, ply & 1)[0])
+                shape = [max(shape[0], full), max(shape[1], full_nr), max(shape[2], depth), max(shape[3], osp.tree_root(g, ply & 1)[3])]
+        if on_sample is not None:
+            pi, has = sp.compute_policy()
+            pi, has = np.array(pi).copy(), np.array(has).copy()
+        a = sp.sample_actions(temperature, threshold)
+        assert np.array_equal(a, osp.sample(temperature, threshold)), f"ply {ply}: actions"
+        if on_sample is not None:
+            on_sample(ply, pi, has, np.array(a))
+        nm = sp.mirror_generate()
+        om = osp.mirror_generate()
+        assert nm == len(om) and np.array_equal(sp.mirror_inputs(), om)
+        pm = sp.mirror_eval()
+        sp.mirror_apply()
+        osp.advance(pm)
+        compare_trees(sp, osp, games, f"ply {ply} after advance")
+        alive, status, plies = sp.game_info()
+        assert [int(x) for x in alive] == [osp.game_alive(g) for g in range(games)]
+        assert [int(x) for x in status] == [osp.game_status(g) for g in range(games)]
+        ply += 1
+    assert sp.alive_count == osp.alive_count
+    for g in range(games):
+        gb, gt, gp, gz = sp.replay(g)
+        ob, ot, op, oz = osp.replay(g)
+        assert np.array_equal(gb, ob) and np.array_equal(gt, ot) and np.array_equal(gz, oz)
+        assert np.array_equal(gp.view(np.uint32), op.view(np.uint32))
+    eng.close()
+    return tuple(shape)
+
+
+def boltzmann_expected(pi, temperature, u):
+    """Agent::sample_action(Boltzmann) restated in float64 (agent.rs:106-133): the heated distribution of one policy row and
+    the cell a uniform draw u in [0, 1) selects.  Returns (cell, min |q - u| over the cumulative distribution q): a draw
+    closer to a step of q than the fp32 rounding of the weights can be moved across it by that rounding."""
+    pi = np.asarray(pi, dtype=np.float32)
+    arg = pi.astype(np.float64) / np.float64(np.float32(temperature))
+    h = np.where(pi >= np.float32(2.0 ** -23), np.exp(arg), 0.0)
+    q = np.cumsum(h / h.sum())
+    return int(np.searchsorted(q, u, side="right")), float(np.abs(q - u).min())
+
+
+def sample_uniform(seed, episode, ply, tree_global):
+    """the u of the RNG contract's purpose 3 (SAMPLE): (word 0 of Philox(key, 0, ply, tree_global, 3) >> 8) * 2^-24"""
+    import ctypes as C
+    from oracle import oracle as O
+    out = (C.c_uint32 * 4)()
+    O.lib().orc_philox(O.stream_key(seed, episode), 0, int(ply), int(tree_global), 3, out)
+    return (int(out[0]) >> 8) * 2.0 ** -24
+
+
+def dirichlet_spread(rows):
+    """mean((P - 1/HW)^2) over rows [trees][HW] of Dirichlet draws, and its analytic value for Dirichlet(alpha, ..., alpha) as a
+    function of alpha: Var(P_i) = (1/HW)(1 - 1/HW) / (HW alpha + 1)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    hw = rows.shape[1]
+    return float(((rows - 1.0 / hw) ** 2).mean()), lambda alpha: (1.0 / hw) * (1.0 - 1.0 / hw) / (hw * alpha + 1.0)
+
+
+def dirichlet_spread_sigma(hw, trees, alpha, draws=300):
+    """standard deviation of dirichlet_spread's statistic over `draws` samples of `trees` rows from numpy's own Dirichlet"""
+    rng = np.random.default_rng(0)
+    x = rng.dirichlet(np.full(hw, alpha), size=(draws, trees))
+    return float((((x - 1.0 / hw) ** 2).mean(axis=(1, 2))).std(ddof=1))
+
+
+def check_root_noise(sp, games, hw, alpha, tag):
+    """`sp` (the engine's SelfPlay or the oracle's: same tree_dump) has just run round_generate(0, K, epsilon = 1.0, alpha): every
+    side-0 root policy row is then a normalised row of Gamma(alpha) draws, i.e. Dirichlet(alpha, ..., alpha).  Checks, against
+    numpy's own Dirichlet and the closed forms, not against the oracle (which shares the sampler's design with the kernel):
+    rows sum to 1 within 1e-6; the spread statistic within 5 measured standard deviations of its analytic value; at
+    alpha = 0.03 the share of exactly-zero entries (draws below the 1e-30 flush) within 5 binomial standard deviations of
+    P(Gamma(alpha) < 1e-30) = 1e-30 ** alpha / Gamma(alpha + 1).  Returns the deviation of the spread in sigmas."""
+    import math
+    rows = np.stack([sp.tree_dump(g, 0)[1][0, 1:] for g in range(games)]).astype(np.float64)
+    assert rows.shape == (games, hw)
+    assert np.all(rows >= 0.0)
+    sums = rows.sum(axis=1)
+    assert np.abs(sums - 1.0).max() < 1e-6, f"{tag}: a row sums to {sums[np.abs(sums - 1.0).argmax()]!r}"
+    s, analytic = dirichlet_spread(rows)
+    sigma = dirichlet_spread_sigma(hw, games, alpha)
+    dev = (s - analytic(alpha)) / sigma
+    print(f"{tag}: alpha {alpha}: spread {s:.6e}, analytic {analytic(alpha):.6e}, sigma {sigma:.3e}: {dev:+.2f} sigma")
+    assert abs(dev) < 5.0, f"{tag}: alpha {alpha}: spread {s!r} is {dev:+.2f} sigma from {analytic(alpha)!r}"
+    if alpha == 0.03:
+        share = float((rows == 0.0).mean())
+        want = 1e-30 ** alpha / math.gamma(1.0 + alpha)
+        sd = math.sqrt(want * (1.0 - want) / rows.size)
+        print(f"{tag}: alpha {alpha}: share of zero entries {share:.5f}, expected {want:.5f}, sd {sd:.5f}: {(share - want) / sd:+.2f} sd")
+        assert abs(share - want) < 5.0 * sd
+    return dev
+
+
+class BoltzmannCheck:
+    """on_sample hook of drive_selfplay_vs_oracle (and of the oracle-only driver of tests/test_oracle_net_rng.py): every move a
+    live game samples must be the cell boltzmann_expected names for the policy read before the call and the u of the RNG
+    contract, unless u lies within 1e-5 of a step of the float64 cumulative distribution (the fp32 weights of the code under
+    test may round across it): those samples are skipped and counted."""
+
+    def __init__(self, seed, game_offset, temperature, episode=0):
+        self.seed, self.game_offset, self.temperature, self.episode = seed, game_offset, temperature, episode
+        self.samples = self.skipped = self.nonuniform = 0
+        self.max_arg = 0.0  # the largest pi / T handed to exp
+        self.mismatches = []
+
+    def __call__(self, ply, pi, has, actions):
+        side = ply & 1
+        for g in range(len(actions)):
+            if not has[g]:
+                assert actions[g] == -1
+                continue
+            u = sample_uniform(self.seed, self.episode, ply, (self.game_offset + g) * 2 + side)
+            cell, margin = boltzmann_expected(pi[g], self.temperature, u)
+            self.samples += 1
+            self.max_arg = max(self.max_arg, float(pi[g].max()) / float(np.float32(self.temperature)))
+            self.nonuniform += len(np.unique(pi[g][pi[g] > 0])) > 1
+            if margin < 1e-5:
+                self.skipped += 1
+            elif cell != int(actions[g]):
+                self.mismatches.append((ply, g, int(actions[g]), cell, u))
+
+    def finish(self, tag, min_samples, min_nonuniform=0):
+        """min_nonuniform: how many samples must have come from a policy with unequal visit counts for the run to count as a test of that
+        regime (while a root has untried actions every simulation expands one, and the policy is uniform over the visited cells: the move
+        is then the same at every temperature)"""
+        print(f"{tag}: T = {self.temperature}: {self.samples} samples ({self.nonuniform} from unequal visit counts, largest pi / T = {self.max_arg:.3f}), "
+              f"{self.skipped} skipped (u within 1e-5 of a step), {len(self.mismatches)} mismatches")
+        assert self.samples >= min_samples and self.nonuniform >= min_nonuniform
+        assert not self.mismatches, f"{tag}: (ply, game, move, expected, u) = {self.mismatches[:5]}"
+        assert self.skipped <= 0.02 * self.samples
+
+
+def episode_records(n, total, sims, k, threshold, mode, seed, max_nodes, epsilon=0.25, alpha=0.03, temperature=1.0):
+    """One whole episode of `total` games through SelfPlay.run: (packed replay records per game, status per game, stats)"""
+    import torch
+    import omok_ai_amd as oa
+    eng = oa.Engine(board_size=n, games=total, max_nodes=max_nodes, max_tables=max_nodes // 2, max_batch_k=k, seed=seed, net_mode=mode)
+    eng.load_random_weights(0)
+    sp = oa.SelfPlay(eng)
+    sp.reset()
+    stats = sp.run(sims, k, epsilon, alpha, temperature, threshold)
+    rec = sp.replay_record_bytes()
+    _, _, plies = sp.game_info()
+    _, status, _ = sp.game_info()
+    lens = [len(sp.replay(g)[1]) for g in range(total)]
+    buf = torch.zeros((sum(lens) + 1) * rec, dtype=torch.uint8, device="cuda")
+    assert sp.replay_pack_into(buf.data_ptr(), sum(lens) + 1) == sum(lens)
+    out = buf.cpu().numpy().reshape(-1, rec)
+    offs = np.concatenate([[0], np.cumsum(lens)])
+    games = [out[offs[g]:offs[g + 1]].copy() for g in range(total)]
+    eng.close()
+    return games, [int(s) for s in status], stats
 
 
 def trained_tensors(n, seed, steps=200):

@@ -14,7 +14,9 @@ import pytest
 import omok_ai_amd as oa
 from omok_ai_amd import binding as B
 from oracle import oracle as O
-from helpers import draw_sequence, random_positions, tree_shape
+from helpers import compare_trees as _compare_trees  # noqa: F401  (tests/test_gpu_headline_path.py takes it from here)
+from helpers import drive_selfplay_vs_oracle as _drive_selfplay_vs_oracle
+from helpers import draw_sequence, random_positions
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -245,77 +247,6 @@ def test_rows_mode_is_row_independent_in_search_rounds():
         assert np.array_equal(p.view(np.uint32), pp.reshape(nreq, -1).view(np.uint32))
         assert np.array_equal(v.view(np.uint32), vp.reshape(-1).view(np.uint32))
     eng.close()
-
-
-def _compare_trees(sp, osp, games, tag):
-    for g in range(games):
-        for side in (0, 1):
-            gi, gf = sp.tree_dump(g, side)
-            oi, of = osp.tree_dump(g, side)
-            assert gi.shape == oi.shape, f"{tag}: game {g} side {side}: {gi.shape[0]} vs {oi.shape[0]} nodes"
-            assert np.array_equal(gi, oi), f"{tag}: node records differ (game {g} side {side})"
-            assert np.array_equal(gf.view(np.uint32), of.view(np.uint32)), f"{tag}: w/policy bits differ (game {g} side {side})"
-            assert sp.tree_root(g, side)[0] == osp.tree_root(g, side)[0]
-            assert np.float32(sp.tree_root(g, side)[1]).tobytes() == np.float32(osp.tree_root(g, side)[1]).tobytes()
-
-
-def _drive_selfplay_vs_oracle(n, games, count, k, max_plies, mode, threshold=6, max_nodes=2048, max_tables=1024, seed=7,
-                              game_offset=5, weight_seed=0):
-    """Plays `games` games step by step on the engine and on the oracle (the oracle consumes the GPU net's p / v, so the
-    comparison isolates the tree arithmetic) and compares canonical tree dumps, request boards, moves and replay tuples bit
-    for bit.  Returns the shape of the deepest search seen by the ORACLE: (fully expanded nodes, fully expanded non-root
-    nodes, max depth, max tables) so that a test can prove it left the shallow root-plus-one-layer regime."""
-    tensors = oa.weights.init_random(n, seed=weight_seed)
-    eng = oa.Engine(board_size=n, games=games, max_nodes=max_nodes, max_tables=max_tables, max_batch_k=k, seed=seed,
-                    game_offset=game_offset, net_mode=mode)
-    eng.load_weights(tensors)
-    sp = oa.SelfPlay(eng)
-    sp.reset()
-    root_p = eng.evaluate_p(O.Environment(n).encode_nn_input(0)[None]).reshape(-1)
-    osp = O.SelfPlay(n, games, cap_nodes=max_nodes, cap_tables=max_tables, seed=seed, game_offset=game_offset)
-    osp.reset(root_p)
-    _compare_trees(sp, osp, games, "reset")
-    shape = [0, 0, 0, 0]
-    ply = 0
-    rounds = (count + k - 1) // k
-    while osp.alive_count > 0 and (max_plies == 0 or ply < max_plies):
-        for rnd in range(rounds):
-            nreq = sp.round_generate(rnd, k, 0.25, 0.03)
-            oin = osp.round_generate(rnd, k, 0.25, 0.03)
-            assert nreq == len(oin), f"ply {ply} round {rnd}: request count"
-            assert np.array_equal(sp.round_inputs(), oin), f"ply {ply} round {rnd}: request boards"
-            if rnd == 0 or (rounds > 20 and rnd % 16 == 15):  # pending children of the round are in the dump as well
-                _compare_trees(sp, osp, games, f"ply {ply} after generate of round {rnd}")
-            p, v = sp.round_eval()
-            sp.round_scatter()
-            osp.round_scatter(p, v)
-        _compare_trees(sp, osp, games, f"ply {ply} after execute")
-        assert osp.error == 0
-        for g in range(games):
-            if osp.game_alive(g):
-                full, full_nr, depth = tree_shape(osp.tree_dump(g, ply & 1)[0])
-                shape = [max(shape[0], full), max(shape[1], full_nr), max(shape[2], depth), max(shape[3], osp.tree_root(g, ply & 1)[3])]
-        a = sp.sample_actions(1.0, threshold)
-        assert np.array_equal(a, osp.sample(1.0, threshold)), f"ply {ply}: actions"
-        nm = sp.mirror_generate()
-        om = osp.mirror_generate()
-        assert nm == len(om) and np.array_equal(sp.mirror_inputs(), om)
-        pm = sp.mirror_eval()
-        sp.mirror_apply()
-        osp.advance(pm)
-        _compare_trees(sp, osp, games, f"ply {ply} after advance")
-        alive, status, plies = sp.game_info()
-        assert [int(x) for x in alive] == [osp.game_alive(g) for g in range(games)]
-        assert [int(x) for x in status] == [osp.game_status(g) for g in range(games)]
-        ply += 1
-    assert sp.alive_count == osp.alive_count
-    for g in range(games):
-        gb, gt, gp, gz = sp.replay(g)
-        ob, ot, op, oz = osp.replay(g)
-        assert np.array_equal(gb, ob) and np.array_equal(gt, ot) and np.array_equal(gz, oz)
-        assert np.array_equal(gp.view(np.uint32), op.view(np.uint32))
-    eng.close()
-    return tuple(shape)
 
 
 @pytest.mark.parametrize("n,games,count,k,max_plies,mode", [

@@ -132,12 +132,10 @@ def _dump(sp, side):
     return ints, floats
 
 
-@pytest.mark.parametrize("n,count,k,waves,plies", [(9, 96, 8, 1, 6), (9, 256, 8, 8, 8), (9, 250, 4, 16, 6), (15, 800, 16, 16, 3)])
-def test_recorded_interleaving_replays_exactly_on_the_literal_oracle(n, count, k, waves, plies):
+def replay_recorded_on_literal(n, count, k, waves, plies, epsilon=0.25, alpha=0.03, temperature=1.0, threshold=4):
     """The engine searches one tree with `waves` wavefronts in recorded mode; the literal oracle (pointer nodes, stored p, explicit
     refresh loops) replays the recorded lock order with the engine's net outputs: canonical tree dumps, root statistics, request
-    boards, sampled moves and the mirror step must be identical.  count = 250 with K = 4 also covers a last group with fewer rounds
-    than waves and a count that is not a multiple of K."""
+    boards, sampled moves and the mirror step must be identical."""
     seed = 13
     eng, sp = _engine(n, k, seed, waves, max_nodes=8192)
     lit = O.Literal(n, 1, seed=seed, cap_nodes=8192)
@@ -147,7 +145,7 @@ def test_recorded_interleaving_replays_exactly_on_the_literal_oracle(n, count, k
         if sp.alive_count == 0:
             break
         side = sp.ply & 1
-        groups = sp.execute_shared_recorded(count, k, waves=waves)
+        groups = sp.execute_shared_recorded(count, k, epsilon, alpha, waves=waves)
         rounds = -(-count // k)
         assert len(groups) == -(-rounds // waves)
         assert sum(len(g[0]) for g in groups) == rounds * k  # every simulation of every round took its turn
@@ -155,14 +153,14 @@ def test_recorded_interleaving_replays_exactly_on_the_literal_oracle(n, count, k
             assert len(bo) == len(v) == len(p)
             if np.any(np.diff(so.astype(np.int32)) < 0):
                 interleaved += 1  # (a wave with a larger index ran before one with a smaller index: the rounds really interleave)
-        lit.shared_run(count, k, 0.25, 0.03, waves, groups)
+        lit.shared_run(count, k, epsilon, alpha, waves, groups)
         gi, gf = _dump(sp, side)
         li, lf = lit.tree_dump(0, side)
         assert gi.shape == li.shape, f"ply {ply}: {gi.shape[0]} vs {li.shape[0]} nodes"
         assert np.array_equal(gi, li), f"ply {ply}: node records differ"
         assert np.array_equal(gf.view(np.uint32), lf.view(np.uint32)), f"ply {ply}: w / policy bits differ"
-        a = sp.sample_actions(1.0, 4)
-        assert np.array_equal(a, lit.sample(1.0, 4)), f"ply {ply}: moves"
+        a = sp.sample_actions(temperature, threshold)
+        assert np.array_equal(a, lit.sample(temperature, threshold)), f"ply {ply}: moves"
         nm = sp.mirror_generate()
         lm, _ = lit.mirror_generate()
         assert nm == len(lm) and np.array_equal(sp.mirror_inputs(), lm)
@@ -177,6 +175,12 @@ def test_recorded_interleaving_replays_exactly_on_the_literal_oracle(n, count, k
         assert interleaved > 0, "the recorded schedules were all sequential: nothing concurrent was tested"
     assert lit.error == 0
     eng.close()
+
+
+@pytest.mark.parametrize("n,count,k,waves,plies", [(9, 96, 8, 1, 6), (9, 256, 8, 8, 8), (9, 250, 4, 16, 6), (15, 800, 16, 16, 3)])
+def test_recorded_interleaving_replays_exactly_on_the_literal_oracle(n, count, k, waves, plies):
+    """count = 250 with K = 4 also covers a last group with fewer rounds than waves and a count that is not a multiple of K."""
+    replay_recorded_on_literal(n, count, k, waves, plies)
 
 
 def test_recorded_single_wave_equals_the_free_running_one():

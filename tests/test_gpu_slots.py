@@ -7,27 +7,9 @@ import torch
 
 import omok_ai_amd as oa
 from omok_ai_amd import binding as B
+from helpers import episode_records as _episode_records
 
 pytestmark = pytest.mark.gpu
-
-
-def _episode_records(n, total, sims, k, threshold, mode, seed, max_nodes):
-    eng = oa.Engine(board_size=n, games=total, max_nodes=max_nodes, max_tables=max_nodes // 2, max_batch_k=k, seed=seed, net_mode=mode)
-    eng.load_random_weights(0)
-    sp = oa.SelfPlay(eng)
-    sp.reset()
-    stats = sp.run(sims, k, 0.25, 0.03, 1.0, threshold)
-    rec = sp.replay_record_bytes()
-    _, _, plies = sp.game_info()
-    _, status, _ = sp.game_info()
-    lens = [len(sp.replay(g)[1]) for g in range(total)]
-    buf = torch.zeros((sum(lens) + 1) * rec, dtype=torch.uint8, device="cuda")
-    assert sp.replay_pack_into(buf.data_ptr(), sum(lens) + 1) == sum(lens)
-    out = buf.cpu().numpy().reshape(-1, rec)
-    offs = np.concatenate([[0], np.cumsum(lens)])
-    games = [out[offs[g]:offs[g + 1]].copy() for g in range(total)]
-    eng.close()
-    return games, [int(s) for s in status], stats
 
 
 @pytest.mark.parametrize("n,slots,total,sims,k,mode", [

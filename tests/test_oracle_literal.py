@@ -79,7 +79,8 @@ def _compare(A, L, games, tag):
     assert L.live_nodes == total_nodes, f"{tag}: allocator balance {L.live_nodes} vs {total_nodes}"
 
 
-def _drive(n, games, count, k, max_plies, net, threshold=30, seed=7, offset=5, episode=None, external_every=0, ext_seed=0):
+def _drive(n, games, count, k, max_plies, net, threshold=30, seed=7, offset=5, episode=None, external_every=0, ext_seed=0,
+           epsilon=0.25, alpha=0.03, temperature=1.0):
     hw = n * n
     root_p, _ = net.forward(O.Environment(n).encode_nn_input(0)[None])
     cap = min(16384, 4 * count + 1024)
@@ -97,8 +98,8 @@ def _drive(n, games, count, k, max_plies, net, threshold=30, seed=7, offset=5, e
     ply = 0
     while A.alive_count > 0 and (max_plies == 0 or ply < max_plies):
         for rnd in range((count + k - 1) // k):
-            in_a = A.round_generate(rnd, k, 0.25, 0.03)
-            in_l, g_l = L.round_generate(rnd, k, 0.25, 0.03)
+            in_a = A.round_generate(rnd, k, epsilon, alpha)
+            in_l, g_l = L.round_generate(rnd, k, epsilon, alpha)
             assert len(in_a) == len(in_l), f"ply {ply} round {rnd}: request count"
             if len(in_a) == 0:
                 continue
@@ -128,8 +129,8 @@ def _drive(n, games, count, k, max_plies, net, threshold=30, seed=7, offset=5, e
             A.set_actions(acts)
             L.set_actions(acts)
         else:
-            acts = A.sample(1.0, threshold)
-            assert np.array_equal(acts, L.sample(1.0, threshold)), f"ply {ply}: actions"
+            acts = A.sample(temperature, threshold)
+            assert np.array_equal(acts, L.sample(temperature, threshold)), f"ply {ply}: actions"
         for g in range(games):
             if acts[g] >= 0:
                 played[g].add(int(acts[g]))
@@ -169,6 +170,28 @@ def test_literal_equals_arena_oracle_fake_net(n, games, count, k, max_plies, min
 def test_literal_equals_arena_oracle_real_net_and_episode_stream():
     """the random-init net of the GPU tests (flat policies: the wide-and-shallow regime), on a non-zero episode stream"""
     _drive(9, 3, 40, 16, 10, RealNet(9), threshold=4, episode=3)
+
+
+@pytest.mark.parametrize("settings", [
+    {"alpha": 1.0},            # integer alpha: one unit exponential, no rejection loop (f == 0)
+    {"alpha": 2.5},            # two unit exponentials and the rejection loop at f = 0.5
+    {"alpha": 33.0},           # the clamp at k = 32 with f = 1, the largest alpha the sampler serves
+    {"epsilon": 0.0},          # no noise in the mix: the root row is still renormalised (pme.rs:63-68)
+    {"epsilon": 1.0},          # (1 - epsilon) * p vanishes: the root policy is pure noise
+    {"temperature": 0.25},     # exp arguments up to 4
+    {"temperature": 0.05},     # exp arguments up to 20
+], ids=lambda s: ",".join(f"{k}={v}" for k, v in s.items()))
+def test_literal_equals_arena_oracle_off_default_settings(settings):
+    """One search setting off its default at a time (the base case of tests/test_gpu_search_settings.py: N = 9, 3 games, 32 simulations,
+    K = 8, 6 plies, every ply Boltzmann): the yardstick of the GPU test agrees with the reference's own data structures there."""
+    _drive(9, 3, 32, 8, 6, RealNet(9), threshold=99, **settings)
+
+
+def test_literal_equals_arena_oracle_off_default_settings_fully_expanded_root():
+    """32 simulations leave a root with untried actions: the noise is in the root's row but steers nothing, and the visit policy is uniform
+    whatever the temperature.  128 simulations are more than the 81 cells: PUCT reads the noisy row, the policy has unequal entries."""
+    shape, _ = _drive(9, 2, 128, 8, 4, RealNet(9), threshold=99, epsilon=0.5, alpha=2.5, temperature=0.25)
+    assert shape[0] >= 1
 
 
 def test_external_moves_on_both_oracles():
