@@ -54,8 +54,8 @@ pub const OMOK_NET_F16X3_FP6: i32 = 3;
 pub const OMOK_NET_F16X3_F16: i32 = 4;
 pub const OMOK_NET_F16X3_MIXED: i32 = 5;
 pub const OMOK_MAX_ARENA: i32 = 16384;
-pub const OMOK_ALPHA_MAX: i32 = 33; // alpha in (0, 33]
-pub const OMOK_TEMPERATURE_INV_MAX: i32 = 80; // 1 / temperature <= 80
+pub const OMOK_ALPHA_MAX: i32 = 33;
+pub const OMOK_TEMPERATURE_INV_MAX: i32 = 80;
 pub const OMOK_OPP_RANDOM: i32 = 0;
 pub const OMOK_OPP_NAIVE: i32 = 1;
 pub const OMOK_TRAIN_MAX_RANKS: i32 = 64;
@@ -201,6 +201,8 @@ pub mod ffi {
         pub fn omok_debug_set_base_cache(e: *mut OmokEngine, enabled: i32) -> c_int;
         pub fn omok_debug_set_children_kernel(e: *mut OmokEngine, which: i32) -> c_int;
         pub fn omok_debug_set_window_rects(e: *mut OmokEngine, enabled: i32) -> c_int;
+        pub fn omok_debug_set_lazy_policy(e: *mut OmokEngine, enabled: i32) -> c_int;
+        pub fn omok_debug_lazy_policy_stats(e: *mut OmokEngine, out: *mut u64) -> c_int;
         pub fn omok_debug_last_plan(e: *mut OmokEngine, out: *mut i32, cap: i32) -> c_int;
         pub fn omok_get_stats(e: *mut OmokEngine, stats: *mut f64) -> c_int;
         pub fn omok_reset_stats(e: *mut OmokEngine) -> c_int;

@@ -517,6 +517,14 @@ int omok_debug_set_children_kernel(omok_engine* e, int32_t which);
  * differ in (a child differs from its base only within its stone's pixel +- 3 clipped to the board; outside that region its difference row holds exact zeros).
  * Results must not change by a bit (tests): skipped pixels contribute exact zeros. */
 int omok_debug_set_window_rects(omok_engine* e, int32_t enabled);
+/* Debugging aid / A-B switch: enabled = 0 makes the rounds of the run loops (omok_selfplay_run, the slots calls, omok_versus_run) scatter every request's policy
+ * eagerly, as omok_execute, the step-wise calls and match episodes always do.  Default 1: such a round launches no softmax / scatter kernel -- the heads
+ * write a request's logits into its node's policy row, marked raw, and the wave that first reads the row (a descent through the node once it is fully expanded, the
+ * root's noise) turns it into the probabilities with the eager kernel's arithmetic; the mirror evaluation of such a ply stays logits in the same way.  Results must
+ * not change by a bit (tests). */
+int omok_debug_set_lazy_policy(omok_engine* e, int32_t enabled);
+/* out[0] = raw rows turned into probabilities at the root-noise site, out[1] = in a descent, since omok_create.  Synchronises the engine's stream. */
+int omok_debug_lazy_policy_stats(omok_engine* e, uint64_t* out);
 /* Debugging aid of the launch-shape tests: what the LAST net forward of the engine (net 1) decided.  Writes min(cap, OMOK_PLAN_INTS) ints and returns that number:
  *   [0] path: 0 = plain rows (omok_evaluate_pv, mirror and root evaluations), 1 = sibling round on the copy path, 2 = on the difference path,
  *       3 = fp32 kernels, -1 = no forward yet;  [1] the host's bound on the rows (live games x K in a search round);

@@ -308,6 +308,16 @@ class Engine:
     def set_base_cache(self, on=True):
         self._chk(B.lib().omok_debug_set_base_cache(self.h, int(bool(on))))
 
+    def set_lazy_policy(self, on=True):
+        """False: the run loops' rounds scatter every request's policy eagerly, as omok_execute and the step-wise calls do (same bits: tests)."""
+        self._chk(B.lib().omok_debug_set_lazy_policy(self.h, int(bool(on))))
+
+    def lazy_policy_stats(self):
+        """raw policy rows turned into probabilities so far: {"noise": at the root-noise site, "descent": in a descent}"""
+        out = (C.c_uint64 * 2)()
+        self._chk(B.lib().omok_debug_lazy_policy_stats(self.h, out))
+        return {"noise": int(out[0]), "descent": int(out[1])}
+
     def set_window_rects(self, on=True):
         """False: fc0 window tiles walk their bin's whole 7x7 window instead of the rectangle their rows can differ in (same bits: tests)."""
         self._chk(B.lib().omok_debug_set_window_rects(self.h, int(bool(on))))

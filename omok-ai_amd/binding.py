@@ -48,6 +48,7 @@ SYMBOLS = [
     "omok_game_log_enable", "omok_game_log_read", "omok_env_replay",
     "omok_replay_augment_records_dev",
     "omok_selfplay_run_slots_logged", "omok_game_log_entry_bytes",
+    "omok_debug_set_lazy_policy", "omok_debug_lazy_policy_stats",
 ]
 
 
@@ -109,6 +110,9 @@ def lib():
     L.omok_debug_set_base_cache.argtypes = [H, C.c_int32]
     L.omok_debug_set_children_kernel.argtypes = [H, C.c_int32]
     L.omok_debug_set_window_rects.argtypes = [H, C.c_int32]
+    if hasattr(L, "omok_debug_set_lazy_policy"):  # (an older build selected with OMOK_MI355X_LIB for an A/B run has neither)
+        L.omok_debug_set_lazy_policy.argtypes = [H, C.c_int32]
+        L.omok_debug_lazy_policy_stats.argtypes = [H, C.POINTER(C.c_uint64)]
     L.omok_debug_last_plan.argtypes = [H, ip, C.c_int32]
     L.omok_set_episode.argtypes = [H, C.c_uint64]
     L.omok_env_place_stone.argtypes = [H, u8p, u8p, C.POINTER(C.c_uint16), ip, C.c_int32, ip]

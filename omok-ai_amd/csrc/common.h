@@ -40,7 +40,7 @@ struct __attribute__((aligned(16))) NodeHdr {
     uint8_t action;
     uint8_t status;
     uint8_t turn;
-    uint8_t has_policy;
+    uint8_t has_policy; // 0: no row (the placeholder prior), 1: probabilities, 2: RAW -- the heads' logits as written, made into probabilities by the first reader
     uint32_t pad;
 };
 static_assert(sizeof(NodeHdr) == 16, "NodeHdr must be 16 bytes");
@@ -110,6 +110,10 @@ struct RoundArgs {
     int32_t* req_cnt;
     int32_t* zero_ptr;
     int zero_n;
+    // lazy policy rows.  lazy_rows > 0 (with scatter_v): the previous round was a lazy one whose forward covered that many rows -- its requests' nodes
+    // hold raw rows and are marked has_policy = 2 beside their backups.  lazy_stats (may be NULL): [0] += rows materialised at the noise site, [1] += in a descent.
+    int lazy_rows;
+    uint32_t* lazy_stats;
 };
 
 // ---- tree_kernels.hip launchers (all asynchronous on `st`) ---------------------------------
@@ -172,14 +176,18 @@ constexpr int MAX_GAMES = 32767;         // games per engine (omok_create)
 constexpr int SCAN_GAMES_PER_THREAD = 32; // k_scan: one workgroup of 1024 threads, each owning this many consecutive games
 // backups = false: the policies only; the backups (k_scatter) are deferred to launch_backups or into the next round's kernel (RoundArgs::scatter_v)
 void launch_scatter(int n, const Store& S, int side, const float* p_dev, const float* v_dev, int max_count, hipStream_t st, bool backups = true);
-void launch_backups(int n, const Store& S, int side, const float* v_dev, hipStream_t st);
+// raw_rows > 0: the round was a lazy one of that many rows at most: its requests' nodes are marked has_policy = 2 (raw rows, see RoundArgs::lazy_rows)
+void launch_backups(int n, const Store& S, int side, const float* v_dev, hipStream_t st, int raw_rows = 0);
+// every raw policy row of trees [tree_first, tree_first + trees) -> probabilities, has_policy = 1 (what a reader outside k_round runs first)
+void launch_materialise(int n, const Store& S, int tree_first, int trees, hipStream_t st);
 // the same from the net's logits (softmax / tanh of the split-precision path fused into the policy scatter): writes v, vpre, the trees
 void launch_softmax_scatter(int n, const Store& S, int side, const float* logits_dev, int lrow, float* v_dev, float* vpre_dev, int max_count,
                             hipStream_t st, bool backups = true);
 void launch_sample(int n, const Store& S, int side, int ply, float temperature, int threshold, uint64_t seed,
                    int64_t game_offset, int32_t* actions_dev, hipStream_t st);
 void launch_mirror_scan(int n, const Store& S, int side, hipStream_t st);
-void launch_advance(int n, const Store& S, int side, const float* p_dev, hipStream_t st);
+// raw: p_dev holds the mirror evaluation's LOGITS rows ([rows][ROWP]); a node ensure_action_exists creates takes its row as a raw policy row (has_policy = 2)
+void launch_advance(int n, const Store& S, int side, const float* p_dev, hipStream_t st, bool raw = false);
 void launch_encode_requests(int n, const Store& S, float* out_dev /*[B][3HW]*/, int max_b, hipStream_t st);
 void launch_env_play(int n, const int32_t* moves_dev, int batch, int len, int32_t* status_dev, uint8_t* boards_dev,
                      uint8_t* turns_dev, uint16_t* legal_dev, hipStream_t st);

@@ -93,6 +93,8 @@ struct omok_engine {
     int32_t* d_actions = nullptr;
     uint32_t* d_error = nullptr; // [0] error bits, [1] alive count
     unsigned long long* d_evals = nullptr;
+    uint32_t* d_lazy = nullptr;         // [4] rows materialised at the noise site, in a descent (omok_debug_lazy_policy_stats); 2 spare
+    bool lazy_policy = true;            // run-loop rounds leave raw policy rows (omok_debug_set_lazy_policy)
     int32_t* d_req_cnt = nullptr;       // [G] requests of every game in the current round (k_round -> k_group: run-loop rounds on the sibling path)
     uint16_t* d_sh_req = nullptr;       // [MAX_TREE_WAVES][KMAX] requests of the waves of a shared-tree round group
     uint32_t* d_sh_cnt = nullptr;       // [2 * KMAX] their counts | first-request offsets
@@ -323,6 +325,7 @@ extern "C" int omok_create(const omok_config* cfg, omok_engine** out) {
     rc |= dalloc(e, &e->d_error, 4);
     rc |= dalloc(e, &e->d_evals, 2);
     rc |= dalloc(e, &e->d_req_cnt, G);
+    rc |= dalloc(e, &e->d_lazy, 4);
     rc |= dalloc(e, &e->d_sh_req, (size_t)MAX_TREE_WAVES * KMAX);
     rc |= dalloc(e, &e->d_sh_cnt, 2 * (size_t)KMAX);
     rc |= dalloc(e, &e->d_flags, 4);
@@ -338,6 +341,7 @@ extern "C" int omok_create(const omok_config* cfg, omok_engine** out) {
     hipMemsetAsync(S.d_bytes, 0, 16, e->st);
     hipMemsetAsync(e->d_error, 0, 16, e->st);
     hipMemsetAsync(e->d_evals, 0, 16, e->st);
+    hipMemsetAsync(e->d_lazy, 0, 16, e->st);
     hipMemsetAsync(S.gs, 0, sizeof(GameState) * G, e->st);
     hipMemsetAsync(S.ts, 0, sizeof(TreeState) * T, e->st);
     if (set_advance_lds_attribute(e->n, advance_lds_bytes(cfg->max_nodes, cfg->max_tables)) != 0) {
@@ -559,14 +563,14 @@ static int eval_blocks(omok_engine* e, int tree_side, int rows, bool pending, Bl
     return n;
 }
 // one forward of a block's rows by its net (search rounds: sibling_side = the trees' side; a match block's k_group takes the block's games only)
-static void block_forward(omok_engine* e, const Block& B, int max_count, int sibling_side = -1, bool skip_softmax = false) {
+static void block_forward(omok_engine* e, const Block& B, int max_count, int sibling_side = -1, bool skip_softmax = false, bool rows_to_nodes = false) {
     Net& X = *B.net;
     if (e->match) {
         X.grp_lo = B.b ? e->split : 0;
         X.grp_hi = B.b ? e->cfg.games : e->split;
         X.grp_sub = B.b ? e->d_mcnt : nullptr;
     }
-    net_forward_requests(X, B.view, max_count, e->st, &e->prof, sibling_side, skip_softmax);
+    net_forward_requests(X, B.view, max_count, e->st, &e->prof, sibling_side, skip_softmax, rows_to_nodes);
     if (e->match) {
         X.grp_hi = -1;
         X.grp_sub = nullptr;
@@ -1049,12 +1053,21 @@ static int need_reset(omok_engine* e) {
 // the net whose v holds the backups' values of a round on `side` (match episodes: the first block's, after match_join)
 static Net& backup_net(omok_engine* e, int side) { return e->match ? net_at(e, side) : e->net; }
 
-// a block's forward and the scatter of its policies (backups_inline: the scatter kernel runs the round's backups too)
-static void forward_and_scatter(omok_engine* e, const Block& B, int side, int rows_cap, bool backups_inline) {
+// May this round of the run loop be a lazy one?  Non-match engines whose forward is a split-precision one that covers the batch and whose logits rows are
+// as long as a policy row; the round's backups must be deferred ones (they mark the rows).  Returns the row bound of the round's forward, 0: an eager round.
+static int lazy_round_rows(const omok_engine* e, int rows_cap) {
+    if (!e->lazy_policy || e->match || !net_logits_cover_batch(e->net, rows_cap) || !net_rows_fit_policy(e->net)) return 0;
+    return rows_cap;
+}
+
+// a block's forward and the scatter of its policies (backups_inline: the scatter kernel runs the round's backups too).  lazy: no scatter kernel at all -- the heads write
+// the logits rows into the nodes' policy rows and v / vpre themselves; the deferred backups mark the rows raw (lazy_round_rows)
+static void forward_and_scatter(omok_engine* e, const Block& B, int side, int rows_cap, bool backups_inline, bool lazy = false) {
     Net& X = *B.net;
     // the split-precision net hands over its logits: softmax / tanh run inside the policy scatter (no [requests][ROWP] round trip of p)
     const bool fused = net_logits_cover_batch(X, rows_cap);
-    block_forward(e, B, rows_cap, side, fused);
+    block_forward(e, B, rows_cap, side, fused, lazy);
+    if (lazy) return;
     e->prof.begin(PC_TREE_OTHER, e->st);
     if (fused) {
         int lrow = 0;
@@ -1068,8 +1081,9 @@ static void forward_and_scatter(omok_engine* e, const Block& B, int side, int ro
 // kernel.  The caller launches the last round's backups itself (launch_backups).
 // A round of a match episode: the one request list in two blocks, one forward per net on its own block, the policies scattered block by block,
 // then v of the second block joined behind the first's (in the first block's net, which the backups read).
+// lazy (run loops, with defer_backups): this round leaves raw policy rows; pending_raw_rows: the round whose backups are pending did (its row bound).
 static void enqueue_round(omok_engine* e, int round, int K, float eps, float alpha, bool eval_and_scatter, int alive, bool defer_backups = false,
-                          bool pending_backups = false) {
+                          bool pending_backups = false, bool lazy = false, int pending_raw_rows = 0) {
     const int side = e->ply & 1;
     // run-loop rounds whose forward groups the requests by parent (sib_round): no k_scan and no k_fill.  k_round zeroes the grouping counters and leaves every
     // game's request count; k_group derives the request offsets and the round's total from them and writes the dense request list.  The step-wise API and match
@@ -1077,7 +1091,8 @@ static void enqueue_round(omok_engine* e, int round, int K, float eps, float alp
     const int max_req = std::min(alive * K, e->net.max_b);
     const bool sib_round = !e->match && eval_and_scatter && net_round_takes_sibling_path(e->net, max_req);
     RoundArgs a{side, round, K, e->ply, eps, alpha, e->key, e->cfg.game_offset, pending_backups ? backup_net(e, side).v : nullptr,
-                sib_round ? e->d_req_cnt : nullptr, sib_round ? e->net.d_gcnt : nullptr, sib_round ? NET_GCNT_INTS : 0};
+                sib_round ? e->d_req_cnt : nullptr, sib_round ? e->net.d_gcnt : nullptr, sib_round ? NET_GCNT_INTS : 0,
+                pending_backups ? pending_raw_rows : 0, e->d_lazy};
     e->prof.round_begin();
     e->prof.begin(PC_ROUND, e->st);
     launch_round(e->n, e->S, a, e->st);
@@ -1096,7 +1111,7 @@ static void enqueue_round(omok_engine* e, int round, int K, float eps, float alp
     if (eval_and_scatter) {
         Block blk[2];
         const int nb = eval_blocks(e, side, alive * K, false, blk);
-        for (int i = 0; i < nb; ++i) forward_and_scatter(e, blk[i], side, alive * K, !e->match && !defer_backups);
+        for (int i = 0; i < nb; ++i) forward_and_scatter(e, blk[i], side, alive * K, !e->match && !defer_backups, lazy);
         if (e->match) { // the blocks' scatters ran no backups: they read one v array in list order
             e->prof.begin(PC_TREE_OTHER, e->st);
             match_join(e, side, false, max_req);
@@ -1107,16 +1122,18 @@ static void enqueue_round(omok_engine* e, int round, int K, float eps, float alp
     e->prof.round_end();
 }
 
-static int enqueue_execute(omok_engine* e, int count, int K, float eps, float alpha, int alive) {
+// run_loop: the caller is one of the whole-episode loops (play_ply), whose rounds may be lazy ones; omok_execute keeps the eager kernels
+static int enqueue_execute(omok_engine* e, int count, int K, float eps, float alpha, int alive, bool run_loop = false) {
     int processed = 0, round = 0;
+    const int raw_rows = run_loop ? lazy_round_rows(e, alive * K) : 0;
     while (processed < count) { // pme.rs:39-42,207
-        enqueue_round(e, round, K, eps, alpha, true, alive, true, round > 0);
+        enqueue_round(e, round, K, eps, alpha, true, alive, true, round > 0, raw_rows > 0, raw_rows);
         processed += K;
         round += 1;
     }
     if (round > 0) { // the last round's backups
         e->prof.begin(PC_TREE_OTHER, e->st);
-        launch_backups(e->n, e->S, e->ply & 1, backup_net(e, e->ply & 1).v, e->st);
+        launch_backups(e->n, e->S, e->ply & 1, backup_net(e, e->ply & 1).v, e->st, raw_rows);
         e->prof.end(e->st);
     }
     return round;
@@ -1186,6 +1203,7 @@ static int execute_shared(omok_engine* e, const char* who, int count, int K, flo
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;
     const int side = e->ply & 1;
     RoundArgs a{side, 0, 0, e->ply, epsilon, alpha, e->key, e->cfg.game_offset};
+    launch_materialise(e->n, e->S, side * e->cfg.games, 1, e->st); // (k_round_shared has its own copy of the descent: it meets no raw row an earlier run loop left)
     e->prof.begin(PC_ROUND, e->st);
     launch_round(e->n, e->S, a, e->st); // K = 0, round 0: the root's Dirichlet noise only (mcts_executor.rs:38-68)
     e->prof.end(e->st);
@@ -1283,15 +1301,19 @@ static void enqueue_log_move(omok_engine* e, int side) {
 
 // the re-rooting of a ply whose mirror batch (at most max_rows rows) has been evaluated: the policies of the opponent's new roots in one array (a match: the
 // second block's behind the first's), the move log's entry, k_advance
-static void enqueue_advance(omok_engine* e, int max_rows) {
+// raw (lazy plies of the run loops): the mirror forward stopped behind the heads; a node k_advance creates takes its LOGITS row as a raw policy row
+static void enqueue_advance(omok_engine* e, int max_rows, bool raw = false) {
     const int side = e->ply & 1;
     if (e->match) match_join(e, 1 - side, true, max_rows);
     enqueue_log_move(e, side);
-    launch_advance(e->n, e->S, side, backup_net(e, 1 - side).p, e->st);
+    int lrow = 0;
+    launch_advance(e->n, e->S, side, raw ? net_logits(e->net, &lrow) : backup_net(e, 1 - side).p, e->st, raw);
     invalidate_nets(e);
 }
 
-static void enqueue_mirror_and_advance(omok_engine* e, int alive) {
+// run_loop: one of the whole-episode loops (play_ply); its mirror evaluation may stay logits (lazy_round_rows: the row of a new root is read by its noise)
+static void enqueue_mirror_and_advance(omok_engine* e, int alive, bool run_loop = false) {
+    const bool raw = run_loop && lazy_round_rows(e, alive) > 0;
     const int side = e->ply & 1;
     e->prof.begin(PC_PLY, e->st);
     launch_mirror_scan(e->n, e->S, side, e->st);
@@ -1300,9 +1322,9 @@ static void enqueue_mirror_and_advance(omok_engine* e, int alive) {
     e->prof.end(e->st);
     Block blk[2];
     const int nb = eval_blocks(e, 1 - side, alive, false, blk);
-    for (int i = 0; i < nb; ++i) block_forward(e, blk[i], alive);
+    for (int i = 0; i < nb; ++i) block_forward(e, blk[i], alive, -1, raw);
     e->prof.begin(PC_PLY, e->st);
-    enqueue_advance(e, alive);
+    enqueue_advance(e, alive, raw);
     e->prof.end(e->st);
 }
 
@@ -1313,11 +1335,11 @@ struct Search { int count, K; float epsilon, alpha, temperature; int threshold; 
 static void play_ply(omok_engine* e, const Search& s, int alive, int scripted = -1) {
     if (scripted >= 0) enqueue_opponent_move(e, scripted);
     else {
-        const int rounds = enqueue_execute(e, s.count, s.K, s.epsilon, s.alpha, alive);
+        const int rounds = enqueue_execute(e, s.count, s.K, s.epsilon, s.alpha, alive, true);
         enqueue_sample(e, s.temperature, s.threshold);
         e->sims += (double)rounds * s.K * alive;
     }
-    enqueue_mirror_and_advance(e, alive);
+    enqueue_mirror_and_advance(e, alive, true);
 }
 
 // ends a ply: the one status read-back and the host's accounting.  *alive: the games that moved -> the games still alive; count_finished: the difference
@@ -1595,6 +1617,7 @@ extern "C" int omok_root_children(omok_engine* e, int32_t game, int32_t side, in
     const size_t t = (size_t)side * e->cfg.games + game, rp = (size_t)e->rowp, nw2 = 2 * (size_t)e->nw;
     const size_t tn = t * (size_t)e->S.stride_nodes, tt = t * (size_t)e->S.stride_tables;
     NodeHdr h0;
+    launch_materialise(e->n, e->S, (int)t, 1, e->st); // (a raw root row of a lazy round -> the probabilities read below)
     HIPCHK(e, hipMemcpyAsync(&h0, e->S.hdr + tn, sizeof(h0), hipMemcpyDeviceToHost, e->st));
     if (sync_and_check(e, "root_children")) return OMOK_ERR_HIP;
     if (h0.table == NONE16 || h0.nch == 0) return 0;
@@ -1980,6 +2003,7 @@ extern "C" int omok_tree_dump(omok_engine* e, int32_t game, int32_t side, int32_
     if (!e || !ints || !floats || game < 0 || game >= e->cfg.games || (side != 0 && side != 1)) return OMOK_ERR_INVALID;
     ENTER(e);
     const size_t t = (size_t)side * e->cfg.games + game;
+    launch_materialise(e->n, e->S, (int)t, 1, e->st); // (raw rows of lazy rounds: the caller sees has_policy = 1 and the eager kernels' bits; changes no later result)
     TreeState ts;
     HIPCHK(e, hipMemcpyAsync(&ts, e->S.ts + t, sizeof(ts), hipMemcpyDeviceToHost, e->st));
     if (sync_and_check(e, "tree_dump")) return OMOK_ERR_HIP;
@@ -2167,6 +2191,22 @@ extern "C" int omok_debug_set_base_cache(omok_engine* e, int32_t enabled) {
     if (!e) return OMOK_ERR_INVALID;
     e->net.base_cache = enabled != 0;
     net_invalidate_sibling_cache(e->net);
+    return OMOK_OK;
+}
+
+extern "C" int omok_debug_set_lazy_policy(omok_engine* e, int32_t enabled) {
+    if (!e) return OMOK_ERR_INVALID;
+    e->lazy_policy = enabled != 0; // (raw rows that exist stay valid: every reader handles them whatever the switch says)
+    return OMOK_OK;
+}
+extern "C" int omok_debug_lazy_policy_stats(omok_engine* e, uint64_t* out) {
+    if (!e || !out) return OMOK_ERR_INVALID;
+    ENTER(e);
+    uint32_t c[2] = {0, 0};
+    HIPCHK(e, hipMemcpyAsync(c, e->d_lazy, sizeof(c), hipMemcpyDeviceToHost, e->st));
+    if (sync_and_check(e, "lazy_policy_stats")) return OMOK_ERR_HIP;
+    out[0] = c[0];
+    out[1] = c[1];
     return OMOK_OK;
 }
 

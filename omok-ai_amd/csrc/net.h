@@ -170,7 +170,19 @@ constexpr int NET_GCNT_INTS = NET_GCNT_P0 + 225; // ints of Net::d_gcnt
 // [WIN_TILES] window tiles, [FULL_TILES] 128-row tiles of the full-row fc0
 constexpr int NET_WORK_DIFF = 0, NET_WORK_COPY = 3, NET_WORK_DIFF_FULL = 6, NET_WORK_WIN_PIXELS = 7, NET_WORK_WIN_TILES = 8, NET_WORK_FULL_TILES = 9, NET_WORK_COUNT = 16;
 // skip_softmax (split-precision modes only): stop behind the heads; the caller turns net_logits() into p / v itself (launch_softmax_scatter).
-void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t st, struct Prof* prof, int sibling_side = -1, bool skip_softmax = false);
+// rows_to_nodes (with skip_softmax, where net_rows_fit_policy): the heads write request d's logits row into the policy row of the node S.req_ref[d] instead of
+// net_logits(), and net.v / net.vpre themselves: the run loop's lazy rounds.  net_logits() then does NOT hold this forward's rows.
+void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t st, struct Prof* prof, int sibling_side = -1, bool skip_softmax = false,
+                          bool rows_to_nodes = false);
+bool net_rows_fit_policy(const Net& net); // a logits row is as long as a policy row (and the forward is a split-precision one)
+// What the heads' epilogues get by value.  req_ref == NULL: dense rows.  Else row d -> policy + ((ref >> 16) * stride_nodes + (ref & 0xFFFF)) * ROWP with
+// ref = req_ref[d], and v[d] = tanhf(vpre[d] = output hw of the row).
+struct LogitsDst {
+    const uint32_t* req_ref;
+    float* policy;
+    float *v, *vpre;
+    int stride_nodes, hw;
+};
 // Forward of explicit f32 inputs already in net.in_f32 ([count][3HW]); count is a host value
 // and must also be stored in S.d_count[0] by the caller.
 void net_forward_inputs(Net& net, const Store& S, int count, hipStream_t st, struct Prof* prof);

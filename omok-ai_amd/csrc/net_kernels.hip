@@ -3087,12 +3087,35 @@ __device__ __forceinline__ void gemm_t_mainloop(uint4* lds, const uint4* __restr
     }
 }
 
+// Where an EPI_LOGITS epilogue puts row d (LogitsDst, net.h).  No request list: the dense rows of out_logits.  With one (the run loop's lazy rounds):
+// request d's row IS its node's policy row -- the same 16-byte pieces from the same lanes, only the row's base differs -- and the lane that holds output HW (the value
+// in front of tanh) also writes vpre[d] and v[d], as k_softmax does for the dense rows.
+__device__ inline float* logits_row(const LogitsDst& D, float* out_logits, size_t sample, int width) {
+    if (!D.req_ref) return out_logits + sample * width;
+    const uint32_t ref = D.req_ref[sample];
+    return D.policy + ((size_t)(ref >> 16) * (size_t)D.stride_nodes + (size_t)(ref & 0xFFFFu)) * width;
+}
+// (two steps, so that an unrolled epilogue holds ONE tanhf: logits_value_pick in front of every piece's store -- o = outputs [col, col + 4) of the row, a few selects --
+//  and logits_value_store once per sample behind its pieces; `have`: this lane held output HW of the sample)
+__device__ inline void logits_value_pick(const LogitsDst& D, int col, const f32x4& o, float& x, bool& have) {
+    const int q = D.hw - col;
+    const bool mine = (unsigned)q < 4u;
+    x = mine ? (q == 0 ? o[0] : q == 1 ? o[1] : q == 2 ? o[2] : o[3]) : x;
+    have = have || mine;
+}
+__device__ inline void logits_value_store(const LogitsDst& D, size_t sample, float x, bool have) {
+    if (D.req_ref && have) {
+        D.vpre[sample] = x;
+        D.v[sample] = tanhf(x);
+    }
+}
+
 template <int MT, int EPI, int TAG, int NST>
 __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, const uint4* __restrict__ act, int ksteps,
                                                 size_t act_row_u4, int k_full, int last_cnt, int lo_off,
                                                 const float* __restrict__ bias, uint4* __restrict__ out_split,
                                                 size_t out_row_u4, float* __restrict__ out_logits, const int32_t* __restrict__ d_count,
-                                                int max_count) {
+                                                int max_count, LogitsDst D) {
     constexpr int MTW = MT / 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint4* lds = (uint4*)smem;
@@ -3114,6 +3137,9 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
     for (int c = 0; c < 2; ++c) {
         const int sample = b0 + 32 * (2 * ws + c) + (lane & 31);
         if (sample >= count) continue;
+        float* lrow = EPI == EPI_LOGITS ? logits_row(D, out_logits, (size_t)sample, MT * 32) : nullptr;
+        float vx = 0.0f;
+        bool vhave = false;
 #pragma unroll
         for (int i = 0; i < MTW; ++i) {
             const int mt = wm * MTW + i;
@@ -3150,10 +3176,12 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
                     f32x4 o;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) o[q] = y[4 * g + q];
-                    *(f32x4*)(out_logits + (size_t)sample * (MT * 32) + 32 * mt + 8 * g + 4 * h) = o;
+                    *(f32x4*)(lrow + 32 * mt + 8 * g + 4 * h) = o;
+                    logits_value_pick(D, 32 * mt + 8 * g + 4 * h, o, vx, vhave);
                 }
             }
         }
+        if (EPI == EPI_LOGITS) logits_value_store(D, (size_t)sample, vx, vhave);
     }
 }
 
@@ -3178,7 +3206,7 @@ __global__ __launch_bounds__(512) void k_gemm_t(const uint4* __restrict__ wp, co
 template <int MTH>
 __global__ __launch_bounds__(512) void k_tail_fused(const uint4* __restrict__ wp_fc1, const uint4* __restrict__ act, const float* __restrict__ bias_fc1,
                                                     const uint4* __restrict__ wp_heads, const float* __restrict__ bias_heads, float* __restrict__ out_logits,
-                                                    const int32_t* __restrict__ d_count, int max_count) {
+                                                    const int32_t* __restrict__ d_count, int max_count, LogitsDst D) {
     constexpr int MTW = MTH / 4;           // heads m-tiles per wave
     constexpr int WFR = MTH * 2;           // heads weight fragments per k-step
     constexpr int LPW = WFR / 8;           // LDS-DMA instructions per wave per heads k-step
@@ -3309,6 +3337,9 @@ __global__ __launch_bounds__(512) void k_tail_fused(const uint4* __restrict__ wp
     for (int c = 0; c < 2; ++c) {
         const int sample = b0 + 32 * (2 * ws + c) + (lane & 31);
         if (sample >= count) continue;
+        float* lrow = logits_row(D, out_logits, (size_t)sample, MTH * 32);
+        float vx = 0.0f;
+        bool vhave = false;
 #pragma unroll
         for (int i = 0; i < MTW; ++i) {
             const int mt = wm * MTW + i;
@@ -3318,9 +3349,11 @@ __global__ __launch_bounds__(512) void k_tail_fused(const uint4* __restrict__ wp
                 f32x4 o;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) o[q] = acc[i][c][4 * g + q] + bv[q];
-                *(f32x4*)(out_logits + (size_t)sample * (MTH * 32) + 32 * mt + 8 * g + 4 * h) = o;
+                *(f32x4*)(lrow + 32 * mt + 8 * g + 4 * h) = o;
+                logits_value_pick(D, 32 * mt + 8 * g + 4 * h, o, vx, vhave);
             }
         }
+        logits_value_store(D, (size_t)sample, vx, vhave);
     }
 }
 
@@ -3345,7 +3378,7 @@ constexpr int gemm_w_lds(int mt) { return (8 * GW_DA * (mt / 8) * 2 + GW_NB * 16
 template <int MT, int EPI>
 __global__ __launch_bounds__(512) void k_gemm_w(const uint4* __restrict__ wp, const uint4* __restrict__ act, int ksteps, size_t act_row_u4,
                                                 const float* __restrict__ bias, uint4* __restrict__ out_split, size_t out_row_u4,
-                                                float* __restrict__ out_logits, const int32_t* __restrict__ d_count, int max_count) {
+                                                float* __restrict__ out_logits, const int32_t* __restrict__ d_count, int max_count, LogitsDst D) {
     static_assert(MT % 8 == 0 && EPI != EPI_PARTIAL, "k_gemm_w: whole-K launches of at least one m-tile per wave");
     constexpr int MTW = MT / 8;               // m-tiles per wave
     constexpr int AF = MTW * 2;               // weight fragments (hi, lo) per wave and k-step
@@ -3445,6 +3478,9 @@ __global__ __launch_bounds__(512) void k_gemm_w(const uint4* __restrict__ wp, co
     for (int ct = 0; ct < 4; ++ct) {
         const int sample = b0 + 32 * ct + sl;
         if (sample >= count) continue;
+        float* lrow = EPI == EPI_LOGITS ? logits_row(D, out_logits, (size_t)sample, MT * 32) : nullptr;
+        float vx = 0.0f;
+        bool vhave = false;
 #pragma unroll
         for (int i = 0; i < MTW; ++i) {
             const int mt = wave * MTW + i;
@@ -3473,10 +3509,12 @@ __global__ __launch_bounds__(512) void k_gemm_w(const uint4* __restrict__ wp, co
                     f32x4 o;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) o[q] = y[4 * g + q];
-                    *(f32x4*)(out_logits + (size_t)sample * (MT * 32) + 32 * mt + 8 * g + 4 * h) = o;
+                    *(f32x4*)(lrow + 32 * mt + 8 * g + 4 * h) = o;
+                    logits_value_pick(D, 32 * mt + 8 * g + 4 * h, o, vx, vhave);
                 }
             }
         }
+        if (EPI == EPI_LOGITS) logits_value_store(D, (size_t)sample, vx, vhave);
     }
 }
 
@@ -3512,7 +3550,7 @@ __global__ __launch_bounds__(256) void k_splitk_finish(const float* __restrict__
 
 // split-K finish of the heads: partials in split order + bias -> logits rows
 __global__ __launch_bounds__(256) void k_splitk_logits(const float* __restrict__ part, int nsplit, size_t cap_rows, int width, const float* __restrict__ bias,
-                                                       float* __restrict__ logits, const int32_t* __restrict__ d_count, int max_count) {
+                                                       float* __restrict__ logits, const int32_t* __restrict__ d_count, int max_count, LogitsDst D) {
     int count = d_count[0];
     if (count > max_count) count = max_count;
     const size_t per_row = (size_t)width / 4, total = (size_t)count * per_row;
@@ -3527,7 +3565,11 @@ __global__ __launch_bounds__(256) void k_splitk_logits(const float* __restrict__
         const f32x4 bv = *(const f32x4*)(bias + col);
 #pragma unroll
         for (int j = 0; j < 4; ++j) a[j] += bv[j];
-        *(f32x4*)(logits + row * width + col) = a;
+        *(f32x4*)(logits_row(D, logits, row, width) + col) = a;
+        float vx = 0.0f;
+        bool vhave = false;
+        logits_value_pick(D, (int)col, a, vx, vhave);
+        logits_value_store(D, row, vx, vhave);
     }
 }
 
@@ -3955,7 +3997,7 @@ static void launch_trunk_fmt(Net& net, const Store& S, int max_count, hipStream_
 template <int MT, int EPI, int TAG, int NST = 3>
 static void launch_gemm(const void* wp, const void* act, int ksteps, size_t act_row_u4, int k_full, int last_cnt, int lo_off,
                         const float* bias, void* out_split, size_t out_row_u4, float* out_logits, const Store& S, int max_count,
-                        hipStream_t st, int device, int nsplit = 1) {
+                        hipStream_t st, int device, int nsplit = 1, const LogitsDst& D = LogitsDst{}) {
     constexpr int LDS = (MT * 2 + 8) * 1024 * NST;
     static bool attr_done[64] = {};
     auto kern = k_gemm_t<MT, EPI, TAG, NST>;
@@ -3965,12 +4007,12 @@ static void launch_gemm(const void* wp, const void* act, int ksteps, size_t act_
     }
     const dim3 grid((max_count + GT_BS - 1) / GT_BS, nsplit);
     kern<<<grid, 512, LDS, st>>>((const uint4*)wp, (const uint4*)act, ksteps, act_row_u4, k_full, last_cnt, lo_off, bias, (uint4*)out_split,
-                                  out_row_u4, out_logits, S.d_count, max_count);
+                                  out_row_u4, out_logits, S.d_count, max_count, D);
 }
 
 template <int MTH>
 static void launch_tail_fused(const void* wp_fc1, const void* act, const float* bias_fc1, const void* wp_heads, const float* bias_heads, float* out_logits, const Store& S,
-                              int max_count, hipStream_t st, int device) {
+                              int max_count, hipStream_t st, int device, const LogitsDst& D) {
     constexpr int LDS = 160 * 1024;
     static bool attr_done[64] = {};
     auto kern = k_tail_fused<MTH>;
@@ -3979,12 +4021,12 @@ static void launch_tail_fused(const void* wp_fc1, const void* act, const float* 
         attr_done[device & 63] = true;
     }
     kern<<<dim3((max_count + GT_BS - 1) / GT_BS), 512, LDS, st>>>((const uint4*)wp_fc1, (const uint4*)act, bias_fc1, (const uint4*)wp_heads, bias_heads, out_logits, S.d_count,
-                                                                 max_count);
+                                                                 max_count, D);
 }
 
 template <int MT, int EPI>
 static void launch_gemm_w(const void* wp, const void* act, int ksteps, size_t act_row_u4, const float* bias, void* out_split, size_t out_row_u4, float* out_logits,
-                          const Store& S, int max_count, hipStream_t st, int device) {
+                          const Store& S, int max_count, hipStream_t st, int device, const LogitsDst& D = LogitsDst{}) {
     constexpr int LDS = gemm_w_lds(MT);
     static_assert(LDS <= 160 * 1024, "k_gemm_w LDS");
     static bool attr_done[64] = {};
@@ -3994,7 +4036,7 @@ static void launch_gemm_w(const void* wp, const void* act, int ksteps, size_t ac
         attr_done[device & 63] = true;
     }
     kern<<<dim3((max_count + GT_BS - 1) / GT_BS), 512, LDS, st>>>((const uint4*)wp, (const uint4*)act, ksteps, act_row_u4, bias, (uint4*)out_split, out_row_u4, out_logits,
-                                                                 S.d_count, max_count);
+                                                                 S.d_count, max_count, D);
 }
 
 // K splits of the difference path's fc0 launches (chosen on the device, bin_prefix_role): the full rows up to 30 ways as far as the
@@ -4246,7 +4288,8 @@ static int tail_tsplit(int rows, int n_cu, size_t part_rows) {
     while (tsplit < 8 && tiles_t * tsplit * 2 <= n_cu && (size_t)(tsplit * 2) * (size_t)(tiles_t * GT_BS) <= part_rows) tsplit *= 2;
     return tsplit;
 }
-static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32, hipStream_t st, Prof* prof, int sib_side = -1, bool skip_softmax = false) {
+static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32, hipStream_t st, Prof* prof, int sib_side = -1, bool skip_softmax = false,
+                          bool rows_to_nodes = false) {
     const int hw = net.hw;
     const int use_sib = sib_env();
     const bool sib = sibling_path(net, from_f32, sib_side);
@@ -4288,6 +4331,9 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     if (prof) { prof->end(st); prof->begin(PC_TAIL, st); }
     // fc1 and heads: whole K, or K split over blockIdx.y (tail_tsplit)
     const int MT = heads_mt(hw);
+    // rows_to_nodes (with skip_softmax): the logits rows go into the requests' policy rows, v and vpre are written here (LogitsDst); the rows are as long as a policy row
+    LogitsDst D{};
+    if (rows_to_nodes && skip_softmax && MT * 32 == net.rowp) D = LogitsDst{S.req_ref, S.policy, net.v, net.vpre, S.stride_nodes, hw};
     const int tiles_t = (max_count + GT_BS - 1) / GT_BS;
     const int tsplit = net.plan_tsplit = tail_tsplit(max_count, net.n_cu, net.part_rows);
     const size_t cap_t = (size_t)tiles_t * GT_BS;
@@ -4299,12 +4345,12 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
         const char* gw_env = getenv("OMOK_GEMM_W");
         const bool gw = gw_env && gw_env[0] == '1';
         if (!gw) {
-            if (MT == 8) launch_tail_fused<8>(net.wt_fc1, h0, bias_fc1, net.wt_heads, bias_heads, net.s0, S, max_count, st, net.device);
-            else launch_tail_fused<4>(net.wt_fc1, h0, bias_fc1, net.wt_heads, bias_heads, net.s0, S, max_count, st, net.device);
+            if (MT == 8) launch_tail_fused<8>(net.wt_fc1, h0, bias_fc1, net.wt_heads, bias_heads, net.s0, S, max_count, st, net.device, D);
+            else launch_tail_fused<4>(net.wt_fc1, h0, bias_fc1, net.wt_heads, bias_heads, net.s0, S, max_count, st, net.device, D);
         } else {
             launch_gemm_w<16, EPI_SPLIT>(net.wt_fc1, h0, 32, 128, bias_fc1, h1, 128, nullptr, S, max_count, st, net.device);
-            if (MT == 8) launch_gemm_w<8, EPI_LOGITS>(net.wt_heads, h1, 32, 128, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
-            else launch_gemm<4, EPI_LOGITS, 2>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device);
+            if (MT == 8) launch_gemm_w<8, EPI_LOGITS>(net.wt_heads, h1, 32, 128, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device, D);
+            else launch_gemm<4, EPI_LOGITS, 2>(net.wt_heads, h1, 32, 128, 32, 1, 2, bias_heads, nullptr, 0, net.s0, S, max_count, st, net.device, 1, D);
         }
     } else {
         launch_gemm<16, EPI_PARTIAL, 1>(net.wt_fc1, h0, 32 / tsplit, 128, 32, 1, 2, bias_fc1, nullptr, cap_t, net.part, S, max_count, st, net.device, tsplit);
@@ -4312,7 +4358,7 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
         if (MT == 8) launch_gemm<8, EPI_PARTIAL, 2>(net.wt_heads, h1, 32 / tsplit, 128, 32, 1, 2, bias_heads, nullptr, cap_t, net.part, S, max_count, st, net.device, tsplit);
         else launch_gemm<4, EPI_PARTIAL, 2>(net.wt_heads, h1, 32 / tsplit, 128, 32, 1, 2, bias_heads, nullptr, cap_t, net.part, S, max_count, st, net.device, tsplit);
         const unsigned lg = (unsigned)(((size_t)max_count * (MT * 8) + 255) / 256);
-        k_splitk_logits<<<lg < 2048 ? lg : 2048, 256, 0, st>>>(net.part, tsplit, cap_t, MT * 32, bias_heads, net.s0, S.d_count, max_count);
+        k_splitk_logits<<<lg < 2048 ? lg : 2048, 256, 0, st>>>(net.part, tsplit, cap_t, MT * 32, bias_heads, net.s0, S.d_count, max_count, D);
     }
     const int sg = max_count < 32768 ? max_count : 32768; // one wave per row up to 32 waves per SIMD: the row loop is a chain of dependent loads
     if (!skip_softmax) k_softmax<<<sg, 64, 0, st>>>(net.s0, MT * 32, hw, net.rowp, net.p, net.v, net.vpre, S.d_count, max_count);
@@ -4576,7 +4622,9 @@ static int net_probe(Net& net, const Store& S, hipStream_t st) {
 
 bool net_logits_cover_batch(const Net& net, int max_count) { return net.mode != OMOK_NET_F32 && max_count <= net.max_b; }
 
-void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t st, Prof* prof, int sibling_side, bool skip_softmax) {
+bool net_rows_fit_policy(const Net& net) { return net.mode != OMOK_NET_F32 && heads_mt(net.hw) * 32 == net.rowp; }
+
+void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t st, Prof* prof, int sibling_side, bool skip_softmax, bool rows_to_nodes) {
     if (max_count <= 0) return;
     if (max_count > net.max_b) max_count = net.max_b;
     if (net.mode == OMOK_NET_F32) {
@@ -4585,7 +4633,7 @@ void net_forward_requests(Net& net, const Store& S, int max_count, hipStream_t s
         forward_f32(net, S, max_count, st, prof);
         net.plan_path = 3; net.plan_rows = max_count; net.plan_nsplit = net.plan_tsplit = 0;
     } else {
-        forward_f16x3(net, S, max_count, false, st, prof, sibling_side, skip_softmax);
+        forward_f16x3(net, S, max_count, false, st, prof, sibling_side, skip_softmax, rows_to_nodes);
     }
 }
 

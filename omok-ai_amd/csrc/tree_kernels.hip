@@ -7,7 +7,8 @@
 //              277-286; terminal shortcut :92-97; random untried action :101-125; place_stone
 //              environment/src/lib.rs:104-166; expand node.rs:61-81; propagate node.rs:83-99 })
 //   k_scan     the order-preserving request concat of pme.rs:194-205 (tree order, then sim order)
-//   k_scatter  pme.rs:222-265
+//   k_scatter  pme.rs:222-265 (the run loop's rounds leave the policy part undone: the heads write the logits into the node's policy row, the
+//              backups mark it raw, and policy_materialise makes the probabilities where a descent or the root's noise first reads the row)
 //   k_sample   alpha-zero/src/agent.rs:43-137 + src/trainer.rs:138-173 (transition record)
 //   k_advance  agent.rs:144-232 + mcts/src/lib.rs:47-93 (transition) + trainer.rs:156-201
 //
@@ -420,13 +421,77 @@ __device__ inline int add_child(const Store& S, const Tree<N>& T, Regs& R, int p
 }
 
 // ---------------------------------------------------------------------------------------------
+// RAW policy rows (NodeHdr::has_policy == POLICY_RAW).  The run loop's rounds do not launch k_softmax_scatter_policy: the net's heads write a request's
+// logits row straight into its node's policy row (cells 0 .. HW-1 the logits, cell HW the value in front of tanh, the pad cells whatever the pad m-tiles give) and
+// scatter_tree marks the node.  A row is only ever read once its node is fully expanded (select_leaf) or the root (apply_noise) -- a handful of the ~900 nodes a move
+// creates -- and the wave that first needs it turns it into the probabilities here: k_softmax_scatter_policy's arithmetic for ONE request, operation for operation
+// (max over the lane's cells ascending then the xor butterfly, expf(l - mx), per-lane partial sums then the butterfly, row / sum, the occupied cells masked to 0, the
+// sequential f32 sum over the cells ascending, renormalised iff F32_EPS <= sum with __fdiv_rn(1, sum)), so the stored row has the eager kernel's bits.  A node's board never
+// changes once published, so it does not matter when this runs.  Wave-wide (all 64 lanes call); the row is visible to this wave's later loads when it returns.
+// ---------------------------------------------------------------------------------------------
+constexpr uint8_t POLICY_RAW = 2;
+#ifndef LAZY_INLINE
+#define LAZY_INLINE inline // (A-B builds: -DLAZY_INLINE=__noinline__; measured in registers: see DESIGN.md 15)
+#endif
+template <int N>
+__device__ LAZY_INLINE void policy_materialise_at(float* __restrict__ prow, const uint64_t* __restrict__ bnode, NodeHdr* hnode, float* s_row) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW, hw = G::HW;
+    const int lane = LANE;
+    float lv[G::IT];
+#pragma unroll
+    for (int jj = 0; jj < G::IT; ++jj) lv[jj] = lane + 64 * jj < hw ? prow[lane + 64 * jj] : -INFINITY;
+    uint64_t occ[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) occ[w] = bnode[w] | bnode[NW + w];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int jj = 0; jj < G::IT; ++jj) mx = fmaxf(mx, lv[jj]);
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    float sum = 0.0f, row[G::IT];
+#pragma unroll
+    for (int jj = 0; jj < G::IT; ++jj) {
+        const int a = lane + 64 * jj;
+        row[jj] = 0.0f;
+        if (a < hw) { row[jj] = expf(lv[jj] - mx); sum += row[jj]; }
+    }
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    __syncthreads(); // (s_row may still be being read)
+#pragma unroll
+    for (int jj = 0; jj < G::IT; ++jj) {
+        const int a = jj * 64 + lane;
+        const float p = a < hw ? row[jj] / sum : 0.0f;
+        const bool empty = a < hw && !((occ[jj] >> lane) & 1ULL);
+        row[jj] = empty ? p : 0.0f; // pme.rs:235-239
+        s_row[a] = row[jj];
+    }
+    __syncthreads();
+    const float acc = seq_sum(s_row, hw); // pme.rs:241-249
+    const bool renorm = F32_EPS <= acc;
+    const float inv = renorm ? __fdiv_rn(1.0f, acc) : 1.0f;
+#pragma unroll
+    for (int jj = 0; jj < G::IT; ++jj) prow[jj * 64 + lane] = renorm ? row[jj] * inv : row[jj];
+    if (lane == 0) hnode->has_policy = 1;
+    __syncthreads();
+}
+// site: 0 = the root in front of its noise, 1 = a node of a descent; s_cnt (LDS, may be NULL): [site] counts the wave's rows (k_round adds them to RoundArgs::lazy_stats
+// when it ends: a pointer into HBM carried through the descent would cost the hot loop registers it does not have)
+template <int N>
+__device__ inline void policy_materialise(const Tree<N>& T, int node, float* s_row, uint32_t* s_cnt = nullptr, int site = 0) {
+    policy_materialise_at<N>(T.pol + (size_t)node * Geo<N>::ROWP, T.board + (size_t)node * (2 * Geo<N>::NW), T.hdr + node, s_row);
+    if (s_cnt && LANE == 0) s_cnt[site] += 1u;
+}
+struct Lazy { float* s_row; uint32_t* s_cnt; }; // what a descent needs to materialise a raw row: the wave's ROWP-float LDS row and its two LDS counters
+
+// ---------------------------------------------------------------------------------------------
 // k_round: Dirichlet noise (round 0) + K simulations for one tree
 // ---------------------------------------------------------------------------------------------
 template <int N>
-__device__ void apply_noise(const Tree<N>& T, const RoundArgs& A, uint32_t tree_global, float* s_row) {
+__device__ void apply_noise(const Tree<N>& T, const RoundArgs& A, uint32_t tree_global, float* s_row, uint32_t* s_cnt = nullptr) {
     using G = Geo<N>;
     const int lane = LANE;
     NodeHdr h0 = T.hdr[0];
+    if (h0.has_policy == POLICY_RAW) policy_materialise<N>(T, 0, s_row, s_cnt, 0); // (after k_advance the new root is usually a node that never filled up)
     uint64_t bb[2 * G::NW];
 #pragma unroll
     for (int i = 0; i < 2 * G::NW; ++i) bb[i] = T.board[i];
@@ -484,13 +549,13 @@ __device__ inline NodeHdr uni(const NodeHdr& h) {
 
 // select_leaf (node.rs:43-58) with the PUCT selector (pme.rs:81-90): from (node, h) down while the node is fully expanded; the last maximal child in
 // insertion order wins (max_by).  Updates node, its header, its visit count as stored in its parent's table, and the algorithmic bytes of the path.
+// It also stops in front of a fully expanded node whose policy row is RAW (lev: the levels passed so far, carried over to the call that resumes): select_leaf_lazy.
 template <int N, bool REC>
-__device__ inline void select_leaf_impl(const Tree<N>& T, NodeHdr& h, int& node, uint32_t& node_n, unsigned long long& path_bytes, PathRec& rec) {
+__device__ inline void select_leaf_impl(const Tree<N>& T, NodeHdr& h, int& node, uint32_t& node_n, unsigned long long& path_bytes, PathRec& rec, int& lev) {
     using G = Geo<N>;
     constexpr int ROWP = G::ROWP;
     const int lane = LANE;
-    int lev = 0;
-    while (h.nch == h.legal && h.nch != 0) {
+    while (h.nch == h.legal && h.nch != 0 && h.has_policy != POLICY_RAW) {
         const uint32_t pn = node_n > 1u ? node_n : 1u;
         const float sq = __fsqrt_rn((float)pn);
         const size_t tb = (size_t)h.table * ROWP;
@@ -558,10 +623,28 @@ __device__ inline void select_leaf_impl(const Tree<N>& T, NodeHdr& h, int& node,
     }
     if (REC) rec.depth = lev;
 }
+// The descent with lazy policy rows: a node that filled up before anything read its raw row gets its probabilities now -- OUTSIDE the loop over the levels, whose live
+// ranges have no register to spare (k_round<15> sits at its 128) -- and the descent resumes at that node.  Returns true if the root's row was one of them.
+// (rec_on: a run-time flag, so that the caller has ONE site that materialises, not one per instantiation of the descent)
 template <int N>
-__device__ inline void select_leaf(const Tree<N>& T, NodeHdr& h, int& node, uint32_t& node_n, unsigned long long& path_bytes) {
+__device__ inline bool select_leaf_lazy(const Tree<N>& T, NodeHdr& h, int& node, uint32_t& node_n, unsigned long long& path_bytes, PathRec& rec, bool rec_on,
+                                        const Lazy& L) {
+    int lev = 0;
+    bool root_done = false;
+    for (;;) {
+        if (rec_on) select_leaf_impl<N, true>(T, h, node, node_n, path_bytes, rec, lev);
+        else select_leaf_impl<N, false>(T, h, node, node_n, path_bytes, rec, lev);
+        if (!(h.nch == h.legal && h.nch != 0)) break; // a leaf; otherwise the descent stands in front of a raw row
+        root_done = root_done || node == 0;
+        policy_materialise<N>(T, uni(node), L.s_row, L.s_cnt, 1);
+        h.has_policy = 1;
+    }
+    return root_done;
+}
+template <int N>
+__device__ inline void select_leaf(const Tree<N>& T, NodeHdr& h, int& node, uint32_t& node_n, unsigned long long& path_bytes, const Lazy& L) {
     PathRec none;
-    select_leaf_impl<N, false>(T, h, node, node_n, path_bytes, none);
+    select_leaf_lazy<N>(T, h, node, node_n, path_bytes, none, false, L);
 }
 
 // Does a stone at cell `a` make exactly five with the `own` stones along direction pair `pr` (0: horizontal, 1: vertical, 2: (-1,-1)/(1,1), 3: (-1,1)/(1,-1))?
@@ -603,7 +686,7 @@ __device__ inline int nth_set_bit_lane(uint64_t w, int r) {
 
 template <int N>
 __device__ void run_sim(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>& C, const RoundArgs& A, uint32_t sim_index,
-                        uint32_t tree_global) {
+                        uint32_t tree_global, const Lazy& L) {
     using G = Geo<N>;
     constexpr int ROWP = G::ROWP, NW = G::NW;
     const int lane = LANE;
@@ -620,7 +703,7 @@ __device__ void run_sim(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>&
     if (cached) h = C.h;
     else { fence_own_stores(R); h = T.hdr[node]; }
     if (h.nch == h.legal && h.nch != 0) { fence_own_stores(R); C.node = -1; } // the descent reads the tables this wave has been writing
-    select_leaf<N>(T, h, node, node_n, path_bytes);
+    select_leaf<N>(T, h, node, node_n, path_bytes, L);
     R.bytes += path_bytes;
     R.memo_node = node;
     R.memo_n = node_n;
@@ -704,7 +787,8 @@ __device__ void run_sim(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>&
 // written in ONE pass (lane i: table slot and header of child i; 2 NW lanes per child: its board words; requests in simulation order).  Node indices, insertion ranks, request
 // order, statuses, the memo and the byte counter are those of the one-by-one sequence: the tests compare the trees bit for bit with the CPU restatement's.
 template <int N>
-__device__ void run_sims(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>& C, const RoundArgs& A, uint32_t first_sim, int count, uint32_t tree_global) {
+__device__ void run_sims(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>& C, const RoundArgs& A, uint32_t first_sim, int count, uint32_t tree_global,
+                         const Lazy& L) {
     using G = Geo<N>;
     constexpr int ROWP = G::ROWP, NW = G::NW;
     const int lane = LANE;
@@ -737,11 +821,9 @@ __device__ void run_sims(const Store& S, const Tree<N>& T, Regs& R, LeafCache<N>
             if (from_root) { root_h = uni(h); root_ok = true; }
         }
         if (h.nch == h.legal && h.nch != 0) { fence_own_stores(R); C.node = -1; }
-        if (from_root) select_leaf_impl<N, true>(T, h, node, node_n, path_bytes, rec);
-        else {
-            select_leaf<N>(T, h, node, node_n, path_bytes);
-            rec.depth = -1;
-        }
+        // (a raw root: only where a caller starts a search at a round other than 0, which skips the noise; root_h must not keep the raw mark of a row that is none any more)
+        if (select_leaf_lazy<N>(T, h, node, node_n, path_bytes, rec, from_root, L)) root_h.has_policy = 1;
+        if (!from_root) rec.depth = -1;
         KP(2); // descents (+ header loads)
         R.memo_node = node;
         R.memo_n = node_n;
@@ -961,6 +1043,8 @@ template <int N>
 __global__ __launch_bounds__(64, KROUND_WPS) void k_round(Store S, RoundArgs A) {
     using G = Geo<N>;
     __shared__ float s_row[G::ROWP];
+    __shared__ uint32_t s_cnt[2]; // raw policy rows this wave materialised: at the noise site, in a descent
+    if (LANE < 2) s_cnt[LANE] = 0u;
     const int g = blockIdx.x;
     const int t = A.side * S.games + g;
     if (A.zero_ptr && g == 0) // (before anything else: the counters of the round before stay readable until here)
@@ -979,7 +1063,7 @@ __global__ __launch_bounds__(64, KROUND_WPS) void k_round(Store S, RoundArgs A) 
     kp_last = __builtin_readcyclecounter();
 #endif
     if (A.scatter_v && ts.n_req > 0) { // the previous round's backups, deferred into this kernel (run loop)
-        scatter_tree<N>(S, T, ts, R, A.scatter_v);
+        scatter_tree<N>(S, T, ts, R, A.scatter_v, A.lazy_rows);
         R.dirty = true;
     }
     // RNG streams are keyed by the GAME (its global id and its own ply), not by the slot or the engine's ply counter: in an episode the
@@ -987,11 +1071,12 @@ __global__ __launch_bounds__(64, KROUND_WPS) void k_round(Store S, RoundArgs A) 
     A.ply = gs0.plies;
     const uint32_t tree_global = (uint32_t)((A.game_offset + gs0.gid) * 2 + A.side);
     KP(0); // state loads + the previous round's backups
-    if (A.round == 0) apply_noise<N>(T, A, tree_global, s_row);
+    if (A.round == 0) apply_noise<N>(T, A, tree_global, s_row, s_cnt);
     KP(1); // noise
     LeafCache<N> C;
-    if (KROUND_BATCH) run_sims<N>(S, T, R, C, A, (uint32_t)(A.round * A.K), A.K, tree_global);
-    else for (int i = 0; i < A.K; ++i) run_sim<N>(S, T, R, C, A, (uint32_t)(A.round * A.K + i), tree_global);
+    const Lazy L{s_row, s_cnt};
+    if (KROUND_BATCH) run_sims<N>(S, T, R, C, A, (uint32_t)(A.round * A.K), A.K, tree_global, L);
+    else for (int i = 0; i < A.K; ++i) run_sim<N>(S, T, R, C, A, (uint32_t)(A.round * A.K + i), tree_global, L);
     if (LANE == 0) {
         TreeState o = ts;
         o.n_nodes = R.n_nodes; o.n_tables = R.n_tables; o.root_n = R.root_n; o.root_w = R.root_w;
@@ -999,6 +1084,10 @@ __global__ __launch_bounds__(64, KROUND_WPS) void k_round(Store S, RoundArgs A) 
         *T.ts = o;
         if (A.req_cnt) A.req_cnt[g] = (int32_t)R.n_req;
         atomicAdd(S.d_bytes, R.bytes);
+        if (A.lazy_stats) {
+            if (s_cnt[0]) atomicAdd(A.lazy_stats, s_cnt[0]);
+            if (s_cnt[1]) atomicAdd(A.lazy_stats + 1, s_cnt[1]);
+        }
 #ifdef KROUND_PROF
         const unsigned int L = (unsigned int)A.round & 63u;
         if (t < 8192)
@@ -1483,7 +1572,7 @@ __global__ __launch_bounds__(64) void k_softmax_scatter_policy(Store S, const fl
 // first (their paths share the slots near the root).  Round 5: before, any round with a second parent took all K backups one by one, a walk of dependent loads and a store
 // fence each -- 4-7 % of the trees in EVERY round from ply 0 on (a leaf fills up every 14 rounds), and with every tree's wave resident at once those were k_round's time.
 template <int N>
-__device__ inline void scatter_tree(const Store& S, const Tree<N>& T, const TreeState& ts, Regs& R, const float* __restrict__ V) {
+__device__ inline void scatter_tree(const Store& S, const Tree<N>& T, const TreeState& ts, Regs& R, const float* __restrict__ V, int raw_rows) {
     using G = Geo<N>;
     constexpr int ROWP = G::ROWP;
     const int lane = LANE, nreq = (int)ts.n_req;
@@ -1496,6 +1585,9 @@ __device__ inline void scatter_tree(const Store& S, const Tree<N>& T, const Tree
         par = (int)hx.parent;
         act = (int)hx.action;
         val = V[(size_t)ts.req_base + lane];
+        // a lazy round (raw_rows = the row bound of its forward, 0: an eager one): the heads wrote this request's logits into the node's policy row, and nothing has
+        // read the node's header since (the rows beyond the bound have no row, as in the eager kernels)
+        if (ts.req_base + (uint32_t)lane < (uint32_t)raw_rows) T.hdr[x].has_policy = POLICY_RAW;
     }
     const int prev_par = __shfl_up(par, 1, 64);
     unsigned long long rem = __ballot(lane < nreq && (lane == 0 || par != prev_par)); // segment starts
@@ -1557,7 +1649,7 @@ __device__ inline void scatter_tree(const Store& S, const Tree<N>& T, const Tree
 }
 
 template <int N>
-__global__ __launch_bounds__(64) void k_scatter(Store S, int side, const float* __restrict__ V) {
+__global__ __launch_bounds__(64) void k_scatter(Store S, int side, const float* __restrict__ V, int raw_rows) {
     const int g = blockIdx.x;
     if (!S.gs[g].alive) return;
     const int t = side * S.games + g;
@@ -1565,12 +1657,29 @@ __global__ __launch_bounds__(64) void k_scatter(Store S, int side, const float* 
     const TreeState ts = *T.ts;
     if (ts.n_req == 0) return;
     Regs R{ts.n_nodes, ts.n_tables, ts.root_n, 0u, ts.error, ts.root_w, 0ull};
-    scatter_tree<N>(S, T, ts, R, V);
+    scatter_tree<N>(S, T, ts, R, V, raw_rows);
     if (LANE == 0) {
         TreeState o = ts;
         o.root_n = R.root_n; o.root_w = R.root_w; o.n_req = 0;
         *T.ts = o;
         atomicAdd(S.d_bytes, R.bytes);
+    }
+}
+
+// Every raw policy row of trees [tree_first, tree_first + gridDim.y) turned into its probabilities (policy_materialise): what the host's readers of policy rows
+// (omok_tree_dump, omok_root_children) and the executors that keep their own copy of the descent (k_round_shared) run first, so that they meet has_policy = 1 and the
+// eager kernels' bits only.  One wave per 64 node headers; raw rows are rare.
+template <int N>
+__global__ __launch_bounds__(64) void k_materialise(Store S, int tree_first) {
+    __shared__ float s_row[Geo<N>::ROWP];
+    const Tree<N> T(S, tree_first + (int)blockIdx.y);
+    const int i = (int)blockIdx.x * 64 + LANE;
+    const uint32_t nn = T.ts->n_nodes < (uint32_t)S.cap_nodes ? T.ts->n_nodes : (uint32_t)S.cap_nodes;
+    unsigned long long m = __ballot((uint32_t)i < nn && T.hdr[(uint32_t)i < nn ? i : 0].has_policy == POLICY_RAW);
+    while (m) {
+        const int l = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        policy_materialise<N>(T, (int)blockIdx.x * 64 + l, s_row);
     }
 }
 
@@ -2410,8 +2519,10 @@ __device__ int transition(const Store& S, const Tree<N>& T, int action, uint8_t*
 }
 
 // Agent::ensure_action_exists (agent.rs:144-197) on tree T: p_row = evaluate_p of (root position + action, Opponent mode)
+// raw (the run loops' lazy plies): p_row is the evaluation's LOGITS row (ROWP floats, as the heads wrote it) and becomes the new node's raw policy row; the
+// softmax, this mask (the child's board holds the root's stones and `action`: the same cells) and the renormalisation are policy_materialise's, when the row is first read
 template <int N>
-__device__ void ensure_action_exists(const Store& S, const Tree<N>& T, int action, const float* __restrict__ p_row, float* s_row) {
+__device__ void ensure_action_exists(const Store& S, const Tree<N>& T, int action, const float* __restrict__ p_row, float* s_row, bool raw) {
     using G = Geo<N>;
     constexpr int ROWP = G::ROWP, NW = G::NW;
     const int lane = LANE;
@@ -2419,21 +2530,21 @@ __device__ void ensure_action_exists(const Store& S, const Tree<N>& T, int actio
     uint64_t bb[2 * NW];
 #pragma unroll
     for (int i = 0; i < 2 * NW; ++i) bb[i] = T.board[i];
-    bool renorm;
-    float inv;
-    masked_policy_row<N>(bb, action, p_row, s_row, renorm, inv);
+    bool renorm = false;
+    float inv = 1.0f;
+    if (!raw) masked_policy_row<N>(bb, action, p_row, s_row, renorm, inv);
     const bool exists = h0.table != NONE16 && T.corder[(size_t)h0.table * ROWP + action] != NONE8;
     if (!exists) { // node.rs:69-71 returns None when the child is already there
         const TreeState ts = *T.ts;
         Regs R{ts.n_nodes, ts.n_tables, ts.root_n, 0u, ts.error, ts.root_w, 0ull};
         if (!get_bit<NW>(bb, action) && !get_bit<NW>(bb + NW, action)) (void)place_and_status<N>(bb, h0.turn, h0.legal, action);
         NodeHdr h0m = h0;
-        const int idx = add_child<N>(S, T, R, 0, h0m, action, bb, ST_IN_PROGRESS, 1 - h0.turn, 1);
+        const int idx = add_child<N>(S, T, R, 0, h0m, action, bb, ST_IN_PROGRESS, 1 - h0.turn, raw ? POLICY_RAW : 1);
         if (idx >= 0) {
 #pragma unroll
             for (int j = 0; j < G::IT; ++j) {
                 const int a = j * 64 + lane;
-                const float x = s_row[a];
+                const float x = raw ? p_row[a] : s_row[a];
                 T.pol[(size_t)idx * ROWP + a] = renorm ? x * inv : x;
             }
         }
@@ -2447,7 +2558,7 @@ __device__ void ensure_action_exists(const Store& S, const Tree<N>& T, int actio
 }
 
 template <int N>
-__global__ __launch_bounds__(64) void k_advance(Store S, int side, const float* __restrict__ P) {
+__global__ __launch_bounds__(64) void k_advance(Store S, int side, const float* __restrict__ P, int raw) {
     using G = Geo<N>;
     constexpr int ROWP = G::ROWP, NW = G::NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2465,8 +2576,8 @@ __global__ __launch_bounds__(64) void k_advance(Store S, int side, const float* 
     // ---- ensure_action_exists (agent.rs:144-197) on the pre-move root: always for the opposite agent (trainer.rs:163-166);
     //      an externally supplied move need not be in the mover's own tree either, so it gets the same treatment there (both
     //      agents hold the same position, hence the same evaluate_p row) ----
-    if (gs.external) ensure_action_exists<N>(S, own, action, P + (size_t)gs.mirror_idx * ROWP, s_row);
-    ensure_action_exists<N>(S, opp, action, P + (size_t)gs.mirror_idx * ROWP, s_row);
+    if (gs.external) ensure_action_exists<N>(S, own, action, P + (size_t)gs.mirror_idx * ROWP, s_row, raw != 0);
+    ensure_action_exists<N>(S, opp, action, P + (size_t)gs.mirror_idx * ROWP, s_row, raw != 0);
     // ---- agent.play_action (agent.rs:206-232): status from the real rules on the root board ----
     int status;
     {
@@ -2955,8 +3066,12 @@ void launch_scatter(int n, const Store& S, int side, const float* p, const float
     DISPATCH_N(n, (k_scatter_policy<9><<<grid, 64, 0, st>>>(S, p, max_count)), (k_scatter_policy<15><<<grid, 64, 0, st>>>(S, p, max_count)));
     if (backups) launch_backups(n, S, side, v, st);
 }
-void launch_backups(int n, const Store& S, int side, const float* v, hipStream_t st) {
-    DISPATCH_N(n, (k_scatter<9><<<S.games, 64, 0, st>>>(S, side, v)), (k_scatter<15><<<S.games, 64, 0, st>>>(S, side, v)));
+void launch_backups(int n, const Store& S, int side, const float* v, hipStream_t st, int raw_rows) {
+    DISPATCH_N(n, (k_scatter<9><<<S.games, 64, 0, st>>>(S, side, v, raw_rows)), (k_scatter<15><<<S.games, 64, 0, st>>>(S, side, v, raw_rows)));
+}
+void launch_materialise(int n, const Store& S, int tree_first, int trees, hipStream_t st) {
+    const dim3 grid((unsigned)((S.cap_nodes + 63) / 64), (unsigned)trees);
+    DISPATCH_N(n, (k_materialise<9><<<grid, 64, 0, st>>>(S, tree_first)), (k_materialise<15><<<grid, 64, 0, st>>>(S, tree_first)));
 }
 void launch_softmax_scatter(int n, const Store& S, int side, const float* logits, int lrow, float* v, float* vpre, int max_count, hipStream_t st,
                             bool backups) {
@@ -2972,9 +3087,9 @@ void launch_sample(int n, const Store& S, int side, int ply, float temperature, 
                (k_sample<15><<<S.games, 64, 0, st>>>(S, side, ply, temperature, threshold, seed, game_offset, actions)));
 }
 void launch_mirror_scan(int n, const Store& S, int side, hipStream_t st) { k_mirror_scan<<<1, 1024, 0, st>>>(S, side); }
-void launch_advance(int n, const Store& S, int side, const float* p, hipStream_t st) {
+void launch_advance(int n, const Store& S, int side, const float* p, hipStream_t st, bool raw) {
     const size_t lds = advance_lds_bytes(S.cap_nodes, S.cap_tables);
-    DISPATCH_N(n, (k_advance<9><<<S.games, 64, lds, st>>>(S, side, p)), (k_advance<15><<<S.games, 64, lds, st>>>(S, side, p)));
+    DISPATCH_N(n, (k_advance<9><<<S.games, 64, lds, st>>>(S, side, p, raw ? 1 : 0)), (k_advance<15><<<S.games, 64, lds, st>>>(S, side, p, raw ? 1 : 0)));
 }
 void launch_encode_requests(int n, const Store& S, float* out, int max_b, hipStream_t st) {
     if (max_b <= 0) return;
