@@ -2191,6 +2191,10 @@ extern "C" int omok_debug_set_base_cache(omok_engine* e, int32_t enabled) {
     if (!e) return OMOK_ERR_INVALID;
     e->net.base_cache = enabled != 0;
     net_invalidate_sibling_cache(e->net);
+    if (e->net2) { // (a match episode's second net, if it is loaded: the same switch)
+        e->net2->base_cache = enabled != 0;
+        net_invalidate_sibling_cache(*e->net2);
+    }
     return OMOK_OK;
 }
 

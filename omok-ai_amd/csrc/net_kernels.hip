@@ -1010,9 +1010,12 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
 // 3072 rows stay on the copy path (forward_f16x3).  DESIGN.md 3.3.
 #ifndef SIB_WAYS_N
 #define SIB_WAYS_N 2 // (round 4, -DSIB_WAYS_N=4 measured on whole configs[1] episodes: 567.2 / 567.9 against 566.5 games/s with 2 -- four slots hit 88 % instead of 86 % of the runs and
-                     //  cost 3.5 GB more: not worth it)
+                     //  cost 3.5 GB more: not worth it.  Round 24, with a tree's first TWO runs of a round in the slots (k_group): over a configs[1] episode 13.7 % of the runs
+                     //  are evaluated in full with 2 slots (17.0 % while only the first run had one), 11.5 % with 4; the benchmark line 635.8 / 633.9 / 637.1 with 2 against
+                     //  634.5 / 639.5 / 639.9 games/s with 4, interleaved on one box: the runs do not separate, 2 stays.  At least 2: the two runs never share a way)
 #endif
 constexpr int SIB_WAYS = SIB_WAYS_N;              // cached base evaluations per game (most recently used leaves of its tree)
+static_assert(SIB_WAYS >= 2 && SIB_WAYS <= 16, "k_group gives a tree's first two runs of a round one way each");
 constexpr int SIB_MIN = 3;                       // runs shorter than this go to k_trunk (a base pass would not pay)
 constexpr int SIB_WIN = 7, SIB_GW = SIB_WIN + 2; // window side, child grid side (window + halo ring)
 constexpr int SIB_CGRID_ROWS = SIB_GW * SIB_GW + 1;
@@ -1053,9 +1056,15 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
                                                              int32_t* __restrict__ tags, uint2* __restrict__ comp, int bn, int do_fill,
                                                              unsigned long long* __restrict__ work, int g_lo, int g_hi, const int32_t* __restrict__ row_sub,
                                                              const int32_t* __restrict__ scan_cnt, unsigned long long* __restrict__ evals) {
-    // Difference path (sib_slot != NULL): base slots.  The FIRST run of a tree uses one of the game's SIB_WAYS slots (SIB_WAYS g + way), whose content is
-    // reused while a tag names the run's parent (a leaf is its tree's expansion target for ~14 rounds); further runs of the tree in the same
-    // round (rare) take a slot behind the games' and are always evaluated.  comp[] lists the (first request row, slot) pairs to evaluate.
+    // Difference path (sib_slot != NULL): base slots.  The first TWO runs of a tree (request order) use the game's SIB_WAYS slots (SIB_WAYS g + way), whose
+    // content is reused while a tag names the run's parent (a leaf is its tree's expansion target for ~14 rounds).  A second run is, four times in five, the
+    // leaf the tree expands NEXT: the old leaf fills up partway through the round's K simulations and the rest of them are children of the new one.  While only
+    // the first run had a slot that leaf was evaluated twice, now and as the first run of the following round; with a slot of its own the following round hits
+    // (tools/base_cache_sim.py, N = 15, 800 simulations, K = 16, 16 games x 30 plies: 990 of 24 000 tree-rounds hold a second run, 806 of them lead the next round,
+    // evaluated runs 3 883 -> 3 082 of 24 990).  One lane decides for both runs: both parents are looked up before a victim is chosen, a miss takes a way the
+    // other run does not use (the first run's children read its slot in the launch that writes the second run's base), and the second run's tag goes in front.
+    // Runs from the third on (rare) take a slot behind the games', are always evaluated and leave no tag.  comp[] lists the (first request row, slot)
+    // pairs to evaluate: the misses and the uncacheable runs, which is what NET_WORK_DIFF_FULL counts.
     constexpr int NP0 = 225, L_P0 = 3, L_FULL = L_P0 + NP0, L_UNC = L_FULL + 1, LC = L_UNC + 1; // [NET_GCNT_RUNS, _SINGLES, _ROWS_IN_RUNS] as in d_gcnt | [L_P0 +] children per net pixel of their stone (P0) | full evaluations, uncacheable runs
     static_assert(NET_GCNT_ROWS_IN_RUNS + 1 == L_P0 && NET_GCNT_UNCACHEABLE == NET_GCNT_FULL_EVALS + 1, "k_group's local counters mirror d_gcnt");
     __shared__ int l_cnt[LC], l_base[LC];
@@ -1128,38 +1137,69 @@ __global__ __launch_bounds__(64 * GROUP_TREES) void k_group(Store S, int side, u
     if (start && len >= SIB_MIN) {
         gslot = atomicAdd(&l_cnt[NET_GCNT_RUNS], 1);
         rbase = atomicAdd(&l_cnt[NET_GCNT_ROWS_IN_RUNS], len);
-        if (sib_slot) {
-            if (lane == __ffsll((long long)qual) - 1) {
-                // SIB_WAYS slots per game, most recently used first; a tag = leaf node | slot << 16, -1 = empty (one slot hits 77 % of the
-                // runs of a configs[1] episode, two 86 %, four 88 %: the descent alternates between a few leaves while their scores cross)
-                int tg[SIB_WAYS], hit = -1, way = 0;
+    }
+    if (sib_slot && qual) { // (both wave-uniform: the shuffles below are executed by whole waves)
+        // The tree's first two qualifying runs, in request order: lane f1 decides for both (the second run's parent comes by shuffle, its way goes back by shuffle).
+        const unsigned long long qual2 = qual & (qual - 1ULL);
+        const int f1 = __ffsll((long long)qual) - 1, f2 = qual2 ? __ffsll((long long)qual2) - 1 : -1;
+        const int p2 = __shfl(parent, f2 < 0 ? f1 : f2, 64);
+        int second = -1; // what lane f1 decided for the second run: way | miss << 8
+        if (lane == f1) {
+            // SIB_WAYS slots per game, most recently used first; a tag = leaf node | slot << 16, -1 = empty (one slot hits 77 % of the
+            // runs of a configs[1] episode, two 86 %, four 88 %: the descent alternates between a few leaves while their scores cross)
+            const bool two = f2 >= 0 && p2 != parent; // (two runs of ONE leaf with a short run between them share the leaf's base: one lookup, one evaluation)
+            int tg[SIB_WAYS], w1 = -1, w2 = -1;
+            unsigned used = 0u;
 #pragma unroll
-                for (int i = 0; i < SIB_WAYS; ++i) tg[i] = tags[SIB_WAYS * g + i];
+            for (int i = 0; i < SIB_WAYS; ++i) {
+                tg[i] = tags[SIB_WAYS * g + i];
+                used |= tg[i] >= 0 ? 1u << (tg[i] >> 16) : 0u;
+            }
+            // both lookups come before any victim is chosen: a run that hits keeps its way
+#pragma unroll
+            for (int i = SIB_WAYS - 1; i >= 0; --i) {
+                if (tg[i] >= 0 && (tg[i] & 0xFFFF) == parent) w1 = tg[i] >> 16;
+                if (two && tg[i] >= 0 && (tg[i] & 0xFFFF) == p2) w2 = tg[i] >> 16;
+            }
+            // a miss: the lowest way never used, else the least recently used one -- of the ways the other run does not use in this round (the first run's children
+            // read its slot in the launch in which the second run's base is written: the two never share a way)
+            auto victim = [&](unsigned taken) {
+                const unsigned free_ways = ~(used | taken) & ((1u << SIB_WAYS) - 1u);
+                if (free_ways) return __ffs((int)free_ways) - 1;
+                int v = 0;
 #pragma unroll
                 for (int i = 0; i < SIB_WAYS; ++i)
-                    if (hit < 0 && tg[i] >= 0 && (tg[i] & 0xFFFF) == parent) hit = i;
-                if (hit >= 0) way = tg[hit] >> 16;
-                else { // miss: the least recently used slot, or the lowest slot never used
-                    if (tg[SIB_WAYS - 1] >= 0) way = tg[SIB_WAYS - 1] >> 16;
-                    else {
-                        unsigned used = 0u;
+                    if (tg[i] >= 0 && !((taken >> (tg[i] >> 16)) & 1u)) v = tg[i] >> 16;
+                return v;
+            };
+            const bool miss1 = w1 < 0, miss2 = two && w2 < 0;
+            if (miss1) {
+                w1 = victim(w2 >= 0 ? 1u << w2 : 0u);
+                mi = atomicAdd(&l_cnt[L_FULL], 1);
+            }
+            if (miss2) w2 = victim(1u << w1);
+            // tag order: the second run's leaf (the leaf the tree expands now), the first run's, the others in their old order
+            int nt[SIB_WAYS], k = 0;
+            if (two) nt[k++] = p2 | (w2 << 16);
+            nt[k++] = parent | (w1 << 16);
 #pragma unroll
-                        for (int i = 0; i < SIB_WAYS; ++i) used |= tg[i] >= 0 ? 1u << (tg[i] >> 16) : 0u;
-                        way = __ffs((int)~used) - 1;
-                    }
-                    hit = SIB_WAYS - 1;
-                    mi = atomicAdd(&l_cnt[L_FULL], 1);
-                }
-                if (hit > 0 || mi >= 0) { // move to the front
+            for (int i = 0; i < SIB_WAYS; ++i) {
+                const int w = tg[i] >= 0 ? tg[i] >> 16 : -1;
+                if (k < SIB_WAYS && w != w1 && (!two || w != w2)) nt[k++] = tg[i];
+            }
+            for (; k < SIB_WAYS; ++k) nt[k] = -1;
 #pragma unroll
-                    for (int i = SIB_WAYS - 1; i > 0; --i)
-                        if (i <= hit) tg[i] = tg[i - 1];
-                    tg[0] = parent | (way << 16);
-#pragma unroll
-                    for (int i = 0; i < SIB_WAYS; ++i) tags[SIB_WAYS * g + i] = tg[i];
-                }
-                bslot = SIB_WAYS * g + way;
-            } else {
+            for (int i = 0; i < SIB_WAYS; ++i)
+                if (nt[i] != tg[i]) tags[SIB_WAYS * g + i] = nt[i];
+            bslot = SIB_WAYS * g + w1;
+            second = f2 >= 0 ? (two ? w2 : w1) | (miss2 ? 256 : 0) : -1;
+        }
+        second = __shfl(second, f1, 64);
+        if (start && len >= SIB_MIN && lane != f1) {
+            if (lane == f2) {
+                bslot = SIB_WAYS * g + (second & 255);
+                if (second & 256) mi = atomicAdd(&l_cnt[L_FULL], 1);
+            } else { // from the third run on: a slot behind the games', always evaluated, no tag
                 ex = atomicAdd(&l_cnt[L_UNC], 1);
                 mi = atomicAdd(&l_cnt[L_FULL], 1);
             }
