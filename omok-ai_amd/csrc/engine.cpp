@@ -27,7 +27,7 @@ hipEvent_t Prof::get() {
     hipEventCreate(&e);
     return e;
 }
-void Prof::begin(int cat, hipStream_t st) {
+void Prof::begin(int cat, hipStream_t st, bool counted) {
     if (!enabled || !active) return;
     if (n_items == cap_items) {
         if (cap_items >= 8192) resolve();
@@ -36,7 +36,7 @@ void Prof::begin(int cat, hipStream_t st) {
             items = (Item*)realloc(items, sizeof(Item) * cap_items);
         }
     }
-    Item it{cat, in_round, get(), get()};
+    Item it{cat, in_round, counted, get(), get()};
     hipEventRecord(it.a, st);
     items[n_items++] = it;
 }
@@ -54,8 +54,9 @@ void Prof::resolve() {
     for (int i = 0; i < n_items; ++i) {
         float t = 0.f;
         if (hipEventElapsedTime(&t, items[i].a, items[i].b) == hipSuccess) {
-            if (items[i].sampled) { ms_s[items[i].cat] += t; launches_s[items[i].cat] += 1; }
-            else { ms[items[i].cat] += t; launches[items[i].cat] += 1; }
+            const int n = items[i].counted ? 1 : 0;
+            if (items[i].sampled) { ms_s[items[i].cat] += t; launches_s[items[i].cat] += n; }
+            else { ms[items[i].cat] += t; launches[items[i].cat] += n; }
         }
         pool[n_pool++] = items[i].a;
         pool[n_pool++] = items[i].b;

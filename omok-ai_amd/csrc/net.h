@@ -215,7 +215,7 @@ struct Prof {
     double scale() const { return rounds_timed > 0 ? (double)rounds_seen / (double)rounds_timed : 1.0; }
     double total_ms(int cat) const { return ms[cat] + ms_s[cat] * scale(); }
     double total_launches(int cat) const { return (double)launches[cat] + (double)launches_s[cat] * scale(); }
-    struct Item { int cat; bool sampled; hipEvent_t a, b; };
+    struct Item { int cat; bool sampled, counted; hipEvent_t a, b; };
     Item* items = nullptr;
     int n_items = 0, cap_items = 0;
     hipEvent_t* pool = nullptr;
@@ -223,7 +223,7 @@ struct Prof {
     double ms[PC_COUNT] = {};
     long long launches[PC_COUNT] = {};
     hipEvent_t get();
-    void begin(int cat, hipStream_t st);
+    void begin(int cat, hipStream_t st, bool counted = true); // counted = false: a further stretch of a category whose launch this round already counted (time only)
     void end(hipStream_t st);
     void resolve(); // synchronises on the recorded events and accumulates ms
     void destroy();

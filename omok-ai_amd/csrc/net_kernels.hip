@@ -25,6 +25,7 @@
 // OMOK_NET_F32: naive fp32 VALU kernels (k-ascending sums), debug / A-B reference on the GPU.
 #include "net.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -277,11 +278,25 @@ struct TrunkGeo {
 // Two exceptions, each measured (profiles/r15_trunk_shared_kernel_stats.txt): k_trunk keeps L0 as inline text and k_sib_children2 its own base_fetch; the reasons stand there.
 
 // One-time prologue of a workgroup: conversions saturate (MODE.FP16_OVFL), trunk weights and side table into LDS (the caller zeroes its grids and synchronises).
+// SKIP_U4: the first uint4s of the weights are not copied (their LDS stays unwritten; the layout and every offset are the same): k_sib_children2 passes block 0's L0
+// fragments, which it never reads.
+// DMA: the weights go to LDS by LDS-DMA (dma16s, the form k_fc0_mx streams with), one instruction per fragment of 64 lanes x 16 B, the fragments dealt to the waves -- the
+// same bytes at the same addresses without the round trip through VGPRs, whose ~14 dependent load -> store trips per thread were most of a 7.5-us prologue.
+// Nothing waits here: the caller runs its own fills, then trunk_lds_dma_wait() in front of its barrier.
+template <bool NT>
+__device__ inline void dma16s(const uint4* sbase, uint32_t voff, const uint4* lds);
+template <int SKIP_U4 = 0, bool DMA = false>
 __device__ __forceinline__ void trunk_lds_prologue(unsigned char* smem, float* lside, const uint4* __restrict__ wt, const float* __restrict__ side, int tid) {
+    static_assert(SKIP_U4 % 64 == 0 && TR_WBYTES % 1024 == 0, "whole fragments");
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1"); // fp6 / f16 conversions saturate (MODE.FP16_OVFL)
-    for (int i = tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
+    if constexpr (DMA) {
+        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = (int)blockDim.x >> 6;
+        for (int f = SKIP_U4 / 64 + wv; f < TR_WBYTES / 1024; f += nwv) dma16s<false>(wt + f * 64, (uint32_t)(tid & 63) * 16u, (const uint4*)smem + f * 64);
+    } else
+        for (int i = SKIP_U4 + tid; i < TR_WBYTES / 16; i += blockDim.x) ((uint4*)smem)[i] = wt[i];
     for (int i = tid; i < TR_SIDE_FLOATS; i += blockDim.x) lside[i] = side[i];
 }
+__device__ __forceinline__ void trunk_lds_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } // (the DMAs are issued from asm: the compiler does not count them)
 // The conv_in fragments of k_sib_children (k_sib_children2 reads the conv tables instead; k_conv_tables fetches them once): 32 registers that are only needed at the top of a pass.  They are fetched again at the END of every pass (from
 // L2, under the stores) instead of living through the blocks, where they pushed lane-constant addresses into scratch whose
 // reloads (a dozen dependent round trips in the store phase) cost more than the whole arithmetic of the pass
@@ -617,8 +632,9 @@ __global__ __launch_bounds__(TrunkGeo<N>::WG_THREADS) void k_trunk(const uint32_
     const float* lside = (const float*)(smem + TR_WBYTES + TG::SPW * TG::GRID_BYTES);
     const int h = lane >> 5;
     // ---- one-time: weights, side table, zero halo grid ----
-    trunk_lds_prologue(smem, (float*)lside, wt, side, tid);
+    trunk_lds_prologue<0, BASE && DELTA>(smem, (float*)lside, wt, side, tid); // (the difference path's base pass: LDS-DMA, as k_sib_children2)
     for (int i = tid; i < TG::SPW * (TG::GRID_BYTES / 4); i += blockDim.x) ((float*)(smem + TR_WBYTES))[i] = 0.0f;
+    if constexpr (BASE && DELTA) trunk_lds_dma_wait();
     __syncthreads();
     int count = (row_list || BASE) ? d_nrows[0] : d_count[0];
     // BASE with d_nrows2: behind the runs' base positions the same launch evaluates the round's SINGLE rows (row_list, d_nrows2[0] of them: requests
@@ -1515,17 +1531,38 @@ __global__ __launch_bounds__(256) void k_win_finish(const float* __restrict__ pa
     row[2 + h] = *(const uint4*)&lo;
 }
 
-// full-row partial sums of fc0 -> one fp32 row per full row (in place, into split 0), in split order
+struct FaccReduceArgs { // what the reduce needs beyond d_gcnt; part == NULL: the launch does not carry the role
+    const float* part;
+    float* facc;
+    const uint2* comp;
+    int facc_single_base;
+};
+// full-row partial sums of fc0 -> one fp32 row per full row, in split order: split 0 first, then splits 1 .. nsplit - 1
 // (evaluated row i: i < nmiss -> the base slot comp[i].y, else the single row i - nmiss behind the base slots)
-__global__ __launch_bounds__(256) void k_facc_reduce(const float* __restrict__ part, size_t cap_rows, const int32_t* __restrict__ d_nrows, const int32_t* __restrict__ d_nsplit,
-                                                     float* __restrict__ facc, const uint2* __restrict__ comp, const int32_t* __restrict__ d_nmiss, int facc_single_base) {
+// The arithmetic, once: the calling thread takes the items first, first + step, ... (an item = four features of one evaluated row).  Called by k_facc_reduce and, on the
+// product's path, by every workgroup of k_sib_children2 (a role of that launch).  A thin round has up to 64 splits and at most one item per thread, so its
+// time is the chain of loads of one item: eight splits' loads are issued together, the adds keep the order.
+__device__ __forceinline__ void facc_reduce_items(const float* __restrict__ part, const int32_t* __restrict__ d_nrows, const int32_t* __restrict__ d_nsplit,
+                                                  float* __restrict__ facc, const uint2* __restrict__ comp, const int32_t* __restrict__ d_nmiss, int facc_single_base,
+                                                  size_t first, size_t step) {
     const size_t total = (size_t)d_nrows[0] * (NF / 4);
     const int nsplit = d_nsplit[0], nmiss = d_nmiss[0];
-    cap_rows = (size_t)d_nsplit[NET_GCNT_FULL_STRIDE - NET_GCNT_FULL_WAYS]; // (d_nsplit = d_gcnt + NET_GCNT_FULL_WAYS)
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        f32x4 a = *(const f32x4*)(part + i * 4);
-        for (int sp = 1; sp < nsplit; ++sp) {
-            const f32x4 b = *(const f32x4*)(part + (size_t)sp * cap_rows * NF + i * 4);
+    const size_t split_floats = (size_t)d_nsplit[NET_GCNT_FULL_STRIDE - NET_GCNT_FULL_WAYS] * NF; // (d_nsplit = d_gcnt + NET_GCNT_FULL_WAYS)
+    for (size_t i = first; i < total; i += step) {
+        const float* p = part + i * 4;
+        f32x4 a = *(const f32x4*)p;
+        int sp = 1;
+        for (; sp + 8 <= nsplit; sp += 8) {
+            f32x4 b[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) b[u] = *(const f32x4*)(p + (size_t)(sp + u) * split_floats);
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[j] += b[u][j];
+        }
+        for (; sp < nsplit; ++sp) {
+            const f32x4 b = *(const f32x4*)(p + (size_t)sp * split_floats);
 #pragma unroll
             for (int j = 0; j < 4; ++j) a[j] += b[j];
         }
@@ -1533,6 +1570,11 @@ __global__ __launch_bounds__(256) void k_facc_reduce(const float* __restrict__ p
         const size_t dst = row < nmiss ? (size_t)comp[row].y : (size_t)(facc_single_base + (row - nmiss));
         *(f32x4*)(facc + dst * NF + (i % (NF / 4)) * 4) = a;
     }
+}
+// (a launch of its own where the children kernel does not carry the role: k_sib_children<DELTA> behind omok_debug_set_children_kernel, and the TPROF instantiation)
+__global__ __launch_bounds__(256) void k_facc_reduce(const float* __restrict__ part, const int32_t* __restrict__ d_nrows, const int32_t* __restrict__ d_nsplit,
+                                                     float* __restrict__ facc, const uint2* __restrict__ comp, const int32_t* __restrict__ d_nmiss, int facc_single_base) {
+    facc_reduce_items(part, d_nrows, d_nsplit, facc, comp, d_nmiss, facc_single_base, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 // DELTA (difference path): a_out holds the FULL rows (one per run, written by k_trunk<BASE | DELTA>); the child's window entries are
@@ -1876,13 +1918,14 @@ static_assert(V2_LDS <= 160 * 1024, "k_sib_children2 LDS");
 #define RING_B(LQ) (((LQ) & 31) < V2_RING ? ((LQ) & 31) : V2_RING - 1)
 // F16LO: the BASE's operand rows are in the FC0_F16 format; OUT_F16: so are the difference rows written here.  <true, ..., false> is the FC0_MIXED format:
 // full rows with f16 residuals, difference rows with block-scaled fp6 residuals.
+constexpr int TP_STAMPS = 32, TP_LAUNCHES = 128; // TPROF's per-workgroup stamps: behind the 32 phase sums, a ring of 128 launches
 template <bool F16LO, int N, bool TPROF = false, bool OUT_F16 = F16LO> // TPROF (OMOK_SIB_PROF=2, timing only): shader-clock cycles per phase of waves 0 and 5, summed over their passes, into tprof[]
 __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restrict__ board, const uint4* __restrict__ wt, const float* __restrict__ side,
                                                        uint4* __restrict__ a_out, size_t row_u4, const uint4* __restrict__ sib_rows,
                                                        const int32_t* __restrict__ d_cnt, const uint4* __restrict__ sib2,
                                                        const uint32_t* __restrict__ sib_slot, const int32_t* __restrict__ bin_start,
                                                        uint4* __restrict__ d_rows, uint2* __restrict__ slot_desc, unsigned long long* __restrict__ tprof,
-                                                       const uint4* __restrict__ conv_tab) {
+                                                       const uint4* __restrict__ conv_tab, const FaccReduceArgs fr) {
     unsigned long long tp_acc[12] = {}, tp_last = 0;
     auto TP = [&](int phase) { // (phase = what ended here)
         if (TPROF) {
@@ -1901,7 +1944,13 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     float* wgrid = (float*)(smem + TR_WBYTES + TR_SIDE_FLOATS * 4) + wv * V2_WAVE_FLOATS; // this wave's cells
     const int h = lane >> 5;
-    trunk_lds_prologue(smem, (float*)lside, wt, side, tid);
+    // TPROF, round 25: per launch and workgroup the constant-rate clock (100 MHz) at entry, behind the prologue's barrier and at the end of its last wave, and the prologue's
+    // shader-clock cycles -> tprof[TP_STAMPS + ((launch % TP_LAUNCHES) * workgroups + workgroup) * 4 ..]; launch = a ticket from tprof[31] / workgroups
+    unsigned long long tp_t0 = 0, tp_c0 = 0;
+    if (TPROF) { tp_t0 = wall_clock64(); tp_c0 = __builtin_readcyclecounter(); }
+    // Block 0's L0 fragments (hi[8] | lo[8], the first 16 of the block) stay out of the copy: block 0's L0 comes from the conv table, and the two L0_tile calls below take
+    // blk1 and blk2 (L1L2_tile reads fragments 16..35 of its block)
+    trunk_lds_prologue<16 * 64, true>(smem, (float*)lside, wt, side, tid);
     for (int i = tid; i < 8 * V2_WAVE_FLOATS; i += blockDim.x) ((float*)(smem + TR_WBYTES + TR_SIDE_FLOATS * 4))[i] = 0.0f;
     for (int i = tid; i < CT_FLOATS / 4; i += blockDim.x) ((uint4*)(smem + V2_TAB_OFF))[i] = conv_tab[i];
     const float* ltab = (const float*)(smem + V2_TAB_OFF); // conv tables: T0 at 0, T1 at CT_T1_OFF
@@ -1914,7 +1963,25 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
         const int wb0 = (int)blockIdx.x * per0 < nsib0 ? (int)blockIdx.x * per0 : nsib0;
         s_next_entry = wb0 + 16; // (entries wb0 .. wb0 + 15: the waves' first two passes)
     }
+    __shared__ unsigned long long* s_tp_rec;
+    if (TPROF && tid == 0) {
+        s_tp_rec = tprof + TP_STAMPS + ((atomicAdd(&tprof[31], 1ULL) / gridDim.x % TP_LAUNCHES) * gridDim.x + blockIdx.x) * 4;
+        s_tp_rec[2] = 0; // (the waves' ends: atomicMax below)
+    }
+    trunk_lds_dma_wait();
     __syncthreads(); // (the only workgroup barrier: from here on a wave touches read-only LDS and its own cells)
+    if (TPROF && tid == 0) {
+        s_tp_rec[0] = tp_t0;
+        s_tp_rec[1] = wall_clock64();
+        s_tp_rec[3] = __builtin_readcyclecounter() - tp_c0;
+    }
+    // Role of this launch (round 25): the full rows' fc0 partials -> facc, this workgroup's grid-stride share, once.  The full-row fc0 ran in the launch before; nothing in this
+    // launch reads facc or writes the partials, and the first readers of facc (the window-tile launch, k_win_finish) come behind the kernel boundary: no workgroup waits.
+    // Items go to the launch's waves 64 at a time, workgroup after workgroup, and inside a workgroup to waves 4..7 first (they wait below): a thin round's few items
+    // (256 games: 512 waves' worth) lie on two waves of EVERY workgroup instead of on all waves of the first 64.
+    if (fr.part)
+        facc_reduce_items(fr.part, d_cnt + NET_GCNT_FULL_ROWS, d_cnt + NET_GCNT_FULL_WAYS, fr.facc, fr.comp, d_cnt + NET_GCNT_FULL_EVALS, fr.facc_single_base,
+                          ((size_t)((wv + 4) & 7) * gridDim.x + blockIdx.x) * 64 + lane, (size_t)gridDim.x * blockDim.x);
     for (int i = 0; i < (wv >> 2); ++i) __builtin_amdgcn_s_sleep(120); // the two waves of a SIMD (w, w + 4) start about half a pass apart
     const int nsib = d_cnt[NET_GCNT_ROWS_IN_RUNS];
 
@@ -2354,6 +2421,7 @@ __global__ __launch_bounds__(512) void k_sib_children2(const uint64_t* __restric
     }
     if (TPROF && lane == 0 && (wv == 0 || wv == 5))
         for (int i = 0; i < 12; ++i) atomicAdd(&tprof[(wv ? 16 : 0) + i], tp_acc[i]);
+    if (TPROF && lane == 0) atomicMax(&s_tp_rec[2], wall_clock64());
 }
 
 #undef OL
@@ -4099,13 +4167,16 @@ static sib_kernel_t sib_kernel(bool delta, bool x16, int n) { // k_sib_children<
                  : (x16 ? k_sib_children<false, true, 15> : k_sib_children<false, false, 15>);
 }
 typedef void (*sib2_kernel_t)(const uint64_t*, const uint4*, const float*, uint4*, size_t, const uint4*, const int32_t*, const uint4*, const uint32_t*, const int32_t*,
-                              uint4*, uint2*, unsigned long long*, const uint4*);
+                              uint4*, uint2*, unsigned long long*, const uint4*, const FaccReduceArgs);
 static sib2_kernel_t sib2_kernel(bool x16, int n, bool mixed = false) { // k_sib_children2<F16LO, N, false, OUT_F16>
     if (mixed) return n == 9 ? k_sib_children2<true, 9, false, false> : k_sib_children2<true, 15, false, false>;
     if (n == 9) return x16 ? k_sib_children2<true, 9> : k_sib_children2<false, 9>;
     return x16 ? k_sib_children2<true, 15> : k_sib_children2<false, 15>;
 }
-static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_count, hipStream_t st, bool delta) {
+static void launch_fc0_full_rows(Net& net, int max_count, hipStream_t st);
+// Returns true if the full rows' fc0 rows (facc) are complete behind its launches: the difference path with k_sib_children2, where the full-row fc0 runs in front of the
+// children and the children launch reduces its partials.  Else launch_fc0_delta runs both.
+static bool launch_trunk_siblings(Net& net, const Store& S, int side, int max_count, hipStream_t st, bool delta, Prof* prof) {
     constexpr int LDS = TR_WBYTES + 4 * SIB_CGRID_BYTES + TR_SIDE_FLOATS * 4;
     static_assert(LDS + 32 <= 160 * 1024, "k_sib_children LDS (+ the static pair-barrier flags)");
     static bool attr_done[64] = {};
@@ -4145,7 +4216,7 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
         net.children_launches[1] += 1.0;
         sib_kernel(false, x16, net.n)<<<256, 512, LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_fc0, net.row_u4,
                                                              (const uint4*)net.d_sib_rows, net.d_gcnt, net.sib_h, nullptr, nullptr, nullptr, nullptr, nullptr);
-        return;
+        return false;
     }
     static const int tprof_mode = getenv("OMOK_SIB_PROF") ? atoi(getenv("OMOK_SIB_PROF")) : 0; // timing experiments only (N = 15, fp6 format): 2 = k_sib_children2's phase profile
     const bool mixed = x16 && net.diff_fp6; // FC0_MIXED: full rows f16, difference rows fp6 (k_sib_children2 only)
@@ -4190,10 +4261,11 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
         static unsigned long long* d_tp = nullptr;
         static unsigned long long acc[32] = {};
         static int launches = 0;
-        if (!d_tp) { hipMalloc(&d_tp, 256); hipMemset(d_tp, 0, 256); hipFuncSetAttribute((const void*)k_sib_children2<false, 15, true>, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS); }
+        constexpr size_t TP_BYTES = 256 + (size_t)TP_LAUNCHES * 256 * 4 * 8;
+        if (!d_tp) { hipMalloc(&d_tp, TP_BYTES); hipMemset(d_tp, 0, TP_BYTES); hipFuncSetAttribute((const void*)k_sib_children2<false, 15, true>, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS); }
         k_sib_children2<false, 15, true><<<256, 512, V2_LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4, (const uint4*)net.d_sib_rows,
                                                                    net.d_gcnt, (const uint4*)net.sib_h, net.d_sib_slot, net.d_bin_start, (uint4*)net.d_rows, (uint2*)net.d_slot_desc,
-                                                                   d_tp, (const uint4*)net.conv_tab);
+                                                                   d_tp, (const uint4*)net.conv_tab, FaccReduceArgs{});
         if (++launches % 100 == 0) {
             hipStreamSynchronize(st);
             hipMemcpy(acc, d_tp, 256, hipMemcpyDeviceToHost);
@@ -4207,18 +4279,48 @@ static void launch_trunk_siblings(Net& net, const Store& S, int side, int max_co
                 fprintf(stderr, " | %.0f cycles per workgroup and launch\n", tot / 256.0 / launches);
             }
         }
-        return;
+        if (launches % TP_LAUNCHES == 0) { // the last 128 launches' stamps: the prologue per workgroup, and how far the launch's last workgroup ends behind the median one
+            static std::vector<unsigned long long> rec((size_t)TP_LAUNCHES * 256 * 4);
+            hipStreamSynchronize(st);
+            hipMemcpy(rec.data(), d_tp + TP_STAMPS, rec.size() * 8, hipMemcpyDeviceToHost);
+            double pro_med = 0, pro_max = 0, cyc_med = 0, cyc_max = 0, dur = 0, tail = 0, tail_max = 0;
+            for (int l = 0; l < TP_LAUNCHES; ++l) {
+                std::vector<double> pro, cyc, end;
+                unsigned long long t0 = ~0ULL;
+                for (int w = 0; w < 256; ++w) {
+                    const unsigned long long* r = &rec[((size_t)l * 256 + w) * 4];
+                    t0 = std::min(t0, r[0]);
+                    pro.push_back((double)(r[1] - r[0]) * 0.01); // us (100 MHz)
+                    cyc.push_back((double)r[3]);
+                    end.push_back((double)r[2]);
+                }
+                std::sort(pro.begin(), pro.end()); std::sort(cyc.begin(), cyc.end()); std::sort(end.begin(), end.end());
+                const double d = (end[255] - (double)t0) * 0.01, tl = (end[255] - end[128]) * 0.01;
+                pro_med += pro[128]; pro_max += pro[255]; cyc_med += cyc[128]; cyc_max += cyc[255]; dur += d; tail += tl / d; tail_max = std::max(tail_max, tl / d);
+            }
+            const double n = TP_LAUNCHES;
+            fprintf(stderr, "[sib2 stamps] launches %d..%d: prologue (entry to behind the barrier) per workgroup, mean over launches of the median %.2f us = %.0f shader cycles, of the "
+                            "slowest %.2f us = %.0f cycles; launch (first entry to last end) %.1f us; (last - median workgroup end) / launch: mean %.2f %%, largest %.2f %%\n",
+                    launches - TP_LAUNCHES, launches - 1, pro_med / n, cyc_med / n, pro_max / n, cyc_max / n, dur / n, 100.0 * tail / n, 100.0 * tail_max);
+        }
+        return false;
     }
     net.children_launches[v2 ? 0 : 1] += 1.0;
     if (v2) {
+        // the full rows' fc0 needs the base pass only; in front of the children, these reduce its partials and k_facc_reduce's launch is gone from the chain (PC_FC0's time;
+        // the category's launch is counted where forward_f16x3 begins it)
+        if (prof) { prof->end(st); prof->begin(PC_FC0, st, false); }
+        launch_fc0_full_rows(net, max_count, st);
+        if (prof) { prof->end(st); prof->begin(PC_TRUNK, st, false); }
         sib2_kernel(x16, net.n, mixed)<<<256, 512, V2_LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4, (const uint4*)net.d_sib_rows,
                                                           net.d_gcnt, (const uint4*)net.sib_h, net.d_sib_slot, net.d_bin_start, (uint4*)net.d_rows, (uint2*)net.d_slot_desc, nullptr,
-                                                          (const uint4*)net.conv_tab);
-        return;
+                                                          (const uint4*)net.conv_tab, FaccReduceArgs{net.part, net.facc, (const uint2*)net.d_comp, (int)net.base_slots});
+        return true;
     }
     sib_kernel(true, x16, net.n)<<<256, 512, LDS, st>>>(S.board, (const uint4*)net.wt_trunk, net.wt_first, (uint4*)net.a_base, net.row_u4,
                                                         (const uint4*)net.d_sib_rows, net.d_gcnt, net.sib_h, net.d_sib_slot, net.d_bin_start,
                                                         (uint4*)net.d_rows, (uint2*)net.d_slot_desc, nullptr);
+    return false;
 }
 
 // One fc0 launch: kernel <EPI, WIN> on operands of format `fmt` -- FC0_FP6: k_fc0_mx on net.wt_fc0 with its block scales, FC0_F16: k_fc0_x3 on net.wt_fc0x.  `grid` workgroups;
@@ -4235,20 +4337,27 @@ static void launch_fc0(const Net& net, int fmt, int grid, hipStream_t st, const 
         k_fc0_mx<EPI, WIN><<<dim3(grid, 1), 256, 0, st>>>((const uint4*)net.wt_fc0, (const uint4*)act, ksup, act_row_u4, full_tiles, last_cnt, fc0_scales(net), bias, out_split,
                                                           out_row_u4, out_part, d_count, max_count, tile_info, (const uint2*)slot_desc, facc, net.n);
 }
-
-// fc0 of a sibling round on the difference path: fp32 fc0 rows of the full rows (split-K: there are ~16x fewer full rows
-// than requests), then one window tile per 128 slots: 98 of the 450 super-steps, + the slot's full row, bias, LeakyReLU, hi|lo.
-static void launch_fc0_delta(Net& net, int max_count, const float* bias_fc0, uint4* h0, hipStream_t st) {
-    const int nsup = net.hw * 2, n_cu = net.n_cu;
-    const int tiles_max = (max_count + GT_BS - 1) / GT_BS;
-    const size_t cap_rows = (size_t)tiles_max * GT_BS;
+// fc0 of the difference path's full rows (the runs' bases evaluated this round and the single rows: ~16x fewer than requests) into fp32 split-K partials, in the format of
+// full operand rows.  Their live count is only known on the device: bin_prefix_role chose the K split and the partial slab's row stride (NET_GCNT_FULL_WAYS,
+// NET_GCNT_FULL_STRIDE).  It reads a_fc0, which the base pass wrote: launch_trunk_siblings puts it in front of k_sib_children2, which then reduces the partials.
+static void launch_fc0_full_rows(Net& net, int max_count, hipStream_t st) {
+    const int n_cu = net.n_cu, tiles_max = (max_count + GT_BS - 1) / GT_BS;
     const int32_t* cnt = net.d_gcnt;
-    // full rows, in the format of full operand rows.  Their live count is only known on the device: bin_prefix_role chose the K split and the partial slab's row stride
-    // (NET_GCNT_FULL_WAYS, NET_GCNT_FULL_STRIDE)
     const int fgrid = ((tiles_max > n_cu ? tiles_max : n_cu) + 7) / 8 * 8; // (tiles x ways <= CUs by construction unless there are more tiles than CUs: then 1 way; whole eighths: xcd_item)
-    launch_fc0<EPI_PARTIAL, false>(net, net.fc0_fmt, fgrid, st, net.a_fc0, nsup, net.row_u4, bias_fc0, nullptr, cap_rows, net.part, cnt + NET_GCNT_FULL_ROWS, max_count,
-                                   cnt + NET_GCNT_FULL_WAYS);
-    k_facc_reduce<<<512, 256, 0, st>>>(net.part, cap_rows, cnt + NET_GCNT_FULL_ROWS, cnt + NET_GCNT_FULL_WAYS, net.facc, (const uint2*)net.d_comp, cnt + NET_GCNT_FULL_EVALS, (int)net.base_slots);
+    launch_fc0<EPI_PARTIAL, false>(net, net.fc0_fmt, fgrid, st, net.a_fc0, net.hw * 2, net.row_u4, net.wt_first + TR_SIDE_FLOATS, nullptr, (size_t)tiles_max * GT_BS, net.part,
+                                   cnt + NET_GCNT_FULL_ROWS, max_count, cnt + NET_GCNT_FULL_WAYS);
+}
+
+// fc0 of a sibling round on the difference path: fp32 fc0 rows of the full rows (launch_fc0_full_rows + the reduce; facc_done: launch_trunk_siblings ran both, the reduce
+// as a role of k_sib_children2), then one window tile per 128 slots: 98 of the 450 super-steps, + the slot's full row, bias, LeakyReLU, hi|lo.
+static void launch_fc0_delta(Net& net, int max_count, const float* bias_fc0, uint4* h0, hipStream_t st, bool facc_done) {
+    const int n_cu = net.n_cu;
+    const int tiles_max = (max_count + GT_BS - 1) / GT_BS;
+    const int32_t* cnt = net.d_gcnt;
+    if (!facc_done) {
+        launch_fc0_full_rows(net, max_count, st);
+        k_facc_reduce<<<512, 256, 0, st>>>(net.part, cnt + NET_GCNT_FULL_ROWS, cnt + NET_GCNT_FULL_WAYS, net.facc, (const uint2*)net.d_comp, cnt + NET_GCNT_FULL_EVALS, (int)net.base_slots);
+    }
     // window tiles, in the format of the difference rows (FC0_MIXED: fp6 behind f16 full rows): whole rounds of workgroups at full K, the tiles of the last partial round
     // split over K (bin_prefix_role)
     const int dfmt = (net.fc0_fmt != FC0_F16 || net.diff_fp6) ? FC0_FP6 : FC0_F16;
@@ -4340,7 +4449,8 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     // (N = 9: 9 window bins + the single rows = 10 tiles at least)
     const bool delta = sib && use_sib >= 2 && max_count >= sib_delta_min_rows(net);
     if (prof) prof->begin(PC_TRUNK, st);
-    if (sib) launch_trunk_siblings(net, S, sib_side, max_count, st, delta);
+    bool facc_done = false;
+    if (sib) facc_done = launch_trunk_siblings(net, S, sib_side, max_count, st, delta, prof);
     else if (net.n == 9) { if (from_f32) launch_trunk_fmt<9, true>(net, S, max_count, st); else launch_trunk_fmt<9, false>(net, S, max_count, st); }
     else {
         if (from_f32) launch_trunk_fmt<15, true>(net, S, max_count, st);
@@ -4356,7 +4466,7 @@ static void forward_f16x3(Net& net, const Store& S, int max_count, bool from_f32
     net.plan_path = sib ? (delta ? 2 : 1) : 0;
     net.plan_rows = max_count;
     net.plan_nsplit = 0;
-    if (delta) launch_fc0_delta(net, max_count, bias_fc0, h0, st);
+    if (delta) launch_fc0_delta(net, max_count, bias_fc0, h0, st, facc_done);
     else { // dense fc0: whole K, or split K into fp32 partials + finish (sum in split order + bias + LeakyReLU + hi|lo)
         const int nsup = hw * 2, tiles128 = (max_count + GT_BS - 1) / GT_BS;
         const int nsplit = net.plan_nsplit = fc0_dense_nsplit(max_count, nsup, net.n_cu, net.part_rows);

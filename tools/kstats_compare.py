@@ -12,8 +12,9 @@ BASE = ("k_trunk<15, false, true, true, true>", "k_fc0_x3<2, false>", "k_facc_re
 def load(path):
     out = {}
     for r in csv.DictReader(open(path)):
-        name = r["Name"].replace("void omok::", "")
-        out[name] = (int(r["Calls"]), float(r["TotalDurationNs"]) / 1e3)
+        name = r["Name"].replace("void omok::", "").replace("omok::", "").split("(")[0]  # (without the parameter list: a changed signature is still the same kernel)
+        calls, t = out.get(name, (0, 0.0))
+        out[name] = (calls + int(r["Calls"]), t + float(r["TotalDurationNs"]) / 1e3)
     return out
 
 
@@ -29,7 +30,8 @@ def main(argv):
         if share < 0.004 and not k.startswith(prefixes) and not k.startswith("k_group"):
             continue
         if not all(k in r for r in runs):
-            print(f"  {k[:44]:44s}  not launched in every run")
+            print(f"  {k[:44]:44s}  not launched in every run: calls " + " ".join(str(r.get(k, (0, 0.0))[0]) for r in runs) + "  average us "
+                  + " ".join(f"{r[k][1] / r[k][0]:.2f}" if k in r else "-" for r in runs))
             continue
         a = [r[k][1] / r[k][0] for r in par]
         b = [r[k][1] / r[k][0] for r in new]
