@@ -287,21 +287,50 @@ int omok_selfplay_run(omok_engine* e, int32_t count, int32_t batch_size, float e
  * beats a win at a higher one.  Without such a cell it falls through to OMOK_OPP_RANDOM.
  * OMOK_OPP_RANDOM: legal_moves[rng.gen_range(0..len)] (trainer.rs:452-455, :534): the r-th empty cell in ascending order, r = mulhi(x0,
  * legal_move_count), x0 = word 0 of Philox(key of the episode, 0, the game's ply, 2 * (game_offset + game) + side to move, purpose 4)
- * (DESIGN.md "RNG contract"). */
+ * (DESIGN.md "RNG contract").
+ * OMOK_OPP_THREAT: a threat-aware player, not one of the reference's: a fixed opponent that a net does not beat merely by extending a three.  It
+ * is defined by the same exact-five test alone.  For a colour c, an empty cell a and a line pair pr (0 horizontal, 1 vertical, 2 and 3 the
+ * diagonals), ra and rb are the runs of consecutive c stones from a outwards along the two opposite rays, and L(c,a,pr) = 1 + ra + rb.
+ *   FIVE(c,a)   L(c,a,pr) == 5 for some pr: the test above (a run of six is no five).
+ *   T(c,a)      the number of winning cells a c stone at a would leave: with c at a, the cells e = a +- k d_pr, k = 1..4, over the four pairs
+ *               (at most 32) that are on the board, empty, and have L(c,e,pr) == 5 along that same pair.  A completion that would make six
+ *               does not count; a four against the edge or an enemy stone has T = 1.
+ *   OPEN3(c,a)  for some pr, L(c,a,pr) == 3 and the two cells just beyond the run's ends are both on the board and empty.
+ *   NEAR(a)     some stone of either colour lies at Chebyshev distance 1 from a.
+ * With `me` the side to move and `opp` the other, the move is the LOWEST empty cell of the first level that has one:
+ *   1  FIVE(me,a); or the last empty cell (Draw is terminal, as in the naive rule)
+ *   2  FIVE(opp,a)
+ *   3  T(me,a) >= 2: an open four, a double four, filling a split three
+ *   4  T(opp,a) >= 2: denies the opponent the same, which blocks an existing open three
+ *   5  OPEN3(me,a)
+ *   6  the r-th cell in ascending order among the empty cells with NEAR, r = mulhi(x0, their count)
+ *   7  no empty cell has NEAR (the empty board): OMOK_OPP_RANDOM's draw over all empty cells
+ * x0 is the word OMOK_OPP_RANDOM draws for that game, ply and side; no new RNG purpose.  Unlike the naive rule a win beats a block at a lower
+ * index, and the side to move matters.  The value 2 is no player and stays an invalid kind. */
 #define OMOK_OPP_RANDOM 0
 #define OMOK_OPP_NAIVE 1
+#define OMOK_OPP_THREAT 3
 /* the forced part of the rule on caller-held positions (boards [B][N*N] Stone bytes, turns [B]): forced_out[b] = the cell the NAIVE rule
  * picks before its random fallback (trainer.rs:514-531), -1 if none (always -1 for RANDOM).  (The rule tries a stone of either colour at
- * every empty cell, so the side to move does not change the answer: turns is read by no kernel.) */
+ * every empty cell, so the side to move does not change the answer: turns is read by no kernel.)  For OMOK_OPP_THREAT the side to move
+ * decides: forced_out[b] = the cell of levels 1..5, -1 for levels 6 and 7, and a turns byte above 1 is OMOK_ERR_INVALID, checked before
+ * anything is launched (kinds 0 and 1 keep ignoring turns). */
 int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out);
 /* step-wise: the scripted player's move (trainer.rs:508-534 / :452-455) for the side to move of every live game, chosen on the device and
  * staged like omok_set_actions (omok_mirror_* / omok_advance follow); actions [G] may be NULL, -1 for finished games.  OMOK_ERR_STATE in a
  * match episode, OMOK_ERR_INVALID for an unknown kind. */
 int omok_opponent_actions(omok_engine* e, int32_t kind, int32_t* actions);
+/* Which level of the OMOK_OPP_THREAT rule decides on caller-held positions (boards [B][N*N] Stone bytes, any other byte counts as empty;
+ * turns [B] = the side to move, 0 Black / 1 White): level_out[b] = 1..7, or 0 on a board with no empty cell; cell_out[b] = the cell of levels
+ * 1..5, else -1; count_out[b] = the number of cells the draw of level 6 or 7 chooses among, 0 for the other levels.  Each output may be NULL.
+ * Touches no engine state and needs no net (like omok_env_check_positions).  batch < 1, NULL boards or turns, or a turns byte above 1:
+ * OMOK_ERR_INVALID, with nothing written. */
+int omok_env_threat_scan(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* cell_out, int32_t* level_out,
+                         int32_t* count_out);
 /* Whole evaluation episode after a fresh omok_selfplay_reset: play_against_naive_player (trainer.rs:487-603: kind = OMOK_OPP_NAIVE,
  * opponent_side = 0, the scripted player is Black and moves first) or _play_against_random_player (:400-485: OMOK_OPP_RANDOM, opponent_side =
  * 1).  On plies where opponent_side (0 = Black, 1 = White) is to move: the scripted move as an external move (ensure_action_exists +
- * play_action, :536-538).  On the others: omok_execute(count, batch_size, epsilon, alpha), sample_action(Best), play_action (:562-577).
+ * play_action, :536-538; kind may be OMOK_OPP_THREAT as well).  On the others: omok_execute(count, batch_size, epsilon, alpha), sample_action(Best), play_action (:562-577).
  * Runs until every game is over or max_plies (> 0) plies were played.  results [3] (may be NULL) = black wins, white wins, draws among the
  * finished games (the reference's tuple, :602); stats as omok_selfplay_run.
  * The net's agent is the engine's tree of side 1 - opponent_side: it receives exactly the calls the reference's single Agent receives.  The

@@ -10,6 +10,7 @@ Names follow the reference so parity tests read like its own code:
   Engine.load_weights2 / load2     the second agent's AgentModel of benchmark/src/main.rs:14-108
   SelfPlay.match_reset             benchmark/src/main.rs: net 1 against net 2, half of the games per colour
   SelfPlay.versus_run              Trainer::play_against_naive_player / _play_against_random_player, src/trainer.rs:400-603
+  Engine.env_threat_scan           which level of the threat-aware scripted player's rule (B.OPP_THREAT, include/omok_mi355x.h) decides a position
   Environment.check_positions      the rules of Environment::place_stone read backwards: is a given board a position of a game in progress?
   SelfPlay.reset_from / analyze    Agent::new (agent.rs:16-35) on given positions instead of Environment::new()
   SelfPlay.match_reset_from        the match of benchmark/src/main.rs from given positions (an opening book), each agent with its own net
@@ -228,13 +229,25 @@ class Engine:
 
     def env_scripted_actions(self, kind, boards, turns):
         """the forced part of the scripted player's rule (src/trainer.rs:514-531) on caller-held positions: the lowest empty cell at
-        which a stone of either side ends the game, -1 where there is none (always -1 for B.OPP_RANDOM); int32 [B]"""
+        which a stone of either side ends the game, -1 where there is none (always -1 for B.OPP_RANDOM); int32 [B].  For B.OPP_THREAT: the
+        cell of levels 1..5 of the threat-aware rule for the side to move turns[b] (0 / 1, anything else raises), -1 for levels 6 and 7"""
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
         turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
         assert len(turns) == len(boards)
         forced = np.zeros(len(boards), dtype=np.int32)
         self._chk(B.lib().omok_env_scripted_actions(self.h, int(kind), B.u8ptr(boards), B.u8ptr(turns), len(boards), B.iptr(forced)))
         return forced
+
+    def env_threat_scan(self, boards, turns):
+        """omok_env_threat_scan on caller-held positions, turns[b] = the side to move (0 Black / 1 White): which level of the B.OPP_THREAT rule
+        (include/omok_mi355x.h) decides.  Returns int32 [B] arrays (cell, level, count): level 1..7, 0 on a full board; cell = the move of
+        levels 1..5, else -1; count = the number of cells the draw of level 6 / 7 chooses among, else 0.  Needs no net."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
+        turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
+        assert len(turns) == len(boards)
+        cell, level, count = (np.zeros(len(boards), dtype=np.int32) for _ in range(3))
+        self._chk(B.lib().omok_env_threat_scan(self.h, B.u8ptr(boards), B.u8ptr(turns), len(boards), B.iptr(cell), B.iptr(level), B.iptr(count)))
+        return cell, level, count
 
     def env_check_positions(self, boards):
         """omok_env_check_positions on caller-held boards [B][HW] (bytes): (verdict int32 [B], stones int32 [B]); verdict 0 = a legal position
@@ -445,14 +458,14 @@ class SelfPlay:
         self._chk(B.lib().omok_set_actions(self.h, B.iptr(a)))
 
     def opponent_actions(self, kind):
-        """the scripted player's move (B.OPP_NAIVE / B.OPP_RANDOM, src/trainer.rs:508-534, 452-455) for the side to move of every live
+        """the scripted player's move (B.OPP_NAIVE / B.OPP_RANDOM, src/trainer.rs:508-534, 452-455; B.OPP_THREAT, the threat-aware rule) for the side to move of every live
         game, chosen on the device and staged like set_actions (the mirror step / advance follow); -1 for finished games"""
         a = np.zeros(self.games, dtype=np.int32)
         self._chk(B.lib().omok_opponent_actions(self.h, int(kind), B.iptr(a)))
         return a
 
     def versus_run(self, kind, opponent_side, count, batch_size, epsilon=0.25, alpha=0.03, max_plies=0):
-        """Evaluation episode after reset() (omok_versus_run): the scripted player `kind` plays the colour opponent_side (0 = Black, moves
+        """Evaluation episode after reset() (omok_versus_run): the scripted player `kind` (B.OPP_NAIVE, B.OPP_RANDOM or B.OPP_THREAT) plays the colour opponent_side (0 = Black, moves
         first: play_against_naive_player, src/trainer.rs:487-603; 1 = White: _play_against_random_player, :400-485), the net the other with
         `count` simulations and sample_action(Best).  Returns ((black_win, white_win, draw), stats)."""
         s = (C.c_double * len(B.STAT_NAMES))()

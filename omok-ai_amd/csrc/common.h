@@ -202,6 +202,10 @@ void launch_clear_actions(const Store& S, hipStream_t st);
 void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int32_t* actions_dev, hipStream_t st);
 // the forced part of the naive rule on caller-held positions: boards_dev [B][HW] Stone bytes -> forced_dev [B] (-1: none)
 void launch_env_scripted(int n, const uint8_t* boards_dev, int kind, int batch, int32_t* forced_dev, hipStream_t st);
+// the threat-aware scripted player (OMOK_OPP_THREAT, kind 3; kernels of its own): its move of every live game, staged and copied like launch_opponent_move's
+void launch_opponent_move_threat(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int32_t* actions_dev, hipStream_t st);
+// its rule on caller-held positions: boards_dev [B][HW], turns_dev [B] (0 / 1) -> cell_dev (levels 1..5, else -1), level_dev, count_dev [B]; each may be NULL
+void launch_env_threat(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int32_t* cell_dev, int32_t* level_dev, int32_t* count_dev, hipStream_t st);
 void launch_policy(int n, const Store& S, int side, float* pi_dev /*[G][HW]*/, uint8_t* has_dev /*[G]*/, hipStream_t st);
 void launch_env_place(int n, uint8_t* boards_dev, uint8_t* turns_dev, uint16_t* legal_dev, const int32_t* actions_dev, int batch,
                       int32_t* status_dev, hipStream_t st);

@@ -1277,7 +1277,8 @@ static void enqueue_sample(omok_engine* e, float temperature, int threshold) {
 // the scripted player's move of every live game (OMOK_OPP_*: the evaluation games further down), staged where the search's sample would be
 static void enqueue_opponent_move(omok_engine* e, int kind) {
     e->prof.begin(PC_PLY, e->st);
-    launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, e->d_actions, e->st);
+    if (kind == OMOK_OPP_THREAT) launch_opponent_move_threat(e->n, e->S, e->ply & 1, e->key, e->cfg.game_offset, e->d_actions, e->st);
+    else launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, e->d_actions, e->st);
     e->prof.end(e->st);
 }
 
@@ -1539,14 +1540,45 @@ extern "C" int omok_play_actions(omok_engine* e, const int32_t* actions) {
 
 // ---- evaluation games against the scripted players (src/trainer.rs:380-394, 400-603) -----------
 static int check_opponent_kind(omok_engine* e, int kind) {
-    if (kind != OMOK_OPP_RANDOM && kind != OMOK_OPP_NAIVE) return fail(e, OMOK_ERR_INVALID, "unknown scripted player %d (OMOK_OPP_RANDOM, OMOK_OPP_NAIVE)", kind);
+    if (kind != OMOK_OPP_RANDOM && kind != OMOK_OPP_NAIVE && kind != OMOK_OPP_THREAT)
+        return fail(e, OMOK_ERR_INVALID, "unknown scripted player %d (OMOK_OPP_RANDOM, OMOK_OPP_NAIVE, OMOK_OPP_THREAT)", kind);
     return 0;
+}
+
+// the threat-aware rule on caller-held positions (each output may be NULL): the side to move decides, so a turns byte above 1 is refused before
+// anything is launched
+static int env_threat(omok_engine* e, const char* what, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* cell_out,
+                      int32_t* level_out, int32_t* count_out) {
+    const size_t B = (size_t)batch;
+    for (size_t b = 0; b < B; ++b)
+        if (turns[b] > 1) return fail(e, OMOK_ERR_INVALID, "%s: turns[%zu] = %d is neither 0 (Black) nor 1 (White)", what, b, (int)turns[b]);
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    Scratch sc;
+    uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
+    uint8_t* d_turns = sc.get<uint8_t>(B);
+    int32_t* d_out = sc.get<int32_t>(3 * B);
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "%s: device allocation failed", what);
+    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
+    hipMemcpyAsync(d_turns, turns, B, hipMemcpyHostToDevice, e->st);
+    launch_env_threat(e->n, d_boards, d_turns, batch, cell_out ? d_out : nullptr, level_out ? d_out + B : nullptr, count_out ? d_out + 2 * B : nullptr, e->st);
+    if (cell_out) hipMemcpyAsync(cell_out, d_out, B * 4, hipMemcpyDeviceToHost, e->st);
+    if (level_out) hipMemcpyAsync(level_out, d_out + B, B * 4, hipMemcpyDeviceToHost, e->st);
+    if (count_out) hipMemcpyAsync(count_out, d_out + 2 * B, B * 4, hipMemcpyDeviceToHost, e->st);
+    return sync_and_check(e, what) ? OMOK_ERR_HIP : OMOK_OK;
+}
+
+// which level of the threat-aware rule decides on caller-held positions, its cell, and how many cells its draw chooses among
+extern "C" int omok_env_threat_scan(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* cell_out, int32_t* level_out,
+                                    int32_t* count_out) {
+    if (!e || !boards || !turns || batch < 1) return OMOK_ERR_INVALID;
+    return env_threat(e, "env_threat_scan", boards, turns, batch, cell_out, level_out, count_out);
 }
 
 // the forced part of the naive player's rule (trainer.rs:514-531, rules of environment/src/lib.rs:104-190) on caller-held positions
 extern "C" int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out) {
     if (!e || !boards || !turns || !forced_out || batch < 1) return OMOK_ERR_INVALID;
     if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
+    if (kind == OMOK_OPP_THREAT) return env_threat(e, "env_scripted_actions", boards, turns, batch, forced_out, nullptr, nullptr); // (this rule does read turns)
     ENTER(e);
     // (the rule tests a stone of either colour at every empty cell, trainer.rs:518,524-527: the answer does not depend on the side to move)
     const size_t B = (size_t)batch;

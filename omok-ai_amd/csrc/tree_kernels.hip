@@ -2148,6 +2148,185 @@ __global__ __launch_bounds__(64) void k_env_scripted(const uint8_t* __restrict__
     if (lane == 0) forced[b] = cell;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The threat-aware scripted player (OMOK_OPP_THREAT; the rule is spelled out in include/omok_mi355x.h).  Not a player of the reference:
+// it is defined by the reference's exact-five test (five_in_pair above) alone.  Per lane one empty cell a; along each of the four line
+// pairs the lane gathers the 19 cells a - 9 d .. a + 9 d into three bit masks (bit 9 + i = cell a + i d; black, white, on the board),
+// and every predicate of the rule is bit arithmetic on those masks: the hypothetical stone at a is bit 9 of the mover's mask, nothing
+// is written anywhere.  (9 = 4 + 5: a completing cell lies at most 4 from a, and whether its run is four or longer shows 5 beyond it.)
+// ---------------------------------------------------------------------------------------------
+template <int N>
+__device__ inline void threat_line(const uint64_t* bb, int x0, int y0, int pr, uint32_t& black, uint32_t& white, uint32_t& inside) {
+    constexpr int NW = Geo<N>::NW;
+    const int dx = pr == 1 ? 0 : -1, dy = pr == 0 ? 0 : (pr == 3 ? 1 : -1); // the pairs of five_in_pair
+    black = white = inside = 0u;
+#pragma unroll
+    for (int i = -9; i <= 9; ++i) {
+        if (i == 0) continue;
+        const int x = x0 + dx * i, y = y0 + dy * i;
+        const bool in = x >= 0 && x < N && y >= 0 && y < N;
+        const int c = in ? y * N + x : 0;
+        const uint32_t on = in ? 1u : 0u;
+        black |= ((uint32_t)get_bit<NW>(bb, c) & on) << (9 + i);
+        white |= ((uint32_t)get_bit<NW>(bb + NW, c) & on) << (9 + i);
+        inside |= on << (9 + i);
+    }
+}
+// runs along one line: bit p of up[k] / dn[k] <=> the k cells directly above / below p all hold a stone of s (k = 0..5; runs of more than
+// 5 need not be told apart, as in five_in_pair)
+struct LineRuns { uint32_t up[6], dn[6]; };
+__device__ inline LineRuns line_runs(uint32_t s) {
+    LineRuns r;
+    r.up[0] = r.dn[0] = ~0u;
+#pragma unroll
+    for (int k = 1; k <= 5; ++k) {
+        r.up[k] = r.up[k - 1] & (s >> k);
+        r.dn[k] = r.dn[k - 1] & (s << k);
+    }
+    return r;
+}
+// bit p: a stone at p makes EXACTLY five along the line (1 + run above + run below == 5)
+__device__ inline uint32_t line_exact_five(const LineRuns& r) {
+    uint32_t five = 0u;
+#pragma unroll
+    for (int k = 0; k <= 4; ++k) five |= (r.up[k] & ~r.up[k + 1]) & (r.dn[4 - k] & ~r.dn[5 - k]);
+    return five;
+}
+
+// The move of the threat-aware rule for the side `me` (0 Black, 1 White) on bb, `legal` empty cells, x0 = the draw of levels 6 and 7.
+// level: 1..7 (0: no empty cell, the result is -1); count: the number of cells the draw of level 6 / 7 chooses among, else 0.
+// Wave-cooperative like scripted_forced_cell: lanes sweep cells 64 j + lane, one ballot per level and sweep, the lowest level with a
+// non-empty ballot gives the cell (ffs of its first such sweep).
+template <int N>
+__device__ inline int scripted_threat_cell(const uint64_t* bb, int legal, int me, uint32_t x0, int& level, int& count) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    constexpr uint32_t CENTRE = 1u << 9, AROUND = 0x3DE0u; // bits 5..13 without bit 9: the cells a +- k d, k = 1..4
+    const int lane = LANE;
+    int first[5] = {-1, -1, -1, -1, -1};
+    unsigned long long near[G::IT];
+    level = 0;
+    count = 0;
+    if (legal <= 0) return -1;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const bool empty = a < G::HW && !(((bb[j] | bb[NW + j]) >> lane) & 1ULL);
+        bool hit[5] = {empty && legal == 1, false, false, false, false}; // (Draw is terminal: the last empty cell is a level-1 cell)
+        bool nr = false;
+        if (empty && legal != 1) {
+            const int xc = a % N, yc = a / N;
+            int t_me = 0, t_opp = 0;
+#pragma unroll 1
+            for (int pr = 0; pr < 4; ++pr) { // (a real loop: unrolled four times four sweeps, the body outgrows the registers)
+                uint32_t black, white, inside;
+                threat_line<N>(bb, xc, yc, pr, black, white, inside);
+                const uint32_t free_cells = inside & ~(black | white); // (bit 9 is 0: the cell a takes the hypothetical stone)
+                const LineRuns rm = line_runs((me == 0 ? black : white) | CENTRE), ro = line_runs((me == 0 ? white : black) | CENTRE);
+                const uint32_t fm = line_exact_five(rm), fo = line_exact_five(ro);
+                hit[0] = hit[0] || (fm & CENTRE) != 0u; // (the runs at bit 9 start next to it: FIVE(c, a) with or without the stone)
+                hit[1] = hit[1] || (fo & CENTRE) != 0u;
+                t_me += __popc(fm & free_cells & AROUND);
+                t_opp += __popc(fo & free_cells & AROUND);
+#pragma unroll
+                for (int ra = 0; ra <= 2; ++ra) { // OPEN3: L == 3 and both cells just beyond the run's ends are free
+                    const int rb = 2 - ra;
+                    const uint32_t three = (rm.up[ra] & ~rm.up[ra + 1]) & (rm.dn[rb] & ~rm.dn[rb + 1]) & CENTRE;
+                    hit[4] = hit[4] || (three != 0u && ((free_cells >> (10 + ra)) & (free_cells >> (8 - rb)) & 1u) != 0u);
+                }
+                nr = nr || ((black | white) & 0x500u) != 0u; // bits 8 and 10: the two neighbours on this line
+            }
+            hit[2] = t_me >= 2;
+            hit[3] = t_opp >= 2;
+        }
+#pragma unroll
+        for (int l = 0; l < 5; ++l) {
+            const unsigned long long m = __ballot(hit[l]);
+            if (first[l] < 0 && m != 0ULL) first[l] = j * 64 + __ffsll((long long)m) - 1;
+        }
+        near[j] = __ballot(nr);
+    }
+#pragma unroll
+    for (int l = 0; l < 5; ++l)
+        if (level == 0 && first[l] >= 0) level = l + 1;
+    if (level != 0) {
+        int cell = -1;
+#pragma unroll
+        for (int l = 0; l < 5; ++l) cell = level == l + 1 ? first[l] : cell;
+        return cell;
+    }
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) count += __popcll(near[j]);
+    if (count == 0) { // level 7, the empty board: OMOK_OPP_RANDOM's draw
+        level = 7;
+        count = legal;
+        return scripted_random_cell<N>(bb, legal, x0);
+    }
+    level = 6; // the r-th cell with a neighbour, as scripted_random_cell picks the r-th empty one
+    int r = (int)__umulhi(x0, (uint32_t)count);
+    int action = -1;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int c = __popcll(near[j]);
+        if (action < 0) {
+            if (r < c) action = j * 64 + nth_set_bit(near[j], r);
+            else r -= c;
+        }
+    }
+    return action;
+}
+
+// k_opponent_move for OMOK_OPP_THREAT: the same load of the root board, the same draw and the same staging
+template <int N>
+__global__ __launch_bounds__(64) void k_opponent_move_threat(Store S, int side, uint64_t seed, int64_t game_offset, int32_t* __restrict__ actions) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int g = blockIdx.x;
+    const int lane = LANE;
+    const GameState gs = S.gs[g];
+    if (!gs.alive) {
+        if (lane == 0) { actions[g] = -1; S.gs[g].last_action = -1; S.gs[g].external = 1; }
+        return;
+    }
+    const uint64_t* root = S.board + (size_t)(side * S.games + g) * (size_t)S.stride_nodes * (2 * NW); // root = node 0
+    uint64_t bb[2 * NW];
+    int legal = G::HW;
+#pragma unroll
+    for (int i = 0; i < 2 * NW; ++i) { bb[i] = root[i]; legal -= __popcll(bb[i]); }
+    const U4 o = philox(seed, 0u, (uint32_t)gs.plies, (uint32_t)((game_offset + gs.gid) * 2 + side), RNG_OPPONENT); // k_opponent_move's word
+    int level, count;
+    const int action = scripted_threat_cell<N>(bb, legal, side, o.x, level, count);
+    if (lane == 0) { actions[g] = action; S.gs[g].last_action = action; S.gs[g].external = 1; }
+}
+
+// the rule on caller-held positions: boards [B][HW] Stone bytes (any other byte counts as empty, as in k_env_scripted), turns [B] (0 / 1,
+// checked by the host) -> cell [B] (levels 1..5, else -1), level [B], count [B]; each output may be NULL
+template <int N>
+__global__ __launch_bounds__(64) void k_env_threat(const uint8_t* __restrict__ boards, const uint8_t* __restrict__ turns, int32_t* __restrict__ cell_out,
+                                                   int32_t* __restrict__ level_out, int32_t* __restrict__ count_out) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int b = blockIdx.x;
+    const int lane = LANE;
+    uint64_t bb[2 * NW];
+    int legal = G::HW;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
+        bb[j] = __ballot(s == 1);
+        bb[NW + j] = __ballot(s == 2);
+        legal -= __popcll(bb[j]) + __popcll(bb[NW + j]);
+    }
+    int level, count;
+    const int cell = scripted_threat_cell<N>(bb, legal, turns[b] & 1, 0u, level, count);
+    if (lane == 0) {
+        if (cell_out) cell_out[b] = level >= 1 && level <= 5 ? cell : -1;
+        if (level_out) level_out[b] = level;
+        if (count_out) count_out[b] = count;
+    }
+}
+
 // k_position_check: is a caller-supplied board a position an alternating game from Environment::new() can be in, and still in progress?
 // boards [B][HW] bytes -> verdict [B], the first that applies: 1 a byte that is no Stone (> 2); 2 stone counts no alternating game produces
 // (neither black = white nor black = white + 1); 3 already won: some stone, taken as the last one placed, makes exactly five in one of the
@@ -3118,6 +3297,13 @@ void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t se
 }
 void launch_env_scripted(int n, const uint8_t* boards, int kind, int batch, int32_t* forced, hipStream_t st) {
     DISPATCH_N(n, (k_env_scripted<9><<<batch, 64, 0, st>>>(boards, kind, forced)), (k_env_scripted<15><<<batch, 64, 0, st>>>(boards, kind, forced)));
+}
+void launch_opponent_move_threat(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int32_t* actions, hipStream_t st) {
+    DISPATCH_N(n, (k_opponent_move_threat<9><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, actions)),
+               (k_opponent_move_threat<15><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, actions)));
+}
+void launch_env_threat(int n, const uint8_t* boards, const uint8_t* turns, int batch, int32_t* cell, int32_t* level, int32_t* count, hipStream_t st) {
+    DISPATCH_N(n, (k_env_threat<9><<<batch, 64, 0, st>>>(boards, turns, cell, level, count)), (k_env_threat<15><<<batch, 64, 0, st>>>(boards, turns, cell, level, count)));
 }
 void launch_policy(int n, const Store& S, int side, float* pi, uint8_t* has, hipStream_t st) {
     DISPATCH_N(n, (k_policy<9><<<S.games, 64, 0, st>>>(S, side, pi, has)), (k_policy<15><<<S.games, 64, 0, st>>>(S, side, pi, has)));

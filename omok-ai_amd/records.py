@@ -7,6 +7,7 @@ root and chosen-child statistics of the mover's tree at the moment of the move. 
 (Engine.env_replay), never through a restatement of the rules here.
 
     python -m omok_ai_amd.records show FILE.npz --game 3
+    python -m omok_ai_amd.records tactics FILE.npz
 """
 import argparse
 import json
@@ -142,6 +143,44 @@ class GameRecords:
             assert int(self.plies[g]) == int(stones[g]), f"game {g}: plies {int(self.plies[g])}, stones {int(stones[g])}"
         return boards
 
+    # ---- tactics (the engine's replay and the threat-aware rule's scan) -----------------------------
+    def tactics(self, engine):
+        """How often a mover overlooked a one-move win or loss.  Walks the plies: the positions of all games after p moves come from
+        Engine.env_replay (upto = p) and are scanned with the side to move by Engine.env_threat_scan (the levels of B.OPP_THREAT,
+        include/omok_mi355x.h: 1 = the mover can make five, 2 = only the opponent can).  Returns a dict:
+          level_before  int8 [G][HW]: the level of the position in front of move p of game g (0 beyond the game's length)
+          missed_win    int32 [G][2]: per side (0 Black, 1 White) the moves with level_before == 1 that did not end the game
+          unblocked     int32 [G][2]: per side the moves with level_before == 2 after which the opponent's position has level 1
+        A record that does not replay (verify) raises AssertionError."""
+        assert engine.n == self.n, f"records of board size {self.n}, engine of {engine.n}"
+        g = self.games
+        level_before = np.zeros((g, self.hw), dtype=np.int8)
+        missed_win, unblocked = np.zeros((g, 2), dtype=np.int32), np.zeros((g, 2), dtype=np.int32)
+        if g == 0:
+            return {"level_before": level_before, "missed_win": missed_win, "unblocked": unblocked}
+        moves, start = self.moves(), np.count_nonzero(self.start_boards, axis=1)
+        rows = np.arange(g)
+        prev = None  # the levels one ply earlier and which games made a move there
+        for p in range(int(self.lengths.max()) + 1):
+            boards, status, played = engine.env_replay(self.start_boards, moves, self.lengths, upto=p)
+            reached = self.lengths >= p
+            assert np.all(played[reached] == p), f"the records stop being legal before move {p}"
+            side = ((start + p) & 1).astype(np.uint8)
+            open_ = reached & (status == 0)  # the game is still in progress after p moves: there is a position to scan
+            level = np.zeros(g, dtype=np.int32)
+            if open_.any():
+                level[open_] = engine.env_threat_scan(boards[open_], side[open_])[1]
+            if prev is not None:
+                plevel, moved = prev
+                mover = 1 - side  # of move p - 1
+                np.add.at(missed_win, (rows[moved & (plevel == 1) & open_], mover[moved & (plevel == 1) & open_]), 1)
+                np.add.at(unblocked, (rows[moved & (plevel == 2) & (level == 1)], mover[moved & (plevel == 2) & (level == 1)]), 1)
+            moved = self.lengths > p
+            if p < self.hw:
+                level_before[moved, p] = level[moved]
+            prev = (level, moved)
+        return {"level_before": level_before, "missed_win": missed_win, "unblocked": unblocked}
+
     # ---- text --------------------------------------------------------------------------------------
     def coordinate(self, cell):
         """column letter (a = x 0) and row number (1 = y 0) of cell = y * n + x"""
@@ -187,8 +226,28 @@ def main(argv=None):
     show = sub.add_parser("show", help="print one game: the final board with move numbers and one line per move")
     show.add_argument("file")
     show.add_argument("--game", type=int, default=0)
+    tac = sub.add_parser("tactics", help="count the overlooked one-move wins and losses by side (needs the GPU: replay and scan run in the engine)")
+    tac.add_argument("file")
     args = ap.parse_args(argv)
     rec = load(args.file)
+    if args.cmd == "tactics":
+        from . import api
+        eng = api.Engine(board_size=rec.n, games=1, max_nodes=16, max_tables=8, max_batch_k=1)
+        try:
+            t = rec.tactics(eng)
+        finally:
+            eng.close()
+        sides = (rec.start_boards != 0).sum(axis=1)[:, None] + np.arange(rec.hw)[None, :] & 1
+        played = rec.cells >= 0
+        out = {"games": rec.games, "moves": int(played.sum())}
+        for s, name in ((0, "black"), (1, "white")):
+            mine = played & (sides == s)
+            out[name] = {"moves": int(mine.sum()), "could_win": int((mine & (t["level_before"] == 1)).sum()), "missed_win": int(t["missed_win"][:, s].sum()),
+                         "had_to_block": int((mine & (t["level_before"] == 2)).sum()), "unblocked": int(t["unblocked"][:, s].sum())}
+        if rec.meta:
+            print("meta: " + json.dumps(rec.meta, sort_keys=True))
+        print("tactics: " + json.dumps(out, sort_keys=True))
+        return 0
     if not 0 <= args.game < rec.games:
         ap.error(f"--game {args.game} outside [0, {rec.games})")
     if rec.meta:

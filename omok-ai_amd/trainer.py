@@ -4,7 +4,7 @@ Per iteration, like the reference: clear the replay memory (:77-78), play `episo
 the engine), back-fill z and augment (:207-324, on the device), cap the memory at `replay_memory_size` (:326-328), run
 `parameter_update_count` training steps on `parameter_update_batch_size` transitions (:329-357), save the model
 (`saves/<model_name>`, :375, ModelIO format), and every `evaluate_every` iterations play `evaluate_games` games against the scripted
-naive player (:380-394, 487-603: `Trainer.evaluate`).  Plots (:371-376) are not part of this mirror.  Parameters and defaults:
+naive player (:380-394, 487-603: `Trainer.evaluate`; Parameters.evaluate_opponent = "threat" puts the threat-aware player in its place).  Plots (:371-376) are not part of this mirror.  Parameters and defaults:
 src/config.rs:83-110 (episode_count 50, evaluate_count 600, test_evaluate_count 800, ...).
 Multi-GPU: every rank plays its own `episode_count` games (global ids rank*episode_count + g) and trains data-parallel
 (gradients averaged per step: by the torch phase's all-reduce, or by the engine in rank order with train_backend="hip_dp"), so all ranks
@@ -44,6 +44,7 @@ class Parameters:  # src/config.rs:83-110
     evaluate_every: int = 10        # `iteration % 10 == 0` (src/trainer.rs:380)
     evaluate_games: int = 100       # play_against_naive_player(100, ..) (:384)
     selfplay_slots: int = 0         # 0 = one episode of episode_count games (omok_selfplay_run); S > 0 = the same games in slots mode on min(S, episode_count) slots (omok_selfplay_run_slots; no reference counterpart)
+    evaluate_opponent: str = "naive"  # the scripted player of the evaluation games: "naive" (the reference's, :508-534), "threat" (the threat-aware player, OMOK_OPP_THREAT) or "random" (:452-455)
     train_backend: str = "torch"    # the training phase (:329-357): "torch" = autograd (train.py), "hip" = the engine's native step (omok_train_run, one rank), "hip_dp" = the native step in two halves with the ranks' gradients averaged in between (any world size)
 
 
@@ -55,6 +56,8 @@ class Trainer:
         self.rank, self.local_rank, self.world = dist.shard_info()
         if self.p.train_backend not in ("torch", "hip", "hip_dp"):
             raise ValueError(f"train_backend {self.p.train_backend!r}: expected \"torch\", \"hip\" or \"hip_dp\"")
+        if self.p.evaluate_opponent not in api.B.OPPONENTS:
+            raise ValueError(f"evaluate_opponent {self.p.evaluate_opponent!r}: expected \"naive\", \"threat\" or \"random\"")
         if self.p.train_backend == "hip" and self.world > 1:
             raise RuntimeError("train_backend=\"hip\" runs on one rank only: the native step does not average gradients over ranks "
                                f"(world size {self.world}); use train_backend=\"hip_dp\" or \"torch\" for data-parallel training")
@@ -68,7 +71,7 @@ class Trainer:
         self.precision_search_rounds = precision_search_rounds  # ... and of the search rounds' own path (sibling base + difference rows)
         self.last_precision = None
         self.seed = seed
-        self.last_evaluation = None  # result of the last games against the naive player (evaluate)
+        self.last_evaluation = None  # result of the last games against the scripted player evaluate_opponent (evaluate)
         sims = -(-self.p.evaluate_count // self.p.evaluate_batch_size) * self.p.evaluate_batch_size
         max_nodes = max_nodes or min(16384, 4 * sims + 1024)
         self.engine = api.Engine(board_size=board_size, games=self.slots or self.p.episode_count, max_nodes=max_nodes,
@@ -240,11 +243,11 @@ class Trainer:
             if self.rank == 0 and p.evaluate_every > 0 and (self.iteration - 1) % p.evaluate_every == 0:  # `iteration % 10 == 0`, 0-based (:380)
                 try:  # like the precision check: a failure (e.g. no memory for the engine) is logged, never fatal
                     black, white, draw = self.evaluate()
-                    versus = (f" | {p.evaluate_games} games against the naive player (naive = Black, net = White, {p.test_evaluate_count} simulations): "
+                    versus = (f" | {p.evaluate_games} games against the {p.evaluate_opponent} player ({p.evaluate_opponent} = Black, net = White, {p.test_evaluate_count} simulations): "
                               f"black_win={black} white_win={white} draw={draw}")
                 except Exception as ex:  # noqa: BLE001
                     self.last_evaluation = {"iteration": self.iteration, "error": repr(ex)}
-                    log(f"[iter={self.iteration}] WARNING: the games against the naive player did not run: {ex!r}")
+                    log(f"[iter={self.iteration}] WARNING: the games against the {p.evaluate_opponent} player did not run: {ex!r}")
             log(f"[iter={self.iteration}] games={int(stats['finished'])} transitions={got} loss={loss:.4f} "
                 f"[v_loss={v_loss:.4f}, p_loss={p_loss:.4f}]" + versus)
         return v_loss, p_loss, loss
@@ -257,7 +260,9 @@ class Trainer:
         like the reference, or [evaluate_games, HW] Stone bytes = the position each game starts from (equal stone counts; the side the stone
         count gives moves first, the naive player stays Black).  save_games: a path = the games' records (records.GameRecords: every move, the
         naive player's marked external, with the net's root and chosen-child statistics) are written there as one .npz; None = no move log is
-        kept.  Returns (black_win, white_win, draw)."""
+        kept.  Parameters.evaluate_opponent ("naive" by default) names the scripted player: "threat", the threat-aware player of
+        include/omok_mi355x.h, keeps telling nets apart that all beat the naive player in every game; it is named in the log line, in
+        last_evaluation and in the records' meta.  Returns (black_win, white_win, draw)."""
         p = self.p
         sims = -(-p.test_evaluate_count // p.evaluate_batch_size) * p.evaluate_batch_size
         max_nodes = min(16384, 4 * sims + 1024)
@@ -273,14 +278,14 @@ class Trainer:
                 sp.reset()
             else:
                 sp.reset_from(np.ascontiguousarray(openings, dtype=np.uint8).reshape(p.evaluate_games, self.n * self.n))
-            (black, white, draw), _ = sp.versus_run(api.B.OPP_NAIVE, 0, p.test_evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha)
+            (black, white, draw), _ = sp.versus_run(api.B.OPPONENTS[p.evaluate_opponent], 0, p.test_evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha)
             if save_games is not None:
                 sp.game_records(meta={"kind": "evaluate", "net": os.path.join(self.save_dir, p.model_name), "iteration": self.iteration,
-                                      "opponent": "naive", "opponent_side": 0, "sims": p.test_evaluate_count, "batch": p.evaluate_batch_size,
+                                      "opponent": p.evaluate_opponent, "opponent_side": 0, "sims": p.test_evaluate_count, "batch": p.evaluate_batch_size,
                                       "seed": self.seed + 1, "openings": openings is not None}).save(save_games)
         finally:
             eng.close()
-        self.last_evaluation = {"iteration": self.iteration, "games": p.evaluate_games, "black_win": black, "white_win": white, "draw": draw}
+        self.last_evaluation = {"iteration": self.iteration, "games": p.evaluate_games, "opponent": p.evaluate_opponent, "black_win": black, "white_win": white, "draw": draw}
         return black, white, draw
 
     def close(self):
