@@ -310,11 +310,19 @@ int omok_selfplay_run(omok_engine* e, int32_t count, int32_t batch_size, float e
 #define OMOK_OPP_RANDOM 0
 #define OMOK_OPP_NAIVE 1
 #define OMOK_OPP_THREAT 3
+/* OMOK_OPP_VCF: the threat-aware player with a forced-win solver.  Its rule is OMOK_OPP_THREAT's with one level put in after level 2: if
+ * omok_env_vcf_solve's rule (below) with max_depth = OMOK_VCF_OPP_DEPTH and max_nodes = OMOK_VCF_OPP_NODES gives verdict 1 for the side to move,
+ * it plays the solver's cell; otherwise levels 3..7 apply unchanged, with the same draw word.  It differs from OMOK_OPP_THREAT only where the
+ * shortest forced win takes three or more attacker moves (a win in two is level 3's own cell).  The value 4 is no player and stays an invalid
+ * kind, like 2. */
+#define OMOK_OPP_VCF 5
+#define OMOK_VCF_OPP_DEPTH 6
+#define OMOK_VCF_OPP_NODES 256
 /* the forced part of the rule on caller-held positions (boards [B][N*N] Stone bytes, turns [B]): forced_out[b] = the cell the NAIVE rule
  * picks before its random fallback (trainer.rs:514-531), -1 if none (always -1 for RANDOM).  (The rule tries a stone of either colour at
  * every empty cell, so the side to move does not change the answer: turns is read by no kernel.)  For OMOK_OPP_THREAT the side to move
  * decides: forced_out[b] = the cell of levels 1..5, -1 for levels 6 and 7, and a turns byte above 1 is OMOK_ERR_INVALID, checked before
- * anything is launched (kinds 0 and 1 keep ignoring turns). */
+ * anything is launched (kinds 0 and 1 keep ignoring turns).  OMOK_OPP_VCF likewise: the cell of levels 1..5 or the solver's cell. */
 int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out);
 /* step-wise: the scripted player's move (trainer.rs:508-534 / :452-455) for the side to move of every live game, chosen on the device and
  * staged like omok_set_actions (omok_mirror_* / omok_advance follow); actions [G] may be NULL, -1 for finished games.  OMOK_ERR_STATE in a
@@ -327,10 +335,49 @@ int omok_opponent_actions(omok_engine* e, int32_t kind, int32_t* actions);
  * OMOK_ERR_INVALID, with nothing written. */
 int omok_env_threat_scan(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* cell_out, int32_t* level_out,
                          int32_t* count_out);
+/* Does the side to move have a forced win by continuous fours (VCF)?  Exact under the exact-five rule: every attacker move leaves a cell that
+ * completes five, so every reply is forced and only the attacker's side of the tree branches.  Not one of the reference's functions; it is
+ * defined by FIVE and T above alone.  `me` is the side to move, `opp` the other; W(a) is the set of the T(me,a) empty cells that complete
+ * exactly five for `me` once `me` has played a.  Inputs: a board, me, max_depth D in 1..16, max_nodes NB in 1..65536; one node counter for
+ * the whole call.
+ *   solve:  for d = 1 .. D:  pv = search(d);  if pv: verdict 1, moves = d, cell = pv[0]
+ *           none found: verdict 0
+ *   search(r):                       (the attacker is to move)
+ *       count one node; if that makes the count exceed NB: the whole call ends with verdict -1
+ *       if some empty a has FIVE(me,a):            return [lowest such a]
+ *       if r == 1:                                 return fail
+ *       Fo = the empty cells b with FIVE(opp,b)
+ *       if |Fo| >= 2:                              return fail
+ *       for a in ascending order over (Fo if |Fo| == 1 else all empty cells) with T(me,a) >= 1:
+ *           if T(me,a) >= 2:                       return [a, lowest of W(a), second lowest of W(a)]
+ *           if r >= 3:   e = the one cell of W(a); place me at a and opp at e;  pv = search(r - 1);  take both back
+ *                        if pv:                    return [a, e] + pv
+ *       return fail
+ * Why it is sound:
+ *   - Before a the attacker had no five, so every completing cell after a lies on a line through a within four steps: W(a) is all of them.
+ *   - The defender has no five after a: either Fo was empty, or a took its one cell.
+ *   - So the defender's only move that does not lose at once is e, and placing e cannot itself make five.
+ *   - The defender's stone at e may make the defender a four: that is the |Fo| == 1 branch one level down, where the attacker must block it
+ *     with a move that is itself a four.
+ *   - A candidate with T = 1 is not recursed at r = 2: its one completing cell gets blocked, so search(1) cannot succeed.
+ *   - Iterative deepening makes `moves` the least number of attacker moves up to and including the five, and `cell` the lowest first move
+ *     that achieves it.
+ * The node count is part of the result (the budget verdict depends on it): no transposition table, no pruning that changes it.
+ * boards [B][N*N] Stone bytes (any other byte counts as empty), turns [B] = the side to move (0 Black / 1 White).  Per position:
+ *   verdict_out  1 a forced win within D attacker moves, 0 none, -1 the node budget ran out
+ *   moves_out    the attacker moves up to and including the five; 0 unless verdict is 1
+ *   cell_out     the first move; -1 unless verdict is 1
+ *   nodes_out    the nodes counted; NB on verdict -1
+ *   pv_out       [B][2 * D - 1] cells: attacker, forced reply, attacker, ... ending with the five, padded with -1; all -1 unless verdict is 1
+ * Each output may be NULL.  Touches no engine state and needs no net.  batch < 1, NULL boards or turns, a turns byte above 1, max_depth outside
+ * 1..16 or max_nodes outside 1..65536: OMOK_ERR_INVALID, with nothing written and nothing launched.  (65536 nodes bounds how long one wave
+ * can run; it is a condition of the call, not a tuned value.) */
+int omok_env_vcf_solve(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t max_depth, int32_t max_nodes,
+                       int32_t* verdict_out, int32_t* cell_out, int32_t* moves_out, int32_t* nodes_out, int32_t* pv_out);
 /* Whole evaluation episode after a fresh omok_selfplay_reset: play_against_naive_player (trainer.rs:487-603: kind = OMOK_OPP_NAIVE,
  * opponent_side = 0, the scripted player is Black and moves first) or _play_against_random_player (:400-485: OMOK_OPP_RANDOM, opponent_side =
  * 1).  On plies where opponent_side (0 = Black, 1 = White) is to move: the scripted move as an external move (ensure_action_exists +
- * play_action, :536-538; kind may be OMOK_OPP_THREAT as well).  On the others: omok_execute(count, batch_size, epsilon, alpha), sample_action(Best), play_action (:562-577).
+ * play_action, :536-538; kind may be OMOK_OPP_THREAT or OMOK_OPP_VCF as well).  On the others: omok_execute(count, batch_size, epsilon, alpha), sample_action(Best), play_action (:562-577).
  * Runs until every game is over or max_plies (> 0) plies were played.  results [3] (may be NULL) = black wins, white wins, draws among the
  * finished games (the reference's tuple, :602); stats as omok_selfplay_run.
  * The net's agent is the engine's tree of side 1 - opponent_side: it receives exactly the calls the reference's single Agent receives.  The

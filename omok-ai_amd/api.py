@@ -11,6 +11,7 @@ Names follow the reference so parity tests read like its own code:
   SelfPlay.match_reset             benchmark/src/main.rs: net 1 against net 2, half of the games per colour
   SelfPlay.versus_run              Trainer::play_against_naive_player / _play_against_random_player, src/trainer.rs:400-603
   Engine.env_threat_scan           which level of the threat-aware scripted player's rule (B.OPP_THREAT, include/omok_mi355x.h) decides a position
+  Engine.env_vcf_solve             does the side to move have a forced win by continuous fours?  (B.OPP_VCF is the scripted player that asks)
   Environment.check_positions      the rules of Environment::place_stone read backwards: is a given board a position of a game in progress?
   SelfPlay.reset_from / analyze    Agent::new (agent.rs:16-35) on given positions instead of Environment::new()
   SelfPlay.match_reset_from        the match of benchmark/src/main.rs from given positions (an opening book), each agent with its own net
@@ -248,6 +249,21 @@ class Engine:
         cell, level, count = (np.zeros(len(boards), dtype=np.int32) for _ in range(3))
         self._chk(B.lib().omok_env_threat_scan(self.h, B.u8ptr(boards), B.u8ptr(turns), len(boards), B.iptr(cell), B.iptr(level), B.iptr(count)))
         return cell, level, count
+
+    def env_vcf_solve(self, boards, turns, max_depth=8, max_nodes=4096):
+        """omok_env_vcf_solve on caller-held positions, turns[b] = the side to move (0 Black / 1 White): does it have a forced win by
+        continuous fours within max_depth (1..16) of its moves and max_nodes (1..65536) search nodes?  (The rule: include/omok_mi355x.h.)
+        Returns int32 arrays (verdict, cell, moves, nodes) [B] and pv [B][2 * max_depth - 1]: verdict 1 a win, 0 none, -1 the node budget
+        ran out; cell = the first move and moves = the attacker moves up to the five (-1 and 0 unless verdict is 1); pv = attacker, forced
+        reply, attacker, ... padded with -1.  Needs no net."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
+        turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
+        assert len(turns) == len(boards)
+        verdict, cell, moves, nodes = (np.zeros(len(boards), dtype=np.int32) for _ in range(4))
+        pv = np.zeros((len(boards), max(2 * int(max_depth) - 1, 1)), dtype=np.int32)
+        self._chk(B.lib().omok_env_vcf_solve(self.h, B.u8ptr(boards), B.u8ptr(turns), len(boards), int(max_depth), int(max_nodes), B.iptr(verdict),
+                                             B.iptr(cell), B.iptr(moves), B.iptr(nodes), B.iptr(pv)))
+        return verdict, cell, moves, nodes, pv
 
     def env_check_positions(self, boards):
         """omok_env_check_positions on caller-held boards [B][HW] (bytes): (verdict int32 [B], stones int32 [B]); verdict 0 = a legal position

@@ -206,6 +206,13 @@ void launch_env_scripted(int n, const uint8_t* boards_dev, int kind, int batch, 
 void launch_opponent_move_threat(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int32_t* actions_dev, hipStream_t st);
 // its rule on caller-held positions: boards_dev [B][HW], turns_dev [B] (0 / 1) -> cell_dev (levels 1..5, else -1), level_dev, count_dev [B]; each may be NULL
 void launch_env_threat(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int32_t* cell_dev, int32_t* level_dev, int32_t* count_dev, hipStream_t st);
+// the forced-win solver (victory by continuous fours, omok_env_vcf_solve) on caller-held positions: depth 1..16 attacker moves, nodes 1..65536 per
+// position -> verdict_dev, cell_dev, moves_dev, nodes_dev [B], pv_dev [B][2 * depth - 1]; each may be NULL
+void launch_env_vcf(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int depth, int nodes, int32_t* verdict_dev, int32_t* cell_dev,
+                    int32_t* moves_dev, int32_t* nodes_dev, int32_t* pv_dev, hipStream_t st);
+// the scripted player that uses it (OMOK_OPP_VCF, kind 5): the threat-aware rule with the solver's cell put in after level 2
+void launch_opponent_move_vcf(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions_dev, hipStream_t st);
+void launch_env_scripted_vcf(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int depth, int nodes, int32_t* forced_dev, hipStream_t st);
 void launch_policy(int n, const Store& S, int side, float* pi_dev /*[G][HW]*/, uint8_t* has_dev /*[G]*/, hipStream_t st);
 void launch_env_place(int n, uint8_t* boards_dev, uint8_t* turns_dev, uint16_t* legal_dev, const int32_t* actions_dev, int batch,
                       int32_t* status_dev, hipStream_t st);

@@ -1278,6 +1278,8 @@ static void enqueue_sample(omok_engine* e, float temperature, int threshold) {
 static void enqueue_opponent_move(omok_engine* e, int kind) {
     e->prof.begin(PC_PLY, e->st);
     if (kind == OMOK_OPP_THREAT) launch_opponent_move_threat(e->n, e->S, e->ply & 1, e->key, e->cfg.game_offset, e->d_actions, e->st);
+    else if (kind == OMOK_OPP_VCF)
+        launch_opponent_move_vcf(e->n, e->S, e->ply & 1, e->key, e->cfg.game_offset, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, e->d_actions, e->st);
     else launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, e->d_actions, e->st);
     e->prof.end(e->st);
 }
@@ -1540,8 +1542,8 @@ extern "C" int omok_play_actions(omok_engine* e, const int32_t* actions) {
 
 // ---- evaluation games against the scripted players (src/trainer.rs:380-394, 400-603) -----------
 static int check_opponent_kind(omok_engine* e, int kind) {
-    if (kind != OMOK_OPP_RANDOM && kind != OMOK_OPP_NAIVE && kind != OMOK_OPP_THREAT)
-        return fail(e, OMOK_ERR_INVALID, "unknown scripted player %d (OMOK_OPP_RANDOM, OMOK_OPP_NAIVE, OMOK_OPP_THREAT)", kind);
+    if (kind != OMOK_OPP_RANDOM && kind != OMOK_OPP_NAIVE && kind != OMOK_OPP_THREAT && kind != OMOK_OPP_VCF)
+        return fail(e, OMOK_ERR_INVALID, "unknown scripted player %d (OMOK_OPP_RANDOM, OMOK_OPP_NAIVE, OMOK_OPP_THREAT, OMOK_OPP_VCF)", kind);
     return 0;
 }
 
@@ -1574,11 +1576,53 @@ extern "C" int omok_env_threat_scan(omok_engine* e, const uint8_t* boards, const
     return env_threat(e, "env_threat_scan", boards, turns, batch, cell_out, level_out, count_out);
 }
 
+// does the side to move have a forced win by continuous fours?  (the rule: include/omok_mi355x.h; each output may be NULL)
+extern "C" int omok_env_vcf_solve(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t max_depth, int32_t max_nodes,
+                                  int32_t* verdict_out, int32_t* cell_out, int32_t* moves_out, int32_t* nodes_out, int32_t* pv_out) {
+    if (!e || !boards || !turns || batch < 1) return OMOK_ERR_INVALID;
+    if (max_depth < 1 || max_depth > 16) return fail(e, OMOK_ERR_INVALID, "env_vcf_solve: max_depth %d outside 1..16", max_depth);
+    if (max_nodes < 1 || max_nodes > 65536) return fail(e, OMOK_ERR_INVALID, "env_vcf_solve: max_nodes %d outside 1..65536", max_nodes);
+    const size_t B = (size_t)batch, len = (size_t)(2 * max_depth - 1);
+    for (size_t b = 0; b < B; ++b)
+        if (turns[b] > 1) return fail(e, OMOK_ERR_INVALID, "env_vcf_solve: turns[%zu] = %d is neither 0 (Black) nor 1 (White)", b, (int)turns[b]);
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    Scratch sc;
+    uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
+    uint8_t* d_turns = sc.get<uint8_t>(B);
+    int32_t* d_out = sc.get<int32_t>((4 + len) * B);
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_vcf_solve: device allocation failed");
+    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
+    hipMemcpyAsync(d_turns, turns, B, hipMemcpyHostToDevice, e->st);
+    int32_t* host[4] = {verdict_out, cell_out, moves_out, nodes_out};
+    launch_env_vcf(e->n, d_boards, d_turns, batch, max_depth, max_nodes, host[0] ? d_out : nullptr, host[1] ? d_out + B : nullptr,
+                   host[2] ? d_out + 2 * B : nullptr, host[3] ? d_out + 3 * B : nullptr, pv_out ? d_out + 4 * B : nullptr, e->st);
+    for (int i = 0; i < 4; ++i)
+        if (host[i]) hipMemcpyAsync(host[i], d_out + i * B, B * 4, hipMemcpyDeviceToHost, e->st);
+    if (pv_out) hipMemcpyAsync(pv_out, d_out + 4 * B, len * B * 4, hipMemcpyDeviceToHost, e->st);
+    return sync_and_check(e, "env_vcf_solve") ? OMOK_ERR_HIP : OMOK_OK;
+}
+
 // the forced part of the naive player's rule (trainer.rs:514-531, rules of environment/src/lib.rs:104-190) on caller-held positions
 extern "C" int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out) {
     if (!e || !boards || !turns || !forced_out || batch < 1) return OMOK_ERR_INVALID;
     if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
     if (kind == OMOK_OPP_THREAT) return env_threat(e, "env_scripted_actions", boards, turns, batch, forced_out, nullptr, nullptr); // (this rule does read turns)
+    if (kind == OMOK_OPP_VCF) { // (reads turns too: the same check, the same copies, the rule with the solver's level)
+        const size_t B = (size_t)batch;
+        for (size_t b = 0; b < B; ++b)
+            if (turns[b] > 1) return fail(e, OMOK_ERR_INVALID, "env_scripted_actions: turns[%zu] = %d is neither 0 (Black) nor 1 (White)", b, (int)turns[b]);
+        HIPCHK(e, hipSetDevice(e->cfg.device));
+        Scratch sc;
+        uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
+        uint8_t* d_turns = sc.get<uint8_t>(B);
+        int32_t* d_forced = sc.get<int32_t>(B);
+        if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_scripted_actions: device allocation failed");
+        hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
+        hipMemcpyAsync(d_turns, turns, B, hipMemcpyHostToDevice, e->st);
+        launch_env_scripted_vcf(e->n, d_boards, d_turns, batch, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, d_forced, e->st);
+        hipMemcpyAsync(forced_out, d_forced, B * 4, hipMemcpyDeviceToHost, e->st);
+        return sync_and_check(e, "env_scripted_actions") ? OMOK_ERR_HIP : OMOK_OK;
+    }
     ENTER(e);
     // (the rule tests a stone of either colour at every empty cell, trainer.rs:518,524-527: the answer does not depend on the side to move)
     const size_t B = (size_t)batch;

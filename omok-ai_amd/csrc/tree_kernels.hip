@@ -2327,6 +2327,250 @@ __global__ __launch_bounds__(64) void k_env_threat(const uint8_t* __restrict__ b
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The forced-win solver: victory by continuous fours (VCF; omok_env_vcf_solve, the rule and why it is sound are spelled out in
+// include/omok_mi355x.h).  One wave = one position.  A node is one sweep of the board with the predicates of the threat-aware rule
+// (threat_line / line_runs / line_exact_five above), one ballot each for FIVE(me), FIVE(opp), T(me) >= 1 and T(me) >= 2.  Everything that
+// steers the search is wave-uniform: the depth-first stack (per level the ballot words of the candidates still to try, the attacker's
+// cell a and the forced reply e) sits in LDS, every lane writes the same value and reads it back, so no barrier is needed; stones are
+// made and unmade as bit sets and clears on the register bitboards.  The completing cells W(a) of the candidate that is tried are
+// computed once more for that cell alone by all lanes alike (a quarter of a sweep at 15 x 15), which keeps per-lane cells off the stack.
+// ---------------------------------------------------------------------------------------------
+struct VcfCell { bool five_me, five_opp; int t, w1, w2; }; // T(me, a) and the two lowest cells of W(a) (-1: none)
+template <int N, bool CELLS>
+__device__ inline VcfCell vcf_cell(const uint64_t* bb, int a, int me) {
+    constexpr uint32_t CENTRE = 1u << 9, AROUND = 0x3DE0u; // as in scripted_threat_cell
+    VcfCell r{false, false, 0, -1, -1};
+    const int xc = a % N, yc = a / N;
+#pragma unroll 1
+    for (int pr = 0; pr < 4; ++pr) {
+        uint32_t black, white, inside;
+        threat_line<N>(bb, xc, yc, pr, black, white, inside);
+        const uint32_t free_cells = inside & ~(black | white);
+        const LineRuns rm = line_runs((me == 0 ? black : white) | CENTRE), ro = line_runs((me == 0 ? white : black) | CENTRE);
+        const uint32_t fm = line_exact_five(rm), fo = line_exact_five(ro);
+        r.five_me = r.five_me || (fm & CENTRE) != 0u;
+        r.five_opp = r.five_opp || (fo & CENTRE) != 0u;
+        uint32_t w = fm & free_cells & AROUND;
+        r.t += __popc(w);
+        if (CELLS) {
+            const int step = (pr == 0 ? 0 : (pr == 3 ? N : -N)) + (pr == 1 ? 0 : -1); // cell a + i d of threat_line: a + i * step
+            while (w != 0u) {
+                const int i = __ffs((int)w) - 1 - 9;
+                w &= w - 1u;
+                const int c = a + i * step;
+                if (r.w1 < 0 || c < r.w1) { r.w2 = r.w1; r.w1 = c; }
+                else if (r.w2 < 0 || c < r.w2) r.w2 = c;
+            }
+        }
+    }
+    return r;
+}
+
+template <int N>
+__device__ inline void vcf_put(uint64_t* bb, int side, int c, bool set) {
+    constexpr int NW = Geo<N>::NW;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const uint64_t bit = (c >> 6) == i ? (1ULL << (c & 63)) : 0ULL;
+        const uint64_t mine = side == 0 ? bit : 0ULL, theirs = side == 0 ? 0ULL : bit;
+        bb[i] = set ? (bb[i] | mine) : (bb[i] & ~mine);
+        bb[NW + i] = set ? (bb[NW + i] | theirs) : (bb[NW + i] & ~theirs);
+    }
+}
+
+constexpr int VCF_MAX_DEPTH = 16;
+template <int N>
+struct VcfLevel { unsigned long long cand[Geo<N>::IT]; int a, e; };
+struct VcfResult { int verdict, cell, moves, nodes, pv_len; };
+
+// solve of the header's rule for the side `me` on bb (every stone it placed is taken back before it returns): iterative deepening d = 1 .. D over
+// search(d), one node counter for the whole call.  pv (LDS, 2 * VCF_MAX_DEPTH - 1 ints) holds the first pv_len cells of the line on verdict 1.
+template <int N>
+__device__ inline VcfResult vcf_search(uint64_t* bb, int me, int D, int NB, VcfLevel<N>* stk, int* pv) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW, IT = G::IT;
+    const int lane = LANE;
+    VcfResult res{0, -1, 0, 0, 0};
+    for (int d = 1; d <= D && res.verdict == 0; ++d) {
+        int L = 0;           // the attacker's move number of the node at hand, r = d - L moves remain
+        bool enter = true;   // a new node (counted and swept), or back at level L for its next candidate
+        while (true) {
+            unsigned long long cand[IT];
+            if (enter) {
+                if (res.nodes == NB) { res.verdict = -1; break; }
+                res.nodes += 1;
+                unsigned long long fme[IT], fopp[IT], t1[IT], t2[IT];
+                int n_fo = 0;
+                bool won = false;
+#pragma unroll
+                for (int j = 0; j < IT; ++j) {
+                    const int a = j * 64 + lane;
+                    const bool empty = a < G::HW && !(((bb[j] | bb[NW + j]) >> lane) & 1ULL);
+                    VcfCell c{false, false, 0, -1, -1};
+                    if (empty) c = vcf_cell<N, false>(bb, a, me);
+                    fme[j] = __ballot(c.five_me);
+                    fopp[j] = __ballot(c.five_opp);
+                    t1[j] = __ballot(c.t >= 1);
+                    t2[j] = __ballot(c.t >= 2);
+                    n_fo += __popcll(fopp[j]);
+                    if (!won && fme[j] != 0ULL) {
+                        won = true;
+                        pv[2 * L] = j * 64 + __ffsll((long long)fme[j]) - 1;
+                    }
+                }
+                if (won) { res.verdict = 1; res.pv_len = 2 * L + 1; break; }
+                const int r = d - L;
+                const bool dead = r == 1 || n_fo >= 2;
+#pragma unroll
+                for (int j = 0; j < IT; ++j) // (at r == 2 a T = 1 candidate is passed over: only the T >= 2 ones can matter)
+                    cand[j] = dead ? 0ULL : ((r >= 3 ? t1[j] : t2[j]) & (n_fo == 1 ? fopp[j] : ~0ULL));
+            } else {
+#pragma unroll
+                for (int j = 0; j < IT; ++j) cand[j] = stk[L].cand[j];
+            }
+            int a = -1;
+#pragma unroll
+            for (int j = 0; j < IT; ++j)
+                if (a < 0 && cand[j] != 0ULL) {
+                    a = j * 64 + __ffsll((long long)cand[j]) - 1;
+                    cand[j] &= cand[j] - 1ULL;
+                }
+            if (a < 0) { // no candidate left: this node fails
+                if (L == 0) break;
+                L -= 1;
+                vcf_put<N>(bb, me, stk[L].a, false);
+                vcf_put<N>(bb, 1 - me, stk[L].e, false);
+                enter = false;
+                continue;
+            }
+            const VcfCell c = vcf_cell<N, true>(bb, a, me);
+            if (c.t >= 2) { // the defender blocks one cell of W(a), the other completes five
+                pv[2 * L] = a;
+                pv[2 * L + 1] = c.w1;
+                pv[2 * L + 2] = c.w2;
+                res.verdict = 1;
+                res.pv_len = 2 * L + 3;
+                break;
+            }
+#pragma unroll
+            for (int j = 0; j < IT; ++j) stk[L].cand[j] = cand[j];
+            stk[L].a = a;
+            stk[L].e = c.w1;
+            vcf_put<N>(bb, me, a, true);
+            vcf_put<N>(bb, 1 - me, c.w1, true);
+            L += 1;
+            enter = true;
+        }
+        for (int l = 0; l < L; ++l) { // success or the budget: the levels below hold the line so far, and their stones are still on bb
+            pv[2 * l] = stk[l].a;
+            pv[2 * l + 1] = stk[l].e;
+            vcf_put<N>(bb, me, stk[l].a, false);
+            vcf_put<N>(bb, 1 - me, stk[l].e, false);
+        }
+        if (res.verdict == 1) { res.moves = d; res.cell = pv[0]; }
+    }
+    return res;
+}
+
+// the solver on caller-held positions: boards [B][HW] Stone bytes (any other byte counts as empty), turns [B] (0 / 1, checked by the host),
+// D in 1..16 and NB in 1..65536 (checked by the host) -> verdict, cell, moves, nodes [B] and pv [B][2 D - 1]; each output may be NULL
+template <int N>
+__global__ __launch_bounds__(64) void k_env_vcf(const uint8_t* __restrict__ boards, const uint8_t* __restrict__ turns, int D, int NB,
+                                                int32_t* __restrict__ verdict_out, int32_t* __restrict__ cell_out, int32_t* __restrict__ moves_out,
+                                                int32_t* __restrict__ nodes_out, int32_t* __restrict__ pv_out) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    __shared__ VcfLevel<N> stk[VCF_MAX_DEPTH];
+    __shared__ int pv[2 * VCF_MAX_DEPTH - 1];
+    const int b = blockIdx.x;
+    const int lane = LANE;
+    uint64_t bb[2 * NW];
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
+        bb[j] = __ballot(s == 1);
+        bb[NW + j] = __ballot(s == 2);
+    }
+    const VcfResult r = vcf_search<N>(bb, turns[b] & 1, D, NB, stk, pv);
+    if (lane == 0) {
+        if (verdict_out) verdict_out[b] = r.verdict;
+        if (cell_out) cell_out[b] = r.cell;
+        if (moves_out) moves_out[b] = r.moves;
+        if (nodes_out) nodes_out[b] = r.nodes;
+    }
+    if (pv_out) {
+        const int len = 2 * D - 1; // (at most 31 cells: one store per lane)
+        if (lane < len) pv_out[(size_t)b * len + lane] = r.verdict == 1 && lane < r.pv_len ? pv[lane] : -1;
+    }
+}
+
+// The move of OMOK_OPP_VCF: the threat-aware rule with one level put in after level 2 -- a forced win by continuous fours within
+// D attacker moves and NB nodes (OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES: the host passes them) is played at its first cell.  solved: that
+// level decided.
+template <int N>
+__device__ inline int scripted_vcf_cell(uint64_t* bb, int legal, int me, uint32_t x0, int D, int NB, int& level, bool& solved, VcfLevel<N>* stk, int* pv) {
+    int count;
+    const int cell = scripted_threat_cell<N>(bb, legal, me, x0, level, count);
+    solved = false;
+    if (level < 3) return cell; // (0: no empty cell)
+    const VcfResult r = vcf_search<N>(bb, me, D, NB, stk, pv);
+    solved = r.verdict == 1;
+    return solved ? r.cell : cell;
+}
+
+// k_opponent_move for OMOK_OPP_VCF: the same load of the root board, the same draw and the same staging as k_opponent_move_threat
+template <int N>
+__global__ __launch_bounds__(64) void k_opponent_move_vcf(Store S, int side, uint64_t seed, int64_t game_offset, int D, int NB, int32_t* __restrict__ actions) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    __shared__ VcfLevel<N> stk[VCF_MAX_DEPTH];
+    __shared__ int pv[2 * VCF_MAX_DEPTH - 1];
+    const int g = blockIdx.x;
+    const int lane = LANE;
+    const GameState gs = S.gs[g];
+    if (!gs.alive) {
+        if (lane == 0) { actions[g] = -1; S.gs[g].last_action = -1; S.gs[g].external = 1; }
+        return;
+    }
+    const uint64_t* root = S.board + (size_t)(side * S.games + g) * (size_t)S.stride_nodes * (2 * NW); // root = node 0
+    uint64_t bb[2 * NW];
+    int legal = G::HW;
+#pragma unroll
+    for (int i = 0; i < 2 * NW; ++i) { bb[i] = root[i]; legal -= __popcll(bb[i]); }
+    const U4 o = philox(seed, 0u, (uint32_t)gs.plies, (uint32_t)((game_offset + gs.gid) * 2 + side), RNG_OPPONENT); // k_opponent_move's word
+    int level;
+    bool solved;
+    const int action = scripted_vcf_cell<N>(bb, legal, side, o.x, D, NB, level, solved, stk, pv);
+    if (lane == 0) { actions[g] = action; S.gs[g].last_action = action; S.gs[g].external = 1; }
+}
+
+// the same rule on caller-held positions -> forced [B]: the cell of levels 1..5 or the solver's, else -1
+template <int N>
+__global__ __launch_bounds__(64) void k_env_scripted_vcf(const uint8_t* __restrict__ boards, const uint8_t* __restrict__ turns, int D, int NB, int32_t* __restrict__ forced) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    __shared__ VcfLevel<N> stk[VCF_MAX_DEPTH];
+    __shared__ int pv[2 * VCF_MAX_DEPTH - 1];
+    const int b = blockIdx.x;
+    const int lane = LANE;
+    uint64_t bb[2 * NW];
+    int legal = G::HW;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
+        bb[j] = __ballot(s == 1);
+        bb[NW + j] = __ballot(s == 2);
+        legal -= __popcll(bb[j]) + __popcll(bb[NW + j]);
+    }
+    int level;
+    bool solved;
+    const int cell = scripted_vcf_cell<N>(bb, legal, turns[b] & 1, 0u, D, NB, level, solved, stk, pv);
+    if (lane == 0) forced[b] = solved || (level >= 1 && level <= 5) ? cell : -1;
+}
+
 // k_position_check: is a caller-supplied board a position an alternating game from Environment::new() can be in, and still in progress?
 // boards [B][HW] bytes -> verdict [B], the first that applies: 1 a byte that is no Stone (> 2); 2 stone counts no alternating game produces
 // (neither black = white nor black = white + 1); 3 already won: some stone, taken as the last one placed, makes exactly five in one of the
@@ -3304,6 +3548,19 @@ void launch_opponent_move_threat(int n, const Store& S, int side, uint64_t seed,
 }
 void launch_env_threat(int n, const uint8_t* boards, const uint8_t* turns, int batch, int32_t* cell, int32_t* level, int32_t* count, hipStream_t st) {
     DISPATCH_N(n, (k_env_threat<9><<<batch, 64, 0, st>>>(boards, turns, cell, level, count)), (k_env_threat<15><<<batch, 64, 0, st>>>(boards, turns, cell, level, count)));
+}
+void launch_env_vcf(int n, const uint8_t* boards, const uint8_t* turns, int batch, int depth, int nodes, int32_t* verdict, int32_t* cell, int32_t* moves,
+                    int32_t* count, int32_t* pv, hipStream_t st) {
+    DISPATCH_N(n, (k_env_vcf<9><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, verdict, cell, moves, count, pv)),
+               (k_env_vcf<15><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, verdict, cell, moves, count, pv)));
+}
+void launch_opponent_move_vcf(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions, hipStream_t st) {
+    DISPATCH_N(n, (k_opponent_move_vcf<9><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, depth, nodes, actions)),
+               (k_opponent_move_vcf<15><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, depth, nodes, actions)));
+}
+void launch_env_scripted_vcf(int n, const uint8_t* boards, const uint8_t* turns, int batch, int depth, int nodes, int32_t* forced, hipStream_t st) {
+    DISPATCH_N(n, (k_env_scripted_vcf<9><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, forced)),
+               (k_env_scripted_vcf<15><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, forced)));
 }
 void launch_policy(int n, const Store& S, int side, float* pi, uint8_t* has, hipStream_t st) {
     DISPATCH_N(n, (k_policy<9><<<S.games, 64, 0, st>>>(S, side, pi, has)), (k_policy<15><<<S.games, 64, 0, st>>>(S, side, pi, has)));

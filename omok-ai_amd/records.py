@@ -181,6 +181,50 @@ class GameRecords:
             prev = (level, moved)
         return {"level_before": level_before, "missed_win": missed_win, "unblocked": unblocked}
 
+    # ---- forced wins (the engine's replay and its forced-win solver) ---------------------------------
+    def forced_wins(self, engine, max_depth=8, max_nodes=4096):
+        """How often a mover had a forced win by continuous fours and let it go.  Walks the plies as tactics does: the positions of all games
+        after p moves come from Engine.env_replay (upto = p) and go to Engine.env_vcf_solve with the mover to move (include/omok_mi355x.h).
+        Returns a dict:
+          moves_before  int8 [G][HW]: the mover's `moves` in front of move p of game g -- the attacker moves of its shortest forced win
+                        within max_depth; 0 none (and beyond the game's length), -1 the node budget ran out
+          had           int32 [G][2]: per side (0 Black, 1 White) the moves with moves_before = m >= 2
+          dropped       int32 [G][2]: per side those of them for which the record shows the win let go: the game ended at move p or p + 1
+                        without the mover winning, or move p + 2 exists and moves_before[p + 2] is not in 1..m - 1.  A record that stops
+                        before it can tell counts as neither.
+        A record that does not replay (verify) raises AssertionError."""
+        assert engine.n == self.n, f"records of board size {self.n}, engine of {engine.n}"
+        g = self.games
+        moves_before = np.zeros((g, self.hw), dtype=np.int8)
+        had, dropped = np.zeros((g, 2), dtype=np.int32), np.zeros((g, 2), dtype=np.int32)
+        if g == 0:
+            return {"moves_before": moves_before, "had": had, "dropped": dropped}
+        moves, start = self.moves(), np.count_nonzero(self.start_boards, axis=1)
+        final = np.zeros(g, dtype=np.int32)  # the status after the last recorded move
+        for p in range(int(self.lengths.max()) + 1):
+            boards, status, played = engine.env_replay(self.start_boards, moves, self.lengths, upto=p)
+            reached = self.lengths >= p
+            assert np.all(played[reached] == p), f"the records stop being legal before move {p}"
+            final[self.lengths == p] = status[self.lengths == p]
+            moved = self.lengths > p
+            if p < self.hw and moved.any():
+                assert not status[moved].any(), f"a game goes on after move {p} ended it"
+                side = ((start[moved] + p) & 1).astype(np.uint8)
+                verdict, _cell, m, _nodes, _pv = engine.env_vcf_solve(boards[moved], side, max_depth, max_nodes)
+                moves_before[moved, p] = np.where(verdict == 1, m, verdict)
+        for i in range(g):
+            length, over = int(self.lengths[i]), final[i] != 0
+            for p in range(length):
+                m, side = int(moves_before[i, p]), int(start[i] + p) & 1
+                if m < 2:
+                    continue
+                had[i, side] += 1
+                if over and p >= length - 2:  # the game ended at move p or p + 1
+                    dropped[i, side] += 0 if (p == length - 1 and final[i] == (2 if side == 0 else 3)) else 1
+                elif p + 2 < length and not 1 <= int(moves_before[i, p + 2]) <= m - 1:
+                    dropped[i, side] += 1
+        return {"moves_before": moves_before, "had": had, "dropped": dropped}
+
     # ---- text --------------------------------------------------------------------------------------
     def coordinate(self, cell):
         """column letter (a = x 0) and row number (1 = y 0) of cell = y * n + x"""
@@ -228,8 +272,27 @@ def main(argv=None):
     show.add_argument("--game", type=int, default=0)
     tac = sub.add_parser("tactics", help="count the overlooked one-move wins and losses by side (needs the GPU: replay and scan run in the engine)")
     tac.add_argument("file")
+    forced = sub.add_parser("forced", help="count the forced wins by continuous fours a side had and let go (needs the GPU: replay and solver run in the engine)")
+    forced.add_argument("file")
+    forced.add_argument("--max-depth", type=int, default=8)
+    forced.add_argument("--max-nodes", type=int, default=4096)
     args = ap.parse_args(argv)
     rec = load(args.file)
+    if args.cmd == "forced":
+        from . import api
+        eng = api.Engine(board_size=rec.n, games=1, max_nodes=16, max_tables=8, max_batch_k=1)
+        try:
+            f = rec.forced_wins(eng, args.max_depth, args.max_nodes)
+        finally:
+            eng.close()
+        out = {"games": rec.games, "moves": int((rec.cells >= 0).sum()), "max_depth": args.max_depth, "max_nodes": args.max_nodes,
+               "budget_exhausted": int((f["moves_before"] < 0).sum())}
+        for s, name in ((0, "black"), (1, "white")):
+            out[name] = {"had": int(f["had"][:, s].sum()), "dropped": int(f["dropped"][:, s].sum())}
+        if rec.meta:
+            print("meta: " + json.dumps(rec.meta, sort_keys=True))
+        print("forced: " + json.dumps(out, sort_keys=True))
+        return 0
     if args.cmd == "tactics":
         from . import api
         eng = api.Engine(board_size=rec.n, games=1, max_nodes=16, max_tables=8, max_batch_k=1)
