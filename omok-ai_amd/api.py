@@ -474,14 +474,14 @@ class SelfPlay:
         self._chk(B.lib().omok_set_actions(self.h, B.iptr(a)))
 
     def opponent_actions(self, kind):
-        """the scripted player's move (B.OPP_NAIVE / B.OPP_RANDOM, src/trainer.rs:508-534, 452-455; B.OPP_THREAT, the threat-aware rule) for the side to move of every live
-        game, chosen on the device and staged like set_actions (the mirror step / advance follow); -1 for finished games"""
+        """the scripted player's move (B.OPP_NAIVE / B.OPP_RANDOM, src/trainer.rs:508-534, 452-455; B.OPP_THREAT, the threat-aware rule; B.OPP_VCF, the same with the
+        forced-win solver) for the side to move of every live game, chosen on the device and staged like set_actions (the mirror step / advance follow); -1 for finished games"""
         a = np.zeros(self.games, dtype=np.int32)
         self._chk(B.lib().omok_opponent_actions(self.h, int(kind), B.iptr(a)))
         return a
 
     def versus_run(self, kind, opponent_side, count, batch_size, epsilon=0.25, alpha=0.03, max_plies=0):
-        """Evaluation episode after reset() (omok_versus_run): the scripted player `kind` (B.OPP_NAIVE, B.OPP_RANDOM or B.OPP_THREAT) plays the colour opponent_side (0 = Black, moves
+        """Evaluation episode after reset() (omok_versus_run): the scripted player `kind` (B.OPP_NAIVE, B.OPP_RANDOM, B.OPP_THREAT or B.OPP_VCF) plays the colour opponent_side (0 = Black, moves
         first: play_against_naive_player, src/trainer.rs:487-603; 1 = White: _play_against_random_player, :400-485), the net the other with
         `count` simulations and sample_action(Best).  Returns ((black_win, white_win, draw), stats)."""
         s = (C.c_double * len(B.STAT_NAMES))()

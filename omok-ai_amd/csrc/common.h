@@ -123,7 +123,7 @@ void launch_reset(int n, const Store& S, const float* root_policy_dev /*ROWP*/, 
 // (omok_match_reset_from): the same rows from net 2; tree side * G + g takes the row of net side ^ (g >= split)
 void launch_reset_from(int n, const Store& S, const uint8_t* boards_dev, const float* p_dev, const float* p2_dev, int split, hipStream_t st);
 // random openings: position b = `stones` plies of the game with global id first_game + b, both sides the RANDOM scripted player drawing like
-// launch_opponent_move -> boards_dev [B][HW] Stone bytes, ok_dev [B] (0: a placement ended the game, the board stops there)
+// launch_opponent_move's OMOK_OPP_RANDOM -> boards_dev [B][HW] Stone bytes, ok_dev [B] (0: a placement ended the game, the board stops there)
 void launch_random_positions(int n, uint64_t key, int64_t first_game, int stones, int batch, uint8_t* boards_dev, uint8_t* ok_dev, hipStream_t st);
 // boards_dev [B][HW] bytes -> verdict_dev [B] (0 legal and in progress, 1 bad byte, 2 impossible stone counts, 3 already won, 4 full board),
 // stones_dev [B] (may be NULL)
@@ -197,22 +197,18 @@ void launch_replay_pack(int n, const Store& S, const long long* offsets_dev, uin
 void launch_replay_offsets(int n, const Store& S, int per_transition, long long* offsets_dev /*[games + 1]*/, hipStream_t st);
 void launch_set_actions(int n, const Store& S, int side, const int32_t* actions_dev, uint32_t* d_flags /*[0] illegal, [1] missing*/, hipStream_t st);
 void launch_clear_actions(const Store& S, hipStream_t st);
-// the scripted players of the evaluation games (src/trainer.rs:400-603), kind 0 = random, 1 = naive: the move of the side to move of every live game, staged like
-// launch_set_actions (external) and copied to actions_dev [G] (-1: finished game)
-void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int32_t* actions_dev, hipStream_t st);
-// the forced part of the naive rule on caller-held positions: boards_dev [B][HW] Stone bytes -> forced_dev [B] (-1: none)
-void launch_env_scripted(int n, const uint8_t* boards_dev, int kind, int batch, int32_t* forced_dev, hipStream_t st);
-// the threat-aware scripted player (OMOK_OPP_THREAT, kind 3; kernels of its own): its move of every live game, staged and copied like launch_opponent_move's
-void launch_opponent_move_threat(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int32_t* actions_dev, hipStream_t st);
-// its rule on caller-held positions: boards_dev [B][HW], turns_dev [B] (0 / 1) -> cell_dev (levels 1..5, else -1), level_dev, count_dev [B]; each may be NULL
-void launch_env_threat(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int32_t* cell_dev, int32_t* level_dev, int32_t* count_dev, hipStream_t st);
+// the scripted players of the evaluation games (kind = OMOK_OPP_*: random and naive of src/trainer.rs:400-603, the threat-aware player, and the one
+// with the forced-win solver, which alone uses depth / nodes = OMOK_VCF_OPP_DEPTH / OMOK_VCF_OPP_NODES): the move of the side to move of every live game,
+// staged like launch_set_actions (external) and copied to actions_dev [G] (-1: finished game)
+void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions_dev, hipStream_t st);
+// the same rule on caller-held positions: boards_dev [B][HW] Stone bytes, turns_dev [B] (0 / 1; read by the threat-aware kinds alone, else may be NULL)
+// -> cell_dev (the cell the rule is forced to, -1 where it would draw), level_dev, count_dev [B]; each may be NULL
+void launch_env_scripted(int n, int kind, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int depth, int nodes, int32_t* cell_dev,
+                         int32_t* level_dev, int32_t* count_dev, hipStream_t st);
 // the forced-win solver (victory by continuous fours, omok_env_vcf_solve) on caller-held positions: depth 1..16 attacker moves, nodes 1..65536 per
 // position -> verdict_dev, cell_dev, moves_dev, nodes_dev [B], pv_dev [B][2 * depth - 1]; each may be NULL
 void launch_env_vcf(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int depth, int nodes, int32_t* verdict_dev, int32_t* cell_dev,
                     int32_t* moves_dev, int32_t* nodes_dev, int32_t* pv_dev, hipStream_t st);
-// the scripted player that uses it (OMOK_OPP_VCF, kind 5): the threat-aware rule with the solver's cell put in after level 2
-void launch_opponent_move_vcf(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions_dev, hipStream_t st);
-void launch_env_scripted_vcf(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int depth, int nodes, int32_t* forced_dev, hipStream_t st);
 void launch_policy(int n, const Store& S, int side, float* pi_dev /*[G][HW]*/, uint8_t* has_dev /*[G]*/, hipStream_t st);
 void launch_env_place(int n, uint8_t* boards_dev, uint8_t* turns_dev, uint16_t* legal_dev, const int32_t* actions_dev, int batch,
                       int32_t* status_dev, hipStream_t st);

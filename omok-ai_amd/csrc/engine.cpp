@@ -814,6 +814,28 @@ extern "C" int omok_evaluate_pv(omok_engine* e, const float* in, int32_t batch, 
 extern "C" int omok_evaluate_logits(omok_engine* e, const float* in, int32_t batch, float* logits, float* vpre) { return evaluate_inputs(e, true, in, batch, logits, vpre); }
 
 // ---- environment -------------------------------------------------------------------------------
+// Caller-held positions onto the device, in the caller's scratch: boards [B][HW] and, where given, turns [B], and a slab of out_words 4-byte words for
+// the call's results.  check_turns: the side to move decides the answer, so a turns byte above 1 is refused before anything is allocated or launched.
+struct DevPositions { uint8_t *boards, *turns; int32_t* out; };
+static int upload_positions(omok_engine* e, Scratch& sc, const char* what, const uint8_t* boards, const uint8_t* turns, int32_t batch, bool check_turns,
+                            size_t out_words, DevPositions& d) {
+    const size_t B = (size_t)batch;
+    for (size_t b = 0; check_turns && b < B; ++b)
+        if (turns[b] > 1) return fail(e, OMOK_ERR_INVALID, "%s: turns[%zu] = %d is neither 0 (Black) nor 1 (White)", what, b, (int)turns[b]);
+    d.boards = sc.get<uint8_t>(B * e->hw);
+    d.turns = turns ? sc.get<uint8_t>(B) : nullptr;
+    d.out = sc.get<int32_t>(out_words);
+    if (sc.failed) return fail(e, OMOK_ERR_HIP, "%s: device allocation failed", what);
+    hipMemcpyAsync(d.boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
+    if (turns) hipMemcpyAsync(d.turns, turns, B, hipMemcpyHostToDevice, e->st);
+    return OMOK_OK;
+}
+// columns i = 0 .. k - 1 of a device slab [k][B] of int32 -> host[i], where that is not NULL
+static void download_columns(omok_engine* e, const int32_t* d_slab, size_t B, int k, int32_t* const* host) {
+    for (int i = 0; i < k; ++i)
+        if (host[i]) hipMemcpyAsync(host[i], d_slab + i * B, B * 4, hipMemcpyDeviceToHost, e->st);
+}
+
 extern "C" int omok_env_play(omok_engine* e, const int32_t* moves, int32_t batch, int32_t len, int32_t* status_out,
                              uint8_t* boards_out, uint8_t* turns_out, uint16_t* legal_out) {
     if (!e || batch < 1 || len < 0 || (len > 0 && !moves)) return OMOK_ERR_INVALID;
@@ -838,13 +860,11 @@ extern "C" int omok_encode_nn_input(omok_engine* e, const uint8_t* boards, const
     if (!e || !boards || !turns || !out || batch < 1 || (mode != 0 && mode != 1)) return OMOK_ERR_INVALID;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     Scratch sc;
-    uint8_t *d_boards = sc.get<uint8_t>((size_t)batch * e->hw), *d_turns = sc.get<uint8_t>((size_t)batch);
-    float* d_out = sc.get<float>((size_t)batch * 3 * e->hw);
-    if (sc.failed) return fail(e, OMOK_ERR_HIP, "encode_nn_input: device allocation failed");
-    hipMemcpyAsync(d_boards, boards, (size_t)batch * e->hw, hipMemcpyHostToDevice, e->st);
-    hipMemcpyAsync(d_turns, turns, (size_t)batch, hipMemcpyHostToDevice, e->st);
-    launch_encode_boards(e->n, d_boards, d_turns, batch, mode, d_out, e->st);
-    hipMemcpyAsync(out, d_out, (size_t)batch * 3 * e->hw * 4, hipMemcpyDeviceToHost, e->st);
+    DevPositions d;
+    const size_t words = (size_t)batch * 3 * e->hw; // (float planes in the 4-byte slab)
+    if (const int rc = upload_positions(e, sc, "encode_nn_input", boards, turns, batch, false, words, d)) return rc;
+    launch_encode_boards(e->n, d.boards, d.turns, batch, mode, (float*)d.out, e->st);
+    hipMemcpyAsync(out, d.out, words * 4, hipMemcpyDeviceToHost, e->st);
     return sync_and_check(e, "encode_nn_input") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
@@ -946,15 +966,13 @@ static const char* verdict_text(int v) {
 // uploads `batch` boards into the caller's scratch and runs k_position_check on them; *d_boards_out (may be NULL) = the device copy
 static int check_positions(omok_engine* e, Scratch& sc, const uint8_t* boards, int batch, int32_t* verdict_out, int32_t* stones_out, uint8_t** d_boards_out) {
     const size_t B = (size_t)batch;
-    uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
-    int32_t* d_out = sc.get<int32_t>(2 * B); // [2][B] verdicts, stone counts
-    if (sc.failed) return fail(e, OMOK_ERR_HIP, "position check: device allocation failed");
-    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
-    launch_position_check(e->n, d_boards, batch, d_out, d_out + B, e->st);
-    hipMemcpyAsync(verdict_out, d_out, B * 4, hipMemcpyDeviceToHost, e->st);
-    if (stones_out) hipMemcpyAsync(stones_out, d_out + B, B * 4, hipMemcpyDeviceToHost, e->st);
+    DevPositions d;
+    if (const int rc = upload_positions(e, sc, "position check", boards, nullptr, batch, false, 2 * B, d)) return rc; // [2][B] verdicts, stone counts
+    launch_position_check(e->n, d.boards, batch, d.out, d.out + B, e->st);
+    int32_t* const host[2] = {verdict_out, stones_out};
+    download_columns(e, d.out, B, 2, host);
     if (sync_and_check(e, "position check")) return OMOK_ERR_HIP;
-    if (d_boards_out) *d_boards_out = d_boards;
+    if (d_boards_out) *d_boards_out = d.boards;
     return OMOK_OK;
 }
 
@@ -1277,10 +1295,7 @@ static void enqueue_sample(omok_engine* e, float temperature, int threshold) {
 // the scripted player's move of every live game (OMOK_OPP_*: the evaluation games further down), staged where the search's sample would be
 static void enqueue_opponent_move(omok_engine* e, int kind) {
     e->prof.begin(PC_PLY, e->st);
-    if (kind == OMOK_OPP_THREAT) launch_opponent_move_threat(e->n, e->S, e->ply & 1, e->key, e->cfg.game_offset, e->d_actions, e->st);
-    else if (kind == OMOK_OPP_VCF)
-        launch_opponent_move_vcf(e->n, e->S, e->ply & 1, e->key, e->cfg.game_offset, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, e->d_actions, e->st);
-    else launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, e->d_actions, e->st);
+    launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, e->d_actions, e->st);
     e->prof.end(e->st);
 }
 
@@ -1547,25 +1562,21 @@ static int check_opponent_kind(omok_engine* e, int kind) {
     return 0;
 }
 
-// the threat-aware rule on caller-held positions (each output may be NULL): the side to move decides, so a turns byte above 1 is refused before
-// anything is launched
-static int env_threat(omok_engine* e, const char* what, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* cell_out,
-                      int32_t* level_out, int32_t* count_out) {
+// the rule of a scripted player on caller-held positions (each output may be NULL).  The threat-aware kinds read the side to move; the naive rule
+// tests a stone of either colour at every empty cell (trainer.rs:518,524-527) and the random one has no forced cell, so neither reads turns: any
+// byte passes there and nothing of it is uploaded
+static int env_scripted(omok_engine* e, const char* what, int kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* cell_out,
+                        int32_t* level_out, int32_t* count_out) {
+    ENTER(e);
     const size_t B = (size_t)batch;
-    for (size_t b = 0; b < B; ++b)
-        if (turns[b] > 1) return fail(e, OMOK_ERR_INVALID, "%s: turns[%zu] = %d is neither 0 (Black) nor 1 (White)", what, b, (int)turns[b]);
-    HIPCHK(e, hipSetDevice(e->cfg.device));
+    const bool sided = kind == OMOK_OPP_THREAT || kind == OMOK_OPP_VCF;
     Scratch sc;
-    uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
-    uint8_t* d_turns = sc.get<uint8_t>(B);
-    int32_t* d_out = sc.get<int32_t>(3 * B);
-    if (sc.failed) return fail(e, OMOK_ERR_HIP, "%s: device allocation failed", what);
-    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
-    hipMemcpyAsync(d_turns, turns, B, hipMemcpyHostToDevice, e->st);
-    launch_env_threat(e->n, d_boards, d_turns, batch, cell_out ? d_out : nullptr, level_out ? d_out + B : nullptr, count_out ? d_out + 2 * B : nullptr, e->st);
-    if (cell_out) hipMemcpyAsync(cell_out, d_out, B * 4, hipMemcpyDeviceToHost, e->st);
-    if (level_out) hipMemcpyAsync(level_out, d_out + B, B * 4, hipMemcpyDeviceToHost, e->st);
-    if (count_out) hipMemcpyAsync(count_out, d_out + 2 * B, B * 4, hipMemcpyDeviceToHost, e->st);
+    DevPositions d;
+    if (const int rc = upload_positions(e, sc, what, boards, sided ? turns : nullptr, batch, sided, 3 * B, d)) return rc;
+    int32_t* const host[3] = {cell_out, level_out, count_out};
+    launch_env_scripted(e->n, kind, d.boards, d.turns, batch, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, host[0] ? d.out : nullptr, host[1] ? d.out + B : nullptr,
+                        host[2] ? d.out + 2 * B : nullptr, e->st);
+    download_columns(e, d.out, B, 3, host);
     return sync_and_check(e, what) ? OMOK_ERR_HIP : OMOK_OK;
 }
 
@@ -1573,7 +1584,7 @@ static int env_threat(omok_engine* e, const char* what, const uint8_t* boards, c
 extern "C" int omok_env_threat_scan(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* cell_out, int32_t* level_out,
                                     int32_t* count_out) {
     if (!e || !boards || !turns || batch < 1) return OMOK_ERR_INVALID;
-    return env_threat(e, "env_threat_scan", boards, turns, batch, cell_out, level_out, count_out);
+    return env_scripted(e, "env_threat_scan", OMOK_OPP_THREAT, boards, turns, batch, cell_out, level_out, count_out);
 }
 
 // does the side to move have a forced win by continuous fours?  (the rule: include/omok_mi355x.h; each output may be NULL)
@@ -1582,58 +1593,25 @@ extern "C" int omok_env_vcf_solve(omok_engine* e, const uint8_t* boards, const u
     if (!e || !boards || !turns || batch < 1) return OMOK_ERR_INVALID;
     if (max_depth < 1 || max_depth > 16) return fail(e, OMOK_ERR_INVALID, "env_vcf_solve: max_depth %d outside 1..16", max_depth);
     if (max_nodes < 1 || max_nodes > 65536) return fail(e, OMOK_ERR_INVALID, "env_vcf_solve: max_nodes %d outside 1..65536", max_nodes);
+    ENTER(e);
     const size_t B = (size_t)batch, len = (size_t)(2 * max_depth - 1);
-    for (size_t b = 0; b < B; ++b)
-        if (turns[b] > 1) return fail(e, OMOK_ERR_INVALID, "env_vcf_solve: turns[%zu] = %d is neither 0 (Black) nor 1 (White)", b, (int)turns[b]);
-    HIPCHK(e, hipSetDevice(e->cfg.device));
     Scratch sc;
-    uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
-    uint8_t* d_turns = sc.get<uint8_t>(B);
-    int32_t* d_out = sc.get<int32_t>((4 + len) * B);
-    if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_vcf_solve: device allocation failed");
-    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
-    hipMemcpyAsync(d_turns, turns, B, hipMemcpyHostToDevice, e->st);
-    int32_t* host[4] = {verdict_out, cell_out, moves_out, nodes_out};
-    launch_env_vcf(e->n, d_boards, d_turns, batch, max_depth, max_nodes, host[0] ? d_out : nullptr, host[1] ? d_out + B : nullptr,
-                   host[2] ? d_out + 2 * B : nullptr, host[3] ? d_out + 3 * B : nullptr, pv_out ? d_out + 4 * B : nullptr, e->st);
-    for (int i = 0; i < 4; ++i)
-        if (host[i]) hipMemcpyAsync(host[i], d_out + i * B, B * 4, hipMemcpyDeviceToHost, e->st);
-    if (pv_out) hipMemcpyAsync(pv_out, d_out + 4 * B, len * B * 4, hipMemcpyDeviceToHost, e->st);
+    DevPositions d;
+    if (const int rc = upload_positions(e, sc, "env_vcf_solve", boards, turns, batch, true, (4 + len) * B, d)) return rc;
+    int32_t* const host[4] = {verdict_out, cell_out, moves_out, nodes_out};
+    launch_env_vcf(e->n, d.boards, d.turns, batch, max_depth, max_nodes, host[0] ? d.out : nullptr, host[1] ? d.out + B : nullptr,
+                   host[2] ? d.out + 2 * B : nullptr, host[3] ? d.out + 3 * B : nullptr, pv_out ? d.out + 4 * B : nullptr, e->st);
+    download_columns(e, d.out, B, 4, host);
+    if (pv_out) hipMemcpyAsync(pv_out, d.out + 4 * B, len * B * 4, hipMemcpyDeviceToHost, e->st);
     return sync_and_check(e, "env_vcf_solve") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
-// the forced part of the naive player's rule (trainer.rs:514-531, rules of environment/src/lib.rs:104-190) on caller-held positions
+// the cell a scripted player's rule is forced to (-1 where it would draw) on caller-held positions: for the naive player the forced part of
+// trainer.rs:514-531 under the rules of environment/src/lib.rs:104-190
 extern "C" int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out) {
     if (!e || !boards || !turns || !forced_out || batch < 1) return OMOK_ERR_INVALID;
     if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
-    if (kind == OMOK_OPP_THREAT) return env_threat(e, "env_scripted_actions", boards, turns, batch, forced_out, nullptr, nullptr); // (this rule does read turns)
-    if (kind == OMOK_OPP_VCF) { // (reads turns too: the same check, the same copies, the rule with the solver's level)
-        const size_t B = (size_t)batch;
-        for (size_t b = 0; b < B; ++b)
-            if (turns[b] > 1) return fail(e, OMOK_ERR_INVALID, "env_scripted_actions: turns[%zu] = %d is neither 0 (Black) nor 1 (White)", b, (int)turns[b]);
-        HIPCHK(e, hipSetDevice(e->cfg.device));
-        Scratch sc;
-        uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
-        uint8_t* d_turns = sc.get<uint8_t>(B);
-        int32_t* d_forced = sc.get<int32_t>(B);
-        if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_scripted_actions: device allocation failed");
-        hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
-        hipMemcpyAsync(d_turns, turns, B, hipMemcpyHostToDevice, e->st);
-        launch_env_scripted_vcf(e->n, d_boards, d_turns, batch, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, d_forced, e->st);
-        hipMemcpyAsync(forced_out, d_forced, B * 4, hipMemcpyDeviceToHost, e->st);
-        return sync_and_check(e, "env_scripted_actions") ? OMOK_ERR_HIP : OMOK_OK;
-    }
-    ENTER(e);
-    // (the rule tests a stone of either colour at every empty cell, trainer.rs:518,524-527: the answer does not depend on the side to move)
-    const size_t B = (size_t)batch;
-    Scratch sc;
-    uint8_t* d_boards = sc.get<uint8_t>(B * e->hw);
-    int32_t* d_forced = sc.get<int32_t>(B);
-    if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_scripted_actions: device allocation failed");
-    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
-    launch_env_scripted(e->n, d_boards, kind, batch, d_forced, e->st);
-    hipMemcpyAsync(forced_out, d_forced, B * 4, hipMemcpyDeviceToHost, e->st);
-    return sync_and_check(e, "env_scripted_actions") ? OMOK_ERR_HIP : OMOK_OK;
+    return env_scripted(e, "env_scripted_actions", kind, boards, turns, batch, forced_out, nullptr, nullptr);
 }
 
 // the scripted player's move of every live game (trainer.rs:508-534 naive, :452-455 random), staged like omok_set_actions
@@ -1730,17 +1708,15 @@ extern "C" int omok_env_place_stone(omok_engine* e, uint8_t* boards, uint8_t* tu
     ENTER(e);
     const size_t B = (size_t)batch;
     Scratch sc;
-    uint8_t *d_boards = sc.get<uint8_t>(B * e->hw), *d_turns = sc.get<uint8_t>(B);
-    uint16_t* d_legal = sc.get<uint16_t>(B);
-    int32_t *d_act = sc.get<int32_t>(B), *d_status = sc.get<int32_t>(B);
-    if (sc.failed) return fail(e, OMOK_ERR_HIP, "env_place_stone: device allocation failed");
-    hipMemcpyAsync(d_boards, boards, B * e->hw, hipMemcpyHostToDevice, e->st);
-    hipMemcpyAsync(d_turns, turns, B, hipMemcpyHostToDevice, e->st);
+    DevPositions d;
+    if (const int rc = upload_positions(e, sc, "env_place_stone", boards, turns, batch, false, 3 * B, d)) return rc; // the slab: actions, status, legal (2 B each)
+    int32_t *d_act = d.out, *d_status = d.out + B;
+    uint16_t* d_legal = (uint16_t*)(d.out + 2 * B);
     hipMemcpyAsync(d_legal, legal, B * 2, hipMemcpyHostToDevice, e->st);
     hipMemcpyAsync(d_act, actions, B * 4, hipMemcpyHostToDevice, e->st);
-    launch_env_place(e->n, d_boards, d_turns, d_legal, d_act, batch, d_status, e->st);
-    hipMemcpyAsync(boards, d_boards, B * e->hw, hipMemcpyDeviceToHost, e->st);
-    hipMemcpyAsync(turns, d_turns, B, hipMemcpyDeviceToHost, e->st);
+    launch_env_place(e->n, d.boards, d.turns, d_legal, d_act, batch, d_status, e->st);
+    hipMemcpyAsync(boards, d.boards, B * e->hw, hipMemcpyDeviceToHost, e->st);
+    hipMemcpyAsync(turns, d.turns, B, hipMemcpyDeviceToHost, e->st);
     hipMemcpyAsync(legal, d_legal, B * 2, hipMemcpyDeviceToHost, e->st);
     hipMemcpyAsync(status_out, d_status, B * 4, hipMemcpyDeviceToHost, e->st);
     return sync_and_check(e, "env_place_stone") ? OMOK_ERR_HIP : OMOK_OK;

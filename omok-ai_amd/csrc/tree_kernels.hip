@@ -18,6 +18,7 @@
 // computed uniformly by all lanes and stored by lane 0.  A __syncthreads() (single-wave
 // workgroup: a fence + waitcnt) separates global stores from later cross-lane loads.
 #include "common.h"
+#include "../../include/omok_mi355x.h" // OMOK_OPP_*: the scripted players' kinds
 #include <type_traits>
 
 namespace omok {
@@ -667,6 +668,34 @@ __device__ inline bool five_in_pair(const uint64_t* own, int a, int pr) {
         run_b += on_b ? 1 : 0;
     }
     return 1 + run_a + run_b == 5;
+}
+// Position b of boards [B][HW] Stone bytes -> bb = black NW | white NW words, one ballot per colour and 64 cells: all 64 lanes call, bb and the result
+// are wave-uniform.  A byte other than 1 (Black) and 2 (White) counts as empty.  Returns the number of stones.
+template <int N>
+__device__ inline int load_position(const uint8_t* boards, int b, uint64_t* bb) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW;
+    const int lane = LANE;
+    int stones = 0;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
+        bb[j] = __ballot(s == 1);
+        bb[NW + j] = __ballot(s == 2);
+        stones += __popcll(bb[j]) + __popcll(bb[NW + j]);
+    }
+    return stones;
+}
+// the same words from the root board of a live game's tree of `side`; returns the number of stones
+template <int N>
+__device__ inline int load_root_board(const Store& S, int side, int g, uint64_t* bb) {
+    constexpr int NW = Geo<N>::NW;
+    const uint64_t* root = S.board + (size_t)(side * S.games + g) * (size_t)S.stride_nodes * (2 * NW); // root = node 0
+    int stones = 0;
+#pragma unroll
+    for (int i = 0; i < 2 * NW; ++i) { bb[i] = root[i]; stones += __popcll(bb[i]); }
+    return stones;
 }
 // index of the r-th (0-based) set bit of w, r < popcount(w); per lane (w and r may differ between lanes)
 __device__ inline int nth_set_bit_lane(uint64_t w, int r) {
@@ -1735,7 +1764,7 @@ __global__ __launch_bounds__(64) void k_reset_from(Store S, const uint8_t* __res
     uint64_t bb[2 * NW];
     int stones = 0;
 #pragma unroll
-    for (int j = 0; j < G::IT; ++j) {
+    for (int j = 0; j < G::IT; ++j) { // (load_position's loop, kept here: through the shared function the kernel's code came out two instructions longer)
         const int a = j * 64 + lane;
         const int s = a < G::HW ? boards[(size_t)g * G::HW + a] : 0;
         bb[j] = __ballot(s == 1);
@@ -2100,54 +2129,6 @@ __device__ inline int scripted_random_cell(const uint64_t* bb, int legal, uint32
     return action;
 }
 
-// k_opponent_move: the scripted player's move for the side to move of every live game, staged like k_set_actions (an external
-// move: nothing is recorded, both trees get ensure_action_exists in k_advance).  kind 1 = naive (forced cell, else random),
-// 0 = random.  Workgroup = one wave = one game; reads the root board of the side-to-move tree only.
-template <int N>
-__global__ __launch_bounds__(64) void k_opponent_move(Store S, int side, int kind, uint64_t seed, int64_t game_offset, int32_t* __restrict__ actions) {
-    using G = Geo<N>;
-    constexpr int NW = G::NW;
-    const int g = blockIdx.x;
-    const int lane = LANE;
-    const GameState gs = S.gs[g];
-    if (!gs.alive) {
-        if (lane == 0) { actions[g] = -1; S.gs[g].last_action = -1; S.gs[g].external = 1; }
-        return;
-    }
-    const uint64_t* root = S.board + (size_t)(side * S.games + g) * (size_t)S.stride_nodes * (2 * NW); // root = node 0
-    uint64_t bb[2 * NW];
-    int legal = G::HW;
-#pragma unroll
-    for (int i = 0; i < 2 * NW; ++i) { bb[i] = root[i]; legal -= __popcll(bb[i]); }
-    int action = kind == 1 ? scripted_forced_cell<N>(bb, legal) : -1;
-    if (action < 0) {
-        const U4 o = philox(seed, 0u, (uint32_t)gs.plies, (uint32_t)((game_offset + gs.gid) * 2 + side), RNG_OPPONENT); // (the game's own ply and id, as k_sample)
-        action = scripted_random_cell<N>(bb, legal, o.x);
-    }
-    if (lane == 0) { actions[g] = action; S.gs[g].last_action = action; S.gs[g].external = 1; }
-}
-
-// the forced part of the rule on caller-held positions: boards [B][HW] Stone bytes -> forced [B] (-1: none; always -1 for kind 0)
-template <int N>
-__global__ __launch_bounds__(64) void k_env_scripted(const uint8_t* __restrict__ boards, int kind, int32_t* __restrict__ forced) {
-    using G = Geo<N>;
-    constexpr int NW = G::NW;
-    const int b = blockIdx.x;
-    const int lane = LANE;
-    uint64_t bb[2 * NW];
-    int legal = G::HW;
-#pragma unroll
-    for (int j = 0; j < G::IT; ++j) {
-        const int a = j * 64 + lane;
-        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
-        bb[j] = __ballot(s == 1);
-        bb[NW + j] = __ballot(s == 2);
-        legal -= __popcll(bb[j]) + __popcll(bb[NW + j]);
-    }
-    const int cell = kind == 1 ? scripted_forced_cell<N>(bb, legal) : -1;
-    if (lane == 0) forced[b] = cell;
-}
-
 // ---------------------------------------------------------------------------------------------
 // The threat-aware scripted player (OMOK_OPP_THREAT; the rule is spelled out in include/omok_mi355x.h).  Not a player of the reference:
 // it is defined by the reference's exact-five test (five_in_pair above) alone.  Per lane one empty cell a; along each of the four line
@@ -2274,57 +2255,6 @@ __device__ inline int scripted_threat_cell(const uint64_t* bb, int legal, int me
         }
     }
     return action;
-}
-
-// k_opponent_move for OMOK_OPP_THREAT: the same load of the root board, the same draw and the same staging
-template <int N>
-__global__ __launch_bounds__(64) void k_opponent_move_threat(Store S, int side, uint64_t seed, int64_t game_offset, int32_t* __restrict__ actions) {
-    using G = Geo<N>;
-    constexpr int NW = G::NW;
-    const int g = blockIdx.x;
-    const int lane = LANE;
-    const GameState gs = S.gs[g];
-    if (!gs.alive) {
-        if (lane == 0) { actions[g] = -1; S.gs[g].last_action = -1; S.gs[g].external = 1; }
-        return;
-    }
-    const uint64_t* root = S.board + (size_t)(side * S.games + g) * (size_t)S.stride_nodes * (2 * NW); // root = node 0
-    uint64_t bb[2 * NW];
-    int legal = G::HW;
-#pragma unroll
-    for (int i = 0; i < 2 * NW; ++i) { bb[i] = root[i]; legal -= __popcll(bb[i]); }
-    const U4 o = philox(seed, 0u, (uint32_t)gs.plies, (uint32_t)((game_offset + gs.gid) * 2 + side), RNG_OPPONENT); // k_opponent_move's word
-    int level, count;
-    const int action = scripted_threat_cell<N>(bb, legal, side, o.x, level, count);
-    if (lane == 0) { actions[g] = action; S.gs[g].last_action = action; S.gs[g].external = 1; }
-}
-
-// the rule on caller-held positions: boards [B][HW] Stone bytes (any other byte counts as empty, as in k_env_scripted), turns [B] (0 / 1,
-// checked by the host) -> cell [B] (levels 1..5, else -1), level [B], count [B]; each output may be NULL
-template <int N>
-__global__ __launch_bounds__(64) void k_env_threat(const uint8_t* __restrict__ boards, const uint8_t* __restrict__ turns, int32_t* __restrict__ cell_out,
-                                                   int32_t* __restrict__ level_out, int32_t* __restrict__ count_out) {
-    using G = Geo<N>;
-    constexpr int NW = G::NW;
-    const int b = blockIdx.x;
-    const int lane = LANE;
-    uint64_t bb[2 * NW];
-    int legal = G::HW;
-#pragma unroll
-    for (int j = 0; j < G::IT; ++j) {
-        const int a = j * 64 + lane;
-        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
-        bb[j] = __ballot(s == 1);
-        bb[NW + j] = __ballot(s == 2);
-        legal -= __popcll(bb[j]) + __popcll(bb[NW + j]);
-    }
-    int level, count;
-    const int cell = scripted_threat_cell<N>(bb, legal, turns[b] & 1, 0u, level, count);
-    if (lane == 0) {
-        if (cell_out) cell_out[b] = level >= 1 && level <= 5 ? cell : -1;
-        if (level_out) level_out[b] = level;
-        if (count_out) count_out[b] = count;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2487,7 +2417,7 @@ __global__ __launch_bounds__(64) void k_env_vcf(const uint8_t* __restrict__ boar
     const int lane = LANE;
     uint64_t bb[2 * NW];
 #pragma unroll
-    for (int j = 0; j < G::IT; ++j) {
+    for (int j = 0; j < G::IT; ++j) { // (load_position's loop, kept here: through the shared function the compiler lays this kernel's code out differently)
         const int a = j * 64 + lane;
         const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
         bb[j] = __ballot(s == 1);
@@ -2510,8 +2440,8 @@ __global__ __launch_bounds__(64) void k_env_vcf(const uint8_t* __restrict__ boar
 // D attacker moves and NB nodes (OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES: the host passes them) is played at its first cell.  solved: that
 // level decided.
 template <int N>
-__device__ inline int scripted_vcf_cell(uint64_t* bb, int legal, int me, uint32_t x0, int D, int NB, int& level, bool& solved, VcfLevel<N>* stk, int* pv) {
-    int count;
+__device__ inline int scripted_vcf_cell(uint64_t* bb, int legal, int me, uint32_t x0, int D, int NB, int& level, int& count, bool& solved, VcfLevel<N>* stk,
+                                        int* pv) {
     const int cell = scripted_threat_cell<N>(bb, legal, me, x0, level, count);
     solved = false;
     if (level < 3) return cell; // (0: no empty cell)
@@ -2520,55 +2450,84 @@ __device__ inline int scripted_vcf_cell(uint64_t* bb, int legal, int me, uint32_
     return solved ? r.cell : cell;
 }
 
-// k_opponent_move for OMOK_OPP_VCF: the same load of the root board, the same draw and the same staging as k_opponent_move_threat
-template <int N>
-__global__ __launch_bounds__(64) void k_opponent_move_vcf(Store S, int side, uint64_t seed, int64_t game_offset, int D, int NB, int32_t* __restrict__ actions) {
-    using G = Geo<N>;
-    constexpr int NW = G::NW;
-    __shared__ VcfLevel<N> stk[VCF_MAX_DEPTH];
-    __shared__ int pv[2 * VCF_MAX_DEPTH - 1];
-    const int g = blockIdx.x;
-    const int lane = LANE;
-    const GameState gs = S.gs[g];
-    if (!gs.alive) {
-        if (lane == 0) { actions[g] = -1; S.gs[g].last_action = -1; S.gs[g].external = 1; }
-        return;
+// ---------------------------------------------------------------------------------------------
+// The four players behind one entry: the move of player KIND (OMOK_OPP_*) for the side `me` on bb, `legal` empty cells, x0 = the game's draw.
+// level / count: the threat-aware rule's; the naive player reports its forced cell as level 1 and either draw over all empty cells as level 7,
+// count = legal (level 0: no empty cell).  solved: the solver decided (OMOK_OPP_VCF alone, which alone uses D, NB and the LDS stack stk / pv).
+// ---------------------------------------------------------------------------------------------
+struct ScriptedMove { int cell, level, count; bool solved; };
+template <int N, int KIND>
+__device__ inline ScriptedMove scripted_move(uint64_t* bb, int legal, int me, uint32_t x0, int D, int NB, VcfLevel<N>* stk, int* pv) {
+    static_assert(KIND == OMOK_OPP_RANDOM || KIND == OMOK_OPP_NAIVE || KIND == OMOK_OPP_THREAT || KIND == OMOK_OPP_VCF, "unknown scripted player");
+    ScriptedMove m{-1, 0, 0, false};
+    if constexpr (KIND == OMOK_OPP_THREAT) m.cell = scripted_threat_cell<N>(bb, legal, me, x0, m.level, m.count);
+    else if constexpr (KIND == OMOK_OPP_VCF) m.cell = scripted_vcf_cell<N>(bb, legal, me, x0, D, NB, m.level, m.count, m.solved, stk, pv);
+    else {
+        if (KIND == OMOK_OPP_NAIVE) m.cell = scripted_forced_cell<N>(bb, legal);
+        if (m.cell >= 0) m.level = 1;
+        else if (legal > 0) {
+            m.level = 7;
+            m.count = legal;
+            m.cell = scripted_random_cell<N>(bb, legal, x0);
+        }
     }
-    const uint64_t* root = S.board + (size_t)(side * S.games + g) * (size_t)S.stride_nodes * (2 * NW); // root = node 0
-    uint64_t bb[2 * NW];
-    int legal = G::HW;
-#pragma unroll
-    for (int i = 0; i < 2 * NW; ++i) { bb[i] = root[i]; legal -= __popcll(bb[i]); }
-    const U4 o = philox(seed, 0u, (uint32_t)gs.plies, (uint32_t)((game_offset + gs.gid) * 2 + side), RNG_OPPONENT); // k_opponent_move's word
-    int level;
-    bool solved;
-    const int action = scripted_vcf_cell<N>(bb, legal, side, o.x, D, NB, level, solved, stk, pv);
-    if (lane == 0) { actions[g] = action; S.gs[g].last_action = action; S.gs[g].external = 1; }
+    return m;
+}
+// the solver's depth-first stack in LDS: only a kernel's OMOK_OPP_VCF instantiation holds it, the other three get no LDS at all
+template <int N, int KIND>
+__device__ inline void scripted_lds(VcfLevel<N>*& stk, int*& pv) {
+    stk = nullptr;
+    pv = nullptr;
+    if constexpr (KIND == OMOK_OPP_VCF) {
+        __shared__ VcfLevel<N> s_stk[VCF_MAX_DEPTH];
+        __shared__ int s_pv[2 * VCF_MAX_DEPTH - 1];
+        stk = s_stk;
+        pv = s_pv;
+    }
 }
 
-// the same rule on caller-held positions -> forced [B]: the cell of levels 1..5 or the solver's, else -1
-template <int N>
-__global__ __launch_bounds__(64) void k_env_scripted_vcf(const uint8_t* __restrict__ boards, const uint8_t* __restrict__ turns, int D, int NB, int32_t* __restrict__ forced) {
-    using G = Geo<N>;
-    constexpr int NW = G::NW;
-    __shared__ VcfLevel<N> stk[VCF_MAX_DEPTH];
-    __shared__ int pv[2 * VCF_MAX_DEPTH - 1];
-    const int b = blockIdx.x;
-    const int lane = LANE;
-    uint64_t bb[2 * NW];
-    int legal = G::HW;
-#pragma unroll
-    for (int j = 0; j < G::IT; ++j) {
-        const int a = j * 64 + lane;
-        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
-        bb[j] = __ballot(s == 1);
-        bb[NW + j] = __ballot(s == 2);
-        legal -= __popcll(bb[j]) + __popcll(bb[NW + j]);
+// k_opponent_move: the move of scripted player KIND for the side to move of every live game, staged like k_set_actions (an external move:
+// nothing is recorded, both trees get ensure_action_exists in k_advance) and copied to actions [G] (-1: finished game).  x0 = word 0 of
+// Philox(seed, 0, the game's own ply, 2 id + side, RNG_OPPONENT), as k_sample keys its draw.  Workgroup = one wave = one game; reads the root
+// board of the side-to-move tree only.  D, NB: OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES (the host passes them).
+template <int N, int KIND>
+__global__ __launch_bounds__(64) void k_opponent_move(Store S, int side, uint64_t seed, int64_t game_offset, int D, int NB, int32_t* __restrict__ actions) {
+    constexpr int NW = Geo<N>::NW;
+    VcfLevel<N>* stk;
+    int* pv;
+    scripted_lds<N, KIND>(stk, pv);
+    const int g = blockIdx.x;
+    const GameState gs = S.gs[g];
+    int action = -1;
+    if (gs.alive) {
+        uint64_t bb[2 * NW];
+        const int legal = Geo<N>::HW - load_root_board<N>(S, side, g, bb);
+        const U4 o = philox(seed, 0u, (uint32_t)gs.plies, (uint32_t)((game_offset + gs.gid) * 2 + side), RNG_OPPONENT);
+        action = scripted_move<N, KIND>(bb, legal, side, o.x, D, NB, stk, pv).cell;
     }
-    int level;
-    bool solved;
-    const int cell = scripted_vcf_cell<N>(bb, legal, turns[b] & 1, 0u, D, NB, level, solved, stk, pv);
-    if (lane == 0) forced[b] = solved || (level >= 1 && level <= 5) ? cell : -1;
+    if (LANE == 0) { actions[g] = action; S.gs[g].last_action = action; S.gs[g].external = 1; }
+}
+
+// the same rule on caller-held positions, x0 = 0: boards [B][HW] Stone bytes, turns [B] (0 / 1, checked by the host; read by OMOK_OPP_THREAT
+// and OMOK_OPP_VCF alone, the other two test a stone of either colour) -> cell [B]: the cell the rule is forced to -- the solver's, or that of
+// levels 1..5 -- else -1 where it would draw; level [B], count [B]; each output may be NULL
+template <int N, int KIND>
+__global__ __launch_bounds__(64) void k_env_scripted(const uint8_t* __restrict__ boards, const uint8_t* __restrict__ turns, int D, int NB,
+                                                     int32_t* __restrict__ cell_out, int32_t* __restrict__ level_out, int32_t* __restrict__ count_out) {
+    constexpr int NW = Geo<N>::NW;
+    VcfLevel<N>* stk;
+    int* pv;
+    scripted_lds<N, KIND>(stk, pv);
+    const int b = blockIdx.x;
+    uint64_t bb[2 * NW];
+    const int legal = Geo<N>::HW - load_position<N>(boards, b, bb);
+    const int me = KIND == OMOK_OPP_THREAT || KIND == OMOK_OPP_VCF ? turns[b] & 1 : 0;
+    const ScriptedMove m = scripted_move<N, KIND>(bb, legal, me, 0u, D, NB, stk, pv);
+    if (LANE == 0) {
+        if (cell_out) cell_out[b] = m.solved || (m.level >= 1 && m.level <= 5) ? m.cell : -1;
+        if (level_out) level_out[b] = m.level;
+        if (count_out) count_out[b] = m.count;
+    }
 }
 
 // k_position_check: is a caller-supplied board a position an alternating game from Environment::new() can be in, and still in progress?
@@ -2586,7 +2545,7 @@ __global__ __launch_bounds__(64) void k_position_check(const uint8_t* __restrict
     int nb = 0, nwh = 0;
     bool bad = false, won = false;
 #pragma unroll
-    for (int j = 0; j < G::IT; ++j) {
+    for (int j = 0; j < G::IT; ++j) { // (load_position's loop with the colours counted apart and the test for a byte that is no Stone)
         const int a = j * 64 + lane;
         const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
         bb[j] = __ballot(s == 1);
@@ -3129,13 +3088,7 @@ __global__ __launch_bounds__(64) void k_env_place(uint8_t* __restrict__ boards, 
     const int b = blockIdx.x;
     const int lane = LANE;
     uint64_t bb[2 * NW];
-#pragma unroll
-    for (int j = 0; j < G::IT; ++j) {
-        const int a = j * 64 + lane;
-        const int s = a < G::HW ? boards[(size_t)b * G::HW + a] : 0;
-        bb[j] = __ballot(s == 1);
-        bb[NW + j] = __ballot(s == 2);
-    }
+    load_position<N>(boards, b, bb);
     const int turn = turns[b] & 1, lg = legal[b];
     const int a = actions[b];
     int st = -1;
@@ -3535,32 +3488,35 @@ void launch_set_actions(int n, const Store& S, int side, const int32_t* actions,
     DISPATCH_N(n, (k_set_actions<9><<<grid, 256, 0, st>>>(S, side, actions, flags)), (k_set_actions<15><<<grid, 256, 0, st>>>(S, side, actions, flags)));
 }
 void launch_clear_actions(const Store& S, hipStream_t st) { k_clear_actions<<<(S.games + 255) / 256, 256, 0, st>>>(S); }
-void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int32_t* actions, hipStream_t st) {
-    DISPATCH_N(n, (k_opponent_move<9><<<S.games, 64, 0, st>>>(S, side, kind, seed, game_offset, actions)),
-               (k_opponent_move<15><<<S.games, 64, 0, st>>>(S, side, kind, seed, game_offset, actions)));
+// f(std::integral_constant<int, kind>()): `kind` (one of OMOK_OPP_*: the host checked it) as the template argument of the scripted kernels
+template <typename F>
+static void dispatch_kind(int kind, F f) {
+    switch (kind) {
+    case OMOK_OPP_RANDOM: f(std::integral_constant<int, OMOK_OPP_RANDOM>()); break;
+    case OMOK_OPP_NAIVE: f(std::integral_constant<int, OMOK_OPP_NAIVE>()); break;
+    case OMOK_OPP_THREAT: f(std::integral_constant<int, OMOK_OPP_THREAT>()); break;
+    case OMOK_OPP_VCF: f(std::integral_constant<int, OMOK_OPP_VCF>()); break;
+    }
 }
-void launch_env_scripted(int n, const uint8_t* boards, int kind, int batch, int32_t* forced, hipStream_t st) {
-    DISPATCH_N(n, (k_env_scripted<9><<<batch, 64, 0, st>>>(boards, kind, forced)), (k_env_scripted<15><<<batch, 64, 0, st>>>(boards, kind, forced)));
+void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions, hipStream_t st) {
+    dispatch_kind(kind, [&](auto k) {
+        constexpr int KIND = decltype(k)::value;
+        DISPATCH_N(n, (k_opponent_move<9, KIND><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, depth, nodes, actions)),
+                   (k_opponent_move<15, KIND><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, depth, nodes, actions)));
+    });
 }
-void launch_opponent_move_threat(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int32_t* actions, hipStream_t st) {
-    DISPATCH_N(n, (k_opponent_move_threat<9><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, actions)),
-               (k_opponent_move_threat<15><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, actions)));
-}
-void launch_env_threat(int n, const uint8_t* boards, const uint8_t* turns, int batch, int32_t* cell, int32_t* level, int32_t* count, hipStream_t st) {
-    DISPATCH_N(n, (k_env_threat<9><<<batch, 64, 0, st>>>(boards, turns, cell, level, count)), (k_env_threat<15><<<batch, 64, 0, st>>>(boards, turns, cell, level, count)));
+void launch_env_scripted(int n, int kind, const uint8_t* boards, const uint8_t* turns, int batch, int depth, int nodes, int32_t* cell, int32_t* level,
+                         int32_t* count, hipStream_t st) {
+    dispatch_kind(kind, [&](auto k) {
+        constexpr int KIND = decltype(k)::value;
+        DISPATCH_N(n, (k_env_scripted<9, KIND><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, cell, level, count)),
+                   (k_env_scripted<15, KIND><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, cell, level, count)));
+    });
 }
 void launch_env_vcf(int n, const uint8_t* boards, const uint8_t* turns, int batch, int depth, int nodes, int32_t* verdict, int32_t* cell, int32_t* moves,
                     int32_t* count, int32_t* pv, hipStream_t st) {
     DISPATCH_N(n, (k_env_vcf<9><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, verdict, cell, moves, count, pv)),
                (k_env_vcf<15><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, verdict, cell, moves, count, pv)));
-}
-void launch_opponent_move_vcf(int n, const Store& S, int side, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions, hipStream_t st) {
-    DISPATCH_N(n, (k_opponent_move_vcf<9><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, depth, nodes, actions)),
-               (k_opponent_move_vcf<15><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, depth, nodes, actions)));
-}
-void launch_env_scripted_vcf(int n, const uint8_t* boards, const uint8_t* turns, int batch, int depth, int nodes, int32_t* forced, hipStream_t st) {
-    DISPATCH_N(n, (k_env_scripted_vcf<9><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, forced)),
-               (k_env_scripted_vcf<15><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, forced)));
 }
 void launch_policy(int n, const Store& S, int side, float* pi, uint8_t* has, hipStream_t st) {
     DISPATCH_N(n, (k_policy<9><<<S.games, 64, 0, st>>>(S, side, pi, has)), (k_policy<15><<<S.games, 64, 0, st>>>(S, side, pi, has)));

@@ -5,7 +5,7 @@ a self-play episode on the same engine, at the configs[1] size.
 Default: 4096 concurrent 15x15 games, 800 simulations per move of the net, K = 16, the naive player as Black (opponent_side = 0), a random-init
 net.  A few untimed self-play plies warm clocks and code objects, then one timed versus episode and one timed self-play episode run on fresh RNG
 streams.  Prints one JSON line: games/s and game-plies/s of both, the result counts by colour.  `--plies P` stops both episodes after P plies
-(the workload of a rocprofv3 --kernel-trace --stats pass: k_opponent_move / k_opponent_move_threat / k_opponent_move_vcf beside k_sample / k_mirror_scan /
+(the workload of a rocprofv3 --kernel-trace --stats pass: k_opponent_move<N, KIND>, one instantiation per scripted player, beside k_sample / k_mirror_scan /
 k_advance).  `--scripted-vs KIND2` adds one episode without any search: `--kind` as Black against KIND2 as White, both moving through
 omok_opponent_actions (the strength of one scripted player against another; its counts by colour land under "scripted").
 
