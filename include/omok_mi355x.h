@@ -374,6 +374,43 @@ int omok_env_threat_scan(omok_engine* e, const uint8_t* boards, const uint8_t* t
  * can run; it is a condition of the call, not a tuned value.) */
 int omok_env_vcf_solve(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t max_depth, int32_t max_nodes,
                        int32_t* verdict_out, int32_t* cell_out, int32_t* moves_out, int32_t* nodes_out, int32_t* pv_out);
+/* The defender's half: which moves of the side to move do not lose to the other side's win by continuous fours?  As exact as the solver:
+ * solve(X, c, D, NB) below is the rule of omok_env_vcf_solve above for the side c on the position X, unchanged -- iterative deepening, one node
+ * counter per call, the same candidate order.  For a position X (a byte other than 1 or 2 counts as empty), `me` the side to move, `opp` the
+ * other, max_depth D in 1..16, max_nodes NB in 1..65536:
+ *   the null move:   R0 = solve(X, opp, D, NB): would opp win by continuous fours if me passed?  threat = (R0.verdict, R0.moves, R0.cell)
+ *   every cell a, each with a node counter of its own:
+ *       a is occupied:      status OMOK_VCFD_OCCUPIED, moves 0, nodes 0, reply -1
+ *       FIVE(me,a):         status OMOK_VCFD_WINS, moves 0, nodes 0, reply -1; no solve is made
+ *       otherwise           R = solve(X with me at a, opp, D, NB):
+ *           R.verdict 0     status OMOK_VCFD_SAFE
+ *           R.verdict 1     status OMOK_VCFD_LOSES
+ *           R.verdict -1    status OMOK_VCFD_UNKNOWN
+ *                           moves = R.moves, nodes = R.nodes, reply = R.cell
+ *   - The last empty cell needs no special case: on the full board solve counts one node per depth and returns verdict 0, so the status is
+ *     OMOK_VCFD_SAFE with nodes = D, or OMOK_VCFD_UNKNOWN where NB < D.
+ *   - A four of the mover's at a needs none either: it is the solver's own |Fo| == 1 branch, where opp must answer it with a move that is
+ *     itself a four.  Such a move may merely postpone the loss; the status says which.
+ *   - The map is NOT monotone: opp may have no win if me passes and yet have one after a stone of me's.  Under the exact-five rule a mover's
+ *     stone can turn its own completing cell into a six, which removes the counter-threat that held the attack off.  So no cell is skipped
+ *     because the null move is safe, and every cell is solved on its own.
+ * boards [B][N*N] Stone bytes, turns [B] = the side to move (0 Black / 1 White).  Per position:
+ *   status_out  [B][N*N] OMOK_VCFD_*
+ *   moves_out   [B][N*N] opp's attacker moves up to and including the five after me at a; 0 unless the status is OMOK_VCFD_LOSES
+ *   nodes_out   [B][N*N] the nodes that cell's solve counted; NB on OMOK_VCFD_UNKNOWN
+ *   reply_out   [B][N*N] opp's first move of that win; -1 unless the status is OMOK_VCFD_LOSES
+ *   threat_out  [B][3]   verdict, moves, cell of the null move
+ * Each output may be NULL.  Touches no engine state and needs no net.  batch < 1, NULL boards or turns, a turns byte above 1, max_depth outside
+ * 1..16 or max_nodes outside 1..65536: OMOK_ERR_INVALID, with nothing written, nothing allocated and nothing launched.  (One wave of the device
+ * runs one solve: 65536 nodes bounds it here as it does in omok_env_vcf_solve.)  The number of cells per status is left to the caller: it is
+ * a sum over the status row. */
+#define OMOK_VCFD_OCCUPIED 0
+#define OMOK_VCFD_SAFE 1
+#define OMOK_VCFD_WINS 2
+#define OMOK_VCFD_LOSES 3
+#define OMOK_VCFD_UNKNOWN 4
+int omok_env_vcf_defend(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t max_depth, int32_t max_nodes,
+                        uint8_t* status_out, uint8_t* moves_out, int32_t* nodes_out, int32_t* reply_out, int32_t* threat_out);
 /* Whole evaluation episode after a fresh omok_selfplay_reset: play_against_naive_player (trainer.rs:487-603: kind = OMOK_OPP_NAIVE,
  * opponent_side = 0, the scripted player is Black and moves first) or _play_against_random_player (:400-485: OMOK_OPP_RANDOM, opponent_side =
  * 1).  On plies where opponent_side (0 = Black, 1 = White) is to move: the scripted move as an external move (ensure_action_exists +

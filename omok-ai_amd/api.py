@@ -12,6 +12,7 @@ Names follow the reference so parity tests read like its own code:
   SelfPlay.versus_run              Trainer::play_against_naive_player / _play_against_random_player, src/trainer.rs:400-603
   Engine.env_threat_scan           which level of the threat-aware scripted player's rule (B.OPP_THREAT, include/omok_mi355x.h) decides a position
   Engine.env_vcf_solve             does the side to move have a forced win by continuous fours?  (B.OPP_VCF is the scripted player that asks)
+  Engine.env_vcf_defend            the defender's half: which moves of the side to move do not lose to the other side's forced win?
   Environment.check_positions      the rules of Environment::place_stone read backwards: is a given board a position of a game in progress?
   SelfPlay.reset_from / analyze    Agent::new (agent.rs:16-35) on given positions instead of Environment::new()
   SelfPlay.match_reset_from        the match of benchmark/src/main.rs from given positions (an opening book), each agent with its own net
@@ -32,6 +33,13 @@ from . import weights as W
 EMPTY, BLACK, WHITE = 0, 1, 2
 TURN_BLACK, TURN_WHITE = 0, 1
 IN_PROGRESS, DRAW, BLACK_WIN, WHITE_WIN = 0, 1, 2, 3
+
+
+def vcf_defend_counts(status):
+    """{safe, wins, loses, unknown: int32 [B]}: the cells of each status in the rows of an omok_env_vcf_defend status array [B][HW]"""
+    status = np.asarray(status)
+    names = (("safe", B.VCFD_SAFE), ("wins", B.VCFD_WINS), ("loses", B.VCFD_LOSES), ("unknown", B.VCFD_UNKNOWN))
+    return {name: np.count_nonzero(status == value, axis=1).astype(np.int32) for name, value in names}
 
 
 class Engine:
@@ -264,6 +272,26 @@ class Engine:
         self._chk(B.lib().omok_env_vcf_solve(self.h, B.u8ptr(boards), B.u8ptr(turns), len(boards), int(max_depth), int(max_nodes), B.iptr(verdict),
                                              B.iptr(cell), B.iptr(moves), B.iptr(nodes), B.iptr(pv)))
         return verdict, cell, moves, nodes, pv
+
+    def env_vcf_defend(self, boards, turns, max_depth=8, max_nodes=4096):
+        """omok_env_vcf_defend on caller-held positions, turns[b] = the side to move: which of its moves do not lose to the other side's
+        forced win by continuous fours within max_depth (1..16) attacker moves and max_nodes (1..65536) nodes per cell?  (The rule:
+        include/omok_mi355x.h.)  Returns a dict: status uint8 [B][HW] (B.VCFD_OCCUPIED / SAFE / WINS / LOSES / UNKNOWN), moves uint8 [B][HW],
+        nodes and reply int32 [B][HW] (the other side's win after a stone there: its attacker moves, the nodes counted, its first move or
+        -1), threat int32 [B][3] (verdict, moves, cell of the other side if the mover passed), and safe, wins, loses, unknown int32 [B]:
+        the cells of each status, summed here from the status rows.  Needs no net."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
+        turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
+        assert len(turns) == len(boards)
+        b = len(boards)
+        status, moves = np.zeros((b, self.hw), dtype=np.uint8), np.zeros((b, self.hw), dtype=np.uint8)
+        nodes, reply = np.zeros((b, self.hw), dtype=np.int32), np.zeros((b, self.hw), dtype=np.int32)
+        threat = np.zeros((b, 3), dtype=np.int32)
+        self._chk(B.lib().omok_env_vcf_defend(self.h, B.u8ptr(boards), B.u8ptr(turns), b, int(max_depth), int(max_nodes), B.u8ptr(status),
+                                              B.u8ptr(moves), B.iptr(nodes), B.iptr(reply), B.iptr(threat)))
+        out = {"status": status, "moves": moves, "nodes": nodes, "reply": reply, "threat": threat}
+        out.update(vcf_defend_counts(status))
+        return out
 
     def env_check_positions(self, boards):
         """omok_env_check_positions on caller-held boards [B][HW] (bytes): (verdict int32 [B], stones int32 [B]); verdict 0 = a legal position

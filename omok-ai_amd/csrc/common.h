@@ -209,6 +209,10 @@ void launch_env_scripted(int n, int kind, const uint8_t* boards_dev, const uint8
 // position -> verdict_dev, cell_dev, moves_dev, nodes_dev [B], pv_dev [B][2 * depth - 1]; each may be NULL
 void launch_env_vcf(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int depth, int nodes, int32_t* verdict_dev, int32_t* cell_dev,
                     int32_t* moves_dev, int32_t* nodes_dev, int32_t* pv_dev, hipStream_t st);
+// the defender's half (omok_env_vcf_defend): per empty cell the solver with the mover's stone there and the other side attacking, and the null move;
+// a wave per (position, cell) -> status_dev, moves_dev [B][HW] bytes, nodes_dev, reply_dev [B][HW], threat_dev [B][3]; each may be NULL
+void launch_env_vcf_defend(int n, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int depth, int nodes, uint8_t* status_dev,
+                           uint8_t* moves_dev, int32_t* nodes_dev, int32_t* reply_dev, int32_t* threat_dev, hipStream_t st);
 void launch_policy(int n, const Store& S, int side, float* pi_dev /*[G][HW]*/, uint8_t* has_dev /*[G]*/, hipStream_t st);
 void launch_env_place(int n, uint8_t* boards_dev, uint8_t* turns_dev, uint16_t* legal_dev, const int32_t* actions_dev, int batch,
                       int32_t* status_dev, hipStream_t st);

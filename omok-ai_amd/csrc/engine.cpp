@@ -835,6 +835,11 @@ static void download_columns(omok_engine* e, const int32_t* d_slab, size_t B, in
     for (int i = 0; i < k; ++i)
         if (host[i]) hipMemcpyAsync(host[i], d_slab + i * B, B * 4, hipMemcpyDeviceToHost, e->st);
 }
+// its row-shaped sibling: `count` elements of a device array [B][k] as they lie -> host, where that is not NULL
+template <typename T>
+static void download_rows(omok_engine* e, const T* d_rows, size_t count, T* host) {
+    if (host) hipMemcpyAsync(host, d_rows, count * sizeof(T), hipMemcpyDeviceToHost, e->st);
+}
 
 extern "C" int omok_env_play(omok_engine* e, const int32_t* moves, int32_t batch, int32_t len, int32_t* status_out,
                              uint8_t* boards_out, uint8_t* turns_out, uint16_t* legal_out) {
@@ -1599,11 +1604,39 @@ extern "C" int omok_env_vcf_solve(omok_engine* e, const uint8_t* boards, const u
     DevPositions d;
     if (const int rc = upload_positions(e, sc, "env_vcf_solve", boards, turns, batch, true, (4 + len) * B, d)) return rc;
     int32_t* const host[4] = {verdict_out, cell_out, moves_out, nodes_out};
+    e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling: tools/vcf_defend_timing.py)
     launch_env_vcf(e->n, d.boards, d.turns, batch, max_depth, max_nodes, host[0] ? d.out : nullptr, host[1] ? d.out + B : nullptr,
                    host[2] ? d.out + 2 * B : nullptr, host[3] ? d.out + 3 * B : nullptr, pv_out ? d.out + 4 * B : nullptr, e->st);
+    e->prof.end(e->st);
     download_columns(e, d.out, B, 4, host);
     if (pv_out) hipMemcpyAsync(pv_out, d.out + 4 * B, len * B * 4, hipMemcpyDeviceToHost, e->st);
     return sync_and_check(e, "env_vcf_solve") ? OMOK_ERR_HIP : OMOK_OK;
+}
+
+// which moves of the side to move do not lose to the other side's forced win by continuous fours?  (the rule: include/omok_mi355x.h; each output
+// may be NULL).  The slab: nodes, reply [B][HW], threat [B][3], then the status and moves bytes [B][HW], each rounded up to whole words
+extern "C" int omok_env_vcf_defend(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t max_depth, int32_t max_nodes,
+                                   uint8_t* status_out, uint8_t* moves_out, int32_t* nodes_out, int32_t* reply_out, int32_t* threat_out) {
+    if (!e || !boards || !turns || batch < 1) return OMOK_ERR_INVALID;
+    if (max_depth < 1 || max_depth > 16) return fail(e, OMOK_ERR_INVALID, "env_vcf_defend: max_depth %d outside 1..16", max_depth);
+    if (max_nodes < 1 || max_nodes > 65536) return fail(e, OMOK_ERR_INVALID, "env_vcf_defend: max_nodes %d outside 1..65536", max_nodes);
+    ENTER(e);
+    const size_t B = (size_t)batch, cells = B * e->hw, byte_words = (cells + 3) / 4;
+    Scratch sc;
+    DevPositions d;
+    if (const int rc = upload_positions(e, sc, "env_vcf_defend", boards, turns, batch, true, 2 * cells + 3 * B + 2 * byte_words, d)) return rc;
+    int32_t *d_nodes = d.out, *d_reply = d.out + cells, *d_threat = d.out + 2 * cells;
+    uint8_t *d_status = (uint8_t*)(d_threat + 3 * B), *d_moves = d_status + 4 * byte_words;
+    e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling: tools/vcf_defend_timing.py)
+    launch_env_vcf_defend(e->n, d.boards, d.turns, batch, max_depth, max_nodes, status_out ? d_status : nullptr, moves_out ? d_moves : nullptr,
+                          nodes_out ? d_nodes : nullptr, reply_out ? d_reply : nullptr, threat_out ? d_threat : nullptr, e->st);
+    e->prof.end(e->st);
+    download_rows(e, d_status, cells, status_out);
+    download_rows(e, d_moves, cells, moves_out);
+    download_rows(e, d_nodes, cells, nodes_out);
+    download_rows(e, d_reply, cells, reply_out);
+    download_rows(e, d_threat, 3 * B, threat_out);
+    return sync_and_check(e, "env_vcf_defend") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
 // the cell a scripted player's rule is forced to (-1 where it would draw) on caller-held positions: for the naive player the forced part of

@@ -2436,6 +2436,71 @@ __global__ __launch_bounds__(64) void k_env_vcf(const uint8_t* __restrict__ boar
     }
 }
 
+// The defender's half (omok_env_vcf_defend, the rule: include/omok_mi355x.h): which moves of the side to move refute the other side's win by
+// continuous fours.  One wave = one (position, cell): wave w0 + blockIdx.x = b * (HW + 1) + a, where a = HW is the null move (the mover passes)
+// and writes the position's threat row.  A 1-D grid cut into chunks by the host, so the launch does not bound the batch.  The wave loads its
+// board as k_env_vcf does, leaves after its stores where the cell is occupied or FIVE(me, a) holds (vcf_cell, the solver's own predicate),
+// else sets the mover's stone and runs vcf_search itself with the OTHER side as attacker: one node counter per cell, the solver's candidate
+// order, nothing of the solver restated.  a is wave-uniform, so everything that steers stays so; one wave per workgroup with the solver's
+// stack in LDS as in k_env_vcf, no barrier, no atomic.  The status counts of a position are the host's (they would need a cross-wave sum).
+// status / moves [B][HW] bytes, nodes / reply [B][HW], threat [B][3] = verdict, moves, cell of the null move; each output may be NULL.
+template <int N>
+__global__ __launch_bounds__(64) void k_env_vcf_defend(const uint8_t* __restrict__ boards, const uint8_t* __restrict__ turns, int D, int NB, long long w0,
+                                                       uint8_t* __restrict__ status_out, uint8_t* __restrict__ moves_out,
+                                                       int32_t* __restrict__ nodes_out, int32_t* __restrict__ reply_out,
+                                                       int32_t* __restrict__ threat_out) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW, HW = G::HW;
+    __shared__ VcfLevel<N> stk[VCF_MAX_DEPTH];
+    __shared__ int pv[2 * VCF_MAX_DEPTH - 1];
+    const long long w = w0 + blockIdx.x; // (the grid covers exactly the waves [w0, w0 + gridDim.x) < B (HW + 1))
+    const size_t b = (size_t)(w / (HW + 1));
+    const int a = (int)(w - (long long)b * (HW + 1));
+    const int lane = LANE;
+    uint64_t bb[2 * NW];
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) { // (k_env_vcf's loop)
+        const int c = j * 64 + lane;
+        const int s = c < HW ? boards[b * HW + c] : 0;
+        bb[j] = __ballot(s == 1);
+        bb[NW + j] = __ballot(s == 2);
+    }
+    const int me = turns[b] & 1;
+    int status = OMOK_VCFD_OCCUPIED;
+    bool solve = true;
+    if (a < HW) {
+        bool occupied = false;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) // (a select over the words: a register array takes no run-time index)
+            occupied = occupied || ((a >> 6) == i && (((bb[i] | bb[NW + i]) >> (a & 63)) & 1ULL) != 0ULL);
+        if (occupied) solve = false;
+        else if (vcf_cell<N, false>(bb, a, me).five_me) {
+            status = OMOK_VCFD_WINS;
+            solve = false;
+        } else vcf_put<N>(bb, me, a, true);
+    }
+    VcfResult r{0, -1, 0, 0, 0};
+    if (solve) { // (a mover's four at a is the solver's |Fo| == 1 branch: the attacker must answer it with a four of its own)
+        r = vcf_search<N>(bb, 1 - me, D, NB, stk, pv);
+        status = r.verdict == 0 ? OMOK_VCFD_SAFE : (r.verdict == 1 ? OMOK_VCFD_LOSES : OMOK_VCFD_UNKNOWN);
+    }
+    if (lane == 0) {
+        if (a == HW) {
+            if (threat_out) {
+                threat_out[b * 3] = r.verdict;
+                threat_out[b * 3 + 1] = r.moves;
+                threat_out[b * 3 + 2] = r.cell;
+            }
+        } else {
+            const size_t o = b * HW + a;
+            if (status_out) status_out[o] = (uint8_t)status;
+            if (moves_out) moves_out[o] = (uint8_t)r.moves;
+            if (nodes_out) nodes_out[o] = r.nodes;
+            if (reply_out) reply_out[o] = r.cell;
+        }
+    }
+}
+
 // The move of OMOK_OPP_VCF: the threat-aware rule with one level put in after level 2 -- a forced win by continuous fours within
 // D attacker moves and NB nodes (OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES: the host passes them) is played at its first cell.  solved: that
 // level decided.
@@ -3517,6 +3582,15 @@ void launch_env_vcf(int n, const uint8_t* boards, const uint8_t* turns, int batc
                     int32_t* count, int32_t* pv, hipStream_t st) {
     DISPATCH_N(n, (k_env_vcf<9><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, verdict, cell, moves, count, pv)),
                (k_env_vcf<15><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, verdict, cell, moves, count, pv)));
+}
+void launch_env_vcf_defend(int n, const uint8_t* boards, const uint8_t* turns, int batch, int depth, int nodes, uint8_t* status, uint8_t* moves,
+                           int32_t* count, int32_t* reply, int32_t* threat, hipStream_t st) {
+    const long long waves = (long long)batch * (n * n + 1); // a wave per (position, cell) and one per position for the null move
+    for (long long w0 = 0; w0 < waves; w0 += 1LL << 30) {   // gridDim.x < 2^31: 2^30 waves per launch
+        const unsigned grid = (unsigned)std::min(waves - w0, 1LL << 30);
+        DISPATCH_N(n, (k_env_vcf_defend<9><<<grid, 64, 0, st>>>(boards, turns, depth, nodes, w0, status, moves, count, reply, threat)),
+                   (k_env_vcf_defend<15><<<grid, 64, 0, st>>>(boards, turns, depth, nodes, w0, status, moves, count, reply, threat)));
+    }
 }
 void launch_policy(int n, const Store& S, int side, float* pi, uint8_t* has, hipStream_t st) {
     DISPATCH_N(n, (k_policy<9><<<S.games, 64, 0, st>>>(S, side, pi, has)), (k_policy<15><<<S.games, 64, 0, st>>>(S, side, pi, has)));

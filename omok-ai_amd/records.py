@@ -8,6 +8,8 @@ root and chosen-child statistics of the mover's tree at the moment of the move. 
 
     python -m omok_ai_amd.records show FILE.npz --game 3
     python -m omok_ai_amd.records tactics FILE.npz
+    python -m omok_ai_amd.records forced FILE.npz
+    python -m omok_ai_amd.records defence FILE.npz --max-depth 8 --max-nodes 4096
 """
 import argparse
 import json
@@ -225,6 +227,49 @@ class GameRecords:
                     dropped[i, side] += 1
         return {"moves_before": moves_before, "had": had, "dropped": dropped}
 
+    # ---- forced losses (the engine's replay, its forced-win solver and its defence map) ------------------
+    def vcf_defence(self, engine, max_depth=8, max_nodes=4096):
+        """How often a mover faced the opponent's forced win by continuous fours, and whether the move in the record held it off.  Walks the
+        plies as forced_wins does: the positions of all games after p moves come from Engine.env_replay (upto = p).  Stage 1: Engine.env_vcf_solve
+        with the side that is NOT to move (the threat if the mover passed).  Stage 2: Engine.env_vcf_defend with the mover to move, on the
+        positions whose threat has verdict 1 and moves >= 2, and only on those (a threat in one move is tactics()'s `unblocked` ground and is
+        not counted twice; this is the report's definition, not a shortcut: a stone of the mover's can create a threat where there was none).
+        Returns a dict, per game and side (0 Black, 1 White) int32 [G][2]:
+          threatened    the positions of stage 2
+          defensible    those of them with at least one WINS or SAFE cell
+          held          defensible, and the played cell is WINS or SAFE
+          conceded      defensible, and the played cell is LOSES: a forced loss walked into with a way out on the board
+          unknown       the played cell of a stage-2 position is UNKNOWN, or stage 1 ran out of its node budget
+        and threat_before int8 [G][HW]: stage 1's `moves` in front of move p; 0 none (and beyond the game's length), -1 the node budget ran out.
+        A record that does not replay (verify) raises AssertionError."""
+        assert engine.n == self.n, f"records of board size {self.n}, engine of {engine.n}"
+        g = self.games
+        out = {name: np.zeros((g, 2), dtype=np.int32) for name in ("threatened", "defensible", "held", "conceded", "unknown")}
+        out["threat_before"] = np.zeros((g, self.hw), dtype=np.int8)
+        if g == 0:
+            return out
+        moves, start = self.moves(), np.count_nonzero(self.start_boards, axis=1)
+        for p in range(min(int(self.lengths.max()), self.hw)):
+            boards, status, played = engine.env_replay(self.start_boards, moves, self.lengths, upto=p)
+            moved = np.flatnonzero(self.lengths > p)
+            assert np.all(played[moved] == p), f"the records stop being legal before move {p}"
+            assert not status[moved].any(), f"a game goes on after move {p} ended it"
+            side = ((start[moved] + p) & 1).astype(np.uint8)
+            verdict, _cell, m, _nodes, _pv = engine.env_vcf_solve(boards[moved], 1 - side, max_depth, max_nodes)
+            out["threat_before"][moved, p] = np.where(verdict == 1, m, verdict)
+            np.add.at(out["unknown"], (moved[verdict < 0], side[verdict < 0]), 1)
+            pick = (verdict == 1) & (m >= 2)
+            if not pick.any():
+                continue
+            rows, sides = moved[pick], side[pick]
+            st = engine.env_vcf_defend(boards[rows], sides, max_depth, max_nodes)["status"]
+            at = st[np.arange(len(rows)), self.cells[rows, p].astype(np.int64)]
+            way_out = ((st == 1) | (st == 2)).any(axis=1)  # OMOK_VCFD_SAFE, OMOK_VCFD_WINS
+            for name, which in (("threatened", np.ones(len(rows), dtype=bool)), ("defensible", way_out),
+                                ("held", way_out & ((at == 1) | (at == 2))), ("conceded", way_out & (at == 3)), ("unknown", at == 4)):
+                np.add.at(out[name], (rows[which], sides[which]), 1)
+        return out
+
     # ---- text --------------------------------------------------------------------------------------
     def coordinate(self, cell):
         """column letter (a = x 0) and row number (1 = y 0) of cell = y * n + x"""
@@ -276,8 +321,27 @@ def main(argv=None):
     forced.add_argument("file")
     forced.add_argument("--max-depth", type=int, default=8)
     forced.add_argument("--max-nodes", type=int, default=4096)
+    defence = sub.add_parser("defence", help="count the opponent's forced wins by continuous fours a side faced, held off and walked into (needs the GPU: replay, solver and defence map run in the engine)")
+    defence.add_argument("file")
+    defence.add_argument("--max-depth", type=int, default=8)
+    defence.add_argument("--max-nodes", type=int, default=4096)
     args = ap.parse_args(argv)
     rec = load(args.file)
+    if args.cmd == "defence":
+        from . import api
+        eng = api.Engine(board_size=rec.n, games=1, max_nodes=16, max_tables=8, max_batch_k=1)
+        try:
+            f = rec.vcf_defence(eng, args.max_depth, args.max_nodes)
+        finally:
+            eng.close()
+        out = {"games": rec.games, "moves": int((rec.cells >= 0).sum()), "max_depth": args.max_depth, "max_nodes": args.max_nodes,
+               "budget_exhausted": int((f["threat_before"] < 0).sum())}
+        for s, name in ((0, "black"), (1, "white")):
+            out[name] = {k: int(f[k][:, s].sum()) for k in ("threatened", "defensible", "held", "conceded", "unknown")}
+        if rec.meta:
+            print("meta: " + json.dumps(rec.meta, sort_keys=True))
+        print("defence: " + json.dumps(out, sort_keys=True))
+        return 0
     if args.cmd == "forced":
         from . import api
         eng = api.Engine(board_size=rec.n, games=1, max_nodes=16, max_tables=8, max_batch_k=1)
