@@ -62,6 +62,7 @@ pub const OMOK_OPP_THREAT: i32 = 3;
 pub const OMOK_OPP_VCF: i32 = 5;
 pub const OMOK_VCF_OPP_DEPTH: i32 = 6;
 pub const OMOK_VCF_OPP_NODES: i32 = 256;
+pub const OMOK_OPP_GUARD: i32 = 7;
 pub const OMOK_VCFD_OCCUPIED: i32 = 0;
 pub const OMOK_VCFD_SAFE: i32 = 1;
 pub const OMOK_VCFD_WINS: i32 = 2;
@@ -164,6 +165,7 @@ pub mod ffi {
         pub fn omok_env_threat_scan(e: *mut OmokEngine, boards: *const u8, turns: *const u8, batch: i32, cell_out: *mut i32, level_out: *mut i32, count_out: *mut i32) -> c_int;
         pub fn omok_env_vcf_solve(e: *mut OmokEngine, boards: *const u8, turns: *const u8, batch: i32, max_depth: i32, max_nodes: i32, verdict_out: *mut i32, cell_out: *mut i32, moves_out: *mut i32, nodes_out: *mut i32, pv_out: *mut i32) -> c_int;
         pub fn omok_env_vcf_defend(e: *mut OmokEngine, boards: *const u8, turns: *const u8, batch: i32, max_depth: i32, max_nodes: i32, status_out: *mut u8, moves_out: *mut u8, nodes_out: *mut i32, reply_out: *mut i32, threat_out: *mut i32) -> c_int;
+        pub fn omok_env_guard_scan(e: *mut OmokEngine, boards: *const u8, turns: *const u8, draws: *const u32, batch: i32, max_depth: i32, max_nodes: i32, cell_out: *mut i32, step_out: *mut i32, level_out: *mut i32, count_out: *mut i32) -> c_int;
         pub fn omok_versus_run(e: *mut OmokEngine, kind: i32, opponent_side: i32, count: i32, batch_size: i32, epsilon: f32, alpha: f32, max_plies: i32, results: *mut i32, stats: *mut f64) -> c_int;
         pub fn omok_selfplay_run_slots(e: *mut OmokEngine, total_games: i32, count: i32, batch_size: i32, epsilon: f32, alpha: f32, temperature: f32, threshold: i32, records_dev: *mut c_void, cap_records: i64, game_offsets: *mut i64, game_lengths: *mut i32, game_status: *mut i32, n_records: *mut i64, stats: *mut f64) -> c_int;
         pub fn omok_selfplay_run_slots_logged(e: *mut OmokEngine, total_games: i32, count: i32, batch_size: i32, epsilon: f32, alpha: f32, temperature: f32, threshold: i32, records_dev: *mut c_void, cap_records: i64, log_dev: *mut c_void, game_offsets: *mut i64, game_lengths: *mut i32, game_status: *mut i32, n_records: *mut i64, stats: *mut f64) -> c_int;

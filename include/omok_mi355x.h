@@ -318,11 +318,33 @@ int omok_selfplay_run(omok_engine* e, int32_t count, int32_t batch_size, float e
 #define OMOK_OPP_VCF 5
 #define OMOK_VCF_OPP_DEPTH 6
 #define OMOK_VCF_OPP_NODES 256
+/* OMOK_OPP_GUARD: the defending player.  It is OMOK_OPP_VCF with its move checked against the other side's win by continuous fours and, where
+ * that move loses, replaced through the defender's map (omok_env_vcf_defend below): a fixed opponent that a net does not beat merely by setting
+ * up a four-three.  `me` is the side to move and `opp` the other; x0 is the game's draw word, the word the other players draw for that game,
+ * ply and side (no new RNG purpose); D and NB are OMOK_VCF_OPP_DEPTH and OMOK_VCF_OPP_NODES; solve is the rule of omok_env_vcf_solve,
+ * unchanged; defend is the rule of omok_env_vcf_defend, unchanged, without its null move, which the player does not need.
+ * Let (c0, L0, solved, n0) be OMOK_OPP_VCF's move on the position X: c0 its cell with the draw made by x0, L0 the threat rule's level, solved
+ * whether the solver's level decided, n0 the number of cells its draw chose among (0 unless the draw decided).
+ *   step 0         L0 = 0, the board has no empty cell: the cell is -1.
+ *   step 1, own    L0 <= 2 or solved: play c0 (a five, the block of a five, the last cell, the player's own forced win).
+ *   step 2, kept   R = solve(X with me at c0, opp, D, NB).  If R.verdict != 1, play c0: a budget verdict keeps the move.
+ *   otherwise      take the status map of defend(X, me, D, NB).  M = the cells with OMOK_VCFD_SAFE (step 3); if there are none, M = the cells
+ *                  with OMOK_VCFD_UNKNOWN (step 4); if both sets are empty, play c0 (step 5: every move loses).  No cell is WINS here, because
+ *                  L0 >= 3, and c0 is LOSES, by the same solve as step 2.
+ *   steps 3 and 4  the threat rule's levels 3..7 restricted to M: the LOWEST a in M of the first level that has one --
+ *                    3  T(me,a) >= 2      4  T(opp,a) >= 2      5  OPEN3(me,a)
+ *                    6  the r-th cell in ascending order of M with NEAR, r = mulhi(x0, their count)
+ *                    7  no cell of M has NEAR: the r-th cell of M
+ * The map is not monotone (see omok_env_vcf_defend), so step 2 is applied to whatever cell the VCF rule chose, from any level, and no cell of
+ * the map is skipped.  By construction the player plays a LOSES cell only where no SAFE cell exists.  The value 6 is no player and stays an
+ * invalid kind, like 2 and 4. */
+#define OMOK_OPP_GUARD 7
 /* the forced part of the rule on caller-held positions (boards [B][N*N] Stone bytes, turns [B]): forced_out[b] = the cell the NAIVE rule
  * picks before its random fallback (trainer.rs:514-531), -1 if none (always -1 for RANDOM).  (The rule tries a stone of either colour at
  * every empty cell, so the side to move does not change the answer: turns is read by no kernel.)  For OMOK_OPP_THREAT the side to move
  * decides: forced_out[b] = the cell of levels 1..5, -1 for levels 6 and 7, and a turns byte above 1 is OMOK_ERR_INVALID, checked before
- * anything is launched (kinds 0 and 1 keep ignoring turns).  OMOK_OPP_VCF likewise: the cell of levels 1..5 or the solver's cell. */
+ * anything is launched (kinds 0 and 1 keep ignoring turns).  OMOK_OPP_VCF likewise: the cell of levels 1..5 or the solver's cell.  OMOK_OPP_GUARD likewise: the
+ * player's cell with x0 = 0 where no draw decided (omok_env_guard_scan's count = 0), else -1. */
 int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out);
 /* step-wise: the scripted player's move (trainer.rs:508-534 / :452-455) for the side to move of every live game, chosen on the device and
  * staged like omok_set_actions (omok_mirror_* / omok_advance follow); actions [G] may be NULL, -1 for finished games.  OMOK_ERR_STATE in a
@@ -411,10 +433,23 @@ int omok_env_vcf_solve(omok_engine* e, const uint8_t* boards, const uint8_t* tur
 #define OMOK_VCFD_UNKNOWN 4
 int omok_env_vcf_defend(omok_engine* e, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t max_depth, int32_t max_nodes,
                         uint8_t* status_out, uint8_t* moves_out, int32_t* nodes_out, int32_t* reply_out, int32_t* threat_out);
+/* The move of OMOK_OPP_GUARD on caller-held positions, and which step of its rule decided (boards [B][N*N] Stone bytes, any other byte counts
+ * as empty; turns [B] = the side to move, 0 Black / 1 White; draws [B] = the draw word x0 of every position, NULL: all 0).  The rule runs with
+ * max_depth and max_nodes in place of D and NB (the player itself always uses OMOK_VCF_OPP_*).  Per position:
+ *   cell_out   the move the player makes with that word, or -1 on a full board
+ *   step_out   0..5, the step of the rule above that decided
+ *   level_out  L0 in steps 1, 2 and 5; the restricted rule's level 3..7 in steps 3 and 4; 0 in step 0
+ *   count_out  the number of cells the deciding draw chose among, else 0
+ * Each output may be NULL.  Touches no engine state and needs no net.  batch < 1, NULL boards or turns, a turns byte above 1, max_depth outside
+ * 1..16 or max_nodes outside 1..4096: OMOK_ERR_INVALID, with nothing written, nothing allocated and nothing launched.  (One wave of the first
+ * pass runs two solves in sequence, so the cap is a sixteenth of the solver's 65536: it bounds how long a wave can run and is a condition of
+ * the call, not a tuned value.) */
+int omok_env_guard_scan(omok_engine* e, const uint8_t* boards, const uint8_t* turns, const uint32_t* draws, int32_t batch, int32_t max_depth,
+                        int32_t max_nodes, int32_t* cell_out, int32_t* step_out, int32_t* level_out, int32_t* count_out);
 /* Whole evaluation episode after a fresh omok_selfplay_reset: play_against_naive_player (trainer.rs:487-603: kind = OMOK_OPP_NAIVE,
  * opponent_side = 0, the scripted player is Black and moves first) or _play_against_random_player (:400-485: OMOK_OPP_RANDOM, opponent_side =
  * 1).  On plies where opponent_side (0 = Black, 1 = White) is to move: the scripted move as an external move (ensure_action_exists +
- * play_action, :536-538; kind may be OMOK_OPP_THREAT or OMOK_OPP_VCF as well).  On the others: omok_execute(count, batch_size, epsilon, alpha), sample_action(Best), play_action (:562-577).
+ * play_action, :536-538; kind may be OMOK_OPP_THREAT, OMOK_OPP_VCF or OMOK_OPP_GUARD as well).  On the others: omok_execute(count, batch_size, epsilon, alpha), sample_action(Best), play_action (:562-577).
  * Runs until every game is over or max_plies (> 0) plies were played.  results [3] (may be NULL) = black wins, white wins, draws among the
  * finished games (the reference's tuple, :602); stats as omok_selfplay_run.
  * The net's agent is the engine's tree of side 1 - opponent_side: it receives exactly the calls the reference's single Agent receives.  The

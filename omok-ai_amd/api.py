@@ -239,7 +239,8 @@ class Engine:
     def env_scripted_actions(self, kind, boards, turns):
         """the forced part of the scripted player's rule (src/trainer.rs:514-531) on caller-held positions: the lowest empty cell at
         which a stone of either side ends the game, -1 where there is none (always -1 for B.OPP_RANDOM); int32 [B].  For B.OPP_THREAT: the
-        cell of levels 1..5 of the threat-aware rule for the side to move turns[b] (0 / 1, anything else raises), -1 for levels 6 and 7"""
+        cell of levels 1..5 of the threat-aware rule for the side to move turns[b] (0 / 1, anything else raises), -1 for levels 6 and 7; for
+        B.OPP_GUARD: the defending player's cell where no draw decided, else -1"""
         boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
         turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
         assert len(turns) == len(boards)
@@ -291,6 +292,23 @@ class Engine:
                                               B.u8ptr(moves), B.iptr(nodes), B.iptr(reply), B.iptr(threat)))
         out = {"status": status, "moves": moves, "nodes": nodes, "reply": reply, "threat": threat}
         out.update(vcf_defend_counts(status))
+        return out
+
+    def env_guard_scan(self, boards, turns, draws=None, max_depth=B.VCF_OPP_DEPTH, max_nodes=B.VCF_OPP_NODES):
+        """omok_env_guard_scan on caller-held positions, turns[b] = the side to move: the move of the defending player B.OPP_GUARD (the rule:
+        include/omok_mi355x.h) with the draw words draws uint32 [B] (None: all 0), and the step of its rule that decided, with max_depth
+        (1..16) and max_nodes (1..4096) in place of the player's own budget.  Returns a dict of int32 [B] arrays: cell (-1 on a full board),
+        step 0..5, level (the VCF rule's in steps 1, 2 and 5, the restricted rule's 3..7 in steps 3 and 4) and count (the cells the deciding
+        draw chose among, else 0).  Needs no net."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, self.hw)
+        turns = np.ascontiguousarray(turns, dtype=np.uint8).reshape(-1)
+        assert len(turns) == len(boards)
+        if draws is not None:
+            draws = np.ascontiguousarray(draws, dtype=np.uint32).reshape(-1)
+            assert len(draws) == len(boards)
+        out = {name: np.zeros(len(boards), dtype=np.int32) for name in ("cell", "step", "level", "count")}
+        self._chk(B.lib().omok_env_guard_scan(self.h, B.u8ptr(boards), B.u8ptr(turns), None if draws is None else draws.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              len(boards), int(max_depth), int(max_nodes), *[B.iptr(out[name]) for name in ("cell", "step", "level", "count")]))
         return out
 
     def env_check_positions(self, boards):
@@ -503,13 +521,13 @@ class SelfPlay:
 
     def opponent_actions(self, kind):
         """the scripted player's move (B.OPP_NAIVE / B.OPP_RANDOM, src/trainer.rs:508-534, 452-455; B.OPP_THREAT, the threat-aware rule; B.OPP_VCF, the same with the
-        forced-win solver) for the side to move of every live game, chosen on the device and staged like set_actions (the mirror step / advance follow); -1 for finished games"""
+        forced-win solver; B.OPP_GUARD, the defending player that consults the forced-loss map) for the side to move of every live game, chosen on the device and staged like set_actions (the mirror step / advance follow); -1 for finished games"""
         a = np.zeros(self.games, dtype=np.int32)
         self._chk(B.lib().omok_opponent_actions(self.h, int(kind), B.iptr(a)))
         return a
 
     def versus_run(self, kind, opponent_side, count, batch_size, epsilon=0.25, alpha=0.03, max_plies=0):
-        """Evaluation episode after reset() (omok_versus_run): the scripted player `kind` (B.OPP_NAIVE, B.OPP_RANDOM, B.OPP_THREAT or B.OPP_VCF) plays the colour opponent_side (0 = Black, moves
+        """Evaluation episode after reset() (omok_versus_run): the scripted player `kind` (B.OPP_NAIVE, B.OPP_RANDOM, B.OPP_THREAT, B.OPP_VCF or B.OPP_GUARD) plays the colour opponent_side (0 = Black, moves
         first: play_against_naive_player, src/trainer.rs:487-603; 1 = White: _play_against_random_player, :400-485), the net the other with
         `count` simulations and sample_action(Best).  Returns ((black_win, white_win, draw), stats)."""
         s = (C.c_double * len(B.STAT_NAMES))()

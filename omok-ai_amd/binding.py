@@ -20,6 +20,9 @@ OPPONENTS = {"random": OPP_RANDOM, "naive": OPP_NAIVE, "threat": OPP_THREAT}
 OPP_VCF = 5  # the threat-aware player with the forced-win solver's level (omok_env_vcf_solve; 4 is no player)
 VCFD_OCCUPIED, VCFD_SAFE, VCFD_WINS, VCFD_LOSES, VCFD_UNKNOWN = 0, 1, 2, 3, 4  # the cell statuses of omok_env_vcf_defend
 OPPONENT_KINDS = {**OPPONENTS, "vcf": OPP_VCF}  # every scripted player by name (OPPONENTS: the ones without a solver)
+VCF_OPP_DEPTH, VCF_OPP_NODES = 6, 256  # OMOK_VCF_OPP_*: the solver budget of the players that use it
+OPP_GUARD = 7  # the defending player: OMOK_OPP_VCF's move checked against the defender's map (omok_env_guard_scan; 6 is no player)
+SCRIPTED_PLAYERS = {**OPPONENT_KINDS, "guard": OPP_GUARD}  # every scripted player by name (OPPONENT_KINDS: the ones that do not consult the map)
 # omok_debug_last_plan: names of its ints; PLAN_PATHS: values of "path"
 PLAN_NAMES = ["path", "rows", "nsplit", "tsplit", "runs", "singles", "run_rows", "full_runs", "tiles", "t_split", "ways", "fways",
               "fc0_format", "n_cu", "nsup", "reserved"]
@@ -38,7 +41,7 @@ SYMBOLS = [
     "omok_create", "omok_destroy", "omok_last_error", "omok_net_num_tensors", "omok_net_tensor_size", "omok_net_load",
     "omok_net_commit", "omok_net_load_file", "omok_net_save_file", "omok_net2_load", "omok_net2_commit", "omok_net2_load_file", "omok_net2_info", "omok_match_reset", "omok_evaluate_pv", "omok_evaluate_logits", "omok_env_play", "omok_env_place_stone", "omok_encode_nn_input", "omok_selfplay_reset", "omok_set_episode", "omok_execute", "omok_execute_shared", "omok_execute_shared_recorded",
     "omok_compute_policy", "omok_play_actions", "omok_set_actions", "omok_root_children",
-    "omok_env_scripted_actions", "omok_opponent_actions", "omok_versus_run", "omok_env_threat_scan", "omok_env_vcf_solve", "omok_env_vcf_defend",
+    "omok_env_scripted_actions", "omok_opponent_actions", "omok_versus_run", "omok_env_threat_scan", "omok_env_vcf_solve", "omok_env_vcf_defend", "omok_env_guard_scan",
     "omok_env_check_positions", "omok_selfplay_reset_from", "omok_root_stats",
     "omok_match_reset_from", "omok_env_random_positions",
     "omok_sample_actions", "omok_advance", "omok_selfplay_run", "omok_selfplay_run_slots", "omok_round_generate", "omok_round_inputs",
@@ -129,6 +132,7 @@ def lib():
     L.omok_env_threat_scan.argtypes = [H, u8p, u8p, C.c_int32, ip, ip, ip]
     L.omok_env_vcf_solve.argtypes = [H, u8p, u8p, C.c_int32, C.c_int32, C.c_int32, ip, ip, ip, ip, ip]
     L.omok_env_vcf_defend.argtypes = [H, u8p, u8p, C.c_int32, C.c_int32, C.c_int32, u8p, u8p, ip, ip, ip]
+    L.omok_env_guard_scan.argtypes = [H, u8p, u8p, C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.c_int32, ip, ip, ip, ip]
     L.omok_versus_run.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, ip, C.POINTER(C.c_double)]
     L.omok_env_check_positions.argtypes = [H, u8p, C.c_int32, ip, ip]
     L.omok_selfplay_reset_from.argtypes = [H, u8p]

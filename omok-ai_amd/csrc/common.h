@@ -200,7 +200,17 @@ void launch_clear_actions(const Store& S, hipStream_t st);
 // the scripted players of the evaluation games (kind = OMOK_OPP_*: random and naive of src/trainer.rs:400-603, the threat-aware player, and the one
 // with the forced-win solver, which alone uses depth / nodes = OMOK_VCF_OPP_DEPTH / OMOK_VCF_OPP_NODES): the move of the side to move of every live game,
 // staged like launch_set_actions (external) and copied to actions_dev [G] (-1: finished game)
-void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions_dev, hipStream_t st);
+// OMOK_OPP_GUARD goes through launch_guard on the engine's scratch guard_out_dev [4][G] and guard_status_dev [G][HW] (unused by the other kinds)
+void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions_dev, hipStream_t st,
+                          int32_t* guard_out_dev = nullptr, uint8_t* guard_status_dev = nullptr);
+// where the defending player's passes take their positions from: the live games' root boards of `side` with the draw word of launch_opponent_move
+// (boards == nullptr: position b = game b, a finished game gets cell -1), or caller-held boards [B][HW], turns [B] and draw words [B] (NULL: all 0)
+struct GuardSrc { const uint8_t* boards; const uint8_t* turns; const uint32_t* draws; int side; uint64_t seed; int64_t game_offset; };
+// OMOK_OPP_GUARD's move of `batch` positions in three stream-ordered launches (first pass, map pass, pick pass; no host read-back between them):
+// out_dev [4][batch] = cell, step, level, count; status_dev [batch][HW] scratch of the map pass; actions_dev (the live form, else NULL): the move staged
+// like launch_opponent_move's
+void launch_guard(int n, const Store& S, const GuardSrc& src, int batch, int depth, int nodes, int32_t* out_dev, uint8_t* status_dev, int32_t* actions_dev,
+                  hipStream_t st);
 // the same rule on caller-held positions: boards_dev [B][HW] Stone bytes, turns_dev [B] (0 / 1; read by the threat-aware kinds alone, else may be NULL)
 // -> cell_dev (the cell the rule is forced to, -1 where it would draw), level_dev, count_dev [B]; each may be NULL
 void launch_env_scripted(int n, int kind, const uint8_t* boards_dev, const uint8_t* turns_dev, int batch, int depth, int nodes, int32_t* cell_dev,

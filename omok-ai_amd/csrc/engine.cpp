@@ -120,6 +120,9 @@ struct omok_engine {
     bool log_started = false;           // a reset has set the log's start since it was enabled: moves are logged, omok_game_log_read answers
     void* log_mem = nullptr;            // the one allocation GameLog points into
     GameLog log{};
+    // OMOK_OPP_GUARD on the live games: allocated on the first use of that kind (ensure_guard_scratch), freed with the engine's allocations
+    int32_t* d_guard_out = nullptr;     // [4][G] cell, step, level, count: the first pass's results and its carry to the pick pass
+    uint8_t* d_guard_status = nullptr;  // [G][HW] the map pass's status rows
     // host-side stats
     double sims = 0, evals = 0, ply_games = 0, finished = 0;
     uint32_t peak_nodes = 0, peak_tables = 0;
@@ -1298,9 +1301,11 @@ static void enqueue_sample(omok_engine* e, float temperature, int threshold) {
 }
 
 // the scripted player's move of every live game (OMOK_OPP_*: the evaluation games further down), staged where the search's sample would be
+// (OMOK_OPP_GUARD: three launches under the one event pair, on the scratch the caller made sure of with ensure_guard_scratch)
 static void enqueue_opponent_move(omok_engine* e, int kind) {
     e->prof.begin(PC_PLY, e->st);
-    launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, e->d_actions, e->st);
+    launch_opponent_move(e->n, e->S, e->ply & 1, kind, e->key, e->cfg.game_offset, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, e->d_actions, e->st,
+                         e->d_guard_out, e->d_guard_status);
     e->prof.end(e->st);
 }
 
@@ -1562,9 +1567,16 @@ extern "C" int omok_play_actions(omok_engine* e, const int32_t* actions) {
 
 // ---- evaluation games against the scripted players (src/trainer.rs:380-394, 400-603) -----------
 static int check_opponent_kind(omok_engine* e, int kind) {
-    if (kind != OMOK_OPP_RANDOM && kind != OMOK_OPP_NAIVE && kind != OMOK_OPP_THREAT && kind != OMOK_OPP_VCF)
-        return fail(e, OMOK_ERR_INVALID, "unknown scripted player %d (OMOK_OPP_RANDOM, OMOK_OPP_NAIVE, OMOK_OPP_THREAT, OMOK_OPP_VCF)", kind);
+    if (kind != OMOK_OPP_RANDOM && kind != OMOK_OPP_NAIVE && kind != OMOK_OPP_THREAT && kind != OMOK_OPP_VCF && kind != OMOK_OPP_GUARD)
+        return fail(e, OMOK_ERR_INVALID, "unknown scripted player %d (OMOK_OPP_RANDOM, OMOK_OPP_NAIVE, OMOK_OPP_THREAT, OMOK_OPP_VCF, OMOK_OPP_GUARD)", kind);
     return 0;
+}
+// the engine-owned scratch of OMOK_OPP_GUARD's three passes on the live games; an engine that never plays that kind allocates nothing
+static int ensure_guard_scratch(omok_engine* e, int kind) {
+    if (kind != OMOK_OPP_GUARD || e->d_guard_status) return 0;
+    const size_t G = (size_t)e->cfg.games;
+    if (dalloc(e, &e->d_guard_out, 4 * G)) return OMOK_ERR_HIP;
+    return dalloc(e, &e->d_guard_status, G * e->hw) ? OMOK_ERR_HIP : 0;
 }
 
 // the rule of a scripted player on caller-held positions (each output may be NULL).  The threat-aware kinds read the side to move; the naive rule
@@ -1639,11 +1651,46 @@ extern "C" int omok_env_vcf_defend(omok_engine* e, const uint8_t* boards, const 
     return sync_and_check(e, "env_vcf_defend") ? OMOK_ERR_HIP : OMOK_OK;
 }
 
+// OMOK_OPP_GUARD on caller-held positions: the three passes in the call's own scratch (the engine's state is not touched).  The slab: cell, step,
+// level, count [B] (the passes' carry as well, so all four are always written on the device), the draw words [B], then the status rows [B][HW]
+static int env_guard(omok_engine* e, const char* what, const uint8_t* boards, const uint8_t* turns, const uint32_t* draws, int32_t batch, int depth, int nodes,
+                     int32_t* const* host) {
+    ENTER(e);
+    const size_t B = (size_t)batch, cells = B * e->hw;
+    Scratch sc;
+    DevPositions d;
+    if (const int rc = upload_positions(e, sc, what, boards, turns, batch, true, 5 * B + (cells + 3) / 4, d)) return rc;
+    uint32_t* d_draws = draws ? (uint32_t*)(d.out + 4 * B) : nullptr;
+    if (draws) hipMemcpyAsync(d_draws, draws, B * 4, hipMemcpyHostToDevice, e->st);
+    e->prof.begin(PC_PLY, e->st); // (timed only under omok_set_profiling)
+    launch_guard(e->n, e->S, GuardSrc{d.boards, d.turns, d_draws, 0, 0, 0}, batch, depth, nodes, d.out, (uint8_t*)(d.out + 5 * B), nullptr, e->st);
+    e->prof.end(e->st);
+    download_columns(e, d.out, B, 4, host);
+    return sync_and_check(e, what) ? OMOK_ERR_HIP : OMOK_OK;
+}
+
+// the defending player's move and the step of its rule that decided (the rule: include/omok_mi355x.h; each output may be NULL)
+extern "C" int omok_env_guard_scan(omok_engine* e, const uint8_t* boards, const uint8_t* turns, const uint32_t* draws, int32_t batch, int32_t max_depth,
+                                   int32_t max_nodes, int32_t* cell_out, int32_t* step_out, int32_t* level_out, int32_t* count_out) {
+    if (!e || !boards || !turns || batch < 1) return OMOK_ERR_INVALID;
+    if (max_depth < 1 || max_depth > 16) return fail(e, OMOK_ERR_INVALID, "env_guard_scan: max_depth %d outside 1..16", max_depth);
+    if (max_nodes < 1 || max_nodes > 4096) return fail(e, OMOK_ERR_INVALID, "env_guard_scan: max_nodes %d outside 1..4096", max_nodes);
+    int32_t* const host[4] = {cell_out, step_out, level_out, count_out};
+    return env_guard(e, "env_guard_scan", boards, turns, draws, batch, max_depth, max_nodes, host);
+}
+
 // the cell a scripted player's rule is forced to (-1 where it would draw) on caller-held positions: for the naive player the forced part of
 // trainer.rs:514-531 under the rules of environment/src/lib.rs:104-190
 extern "C" int omok_env_scripted_actions(omok_engine* e, int32_t kind, const uint8_t* boards, const uint8_t* turns, int32_t batch, int32_t* forced_out) {
     if (!e || !boards || !turns || !forced_out || batch < 1) return OMOK_ERR_INVALID;
     if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
+    if (kind == OMOK_OPP_GUARD) { // the player's cell with x0 = 0 where no draw decided
+        std::vector<int32_t> cell((size_t)batch), count((size_t)batch);
+        int32_t* const host[4] = {cell.data(), nullptr, nullptr, count.data()};
+        if (const int rc = env_guard(e, "env_scripted_actions", boards, turns, nullptr, batch, OMOK_VCF_OPP_DEPTH, OMOK_VCF_OPP_NODES, host)) return rc;
+        for (size_t b = 0; b < (size_t)batch; ++b) forced_out[b] = count[b] == 0 ? cell[b] : -1;
+        return OMOK_OK;
+    }
     return env_scripted(e, "env_scripted_actions", kind, boards, turns, batch, forced_out, nullptr, nullptr);
 }
 
@@ -1654,6 +1701,7 @@ extern "C" int omok_opponent_actions(omok_engine* e, int32_t kind, int32_t* acti
     if (no_match(e, "omok_opponent_actions")) return OMOK_ERR_STATE;
     if (check_opponent_kind(e, kind)) return OMOK_ERR_INVALID;
     ENTER(e);
+    if (const int rc = ensure_guard_scratch(e, kind)) return rc;
     enqueue_opponent_move(e, kind);
     if (actions) HIPCHK(e, hipMemcpyAsync(actions, e->d_actions, sizeof(int32_t) * e->cfg.games, hipMemcpyDeviceToHost, e->st));
     if (sync_and_check(e, "opponent_actions")) return OMOK_ERR_HIP;
@@ -1674,6 +1722,7 @@ extern "C" int omok_versus_run(omok_engine* e, int32_t kind, int32_t opponent_si
     if (e->ply != e->start_ply)
         return fail(e, OMOK_ERR_STATE, "omok_versus_run starts at a fresh reset: %d move(s) were played since (the episode is at ply %d)", e->ply - e->start_ply, e->ply);
     HIPCHK(e, hipSetDevice(e->cfg.device));
+    if (const int rc = ensure_guard_scratch(e, kind)) return rc;
     const Search s{count, batch_size, epsilon, alpha, 1.0f, 0}; // threshold 0: sample_action(Best) on every ply of the net (:576, :430)
     uint32_t bits = 0, alive = 0;
     if (read_status(e, &bits, &alive)) return OMOK_ERR_HIP;

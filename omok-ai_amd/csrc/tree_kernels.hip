@@ -2595,6 +2595,209 @@ __global__ __launch_bounds__(64) void k_env_scripted(const uint8_t* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The defending scripted player (OMOK_OPP_GUARD; the rule: include/omok_mi355x.h): OMOK_OPP_VCF's move, checked against the other side's win by
+// continuous fours and, where it loses, replaced through the defender's map.  Three stream-ordered launches, no host read-back in between:
+//   k_guard_first  one wave per position: scripted_move<N, OMOK_OPP_VCF>, then for L0 >= 3 and not solved the mover's stone at c0 and
+//                  vcf_search for the other side.  Decides steps 0, 1 and 2; else leaves step = GUARD_MAP_NEEDED with c0, L0, n0 as the carry.
+//   k_guard_map    k_env_vcf_defend's launch shape without the null move: one wave per (position, cell) on a chunked 1-D grid; the waves of a
+//                  position without the flag leave after reading it, the others write that cell's status byte.
+//   k_guard_pick   one wave per position, leaves unless flagged: M from the status row by ballots, the threat rule's levels 3..7 on M.
+// Positions come from a GuardSrc: the live games' root boards with k_opponent_move's Philox word (boards == nullptr; position b = game b), or
+// caller-held boards with given draw words.  out [4][B] = cell, step, level, count is both the result and the carry between the passes.
+// With `actions` (the live form) the deciding pass stages the move exactly as k_opponent_move does.
+// ---------------------------------------------------------------------------------------------
+constexpr int GUARD_MAP_NEEDED = -1; // a step value only between the passes: k_guard_pick replaces it with 3, 4 or 5
+
+// position b of src -> bb, legal, me, x0; false: a finished game of the live form (nothing is loaded)
+template <int N>
+__device__ inline bool guard_load(const Store& S, const GuardSrc& src, int b, uint64_t* bb, int& legal, int& me, uint32_t& x0) {
+    if (src.boards == nullptr) {
+        const GameState gs = S.gs[b];
+        if (!gs.alive) return false;
+        me = src.side;
+        legal = Geo<N>::HW - load_root_board<N>(S, me, b, bb);
+        x0 = philox(src.seed, 0u, (uint32_t)gs.plies, (uint32_t)((src.game_offset + gs.gid) * 2 + me), RNG_OPPONENT).x; // (k_opponent_move's word)
+    } else {
+        legal = Geo<N>::HW - load_position<N>(src.boards, b, bb);
+        me = src.turns[b] & 1;
+        x0 = src.draws ? src.draws[b] : 0u;
+    }
+    return true;
+}
+
+// lane 0: the result of position b, and in the live form the staged move
+__device__ inline void guard_store(const Store& S, int b, int B, int cell, int step, int level, int count, int32_t* __restrict__ out, int32_t* __restrict__ actions) {
+    out[b] = cell;
+    out[(size_t)B + b] = step;
+    out[2 * (size_t)B + b] = level;
+    out[3 * (size_t)B + b] = count;
+    if (actions && step != GUARD_MAP_NEEDED) { actions[b] = cell; S.gs[b].last_action = cell; S.gs[b].external = 1; }
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void k_guard_first(Store S, GuardSrc src, int D, int NB, int B, int32_t* __restrict__ out, int32_t* __restrict__ actions) {
+    constexpr int NW = Geo<N>::NW;
+    __shared__ VcfLevel<N> stk[VCF_MAX_DEPTH];
+    __shared__ int pv[2 * VCF_MAX_DEPTH - 1];
+    const int b = blockIdx.x;
+    uint64_t bb[2 * NW];
+    int legal, me, cell = -1, step = 0, level = 0, count = 0; // (a finished game: -1, like k_opponent_move)
+    uint32_t x0;
+    if (guard_load<N>(S, src, b, bb, legal, me, x0)) {
+        const ScriptedMove m = scripted_move<N, OMOK_OPP_VCF>(bb, legal, me, x0, D, NB, stk, pv);
+        cell = m.cell;
+        level = m.level;
+        count = m.solved ? 0 : m.count; // n0: 0 unless the draw decided
+        if (level >= 1) step = 1;       // own: a five, its block, the last cell, the player's forced win
+        if (level >= 3 && !m.solved) {  // kept, unless the other side then wins by continuous fours (a budget verdict keeps the move)
+            vcf_put<N>(bb, me, cell, true);
+            step = vcf_search<N>(bb, 1 - me, D, NB, stk, pv).verdict == 1 ? GUARD_MAP_NEEDED : 2;
+        }
+    }
+    if (LANE == 0) guard_store(S, b, B, cell, step, level, count, out, actions);
+}
+
+// wave w0 + blockIdx.x = b * HW + a (the grid covers exactly the waves [w0, w0 + gridDim.x) < B * HW); status [B][HW] OMOK_VCFD_* of the flagged positions
+template <int N>
+__global__ __launch_bounds__(64) void k_guard_map(Store S, GuardSrc src, int D, int NB, int B, long long w0, const int32_t* __restrict__ out,
+                                                  uint8_t* __restrict__ status_out) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW, HW = G::HW;
+    __shared__ VcfLevel<N> stk[VCF_MAX_DEPTH];
+    __shared__ int pv[2 * VCF_MAX_DEPTH - 1];
+    const long long w = w0 + blockIdx.x;
+    const int b = (int)(w / HW);
+    const int a = (int)(w - (long long)b * HW);
+    if (out[(size_t)B + b] != GUARD_MAP_NEEDED) return;
+    uint64_t bb[2 * NW];
+    int legal, me;
+    uint32_t x0;
+    guard_load<N>(S, src, b, bb, legal, me, x0); // (a flagged position is a live one)
+    bool occupied = false;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) // (k_env_vcf_defend's select over the words)
+        occupied = occupied || ((a >> 6) == i && (((bb[i] | bb[NW + i]) >> (a & 63)) & 1ULL) != 0ULL);
+    int status = OMOK_VCFD_OCCUPIED;
+    if (!occupied) {
+        if (vcf_cell<N, false>(bb, a, me).five_me) status = OMOK_VCFD_WINS; // (none here, L0 >= 3: kept so that the row is defend's row)
+        else {
+            vcf_put<N>(bb, me, a, true);
+            const int verdict = vcf_search<N>(bb, 1 - me, D, NB, stk, pv).verdict;
+            status = verdict == 0 ? OMOK_VCFD_SAFE : (verdict == 1 ? OMOK_VCFD_LOSES : OMOK_VCFD_UNKNOWN);
+        }
+    }
+    if (LANE == 0) status_out[(size_t)b * HW + a] = (uint8_t)status;
+}
+
+// The threat-aware rule's levels 3..7 restricted to the cells M (empty cells, wave-uniform ballot words): scripted_threat_cell's sweep with M
+// ANDed into levels 3..5 and into NEAR; level 7: no cell of M has NEAR, the draw goes over M.  M is not empty.
+template <int N>
+__device__ inline int guard_pick_cell(const uint64_t* bb, const unsigned long long* M, int me, uint32_t x0, int& level, int& count) {
+    using G = Geo<N>;
+    constexpr uint32_t CENTRE = 1u << 9, AROUND = 0x3DE0u; // as in scripted_threat_cell
+    const int lane = LANE;
+    int first[3] = {-1, -1, -1};
+    unsigned long long near[G::IT];
+    level = 0;
+    count = 0;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        bool hit[3] = {false, false, false};
+        bool nr = false;
+        if ((M[j] >> lane) & 1ULL) {
+            const int xc = a % N, yc = a / N;
+            int t_me = 0, t_opp = 0;
+#pragma unroll 1
+            for (int pr = 0; pr < 4; ++pr) {
+                uint32_t black, white, inside;
+                threat_line<N>(bb, xc, yc, pr, black, white, inside);
+                const uint32_t free_cells = inside & ~(black | white);
+                const LineRuns rm = line_runs((me == 0 ? black : white) | CENTRE), ro = line_runs((me == 0 ? white : black) | CENTRE);
+                t_me += __popc(line_exact_five(rm) & free_cells & AROUND);
+                t_opp += __popc(line_exact_five(ro) & free_cells & AROUND);
+#pragma unroll
+                for (int ra = 0; ra <= 2; ++ra) {
+                    const int rb = 2 - ra;
+                    const uint32_t three = (rm.up[ra] & ~rm.up[ra + 1]) & (rm.dn[rb] & ~rm.dn[rb + 1]) & CENTRE;
+                    hit[2] = hit[2] || (three != 0u && ((free_cells >> (10 + ra)) & (free_cells >> (8 - rb)) & 1u) != 0u);
+                }
+                nr = nr || ((black | white) & 0x500u) != 0u;
+            }
+            hit[0] = t_me >= 2;
+            hit[1] = t_opp >= 2;
+        }
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+            const unsigned long long m = __ballot(hit[l]);
+            if (first[l] < 0 && m != 0ULL) first[l] = j * 64 + __ffsll((long long)m) - 1;
+        }
+        near[j] = __ballot(nr);
+    }
+#pragma unroll
+    for (int l = 0; l < 3; ++l)
+        if (level == 0 && first[l] >= 0) level = l + 3;
+    if (level != 0) {
+        int cell = -1;
+#pragma unroll
+        for (int l = 0; l < 3; ++l) cell = level == l + 3 ? first[l] : cell;
+        return cell;
+    }
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) count += __popcll(near[j]);
+    level = 6;
+    if (count == 0) { // level 7: the draw over M itself
+        level = 7;
+#pragma unroll
+        for (int j = 0; j < G::IT; ++j) { near[j] = M[j]; count += __popcll(M[j]); }
+    }
+    int r = (int)__umulhi(x0, (uint32_t)count);
+    int action = -1;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int c = __popcll(near[j]);
+        if (action < 0) {
+            if (r < c) action = j * 64 + nth_set_bit(near[j], r);
+            else r -= c;
+        }
+    }
+    return action;
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void k_guard_pick(Store S, GuardSrc src, int B, const uint8_t* __restrict__ status, int32_t* __restrict__ out,
+                                                   int32_t* __restrict__ actions) {
+    using G = Geo<N>;
+    constexpr int NW = G::NW, HW = G::HW;
+    const int b = blockIdx.x;
+    if (out[(size_t)B + b] != GUARD_MAP_NEEDED) return;
+    const int lane = LANE;
+    uint64_t bb[2 * NW];
+    int legal, me;
+    uint32_t x0;
+    guard_load<N>(S, src, b, bb, legal, me, x0);
+    unsigned long long safe[G::IT], unknown[G::IT];
+    bool any_safe = false, any_unknown = false;
+#pragma unroll
+    for (int j = 0; j < G::IT; ++j) {
+        const int a = j * 64 + lane;
+        const int s = a < HW ? status[(size_t)b * HW + a] : OMOK_VCFD_OCCUPIED;
+        safe[j] = __ballot(s == OMOK_VCFD_SAFE);
+        unknown[j] = __ballot(s == OMOK_VCFD_UNKNOWN);
+        any_safe = any_safe || safe[j] != 0ULL;
+        any_unknown = any_unknown || unknown[j] != 0ULL;
+    }
+    int cell = out[b], step = 5, level = out[2 * (size_t)B + b], count = out[3 * (size_t)B + b]; // step 5, every move loses: c0 with L0 and n0
+    if (any_safe || any_unknown) {
+        step = any_safe ? 3 : 4;
+#pragma unroll
+        for (int j = 0; j < G::IT; ++j) safe[j] = any_safe ? safe[j] : unknown[j];
+        cell = guard_pick_cell<N>(bb, safe, me, x0, level, count);
+    }
+    if (lane == 0) guard_store(S, b, B, cell, step, level, count, out, actions);
+}
+
 // k_position_check: is a caller-supplied board a position an alternating game from Environment::new() can be in, and still in progress?
 // boards [B][HW] bytes -> verdict [B], the first that applies: 1 a byte that is no Stone (> 2); 2 stone counts no alternating game produces
 // (neither black = white nor black = white + 1); 3 already won: some stone, taken as the last one placed, makes exactly five in one of the
@@ -3563,7 +3766,12 @@ static void dispatch_kind(int kind, F f) {
     case OMOK_OPP_VCF: f(std::integral_constant<int, OMOK_OPP_VCF>()); break;
     }
 }
-void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions, hipStream_t st) {
+void launch_opponent_move(int n, const Store& S, int side, int kind, uint64_t seed, int64_t game_offset, int depth, int nodes, int32_t* actions, hipStream_t st,
+                          int32_t* guard_out, uint8_t* guard_status) {
+    if (kind == OMOK_OPP_GUARD) { // three launches on the engine's scratch: out [4][G], status [G][HW]
+        launch_guard(n, S, GuardSrc{nullptr, nullptr, nullptr, side, seed, game_offset}, S.games, depth, nodes, guard_out, guard_status, actions, st);
+        return;
+    }
     dispatch_kind(kind, [&](auto k) {
         constexpr int KIND = decltype(k)::value;
         DISPATCH_N(n, (k_opponent_move<9, KIND><<<S.games, 64, 0, st>>>(S, side, seed, game_offset, depth, nodes, actions)),
@@ -3577,6 +3785,18 @@ void launch_env_scripted(int n, int kind, const uint8_t* boards, const uint8_t* 
         DISPATCH_N(n, (k_env_scripted<9, KIND><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, cell, level, count)),
                    (k_env_scripted<15, KIND><<<batch, 64, 0, st>>>(boards, turns, depth, nodes, cell, level, count)));
     });
+}
+void launch_guard(int n, const Store& S, const GuardSrc& src, int batch, int depth, int nodes, int32_t* out, uint8_t* status, int32_t* actions, hipStream_t st) {
+    DISPATCH_N(n, (k_guard_first<9><<<batch, 64, 0, st>>>(S, src, depth, nodes, batch, out, actions)),
+               (k_guard_first<15><<<batch, 64, 0, st>>>(S, src, depth, nodes, batch, out, actions)));
+    const long long waves = (long long)batch * (n * n); // a wave per (position, cell), as launch_env_vcf_defend cuts them
+    for (long long w0 = 0; w0 < waves; w0 += 1LL << 30) {
+        const unsigned grid = (unsigned)std::min(waves - w0, 1LL << 30);
+        DISPATCH_N(n, (k_guard_map<9><<<grid, 64, 0, st>>>(S, src, depth, nodes, batch, w0, out, status)),
+                   (k_guard_map<15><<<grid, 64, 0, st>>>(S, src, depth, nodes, batch, w0, out, status)));
+    }
+    DISPATCH_N(n, (k_guard_pick<9><<<batch, 64, 0, st>>>(S, src, batch, status, out, actions)),
+               (k_guard_pick<15><<<batch, 64, 0, st>>>(S, src, batch, status, out, actions)));
 }
 void launch_env_vcf(int n, const uint8_t* boards, const uint8_t* turns, int batch, int depth, int nodes, int32_t* verdict, int32_t* cell, int32_t* moves,
                     int32_t* count, int32_t* pv, hipStream_t st) {

@@ -44,7 +44,7 @@ class Parameters:  # src/config.rs:83-110
     evaluate_every: int = 10        # `iteration % 10 == 0` (src/trainer.rs:380)
     evaluate_games: int = 100       # play_against_naive_player(100, ..) (:384)
     selfplay_slots: int = 0         # 0 = one episode of episode_count games (omok_selfplay_run); S > 0 = the same games in slots mode on min(S, episode_count) slots (omok_selfplay_run_slots; no reference counterpart)
-    evaluate_opponent: str = "naive"  # the scripted player of the evaluation games: "naive" (the reference's, :508-534), "threat" (the threat-aware player, OMOK_OPP_THREAT), "vcf" (that player with the forced-win solver, OMOK_OPP_VCF) or "random" (:452-455)
+    evaluate_opponent: str = "naive"  # the scripted player of the evaluation games: "naive" (the reference's, :508-534), "threat" (the threat-aware player, OMOK_OPP_THREAT), "vcf" (that player with the forced-win solver, OMOK_OPP_VCF), "guard" (the defending player, OMOK_OPP_GUARD) or "random" (:452-455)
     train_backend: str = "torch"    # the training phase (:329-357): "torch" = autograd (train.py), "hip" = the engine's native step (omok_train_run, one rank), "hip_dp" = the native step in two halves with the ranks' gradients averaged in between (any world size)
 
 
@@ -56,8 +56,8 @@ class Trainer:
         self.rank, self.local_rank, self.world = dist.shard_info()
         if self.p.train_backend not in ("torch", "hip", "hip_dp"):
             raise ValueError(f"train_backend {self.p.train_backend!r}: expected \"torch\", \"hip\" or \"hip_dp\"")
-        if self.p.evaluate_opponent not in api.B.OPPONENT_KINDS:
-            raise ValueError(f"evaluate_opponent {self.p.evaluate_opponent!r}: expected \"naive\", \"threat\", \"vcf\" or \"random\"")
+        if self.p.evaluate_opponent not in api.B.SCRIPTED_PLAYERS:
+            raise ValueError(f"evaluate_opponent {self.p.evaluate_opponent!r}: expected \"naive\", \"threat\", \"vcf\", \"guard\" or \"random\"")
         if self.p.train_backend == "hip" and self.world > 1:
             raise RuntimeError("train_backend=\"hip\" runs on one rank only: the native step does not average gradients over ranks "
                                f"(world size {self.world}); use train_backend=\"hip_dp\" or \"torch\" for data-parallel training")
@@ -278,7 +278,7 @@ class Trainer:
                 sp.reset()
             else:
                 sp.reset_from(np.ascontiguousarray(openings, dtype=np.uint8).reshape(p.evaluate_games, self.n * self.n))
-            (black, white, draw), _ = sp.versus_run(api.B.OPPONENT_KINDS[p.evaluate_opponent], 0, p.test_evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha)
+            (black, white, draw), _ = sp.versus_run(api.B.SCRIPTED_PLAYERS[p.evaluate_opponent], 0, p.test_evaluate_count, p.evaluate_batch_size, p.epsilon, p.alpha)
             if save_games is not None:
                 sp.game_records(meta={"kind": "evaluate", "net": os.path.join(self.save_dir, p.model_name), "iteration": self.iteration,
                                       "opponent": p.evaluate_opponent, "opponent_side": 0, "sims": p.test_evaluate_count, "batch": p.evaluate_batch_size,

@@ -9,8 +9,8 @@ streams.  Prints one JSON line: games/s and game-plies/s of both, the result cou
 k_advance).  `--scripted-vs KIND2` adds one episode without any search: `--kind` as Black against KIND2 as White, both moving through
 omok_opponent_actions (the strength of one scripted player against another; its counts by colour land under "scripted").
 
-    python tools/versus_bench.py [--games 4096] [--sims 800] [--batch 16] [--kind naive|random|threat|vcf] [--opponent-side 0] [--plies 0] [--no-selfplay]
-                                 [--scripted-vs naive|random|threat|vcf]
+    python tools/versus_bench.py [--games 4096] [--sims 800] [--batch 16] [--kind naive|random|threat|vcf|guard] [--opponent-side 0] [--plies 0] [--no-selfplay]
+                                 [--scripted-vs naive|random|threat|vcf|guard]
 """
 import argparse
 import json
@@ -31,14 +31,14 @@ def main(argv=None):
     ap.add_argument("--sims", type=int, default=800)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--board", type=int, default=15)
-    ap.add_argument("--kind", choices=sorted(B.OPPONENT_KINDS), default="naive")
-    ap.add_argument("--scripted-vs", choices=sorted(B.OPPONENT_KINDS), default=None, help="one more episode: --kind (Black) against this player (White), no search")
+    ap.add_argument("--kind", choices=sorted(B.SCRIPTED_PLAYERS), default="naive")
+    ap.add_argument("--scripted-vs", choices=sorted(B.SCRIPTED_PLAYERS), default=None, help="one more episode: --kind (Black) against this player (White), no search")
     ap.add_argument("--opponent-side", type=int, default=0)
     ap.add_argument("--plies", type=int, default=0, help="stop the timed episodes after this many plies (0: whole episodes)")
     ap.add_argument("--warmup-plies", type=int, default=2)
     ap.add_argument("--no-selfplay", action="store_true")
     a = ap.parse_args(argv)
-    kind = B.OPPONENT_KINDS[a.kind]
+    kind = B.SCRIPTED_PLAYERS[a.kind]
     max_nodes = min(16384, 4 * a.sims + 1024)
     eng = oa.Engine(board_size=a.board, games=a.games, max_nodes=max_nodes, max_tables=max(256, max_nodes // 4), max_batch_k=a.batch, seed=1)
     eng.load_random_weights(0)
@@ -72,7 +72,7 @@ def main(argv=None):
     if not a.no_selfplay:
         out["selfplay"] = episode(False)
     if a.scripted_vs is not None:
-        kinds = (kind, B.OPPONENT_KINDS[a.scripted_vs])
+        kinds = (kind, B.SCRIPTED_PLAYERS[a.scripted_vs])
         sp.reset()
         t = time.perf_counter()
         while sp.alive_count > 0 and (a.plies == 0 or sp.ply < a.plies):
