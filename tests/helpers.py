@@ -56,16 +56,17 @@ def compare_trees(sp, osp, games, tag):
 
 
 def drive_selfplay_vs_oracle(n, games, count, k, max_plies, mode, threshold=6, max_nodes=2048, max_tables=1024, seed=7,
-                             game_offset=5, weight_seed=0, epsilon=0.25, alpha=0.03, temperature=1.0, on_sample=None):
+                             game_offset=5, weight_seed=0, epsilon=0.25, alpha=0.03, temperature=1.0, on_sample=None, tensors=None):
     """Plays `games` games step by step on the engine and on the oracle (the oracle consumes the GPU net's p / v, so the
     comparison isolates the tree arithmetic) and compares canonical tree dumps, request boards, moves and replay tuples bit
     for bit.  Returns the shape of the deepest search seen by the ORACLE: (fully expanded nodes, fully expanded non-root
     nodes, max depth, max tables) so that a test can prove it left the shallow root-plus-one-layer regime.
     on_sample(ply, pi [games][hw], has [games], actions [games]): called with the engine's compute_policy read BEFORE the
-    ply's sample_actions and the moves that call chose."""
+    ply's sample_actions and the moves that call chose.  tensors: the net's 31 tensors, in place of the random-init net `weight_seed`."""
     import omok_ai_amd as oa
     from oracle import oracle as O
-    tensors = oa.weights.init_random(n, seed=weight_seed)
+    if tensors is None:
+        tensors = oa.weights.init_random(n, seed=weight_seed)
     eng = oa.Engine(board_size=n, games=games, max_nodes=max_nodes, max_tables=max_tables, max_batch_k=k, seed=seed,
                     game_offset=game_offset, net_mode=mode)
     eng.load_weights(tensors)
@@ -121,6 +122,94 @@ def drive_selfplay_vs_oracle(n, games, count, k, max_plies, mode, threshold=6, m
         assert np.array_equal(gp.view(np.uint32), op.view(np.uint32))
     eng.close()
     return tuple(shape)
+
+
+def drive_injected_vs_oracle(n, games, count, k, max_plies, mode, kind_seed, threshold=6, max_nodes=2048, max_tables=1024, seed=7,
+                              game_offset=5, weight_seed=0, epsilon=0.25, alpha=0.03, temperature=1.0, opening=0):
+    """drive_selfplay_vs_oracle with the net taken out of the loop: after the reset (whose root row is the net's, as there) neither
+    side evaluates anything.  Every round's (p, v) and every mirror batch's p come from tests/adversarial_outputs.py and go into the
+    engine through round_inject / mirror_inject and into the oracle as arguments, so the tree kernels meet rows no net emits: exact
+    ties, zero and denormal rows, legal sums at and around 2^-23, v = +-1, +-0.  Compared bit for bit at the same points.  Returns the
+    coverage counts (adversarial_outputs.coverage) of the ORACLE's dumps of both trees of every live game after every ply's simulations
+    and after every advance (each of those dumps has just been compared with the device's, bit for bit).
+    opening: that many moves of draw_sequence(n) are played first as external moves (set_actions; their mirror rows are injected
+    too), so that the searched plies start on a board with few empty cells and PUCT runs between visited children from the first ply on.
+    Without noise only rows that can become a searched root (mirror rows, requests at even depth) are kept finite under the root's
+    unguarded renormalisation (adversarial_outputs.root_candidates); every other request keeps every kind."""
+    import omok_ai_amd as oa
+    import adversarial_outputs as AO
+    from oracle import oracle as O
+    tensors = oa.weights.init_random(n, seed=weight_seed)
+    eng = oa.Engine(board_size=n, games=games, max_nodes=max_nodes, max_tables=max_tables, max_batch_k=k, seed=seed,
+                    game_offset=game_offset, net_mode=mode)
+    eng.load_weights(tensors)
+    sp = oa.SelfPlay(eng)
+    sp.reset()
+    root_p = eng.evaluate_p(O.Environment(n).encode_nn_input(0)[None]).reshape(-1)
+    osp = O.SelfPlay(n, games, cap_nodes=max_nodes, cap_tables=max_tables, seed=seed, game_offset=game_offset)
+    osp.reset(root_p)
+    compare_trees(sp, osp, games, "reset")
+    no_noise = epsilon == 0.0
+    counts = {}
+    ply = 0
+    rounds = (count + k - 1) // k
+    for cell in draw_sequence(n)[:opening]:
+        acts = np.full(games, cell, dtype=np.int32)
+        sp.set_actions(acts)
+        osp.set_actions(acts)
+        nm = sp.mirror_generate()
+        om = osp.mirror_generate()
+        assert nm == len(om) == games and np.array_equal(sp.mirror_inputs(), om)
+        pm = AO.mirror_rows(kind_seed, ply, om, no_noise)
+        sp.mirror_inject(pm)
+        sp.mirror_apply()
+        osp.advance(pm)
+        assert osp.error == 0 and osp.alive_count == games
+        ply += 1
+    if opening:
+        compare_trees(sp, osp, games, "after the opening")
+    while osp.alive_count > 0 and (max_plies == 0 or ply - opening < max_plies):
+        side = ply & 1
+        for rnd in range(rounds):
+            nreq = sp.round_generate(rnd, k, epsilon, alpha)
+            oin = osp.round_generate(rnd, k, epsilon, alpha)
+            assert nreq == len(oin), f"ply {ply} round {rnd}: request count"
+            assert np.array_equal(sp.round_inputs(), oin), f"ply {ply} round {rnd}: request boards"
+            if rnd == 0 or (rounds > 20 and rnd % 16 == 15):
+                compare_trees(sp, osp, games, f"ply {ply} after generate of round {rnd}")
+            p, v = AO.rows(kind_seed, ply, rnd, oin, AO.root_candidates(osp, side, len(oin)) if no_noise else False)
+            sp.round_inject(p, v)
+            sp.round_scatter()
+            osp.round_scatter(p, v)
+        compare_trees(sp, osp, games, f"ply {ply} after execute")
+        assert osp.error == 0
+        counts = AO.add_counts(counts, AO.coverage([osp.tree_dump(g, sd) for g in range(games) if osp.game_alive(g) for sd in (0, 1)]))
+        a = sp.sample_actions(temperature, threshold)
+        assert np.array_equal(a, osp.sample(temperature, threshold)), f"ply {ply}: actions"
+        moved = [g for g in range(games) if osp.game_alive(g)]
+        nm = sp.mirror_generate()
+        om = osp.mirror_generate()
+        assert nm == len(om) and np.array_equal(sp.mirror_inputs(), om)
+        pm = AO.mirror_rows(kind_seed, ply, om, no_noise)
+        sp.mirror_inject(pm)
+        sp.mirror_apply()
+        osp.advance(pm)
+        assert osp.error == 0
+        compare_trees(sp, osp, games, f"ply {ply} after advance")
+        counts = AO.add_counts(counts, AO.coverage([osp.tree_dump(g, sd) for g in moved if osp.game_alive(g) for sd in (0, 1)]))
+        alive, status, plies = sp.game_info()
+        assert [int(x) for x in alive] == [osp.game_alive(g) for g in range(games)]
+        assert [int(x) for x in status] == [osp.game_status(g) for g in range(games)]
+        assert [int(x) for x in plies] == [osp.game_plies(g) for g in range(games)]
+        ply += 1
+    assert sp.alive_count == osp.alive_count
+    for g in range(games):
+        gb, gt, gp, gz = sp.replay(g)
+        ob, ot, op, oz = osp.replay(g)
+        assert np.array_equal(gb, ob) and np.array_equal(gt, ot) and np.array_equal(gz.view(np.uint32), oz.view(np.uint32))
+        assert np.array_equal(gp.view(np.uint32), op.view(np.uint32))
+    eng.close()
+    return counts
 
 
 def boltzmann_expected(pi, temperature, u):

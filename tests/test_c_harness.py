@@ -15,10 +15,20 @@ def _run():
     return subprocess.run([HARNESS], capture_output=True, text=True, timeout=600)
 
 
+def _link_if_missing():
+    """The C caller is a build product kept inside tests/c/, so a fresh copy of tests/ laid over a built tree has none.  The test without a GPU
+    then links it against the built library (the recipe build() runs; a failing recipe fails the test with its output).  The GPU test does not:
+    there a missing program means build() did not make it."""
+    if not os.path.exists(HARNESS):
+        made = subprocess.run(["make", "-s", "-C", os.path.dirname(HARNESS)], capture_output=True, text=True, timeout=600)
+        assert made.returncode == 0, (made.returncode, made.stdout[-2000:], made.stderr[-2000:])
+
+
 def test_c_caller_sees_a_clean_error_without_a_gpu():
     import torch
     if torch.cuda.is_available():
         pytest.skip("GPU present: the gpu test runs the harness")
+    _link_if_missing()
     out = _run()
     assert out.returncode == 3, (out.returncode, out.stdout, out.stderr)
     assert "OMOK_ERR_HIP" in out.stdout and "no CPU path" in out.stdout

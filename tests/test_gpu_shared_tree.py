@@ -18,10 +18,13 @@ from test_oracle_selfplay import check_tree_invariants
 pytestmark = pytest.mark.gpu
 
 
-def _engine(n, k, seed, waves, max_nodes=4096, net_mode=0):
+def _engine(n, k, seed, waves, max_nodes=4096, net_mode=0, tensors=None):
     eng = oa.Engine(board_size=n, games=1, max_nodes=max_nodes, max_tables=max_nodes // 2, max_batch_k=k, seed=seed, max_tree_waves=waves,
                     net_mode=net_mode)
-    eng.load_random_weights(0)
+    if tensors is None:
+        eng.load_random_weights(0)
+    else:
+        eng.load_weights(tensors)
     sp = oa.SelfPlay(eng)
     sp.reset()
     return eng, sp
@@ -132,12 +135,12 @@ def _dump(sp, side):
     return ints, floats
 
 
-def replay_recorded_on_literal(n, count, k, waves, plies, epsilon=0.25, alpha=0.03, temperature=1.0, threshold=4):
+def replay_recorded_on_literal(n, count, k, waves, plies, epsilon=0.25, alpha=0.03, temperature=1.0, threshold=4, tensors=None):
     """The engine searches one tree with `waves` wavefronts in recorded mode; the literal oracle (pointer nodes, stored p, explicit
     refresh loops) replays the recorded lock order with the engine's net outputs: canonical tree dumps, root statistics, request
     boards, sampled moves and the mirror step must be identical."""
     seed = 13
-    eng, sp = _engine(n, k, seed, waves, max_nodes=8192)
+    eng, sp = _engine(n, k, seed, waves, max_nodes=8192, tensors=tensors)  # (tensors: a net other than the random-init one)
     lit = O.Literal(n, 1, seed=seed, cap_nodes=8192)
     lit.reset(eng.evaluate_p(O.Environment(n).encode_nn_input(0)[None]).reshape(-1))
     interleaved = 0
